@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the hot path: rays/s for 4096 rays x 128 samples through the 8x256 NeRF MLP (PE + MLP + composite).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f16|f16x3|f32|bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f16|f16x3|f32|bf16] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment makes this script its own launcher: it re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`, one rank per GPU over RCCL (when a
@@ -12,7 +12,9 @@ One JSON line on rank 0 (contract in the task statement). A "step" = one pass of
 (ray packing -> z stratification -> fused PE+MLP kernel -> compositing scan) over one batch of 4096
 synthetic LLFF-shaped rays already resident in HBM; with N > 1 every rank renders its own 4096 rays
 (weak scaling) and the step ends with the packed blur-loss partial all-reduce over RCCL, the only
-exchange the path has. Beside the contract keys:
+exchange the path has.  A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs DIR is given (DIR/rgb_map.npy, depth_map.npy, acc_map.npy; `.rank<r>` before the suffix with N > 1) and
+prints the line with the contract keys.  --full adds, beside them:
 
   roofline       the dominant kernel (k_nerf_mlp), HIP events on the launch stream
   modes          the same kernel in every arithmetic mode
@@ -66,6 +68,12 @@ def parse(argv=None):
     ap.add_argument("--no-c2f", action="store_true")
     ap.add_argument("--no-awp", action="store_true")
     ap.add_argument("--no-strong", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (per-step median, rooflines, arithmetic modes, oracle parity, c2f / AWP / "
+                         "training legs, strong scaling, CPU baseline; the --no-* options above select among them); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the render's rgb / depth / acc maps; the all-reduced loss partials with N > 1) "
+                         "as DIR/<name>.npy in float32")
     return ap.parse_args(argv)
 
 
@@ -235,6 +243,19 @@ def per_step_ms(fn, steps):
         ev[i + 1].record()
     ev[-1].synchronize()
     return sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(steps))
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """every floating-point tensor of `arrays` as out_dir/<name>.npy (float32; float64 kept), `.rank<r>` before the suffix with N > 1"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    for name, t in arrays.items():
+        if not (torch.is_tensor(t) and t.is_floating_point()):
+            continue
+        v = t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), v if v.dtype == np.float64 else v.astype(np.float32))
 
 
 def oracle_parity(sd, rays, S, K, precisions):
@@ -609,16 +630,18 @@ def main(argv=None):
     R, S = a.rays, a.samples
     K = W.synthetic_camera()
     rays = torch.as_tensor(W.synthetic_rays(100 + rank, R), device="cuda")
-    target = torch.rand((R, 3), device="cuda")
+    target = torch.rand((R, 3), device="cuda")      # (torch's default generator: the same fixed seed in every process)
     ones = torch.ones((R, 1), device="cuda")
     crf = CRF("gamma")
     model, sd = make_model(a.precision)
     kw = dict(ndc=True, near=0., far=1., use_viewdirs=True, N_samples=S, N_importance=0, retraw=False)
 
     pending = []
+    last = {}                 # what the latest step computed: the render's maps (and the reduced loss partials with N > 1)
 
     def step():
-        rgb, depth, acc, _ = model.render(400, 400, K, rays=rays, **kw)
+        rgb, depth, acc, extras = model.render(400, 400, K, rays=rays, **kw)
+        last.update(extras, rgb_map=rgb, depth_map=depth, acc_map=acc)
         if dist:   # the path's one exchange: packed loss partials (evdeblurnerf_amd/dist.py)
             p, _ = blur_loss_partials(crf, rgb, ones, target)
             # the reduced loss is a logging value, nothing in the next step consumes it: the all-reduce (RCCL's own stream)
@@ -626,19 +649,23 @@ def main(argv=None):
             if pending:
                 pending.pop().wait()
             pending.append(dist.all_reduce(p, async_op=True))
+            last["loss_partials"] = p
         return rgb
 
     dt = time_steps(step, a.steps, a.warmup, dist, drain=lambda: [w.wait() for w in pending], settle_steps=a.settle)
-    med = per_step_ms(lambda: model.render(400, 400, K, rays=rays, **kw), max(20, min(a.steps, 200)))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, last, rank, world)
     result = headline(R, S, world, a.steps, a.warmup, dt, a.precision, a.settle)
-    result["ms_per_step_median"] = med[len(med) // 2]
+    if a.full:
+        med = per_step_ms(lambda: model.render(400, 400, K, rays=rays, **kw), max(20, min(a.steps, 200)))
+        result["ms_per_step_median"] = med[len(med) // 2]
     result["ranks"] = {"world_size": world, "backend": backend,
                        "launcher": ("bench.py self-launch" if os.environ.get("EVD_BENCH_SELF_LAUNCH") else
                                     "external torchrun" if world > 1 else "none"),
                        "devices": rank_devices(dist, world)}
     lean = world > 1          # N > 1 runs: headline kernel + the strong-scaling leg (the other legs are N = 1 measurements)
 
-    if rank == 0:
+    if rank == 0 and a.full:
         # ---- roofline of the dominant kernel (fused PE+MLP), measured live with HIP events
         rb = torch.empty((R, 11), device="cuda")
         z = torch.empty((R, S), device="cuda")
@@ -798,7 +825,7 @@ def main(argv=None):
 
     # ---- the shipped configuration (every rank builds the model: the strong-scaling leg shards one frame's rows over the ranks)
     c2f_model = None
-    if not a.no_c2f or not a.no_strong:
+    if a.full and (not a.no_c2f or not a.no_strong):
         c2f_prec = a.precision                                          # f16c: fine level compensated (float16 grid copies), coarse level float32-grade on float32 grids
         # training: f16c = the compensated forward (the headline's arithmetic) in front of the float16 backward; f16m / f16 / f16x3 beside it
         train_prec = a.precision if a.precision in ("f16", "bf16", "f16x3", "f16c") else "f16"
@@ -853,7 +880,7 @@ def main(argv=None):
         del c2f_model
 
     if rank == 0:
-        if not a.no_cpu_baseline and not lean:
+        if a.full and not a.no_cpu_baseline and not lean:
             from oracle import oracle as O
             fast = True
             try:
