@@ -854,8 +854,6 @@ __global__ __launch_bounds__(64 * VM_WAVES, OCC) void k_voxel_sample_m(const Gri
 // atomics (lane = channel, a window cell owned by one wavefront, every wavefront walks the tile's 128 (sample, tap) entries in order;
 // the box of the benchmark's NDC rays is 42-60 cells, 22-28 of them touched by the 128 taps): correct, and 0.92 -> 1.43 ms per 2^19
 // samples, iteration 22.6 -> 30.3 ms -- the walk is a chain of dependent LDS read-modify-writes, again.
-// BINNED (kernel_voxel_scatter.hip): the atomics of phase B are replaced by one row of per-channel contributions per sample and the
-// tap records; a second pass adds them tile by tile in LDS.  d basis and d pts are computed here either way.
 constexpr int VSB_MAXF = 64, VSB_TAPS = 18;
 #ifdef EVD_VSB_BATCH
 constexpr int VSB_BATCH = EVD_VSB_BATCH;
@@ -880,24 +878,14 @@ __device__ __forceinline__ float row_sum_dpp(float v) {
     return v;
 }
 
-// MODE: 0 = every tap by a direct atomic; 1 = pass 1 of the binned form (rows + tap records + keys, no atomics); 2 = HYBRID: the plane
-// taps by direct atomics, the line taps deferred -- their rows and tap records are written and k_scatter_lines adds them through
-// privatised LDS slices of the (small) line gradients: a third of the kernel's atomic requests go away.
-// MODE 3 (opt-in, EVD_SCATTER_WIN=1) = the hybrid form with the x-y plane's taps deferred as well (k_scatter_xy, kernel_voxel_scatter.hip):
-// their rows (64 channels) and tap records are written here and this kernel's atomics are the two 16-channel planes only.  Measured at 2^19
-// fine-level samples: this kernel 0.89 -> 0.76 ms although two thirds of its atomic requests are gone -- it is a latency chain per tile (point
-// load, tap table, GEMM, gathers, barriers), not atomic-bound any more -- plus 0.10 ms for k_scatter_xy on rays along z: 1.08 -> 1.02 ms in
-// total, but 0.89 -> 1.35 ms on oblique rays (k_scatter_xy's tap-by-tap path runs after this kernel instead of under it).  Deciding per tile
-// HERE which form a tile takes (window test in the tap-table phase) cost this kernel 0.3 ms and lost everywhere.  (The same reduction INSIDE this kernel --
-// window, M in LDS, 16 MFMAs per wavefront, between the gather phase and the sweep -- was built first and measured 1.09 -> 1.47 ms: the
-// kernel is a latency chain per tile that lives on three blocks per CU, and the extra phase with its two barriers, or the spills it forces
-// at 168 registers, costs more than the atomics it saves.)
-template <int MODE, bool MM, int CT>
+// HYBRID = false: every tap by a direct atomic.  HYBRID = true: the plane taps by direct atomics, the line taps deferred -- their rows
+// (rows_l) and tap records (ltap) are written and k_scatter_lines adds them through privatised LDS slices of the (small) line gradients:
+// a third of the kernel's atomic requests go away.
+template <bool HYBRID, bool MM, int CT>
 __global__ __launch_bounds__(256, MM ? (CT <= 96 ? 3 : 2) : 1) void k_voxel_sample_bwd(const GridParams g, const float* __restrict__ pts, long n,
                                                           const float* __restrict__ d_out, int d_stride, int d_col, GridGrads gg,
-                                                          float* __restrict__ d_pts, const BinOut bo) {
+                                                          float* __restrict__ d_pts, float* rows_l, LTap* ltap) {
     constexpr int STRD = CT + 1, FSTR = MM ? 33 : VSB_MAXF + 1;      // odd row strides (conflict-free column access)
-    constexpr bool BINNED = MODE == 1, HYBRID = MODE == 2 || MODE == 3, XYDEF = MODE == 3;
 
     __shared__ float tfr[VS_SAMPLES * 3 * 6], dpt[VS_SAMPLES * 3];
     __shared__ int tax[VS_SAMPLES * 3 * 3];
@@ -946,12 +934,6 @@ __global__ __launch_bounds__(256, MM ? (CT <= 96 ? 3 : 2) : 1) void k_voxel_samp
         macc[r] = 0.f;
         bas_reg[r] = mm_wave ? g.basis[(long)(2 * r + kb) * ctot + 32 * wv + mn] : 0.f;
     }
-#ifdef EVD_SB_STAMP      // developer build: where does a tile's time go?  shader-clock cycles per phase, summed over the block's tiles (thread 0)
-    long long sb_t[6] = {0, 0, 0, 0, 0, 0}, sb_last = __builtin_readcyclecounter();
-#define SB_STAMP(k) { const long long now_ = __builtin_readcyclecounter(); sb_t[k] += now_ - sb_last; sb_last = now_; }
-#else
-#define SB_STAMP(k)
-#endif
     for (long tile = blockIdx.x; tile * VS_SAMPLES < n; tile += gridDim.x) {
         const long s0 = tile * VS_SAMPLES;
         for (int o = tid; o < VS_SAMPLES * F; o += 256) {
@@ -985,43 +967,12 @@ __global__ __launch_bounds__(256, MM ? (CT <= 96 ? 3 : 2) : 1) void k_voxel_samp
                     const int C = sel3(i, g.n_comp[0], g.n_comp[1], g.n_comp[2]);
                     LTap lt_;
                     lt_.c0 = (int)it.il[0] / C; lt_.c1 = (int)it.il[1] / C; lt_.w0 = it.wl[0]; lt_.w1 = it.wl[1];
-                    bo.ltap[s * 3 + i] = lt_;
-                }
-            }
-            if constexpr (XYDEF) {
-                if (i == 0) {                       // the x-y plane's taps of this sample, for k_scatter_xy (dead samples: zero weights)
-                    const int Wp = g.grid[0];
-                    const int cell0 = (int)(it.ip[0] / c0n), cell3 = (int)(it.ip[3] / c0n);
-                    const int cy0 = cell0 / Wp, cx0 = cell0 - cy0 * Wp, cy1 = cell3 / Wp, cx1 = cell3 - cy1 * Wp;
-                    PTap pt_;
-                    pt_.cx0 = (unsigned short)cx0; pt_.cx1 = (unsigned short)cx1; pt_.cy0 = (unsigned short)cy0; pt_.cy1 = (unsigned short)cy1;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) pt_.w[t] = live ? it.wp[t] : 0.f;
-                    if (live) bo.ptap[s] = pt_;
-                }
-            }
-            if constexpr (BINNED) {
-                if (live) {                         // tap records + the plane's tile key of this (sample, component)
-                    const int C = sel3(i, g.n_comp[0], g.n_comp[1], g.n_comp[2]), Wp = sel3(i, g.grid[0], g.grid[0], g.grid[1]);
-                    const int cell0 = (int)(it.ip[0] / C), cell3 = (int)(it.ip[3] / C);
-                    const int cy0 = cell0 / Wp, cx0 = cell0 - cy0 * Wp, cy1 = cell3 / Wp, cx1 = cell3 - cy1 * Wp;
-                    PTap pt_;
-                    pt_.cx0 = (unsigned short)cx0; pt_.cx1 = (unsigned short)cx1; pt_.cy0 = (unsigned short)cy0; pt_.cy1 = (unsigned short)cy1;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) pt_.w[t] = it.wp[t];
-                    bo.ptap[s * 3 + i] = pt_;
-                    LTap lt_;
-                    lt_.c0 = (int)(it.il[0] / C); lt_.c1 = (int)(it.il[1] / C); lt_.w0 = it.wl[0]; lt_.w1 = it.wl[1];
-                    bo.ltap[s * 3 + i] = lt_;
-                    unsigned* kp = sel3(i, bo.keys[0], bo.keys[1], bo.keys[2]);
-                    kp[s] = (unsigned)((cy0 / SC_TS) * sel3(i, bo.tiles_x[0], bo.tiles_x[1], bo.tiles_x[2]) + cx0 / SC_TS);
-                    if (i == 0) bo.ids[s] = (unsigned)s;
+                    ltap[s * 3 + i] = lt_;
                 }
             }
         }
         if (tid < VS_SAMPLES * 3) dpt[tid] = 0.f;
         __syncthreads();
-        SB_STAMP(0);                                // d out rows, points, tap table
         if (mm) {
             if (mm_wave) {                          // D[sample][channel] = sum_f d out[sample][f] basis[f][channel]
                 f32x16 a16;
@@ -1041,7 +992,6 @@ __global__ __launch_bounds__(256, MM ? (CT <= 96 ? 3 : 2) : 1) void k_voxel_samp
             }
         }
         if (d_pts) __syncthreads();                 // the point gradient below reads d coef
-        SB_STAMP(1);                                // d coef GEMM
         if (chan_on) {                              // pv, lv: lanes over channels, two samples per sweep
             // The taps of VSB_BATCH samples are loaded before the first is used.  (As one loop with "#pragma unroll 4" hipcc left it rolled --
             // the DPP row sums and LDS atomics of the d pts part are convergent operations --: six loads, then a wait for all six, 16 times
@@ -1101,42 +1051,25 @@ __global__ __launch_bounds__(256, MM ? (CT <= 96 ? 3 : 2) : 1) void k_voxel_samp
             }
         }
         __syncthreads();
-        SB_STAMP(2);                                // gathers, pv / lv, d pts
         // (Re-measured in round 2 with the half-tile walk that keeps a ray's runs together -- successive samples of an NDC ray address
         // ~12 distinct x-y cells and ~7 x / y line cells per 32 samples --: summing the run in a register before ONE atomic is 1.5-1.9x
         // SLOWER, 2.76 vs 1.46 ms at 2^19 samples: the walk is a chain of dependent LDS reads, the sweep below is not.)
-        if constexpr (BINNED) {
+        if constexpr (HYBRID) {
             if (chan_on) {
-                for (int sl = ss; sl < VS_SAMPLES && s0 + sl < n; sl += 2) {
-                    const float dc = dco[sl * STRD + ql];
-                    bo.rows_p[(s0 + sl) * ctot + ql] = dc * lvs[sl * STRD + ql];
-                    bo.rows_l[(s0 + sl) * ctot + ql] = dc * pvs[sl * STRD + ql];
-                }
-            }
-        } else {
-            if constexpr (HYBRID) {
-                if (chan_on) {
-                    for (int sl = ss; sl < VS_SAMPLES && s0 + sl < n; sl += 2) bo.rows_l[(s0 + sl) * ctot + ql] = dco[sl * STRD + ql] * pvs[sl * STRD + ql];
-                }
-            }
-            if constexpr (XYDEF) {
-                if (ql < c0n) {
-                    for (int sl = ss; sl < VS_SAMPLES && s0 + sl < n; sl += 2) bo.rows_p[(s0 + sl) * c0n + ql] = dco[sl * STRD + ql] * lvs[sl * STRD + ql];
-                }
-            }
-            for (int sl = ss; sl < VS_SAMPLES; sl += 2) {
-#pragma unroll
-                for (int m = 0; m < MQ; ++m) {
-                    if (!q_ptr[m] || (HYBRID && !q_plane[m]) || (XYDEF && q_slot[m] < 4)) continue;
-                    const float w = tw[sl * VSB_TAPS + q_slot[m]];
-                    if (w == 0.f) continue;
-                    const int c = q_c[m];
-                    const float other = q_plane[m] ? lvs[sl * STRD + c] : pvs[sl * STRD + c];
-                    unsafeAtomicAdd(q_ptr[m] + tix[sl * VSB_TAPS + q_slot[m]], dco[sl * STRD + c] * other * w);
-                }
+                for (int sl = ss; sl < VS_SAMPLES && s0 + sl < n; sl += 2) rows_l[(s0 + sl) * ctot + ql] = dco[sl * STRD + ql] * pvs[sl * STRD + ql];
             }
         }
-        SB_STAMP(3);                                // rows + the atomic sweep (issue only: nothing waits for the adds here)
+        for (int sl = ss; sl < VS_SAMPLES; sl += 2) {
+#pragma unroll
+            for (int m = 0; m < MQ; ++m) {
+                if (!q_ptr[m] || (HYBRID && !q_plane[m])) continue;
+                const float w = tw[sl * VSB_TAPS + q_slot[m]];
+                if (w == 0.f) continue;
+                const int c = q_c[m];
+                const float other = q_plane[m] ? lvs[sl * STRD + c] : pvs[sl * STRD + c];
+                unsafeAtomicAdd(q_ptr[m] + tix[sl * VSB_TAPS + q_slot[m]], dco[sl * STRD + c] * other * w);
+            }
+        }
         if (d_pts && tid < VS_SAMPLES * 3 && s0 + tid / 3 < n) d_pts[(s0 + tid / 3) * 3 + tid % 3] = dpt[tid];
         if (gg.basis && mm) {
             if (mm_wave) {                          // D[f][channel] += sum_s d out[s][f] coef[s][channel]
@@ -1160,16 +1093,7 @@ __global__ __launch_bounds__(256, MM ? (CT <= 96 ? 3 : 2) : 1) void k_voxel_samp
             }
         }
         __syncthreads();
-        SB_STAMP(4);                                // basis_mat gradient GEMM, d pts rows, the tile's last barrier
     }
-#ifdef EVD_SB_STAMP
-    if constexpr (HYBRID) {
-        if (tid == 0) {
-            for (int k = 0; k < 5; ++k) bo.rows_l[blockIdx.x * 8 + k] = (float)sb_t[k];
-            bo.rows_l[blockIdx.x * 8 + 5] = -7.f;
-        }
-    }
-#endif
     if (gg.basis && mm) {
         if (mm_wave) {
 #pragma unroll
@@ -1193,15 +1117,15 @@ __global__ __launch_bounds__(256, MM ? (CT <= 96 ? 3 : 2) : 1) void k_voxel_samp
 //   0  tap geometry of its 48 (sample, component) pairs on 48 lanes -> its LDS slice (+ the line tap records for k_scatter_lines)
 //   1  d coef^T = basis^T . d out^T on v_mfma_f32_16x16x4_f32 (6 channel tiles x 8 steps; d out as the register-resident B operand)
 //   2  the gather exactly as the forward does it: 3 items (sample, 8 channels) per lane, 36 16-byte loads in flight, then per item
-//      pv, lv;  line rows d coef pv -> HBM (k_scatter_lines);  coef = pv lv -> HBM (k_basis_grad);  plane rows d coef lv -> LDS in place;
+//      pv, lv;  line rows d coef pv -> HBM (k_scatter_lines);  coef = pv lv -> LDS;  plane rows d coef lv -> LDS in place;
 //      the point gradient's per-item partial sums -> LDS
 //   3  the plane taps, lanes over channels (every atomic instruction covers whole 64-byte runs).  A 64-channel component (the x-y
 //      plane) is walked sample by sample with the sum kept in a REGISTER while successive samples address the same cell -- the rays of an
 //      NDC scene run along z, a tile's 16 samples touch 1-4 x-y cells -- and flushed by one atomic per (run, tap); the 16 / 32-channel
 //      components (their taps move with every sample) add tap by tap
 //   4  the point gradient: 48 lanes sum the partials of their (sample, axis)
-// The basis_mat gradient d out^T . coef is a plain GEMM over all samples and runs as its own small kernel (k_basis_grad) on the coefficient
-// rows written in phase 2; the line taps go through k_scatter_lines as in the hybrid form.
+//   5  the basis_mat gradient d out^T . coef of the tile's samples, accumulated in registers across the wavefront's tiles
+// The line taps go through k_scatter_lines as in the block-cooperative hybrid form.
 constexpr int VBW_SAMPLES = 16, VBW_WAVES = 4;
 constexpr int VBW_BSTR = 112;                   // basis_mat row stride in LDS: 16 (mod 32) words, so that the MFMA A reads (lane = channel + 16 x row step) hit 64 banks
 constexpr int VBW_CSTR = 97;                    // d coef / plane-row stride (ctot <= 96), odd: lanes over channels read conflict-free
@@ -1212,27 +1136,12 @@ struct VbwTaps {
     float fw, fn, kx, ky, kl;                   // fractional position in the plane cell; d (pixel coordinate) / d (point coordinate)
     int pad;
 };
-constexpr int VBW_LROW = 33;                    // line rows of components 1 and 2 kept in LDS ([16][33]: n_comp[1] + n_comp[2] <= 32)
 // a wavefront's slice: tap tables | d coef -> plane rows [16][CSTR] | point-gradient partial sums [16][3 quads][3] | the coefficient rows
-// pv lv [16][96] of the in-kernel basis gradient (the LINES12 form keeps its line rows [16][LROW] there and the coefficients in registers).
-// 16 KiB per wavefront: two workgroups of four per CU (2 x 78 KiB of the 160 KiB)
+// pv lv [16][96] of the in-kernel basis gradient.  16 KiB per wavefront: two workgroups of four per CU (2 x 78 KiB of the 160 KiB)
 constexpr int VBW_FSTR = 96;                    // coefficient row stride: the MFMA B reads (32 channels x 2 samples per step) cover the 64 banks
 constexpr size_t VBW_SLICE = VBW_SAMPLES * 3 * sizeof(VbwTaps) + (size_t)VBW_SAMPLES * VBW_CSTR * 4 + (size_t)VBW_SAMPLES * 9 * 4 + (size_t)VBW_SAMPLES * VBW_FSTR * 4;
-static_assert((size_t)VBW_SAMPLES * VBW_LROW * 4 <= (size_t)VBW_SAMPLES * VBW_FSTR * 4 && VBW_MAXG * 8 <= VBW_FSTR, "line rows alias the coefficient rows");
+static_assert(VBW_MAXG * 8 <= VBW_FSTR, "a sample's coefficients fit its row");
 constexpr size_t VBW_LDS = (size_t)32 * VBW_BSTR * 4 + VBW_WAVES * VBW_SLICE;
-// ISS (round 6): the last wavefront of the workgroup ISSUES the plane taps' atomics of the other three.  The VM counter retires in order, so a
-// wavefront that adds its own taps cannot start the next tile's loads before its ~40 atomic instructions have retired: with everything else
-// removed the kernel's atomics take 0.20 ms per 2^19 samples, everything but the atomics 0.2x ms, together 0.42 ms (profiles/r06_scatter_ablation.log)
-// -- the two do not overlap inside a wavefront.  A compute wavefront now leaves a tile's plane rows and tap cells in a hand-off buffer in LDS
-// ([16][96] rows | cells | weights: 7.5 KiB) and goes on; the issuer walks the buffers of its three producers (run-length merge as before) and
-// is the only wavefront whose VM counter carries atomics.  The coefficients pv lv of the basis gradient replace d coef in place (no separate
-// rows): the slice shrinks to 10 KiB, 66.5 KiB per workgroup, two workgroups per CU as before.
-constexpr int VBI_CW = VBW_WAVES - 1;                                                                // compute wavefronts of an issuer-form workgroup
-constexpr int VBI_HROW = 96;                                                                          // hand-off row stride (ctot <= 96)
-constexpr size_t VBI_SLICE = VBW_SAMPLES * 3 * sizeof(VbwTaps) + (size_t)VBW_SAMPLES * VBW_CSTR * 4 + (size_t)VBW_SAMPLES * 9 * 4 + 64;
-constexpr size_t VBI_HAND = (size_t)VBW_SAMPLES * VBI_HROW * 4 + (size_t)VBW_SAMPLES * 3 * 4 * 8;   // rows | int cell[48][4] | float weight[48][4]
-constexpr size_t VBI_LDS = (size_t)32 * VBW_BSTR * 4 + VBI_CW * (VBI_SLICE + VBI_HAND) + 64;
-static_assert(VBI_SLICE % 16 == 0 && VBI_HAND % 16 == 0 && 2 * VBI_LDS <= 160 * 1024, "two issuer-form workgroups per CU");
 static_assert(sizeof(VbwTaps) % 8 == 0 && VBW_SLICE % 16 == 0, "slice alignment");
 
 // vs_geometry + the quantities the point gradient needs; same formulas, same order (the forward's weights bit for bit)
@@ -1274,14 +1183,11 @@ __device__ __forceinline__ void vbw_geometry(const GridParams& g, const float (&
     tp.pad = 0;
 }
 
-// LINES12: the line taps of components 1 and 2 (the x / y lines of an NDC scene: one cell for a whole run of samples) are summed along
-// runs and added here, like the plane taps; only component 0's line (the z line, a new cell every sample) leaves as rows for k_scatter_lines
-// BAS (round 4): the basis_mat gradient d out^T . coef INSIDE this kernel.  The workgroups are persistent (a wavefront walks tiles
-// blockIdx.x, blockIdx.x + gridDim.x, ...: basis_mat is staged in LDS once per workgroup instead of once per 64 samples), a wavefront keeps
-// the 8 coefficients of each of its three gather items in registers over the plane-tap phase, puts them where the plane rows were
-// (its slice's d coef array is free by then) and adds its 16 samples' [F x ctot] product to 3 x 16 accumulator registers on
+// The basis_mat gradient d out^T . coef INSIDE this kernel (round 4).  The workgroups are persistent (a wavefront walks tiles
+// blockIdx.x, blockIdx.x + gridDim.x, ...: basis_mat is staged in LDS once per workgroup instead of once per 64 samples), a wavefront leaves
+// the coefficients pv lv of its gather items in its slice (cfl) and adds its 16 samples' [F x ctot] product to 3 x 16 accumulator registers on
 // v_mfma_f32_32x32x2_f32 (d out rows as the A operand straight from L2); one fold through LDS + one atomic flush per workgroup at the end.
-// Gone: the coefficient rows [n, ctot] (201 MB written and read back per 2^19 samples) and the k_basis_grad launch.
+// Round 3 wrote coefficient rows [n, ctot] to HBM for a separate GEMM kernel: 201 MB written and read back per 2^19 samples, and a launch.
 // The plane-tap walk (phase 3 of k_voxel_sample_bwd_w): a lane owns a (tap, channel), walks the tile's 16 samples with the sum of a RUN of
 // samples on one cell in a register and adds it once per run.  Round 6 -- the kernel is bound by the number of instructions its two wavefronts per
 // SIMD issue (~5.5 k per tile and wavefront, 4 cycles each; a build WITHOUT the atomics showed the walk alone at 33.6 k of a tile's 51.8 k
@@ -1304,11 +1210,7 @@ __device__ __forceinline__ void vbw_walk_pass(float* __restrict__ gp, int c, boo
         acc += vbw_mul_legacy(w[sm], r[sm]);
         const bool flush = sm == VBW_SAMPLES - 1 || cell[sm + 1 < VBW_SAMPLES ? sm + 1 : sm] != cell[sm];
         if (flush) {
-#ifdef EVD_VBW_NO_ATOMICS     // developer ablation: everything but the plane taps' atomics (the sum is kept alive)
-            if (act && acc == 1.2345e38f) gp[cell[sm] + c] = acc;
-#else
             if (act && acc != 0.f) unsafeAtomicAdd(gp + cell[sm] + c, acc);
-#endif
             acc = 0.f;
         }
     }
@@ -1338,11 +1240,7 @@ __device__ __forceinline__ void vbw_walk_plane64(float* __restrict__ gp, int c, 
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int cell = fc(sm, t);
-#ifdef EVD_VBW_NO_ATOMICS
-                if (acc[t] == 1.2345e38f) gp[cell + c] = acc[t];
-#else
                 if (acc[t] != 0.f) unsafeAtomicAdd(gp + cell + c, acc[t]);
-#endif
                 acc[t] = 0.f;
             }
         }
@@ -1352,32 +1250,20 @@ __device__ __forceinline__ void vbw_walk_plane64(float* __restrict__ gp, int c, 
 // HALF (round 6): phase 2 re-gathers the grid values from the FLOAT16 copies (GridParams::plane_h / line_h) -- the values the forward of the
 // half-precision arithmetic modes interpolated (evd_voxel_api.hip grids_half_for), so the products d coef x value are the gradient of the function
 // that forward computed; half the gather's loads and bytes, weight x value + sum as one v_fma_mix_f32 on the float16 value (as k_voxel_sample_m).
-template <bool DPTS, bool LINES12, bool BAS, bool ISS = false, bool HALF = false>
+template <bool DPTS, bool HALF>
 __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const GridParams g, const float* __restrict__ pts, long n,
                                                                           const float* __restrict__ d_out, int d_stride, int d_col, GridGrads gg,
                                                                           float* __restrict__ d_pts, float* __restrict__ rows_l, LTap* __restrict__ ltap,
-                                                                          float* __restrict__ coef_out, unsigned* __restrict__ lmax) {
+                                                                          unsigned* __restrict__ lmax) {
     extern __shared__ __attribute__((aligned(16))) char vbw_smem[];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int c0n = g.n_comp[0], c1n = g.n_comp[1], c2n = g.n_comp[2], ctot = c0n + c1n + c2n, F = g.app_dim;
-    static_assert(!ISS || (BAS && !LINES12), "the issuer form is the persistent kernel with the basis gradient inside, lines through k_scatter_lines");
-    constexpr int NCW = ISS ? VBI_CW : VBW_WAVES;                                    // wavefronts that own tiles
     float* bs = reinterpret_cast<float*>(vbw_smem);                                  // basis_mat [32][VBW_BSTR], rows >= F are zero
-    char* slice = vbw_smem + (size_t)32 * VBW_BSTR * 4 + (size_t)(wv < NCW ? wv : 0) * (ISS ? VBI_SLICE : VBW_SLICE);
+    char* slice = vbw_smem + (size_t)32 * VBW_BSTR * 4 + (size_t)wv * VBW_SLICE;
     VbwTaps* taps = reinterpret_cast<VbwTaps*>(slice);
     float* dco = reinterpret_cast<float*>(slice + VBW_SAMPLES * 3 * sizeof(VbwTaps));   // d coef [16][VBW_CSTR], later the plane rows d coef lv
     float* dpart = dco + VBW_SAMPLES * VBW_CSTR;                                     // [16][3 quads of 8-channel groups][3 axes] d pts partial sums
-    float* cfl = ISS ? dco : dpart + VBW_SAMPLES * 9;                                // [16][VBW_FSTR] coefficients pv lv (BAS); ISS: in place of d coef
-    float* lrow = cfl;                                                               // [16][VBW_LROW] line rows d coef pv of components 1, 2 (LINES12)
-    constexpr bool CF_LDS = BAS && !LINES12;
-    constexpr int CFSTR = ISS ? VBW_CSTR : VBW_FSTR;                                 // row stride of the coefficient rows
-    // ISS: hand-off buffers [NCW] behind the slices, then the flags (0 free, 1 full, 2 producer finished)
-    char* hand0 = vbw_smem + (size_t)32 * VBW_BSTR * 4 + (size_t)VBI_CW * VBI_SLICE;
-    float* hrow = reinterpret_cast<float*>(hand0 + (size_t)(wv < NCW ? wv : 0) * VBI_HAND);
-    int* hcell = reinterpret_cast<int*>(hrow + VBW_SAMPLES * VBI_HROW);
-    float* hwgt = reinterpret_cast<float*>(hcell + VBW_SAMPLES * 3 * 4);
-    volatile int* flags = reinterpret_cast<volatile int*>(hand0 + (size_t)VBI_CW * VBI_HAND);
-    if (ISS && threadIdx.x < 16) flags[threadIdx.x] = 0;
+    float* cfl = dpart + VBW_SAMPLES * 9;                                            // [16][VBW_FSTR] coefficients pv lv
     const int ng = ctot / 8;
     // basis_mat -> LDS (the block's only shared state) as the A operands of phase 1 (round 6): d coef^T = basis^T . d out^T on
     // v_mfma_f32_16x16x32_f16 in the split form (hi = f16(x), lo = f16(x - hi): A_hi B_hi + A_hi B_lo + A_lo B_hi, 2^-21 per product) --
@@ -1416,12 +1302,10 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
     auto wave_sync = []() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); };
     constexpr int NCT = 3;                        // 32-channel tiles of the basis gradient (ctot <= 96)
     f32x16 bacc[NCT];
-    if (BAS) {
 #pragma unroll
-        for (int c = 0; c < NCT; ++c)
+    for (int c = 0; c < NCT; ++c)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) bacc[c][r] = 0.f;
-    }
+        for (int r = 0; r < 16; ++r) bacc[c][r] = 0.f;
 #ifdef EVD_VBW_STAMP    // developer build (tools/dev/stamp_scatter_w.py): shader-clock cycles of this wavefront's phases, summed over its tiles
     long long tph[7] = {0, 0, 0, 0, 0, 0, 0}, tq0, tq1;
 #define EVD_VBW_T0() tq0 = __builtin_readcyclecounter()
@@ -1432,53 +1316,7 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
 #endif
     float rmaxv = 0.f;                            // max |line row value| this lane wrote (k_scatter_lines' fixed-point scale: saves it a pass over the rows)
     const long wtiles = (n + VBW_SAMPLES - 1) / VBW_SAMPLES;
-    auto lds_done = []() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
-    if (ISS && wv >= NCW) {
-        // the issuer: polls its producers' flags; a full buffer's taps are walked exactly like phase 3 below (lanes = (tap, channel), the sum
-        // of a run of samples on one cell in a register, one atomic per run), then the buffer is handed back.  No load of this wavefront ever
-        // waits behind its atomics: it has none but LDS reads.
-        int fin = 0;
-        while (fin != (1 << NCW) - 1) {
-            bool idle = true;
-#pragma unroll 1
-            for (int w = 0; w < NCW; ++w) {
-                if (fin >> w & 1) continue;
-                const int f = __builtin_amdgcn_readfirstlane(flags[w]);
-                if (f == 2) { fin |= 1 << w; continue; }
-                if (f != 1) continue;
-                asm volatile("" ::: "memory");      // (no read of the buffer may be moved in front of the flag's)
-                idle = false;
-                const float* hr = reinterpret_cast<const float*>(hand0 + (size_t)w * VBI_HAND);
-                const int* hc = reinterpret_cast<const int*>(hr + VBW_SAMPLES * VBI_HROW);
-                const float* hw = reinterpret_cast<const float*>(hc + VBW_SAMPLES * 3 * 4);
-                int coff = 0;
-#pragma unroll 1
-                for (int i = 0; i < 3; ++i) {
-                    const int C = sel3(i, c0n, c1n, c2n);
-                    float* gp = sel3(i, gg.plane[0], gg.plane[1], gg.plane[2]);
-                    if (gp) {
-                        const int tpp = 64 / C < 4 ? 64 / C : 4, j = lane / C, c = lane % C;
-                        if (C == 64) {
-                            vbw_walk_plane64(gp, lane, [&](int sm) { return *reinterpret_cast<const f32x4*>(hw + (sm * 3 + i) * 4); },
-                                             [&](int sm, int t) { return hc[(sm * 3 + i) * 4 + t]; }, [&](int sm) { return hr[sm * VBI_HROW + coff + lane]; });
-                        } else {
-#pragma unroll 1
-                            for (int t0 = 0; t0 < 4; t0 += tpp) {
-                                const int t = t0 + (j < tpp ? j : 0);
-                                vbw_walk_pass(gp, c, j < tpp, [&](int sm) { return hw[(sm * 3 + i) * 4 + t]; }, [&](int sm) { return hc[(sm * 3 + i) * 4 + t]; },
-                                              [&](int sm) { return hr[sm * VBI_HROW + coff + c]; });
-                            }
-                        }
-                    }
-                    coff += C;
-                }
-                lds_done();                           // every read of the buffer has returned
-                if (lane == 0) flags[w] = 0;
-            }
-            if (idle) __builtin_amdgcn_s_sleep(8);
-        }
-    }
-    for (long wt = (long)blockIdx.x * NCW + wv; wv < NCW && wt < wtiles; wt += (long)gridDim.x * NCW) {
+    for (long wt = (long)blockIdx.x * VBW_WAVES + wv; wt < wtiles; wt += (long)gridDim.x * VBW_WAVES) {
     const long s0 = wt * VBW_SAMPLES;
     EVD_VBW_T0();
     // d out as the MFMA B operand: lane (col = sample, kh) holds d out[sample][4 step + kh]
@@ -1498,7 +1336,7 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
         VbwTaps tp;
         vbw_geometry(g, pt, i, live, tp);
         taps[lane] = tp;
-        if (live && ltap && !(LINES12 && i > 0)) {
+        if (live && ltap) {
             const int C = sel3(i, c0n, c1n, c2n);
             LTap lt_;
             lt_.c0 = tp.il[0] / C; lt_.c1 = tp.il[1] / C; lt_.w0 = tp.wl[0]; lt_.w1 = tp.wl[1];
@@ -1507,12 +1345,6 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
     }
     wave_sync();                                  // the tap tables are the wavefront's own
     EVD_VBW_T(0);
-#ifdef EVD_VBW_ATOMICS_ONLY      // developer ablation (tools/dev/scatter_atomics_only.sh): geometry + the plane-tap phase on constant rows -- what the atomics of the REAL address stream cost alone
-    for (int o = lane; o < VBW_SAMPLES * VBW_CSTR; o += 64) dco[o] = 1.f;
-    f32x4 cfk[1][2];
-    constexpr int UNR = 1, TRIPS = 1;
-    const int items = 0;
-#else
     // phase 1: D[channel 16 ct + 4 kh + r][sample col] = sum_f basis[f][channel] d out[sample][f]
     {
         float m = 0.f, binv;
@@ -1547,8 +1379,7 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
     const int items = VBW_SAMPLES * ng;
     // items in flight per lane and trip: three (144 registers of raw taps) -- two where the wavefront also carries the basis accumulators
     // (48 registers) AND the point gradient's operands: at three that form spills 27 registers into the tile loop
-    constexpr int UNR = (BAS && DPTS && !HALF) ? 2 : 3, TRIPS = 3 / UNR + (3 % UNR ? 1 : 0);      // (HALF: 24 instead of 48 registers of raw taps per item)
-    f32x4 cfk[TRIPS * UNR][2];                    // BAS: the coefficients of this lane's items (ng <= 12: items <= 3 x 64)
+    constexpr int UNR = (DPTS && !HALF) ? 2 : 3, TRIPS = 3 / UNR + (3 % UNR ? 1 : 0);      // (HALF: 24 instead of 48 registers of raw taps per item)
 #pragma unroll
     for (int trip = 0; trip < TRIPS; ++trip) {
         const int base = lane + trip * UNR * 64;
@@ -1586,9 +1417,6 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
 #pragma unroll
                     for (int v = 0; v < 2; ++v) rawl[q][k][v] = *reinterpret_cast<const f32x4*>(li + tp.il[k] + 4 * v);
             }
-        }
-        if (ISS && trip == 0) {                   // (the gather's loads are in flight) the issuer is done with the previous tile's buffer
-            while (__builtin_amdgcn_readfirstlane(flags[wv]) != 0) __builtin_amdgcn_s_sleep(2);
         }
 #pragma unroll
         for (int q = 0; q < UNR; ++q) {
@@ -1651,12 +1479,7 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
                     cf[k] = pv[k] * lv[k];
                     rp[k] = dc[k] * lv[k];
                 }
-                if (LINES12 && comp[q] > 0) {
-                    if (on[q]) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) lrow[sl[q] * VBW_LROW + cb - c0n + 4 * v + k] = rl[k];
-                    }
-                } else if (live && rows_l) {
+                if (live && rows_l) {
                     *reinterpret_cast<f32x4*>(rows_l + (s0 + sl[q]) * ctot + cb + 4 * v) = rl;
                     if (lmax) {
 #pragma unroll
@@ -1666,26 +1489,11 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
                         }
                     }
                 }
-                if (ISS) {                        // the plane rows into the hand-off buffer, the coefficients in place of d coef
-                    if (on[q]) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            hrow[sl[q] * VBI_HROW + cb + 4 * v + k] = rp[k];
-                            drow[4 * v + k] = cf[k];
-                        }
-                    }
-                } else {
-                if (CF_LDS) {
-                    if (on[q]) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) cfl[sl[q] * VBW_FSTR + cb + 4 * v + k] = cf[k];
-                    }
-                } else if (BAS) cfk[trip * UNR + q][v] = cf;
-                else if (live && coef_out) *reinterpret_cast<f32x4*>(coef_out + (s0 + sl[q]) * ctot + cb + 4 * v) = cf;
                 if (on[q]) {
 #pragma unroll
+                    for (int k = 0; k < 4; ++k) cfl[sl[q] * VBW_FSTR + cb + 4 * v + k] = cf[k];
+#pragma unroll
                     for (int k = 0; k < 4; ++k) drow[4 * v + k] = rp[k];
-                }
                 }
                 if (DPTS) {
                     // d feature / d point through the interpolation weights (the ATen grid_sample backward: taps outside the grid contribute
@@ -1718,19 +1526,13 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
             }
         }
     }
-#endif
     wave_sync();
     EVD_VBW_T(2);
     // the A operand of the basis gradient's MFMAs (d out[sample 2 u + kb][f = lane & 31]) is fetched HERE, in front of the plane taps'
     // atomics: the VM counter retires in order, a load issued behind them waits for every one of them (stamps: the 24 MFMAs of phase 5 took
     // 14 k cycles with their eight loads issued one by one behind the atomics, a fifth of the tile)
     float bav[VBW_SAMPLES / 2];
-#ifdef EVD_VBW_ATOMICS_ONLY
-    constexpr bool BASX = false;
-#else
-    constexpr bool BASX = BAS;
-#endif
-    if (BASX) {
+    {
         const int mn = lane & 31, kb = lane >> 5;
 #pragma unroll
         for (int u = 0; u < VBW_SAMPLES / 2; ++u) {
@@ -1743,20 +1545,10 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
 #pragma unroll
         for (int u = 0; u < VBW_SAMPLES / 2; ++u) asm volatile("" : "+v"(bav[u]));
     }
-    if (ISS) {                                    // hand the tile's plane taps to the issuer: cells and weights next to the rows phase 2 wrote
-        if (lane < VBW_SAMPLES * 3) {
-            const VbwTaps& tp = taps[lane];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) { hcell[lane * 4 + t] = tp.ip[t]; hwgt[lane * 4 + t] = tp.wp[t]; }
-        }
-        lds_done();
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) flags[wv] = 1;
-    }
     // phase 3: plane taps.  dco now holds the plane rows d coef lv.
     int coff = 0;
 #pragma unroll 1
-    for (int i = 0; i < 3 && !ISS; ++i) {
+    for (int i = 0; i < 3; ++i) {
         const int C = sel3(i, c0n, c1n, c2n);
         float* gp = sel3(i, gg.plane[0], gg.plane[1], gg.plane[2]);
         if (gp) {
@@ -1780,29 +1572,6 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
         }
         coff += C;
     }
-    if (LINES12) {
-        // line taps of components 1 and 2: lanes = (tap, channel of comp 1 | comp 2), 2 x (n_comp[1] + n_comp[2]) <= 64 lanes, one walk
-        const int c12 = c1n + c2n, tq = lane / c12, cc = lane % c12;
-        if (lane < 2 * c12) {
-            const int i = cc < c1n ? 1 : 2, c = cc < c1n ? cc : cc - c1n;
-            float* gl = i == 1 ? gg.line[1] : gg.line[2];
-            float acc = 0.f;
-            bool any = false;
-#pragma unroll 4
-            for (int s = 0; s < VBW_SAMPLES; ++s) {
-                const VbwTaps& tp = taps[s * 3 + i];
-                const float w = tp.wl[tq];
-                const int cell = tp.il[tq];
-                if (w != 0.f) { acc += w * lrow[s * VBW_LROW + cc]; any = true; }
-                const bool flush = s == VBW_SAMPLES - 1 || taps[(s + 1) * 3 + i].il[tq] != cell;
-                if (flush) {
-                    if (any && gl) unsafeAtomicAdd(gl + cell + c, acc);
-                    acc = 0.f;
-                    any = false;
-                }
-            }
-        }
-    }
     EVD_VBW_T(3);
     // phase 4: the point gradient of (sample, axis): the three quads' partial sums
     if (DPTS && lane < VBW_SAMPLES * 3) {
@@ -1812,42 +1581,21 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
         if (s0 + sl < n) d_pts[(s0 + sl) * 3 + a] = sum;
     }
     EVD_VBW_T(4);
-    if (BASX) {
-        // phase 5: d basis_mat += d out^T . coef over the tile's 16 samples (coefficient rows: written to the slice by phase 2; the
-        // LINES12 form kept them in registers and puts them where the consumed plane rows were)
-        const float* crows = CF_LDS ? cfl : dco;
-        if (!CF_LDS) {
-            wave_sync();
-#pragma unroll
-            for (int q = 0; q < TRIPS * UNR; ++q) {
-                const int t = lane + q * 64;
-                if (t < items) {
-                    float* crow = dco + (t / ng) * VBW_CSTR + (t % ng) * 8;
-#pragma unroll
-                    for (int v = 0; v < 2; ++v)
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) crow[4 * v + k] = cfk[q][v][k];
-                }
-            }
-            wave_sync();
-        }
+    {
+        // phase 5: d basis_mat += d out^T . coef over the tile's 16 samples (coefficient rows: written to the slice by phase 2)
         const int mn = lane & 31, kb = lane >> 5;
 #pragma unroll
         for (int u = 0; u < VBW_SAMPLES / 2; ++u) {
             const float av = bav[u];
 #pragma unroll
             for (int c = 0; c < NCT; ++c) {
-                const float bv = 32 * c + mn < ctot ? crows[(2 * u + kb) * (CF_LDS ? CFSTR : VBW_CSTR) + 32 * c + mn] : 0.f;
+                const float bv = 32 * c + mn < ctot ? cfl[(2 * u + kb) * VBW_FSTR + 32 * c + mn] : 0.f;
                 bacc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, bacc[c], 0, 0, 0);
             }
         }
     }
     wave_sync();                                  // the slice is rewritten by the next tile
     EVD_VBW_T(5);
-    }
-    if (ISS && wv < NCW) {                        // the last tile has been taken; tell the issuer this producer is finished
-        while (__builtin_amdgcn_readfirstlane(flags[wv]) != 0) __builtin_amdgcn_s_sleep(2);
-        if (lane == 0) flags[wv] = 2;
     }
 #ifdef EVD_VBW_STAMP
     if (lane == 0 && rows_l) {
@@ -1862,12 +1610,12 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
         const unsigned mb = __float_as_uint(rmaxv);                    // (non-negative floats order like their bit patterns; +inf above all)
         if (lane == 0 && mb > *reinterpret_cast<volatile unsigned*>(lmax)) atomicMax(lmax, mb);
     }
-    if (BAS && gg.basis) {
+    if (gg.basis) {
         // the block's four wavefronts fold their sums through LDS (the basis_mat image is no longer needed), then ONE atomic flush per block
         const int mn = lane & 31, kb = lane >> 5;
         __syncthreads();
         for (int w = 0; w < VBW_WAVES; ++w) {
-            if (wv == w && w < NCW) {
+            if (wv == w) {
 #pragma unroll
                 for (int c = 0; c < NCT; ++c)
 #pragma unroll
@@ -1883,58 +1631,6 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
             const float v = bs[f * VBW_BSTR + ch];
             if (v != 0.f) unsafeAtomicAdd(gg.basis + o, v);
         }
-    }
-}
-
-// d basis_mat[f][c] += sum_s d out[s][f] coef[s][c] over all samples: exact-float32 MFMA (32 x 32 x 2 per sample pair and 32-channel
-// tile), every wavefront a strided share of the sample pairs, one atomic flush per wavefront.  HBM-bound: it reads d out and the
-// coefficient rows once (512 B per sample).
-template <int NCT>
-__global__ __launch_bounds__(256) void k_basis_grad(const float* __restrict__ d_out, int d_stride, int d_col, const float* __restrict__ coef, long n, int ctot, int F,
-                                                    float* __restrict__ d_basis) {
-    const int lane = threadIdx.x & 63, mn = lane & 31, kb = lane >> 5;
-    const long gw = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (long)gridDim.x * 4, pairs = (n + 1) / 2;
-    f32x16 acc[NCT];
-#pragma unroll
-    for (int c = 0; c < NCT; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-    constexpr int UN = 4;
-    for (long p0 = gw * UN; p0 < pairs; p0 += nw * UN) {
-        float a[UN], b[UN][NCT];
-#pragma unroll
-        for (int u = 0; u < UN; ++u) {
-            const long s = 2 * (p0 + u) + kb;
-            const bool ok = p0 + u < pairs && s < n;
-            a[u] = (ok && mn < F) ? d_out[s * (long)d_stride + d_col + mn] : 0.f;
-#pragma unroll
-            for (int c = 0; c < NCT; ++c) b[u][c] = (ok && 32 * c + mn < ctot) ? coef[s * ctot + 32 * c + mn] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < UN; ++u)
-#pragma unroll
-            for (int c = 0; c < NCT; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u][c], acc[c], 0, 0, 0);
-    }
-    // the block's four wavefronts fold their sums in LDS (plain stores + one barrier each, no LDS atomics), then ONE atomic flush per block:
-    // the grid fills every wavefront slot of the chip (the loads are 4-byte lane loads: bandwidth comes from the number of wavefronts)
-    __shared__ float fold[32 * 97];
-    const int wv = threadIdx.x >> 6;
-    for (int w = 0; w < 4; ++w) {
-        if (wv == w) {
-#pragma unroll
-            for (int c = 0; c < NCT; ++c)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int f = (r & 3) + 8 * (r >> 2) + 4 * kb, ch = 32 * c + mn;
-                    fold[f * 97 + ch] = w == 0 ? acc[c][r] : fold[f * 97 + ch] + acc[c][r];
-                }
-        }
-        __syncthreads();
-    }
-    for (int o = threadIdx.x; o < F * ctot; o += 256) {
-        const int f = o / ctot, ch = o % ctot;
-        const float v = fold[f * 97 + ch];
-        if (v != 0.f) unsafeAtomicAdd(d_basis + o, v);
     }
 }
 
@@ -2237,64 +1933,42 @@ int launch_voxel_sample(const GridParams& g, bool half_grids, const float* pts, 
 // Persistent blocks of the scatter's main kernel.  The 96-channel MFMA instantiation keeps three blocks per CU: exactly that many blocks
 // (768 on the 256 CUs of an MI355X), each walking its share of the tiles, measured best -- 0.98 / 0.79 ms per 2^19 samples (rays along z /
 // oblique) against 1.02 / 0.82 with 3072 blocks, 1.14 / 0.94 with 1024 (a ragged last round) and 1.07 / 0.97 with 512: every block pays
-// for its basis_mat column and flushes its basis_mat gradient (192 atomic requests) once.  EVD_SCATTER_BLOCKS overrides.
+// for its basis_mat column and flushes its basis_mat gradient (192 atomic requests) once.
 static long scatter_blocks_cap(bool three_per_cu) {
-    const char* e = getenv("EVD_SCATTER_BLOCKS");
-    const long v = e ? atol(e) : 0;
-    if (v > 0) return v;
     if (!three_per_cu) return 3072;
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 3072;
     return 3L * cus;
 }
 
+// HYBRID: plane taps by direct atomics here, line taps left as rows + tap records (rows_l, ltap) for k_scatter_lines; else every tap here
+template <bool HYBRID>
+static int launch_sample_bwd_block(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
+                                   float* d_pts, float* rows_l, LTap* ltap, hipStream_t st) {
+    if (g.app_dim > VSB_MAXF) return fail(EVD_E_INVALID, "evd_voxel_sample_bwd: app_dim %d > %d", g.app_dim, VSB_MAXF);
+    const long tiles = cdiv(n, VS_SAMPLES);
+    const bool mm = g.app_dim == 32 && (g.n_comp[0] + g.n_comp[1] + g.n_comp[2]) % 32 == 0;
+    const int ct = g.n_comp[0] + g.n_comp[1] + g.n_comp[2];
+    const long cap = scatter_blocks_cap(mm && ct <= 96);
+    const unsigned blocks = (unsigned)(tiles < cap ? tiles : cap);
+    if (mm && ct <= 96) k_voxel_sample_bwd<HYBRID, true, 96><<<blocks, 256, 0, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, rows_l, ltap);
+    else if (mm) k_voxel_sample_bwd<HYBRID, true, VS_MAXC><<<blocks, 256, 0, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, rows_l, ltap);
+    else k_voxel_sample_bwd<HYBRID, false, VS_MAXC><<<blocks, 256, 0, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, rows_l, ltap);
+    EVD_LAUNCH_CHECK();
+    return EVD_OK;
+}
+
 int launch_voxel_sample_bwd(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
                             float* d_pts, hipStream_t st) {
-    if (g.app_dim > VSB_MAXF) return fail(EVD_E_INVALID, "evd_voxel_sample_bwd: app_dim %d > %d", g.app_dim, VSB_MAXF);
-    const long tiles = cdiv(n, VS_SAMPLES);
-    const bool mm = g.app_dim == 32 && (g.n_comp[0] + g.n_comp[1] + g.n_comp[2]) % 32 == 0;
-    const int ct = g.n_comp[0] + g.n_comp[1] + g.n_comp[2];
-    const long cap = scatter_blocks_cap(mm && ct <= 96);
-    const unsigned blocks = (unsigned)(tiles < cap ? tiles : cap);
-    if (mm && ct <= 96) k_voxel_sample_bwd<0, true, 96><<<blocks, 256, 0, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, BinOut{});
-    else if (mm) k_voxel_sample_bwd<0, true, VS_MAXC><<<blocks, 256, 0, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, BinOut{});
-    else k_voxel_sample_bwd<0, false, VS_MAXC><<<blocks, 256, 0, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, BinOut{});
-    EVD_LAUNCH_CHECK();
-    return EVD_OK;
+    return launch_sample_bwd_block<false>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, nullptr, nullptr, st);
 }
 
-int launch_voxel_sample_bwd_pass1(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
-                                  float* d_pts, const BinOut& bo, hipStream_t st) {
-    if (g.app_dim > VSB_MAXF) return fail(EVD_E_INVALID, "evd_voxel_sample_bwd: app_dim %d > %d", g.app_dim, VSB_MAXF);
-    const long tiles = cdiv(n, VS_SAMPLES);
-    const bool mm = g.app_dim == 32 && (g.n_comp[0] + g.n_comp[1] + g.n_comp[2]) % 32 == 0;
-    const int ct = g.n_comp[0] + g.n_comp[1] + g.n_comp[2];
-    const unsigned blocks = (unsigned)(tiles < 3072 ? tiles : 3072);
-    if (mm && ct <= 96) k_voxel_sample_bwd<1, true, 96><<<blocks, 256, 0, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, bo);
-    else if (mm) k_voxel_sample_bwd<1, true, VS_MAXC><<<blocks, 256, 0, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, bo);
-    else k_voxel_sample_bwd<1, false, VS_MAXC><<<blocks, 256, 0, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, bo);
-    EVD_LAUNCH_CHECK();
-    return EVD_OK;
-}
-
-// hybrid: plane taps by direct atomics here, line taps left as rows + tap records (bo.rows_l, bo.ltap) for k_scatter_lines
 int launch_voxel_sample_bwd_planes(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
-                                   float* d_pts, const BinOut& bo, hipStream_t st) {
-    if (g.app_dim > VSB_MAXF) return fail(EVD_E_INVALID, "evd_voxel_sample_bwd: app_dim %d > %d", g.app_dim, VSB_MAXF);
-    const long tiles = cdiv(n, VS_SAMPLES);
-    const bool mm = g.app_dim == 32 && (g.n_comp[0] + g.n_comp[1] + g.n_comp[2]) % 32 == 0;
-    const int ct = g.n_comp[0] + g.n_comp[1] + g.n_comp[2];
-    const long cap = scatter_blocks_cap(mm && ct <= 96);
-    const unsigned blocks = (unsigned)(tiles < cap ? tiles : cap);
-    if (mm && ct <= 96 && bo.rows_p) k_voxel_sample_bwd<3, true, 96><<<blocks, 256, 0, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, bo);
-    else if (mm && ct <= 96) k_voxel_sample_bwd<2, true, 96><<<blocks, 256, 0, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, bo);
-    else if (mm) k_voxel_sample_bwd<2, true, VS_MAXC><<<blocks, 256, 0, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, bo);
-    else k_voxel_sample_bwd<2, false, VS_MAXC><<<blocks, 256, 0, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, bo);
-    EVD_LAUNCH_CHECK();
-    return EVD_OK;
+                                   float* d_pts, float* rows_l, LTap* ltap, hipStream_t st) {
+    return launch_sample_bwd_block<true>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, rows_l, ltap, st);
 }
 
-// the wavefront-autonomous form (k_voxel_sample_bwd_w + k_basis_grad); the caller runs k_scatter_lines on rows_l / ltap afterwards
+// the wavefront-autonomous form (k_voxel_sample_bwd_w); the caller runs k_scatter_lines on rows_l / ltap afterwards
 bool voxel_sample_bwd_w_ok(const GridParams& g) {
     const int ct = g.n_comp[0] + g.n_comp[1] + g.n_comp[2];
     auto okc = [](int c) { return c == 8 || c == 16 || c == 32 || c == 64; };
@@ -2304,71 +1978,27 @@ bool voxel_sample_bwd_w_ok(const GridParams& g) {
     return g.app_dim >= 4 && g.app_dim <= 32 && g.app_dim % 4 == 0 && ct % 32 == 0 && ct <= 96 && okc(g.n_comp[0]) && okc(g.n_comp[1]) && okc(g.n_comp[2]) &&
            pm2 * 64 < (1L << 31) && g.app_act == EVD_ACT_NONE;
 }
-// OPT-IN (EVD_SCATTER_LINES_INKERNEL=1): the line taps of components 1 and 2 added inside the kernel (run-length walk) when their channels
-// fit one pass of 64 lanes.  Measured: 0.725 -> 0.691 ms per 2^19 samples on the micro-benchmark's rays, but the whole blurfactory iteration
-// 19.7 -> 20.3 ms: every ray of a batch adds to the same few hundred x / y line cells, and same-address float atomics serialise at the
-// memory side (the LDS slices of k_scatter_lines exist for exactly that).
-bool voxel_sample_bwd_w_lines12(const GridParams& g) {
-    static const bool on = env_flag("EVD_SCATTER_LINES_INKERNEL");
-    return on && 2 * (g.n_comp[1] + g.n_comp[2]) <= 64 && g.n_comp[1] + g.n_comp[2] <= 32;
-}
 int launch_voxel_sample_bwd_w(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
-                              float* d_pts, float* rows_l, LTap* ltap, float* coef, hipStream_t st, unsigned* lmax, bool half_grids) {
-    // EVD_SCATTER_BASIS=separate (developer switch): round 3's form -- coefficient rows to HBM + the k_basis_grad launch
-    static const bool bas_sep = [] { const char* e = getenv("EVD_SCATTER_BASIS"); return e && !strcmp(e, "separate"); }();
-    const bool bas = gg.basis && !bas_sep;
+                              float* d_pts, float* rows_l, LTap* ltap, unsigned* lmax, bool half_grids, hipStream_t st) {
     int cus = 256;
     { int dev = 0, v = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
-    const bool l12 = voxel_sample_bwd_w_lines12(g);
-    // EVD_SCATTER_ISSUER=1 (developer switch, OFF by default): one wavefront of four issues the others' atomics.  Measured with the walk of
-    // round 6 (profiles/r06_scatter_issuer_ab.log): 0.444 against 0.433 ms per 2^19 samples -- the kernel is bound by the instructions it
-    // issues and, since the walk was cut, by the rate at which atomics retire (17 of 20.5 G requests/s), not by a wavefront's loads waiting
-    // behind its own atomics; a quarter fewer compute wavefronts cost what the decoupling buys.
-    static const bool iss_on = [] { const char* e = getenv("EVD_SCATTER_ISSUER"); return e && e[0] == '1'; }();
-    const bool iss = bas && !l12 && iss_on;
-    const long tiles = cdiv(n, (long)VBW_SAMPLES * (iss ? VBI_CW : VBW_WAVES));
-    // persistent workgroups with the basis gradient in registers: two per CU (the LDS slices allow no more); else one tile per wavefront
-    const unsigned blocks = (unsigned)(bas ? (tiles < 2L * cus ? tiles : 2L * cus) : tiles);
-    float* coef_w = (gg.basis && !bas) ? coef : nullptr;
-#define EVD_VBW(DP, L12, BAS) { EVD_SET_MAX_LDS((&k_voxel_sample_bwd_w<DP, L12, BAS>), VBW_LDS); \
-        k_voxel_sample_bwd_w<DP, L12, BAS><<<blocks, 64 * VBW_WAVES, VBW_LDS, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, rows_l, ltap, coef_w, lmax); }
-#define EVD_VBI(DP) { EVD_SET_MAX_LDS((&k_voxel_sample_bwd_w<DP, false, true, true>), VBI_LDS); \
-        k_voxel_sample_bwd_w<DP, false, true, true><<<blocks, 64 * VBW_WAVES, VBI_LDS, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, rows_l, ltap, coef_w, lmax); }
-#define EVD_VBH(DP) { EVD_SET_MAX_LDS((&k_voxel_sample_bwd_w<DP, false, true, false, true>), VBW_LDS); \
-        k_voxel_sample_bwd_w<DP, false, true, false, true><<<blocks, 64 * VBW_WAVES, VBW_LDS, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, rows_l, ltap, coef_w, lmax); }
-    // the float16 copies of the grids for the re-gather (the default form of the kernel only): EVD_SCATTER_HALF=0 keeps the float32 grids (A/B)
-    static const bool half_on = [] { const char* e = getenv("EVD_SCATTER_HALF"); return !(e && e[0] == '0'); }();
+    const long tiles = cdiv(n, (long)VBW_SAMPLES * VBW_WAVES);
+    // persistent workgroups with the basis gradient in registers: two per CU (the LDS slices allow no more)
+    const unsigned blocks = (unsigned)(tiles < 2L * cus ? tiles : 2L * cus);
+#define EVD_VBW(DP, H) { EVD_SET_MAX_LDS((&k_voxel_sample_bwd_w<DP, H>), VBW_LDS); \
+        k_voxel_sample_bwd_w<DP, H><<<blocks, 64 * VBW_WAVES, VBW_LDS, st>>>(g, pts, n, d_out, d_stride, d_col, gg, d_pts, rows_l, ltap, lmax); }
+    // the re-gather reads the float16 copies of the grids where the forward did
     bool have_h = true;
     for (int i = 0; i < 3; ++i) have_h = have_h && g.plane_h[i] && g.line_h[i];
-    if (half_grids && half_on && have_h && bas && !l12 && !iss) {
-        if (d_pts) EVD_VBH(true)
-        else EVD_VBH(false)
-    } else if (iss) {
-        if (d_pts) EVD_VBI(true)
-        else EVD_VBI(false)
-    } else if (bas) {
-        if (d_pts && l12) EVD_VBW(true, true, true)
-        else if (d_pts) EVD_VBW(true, false, true)
-        else if (l12) EVD_VBW(false, true, true)
-        else EVD_VBW(false, false, true)
+    if (half_grids && have_h) {
+        if (d_pts) EVD_VBW(true, true)
+        else EVD_VBW(false, true)
     } else {
-        if (d_pts && l12) EVD_VBW(true, true, false)
-        else if (d_pts) EVD_VBW(true, false, false)
-        else if (l12) EVD_VBW(false, true, false)
-        else EVD_VBW(false, false, false)
+        if (d_pts) EVD_VBW(true, false)
+        else EVD_VBW(false, false)
     }
 #undef EVD_VBW
-#undef EVD_VBI
-#undef EVD_VBH
     EVD_LAUNCH_CHECK();
-    if (gg.basis && !bas) {
-        const int ct = g.n_comp[0] + g.n_comp[1] + g.n_comp[2];
-        const unsigned gb = (unsigned)(cdiv(n, 64L) < 8L * cus ? cdiv(n, 64L) : 8L * cus);     // 8 blocks of 4 wavefronts per CU: every wavefront slot
-        if (ct <= 32) k_basis_grad<1><<<gb, 256, 0, st>>>(d_out, d_stride, d_col, coef, n, ct, g.app_dim, gg.basis);
-        else if (ct <= 64) k_basis_grad<2><<<gb, 256, 0, st>>>(d_out, d_stride, d_col, coef, n, ct, g.app_dim, gg.basis);
-        else k_basis_grad<3><<<gb, 256, 0, st>>>(d_out, d_stride, d_col, coef, n, ct, g.app_dim, gg.basis);
-        EVD_LAUNCH_CHECK();
-    }
     return EVD_OK;
 }
 

@@ -33,35 +33,19 @@ struct VoxMlpParams {
     int rev_trig = 0;                   // k_voxel_mlp_resident: the encodings' sines on the hardware unit behind the two-float revolution reduction (the f16c render's coarse level)
 };
 
-// ---- binned scatter (kernel_voxel_scatter.hip): what the first pass of the tri-plane backward leaves per sample for the second
-struct PTap { unsigned short cx0, cx1, cy0, cy1; float w[4]; };     // clamped cell coordinates of the 4 bilinear taps of one plane + weights (0 = outside)
+// ---- tri-plane scatter (kernel_voxel_scatter.hip): the hybrid form leaves per sample a row of line contributions d coef x plane value
+// ([n, ctot], rows_l) and the line tap records for k_scatter_lines
 struct LTap { int c0, c1; float w0, w1; };                          // the 2 taps of one line
-constexpr int SC_TS = 16;                                           // plane tiles of 16 x 16 cells (+ 1 halo row / column in LDS)
-struct BinOut {
-    float* rows_p;          // [n, ctot]  d coef x line value: what every plane tap adds, times its weight ([n, n_comp[0]]: the x-y plane only, in the hybrid form)
-    float* rows_l;          // [n, ctot]  d coef x plane value, for the line taps
-    PTap* ptap;             // [n, 3]  ([n]: the x-y plane only, in the hybrid form)
-    LTap* ltap;             // [n, 3]
-    unsigned* keys[3];      // [n] tile of tap 0 in plane i
-    unsigned* ids;          // [n] 0 .. n-1 (the sort's values)
-    int tiles_x[3];
-};
-bool voxel_scatter_binned_ok(const GridParams& g, const GridGrads& gg, long n);
-size_t voxel_scatter_workspace_bytes(const GridParams& g, long n);
-int launch_voxel_sample_bwd_pass1(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
-                                  float* d_pts, const BinOut& bo, hipStream_t st);
-int launch_voxel_sample_bwd_planes(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
-                                   float* d_pts, const BinOut& bo, hipStream_t st);
-bool voxel_sample_bwd_w_ok(const GridParams& g);
-bool voxel_sample_bwd_w_lines12(const GridParams& g);
-int launch_voxel_sample_bwd_w(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
-                              float* d_pts, float* rows_l, LTap* ltap, float* coef, hipStream_t st, unsigned* lmax = nullptr, bool half_grids = false);
+bool voxel_scatter_hybrid_ok(const GridParams& g, long n);
 size_t voxel_scatter_hybrid_workspace_bytes(const GridParams& g, long n);
 // half_grids: the re-gather of the grid values reads the float16 copies (the forward of the half-precision modes did: kernel_voxel.hip HALF)
 int launch_voxel_sample_bwd_hybrid(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
                                    float* d_pts, void* workspace, size_t workspace_bytes, hipStream_t st, bool half_grids = false);
-int launch_voxel_sample_bwd_binned(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
-                                   float* d_pts, void* workspace, size_t workspace_bytes, hipStream_t st);
+int launch_voxel_sample_bwd_planes(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
+                                   float* d_pts, float* rows_l, LTap* ltap, hipStream_t st);
+bool voxel_sample_bwd_w_ok(const GridParams& g);
+int launch_voxel_sample_bwd_w(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
+                              float* d_pts, float* rows_l, LTap* ltap, unsigned* lmax, bool half_grids, hipStream_t st);
 
 constexpr int TV_MAX_BLOCKS = 4096;     // partial (dh^2, dw^2) pairs per tensor
 struct TvShape { int C[6], H[6], W[6], blocks[6]; };

@@ -107,8 +107,8 @@ class _VoxelSample(torch.autograd.Function):
         grads, gs = _grid_grads(net, ctx.saved_tensors, in_place=getattr(net, "_grads_in_place", _GRADS_IN_PLACE) and not torch.is_grad_enabled())
         d_pts = torch.empty_like(pts) if ctx.needs_input_grad[0] else None
         # scratch for the hybrid form of the scatter (csrc/kernel_voxel_scatter.hip: plane taps by direct float atomics, line taps through
-        # fixed-point LDS slices -- a third fewer atomic requests, 24-27 % faster); EVD_SCATTER=direct passes none: every tap an atomic
-        nb = int(L.lib().evd_voxel_sample_bwd_workspace_bytes(net._h, pts.shape[0])) if os.environ.get("EVD_SCATTER") != "direct" else 0
+        # fixed-point LDS slices -- a third fewer atomic requests, 24-27 % faster)
+        nb = int(L.lib().evd_voxel_sample_bwd_workspace_bytes(net._h, pts.shape[0]))
         ws = torch.empty((nb,), dtype=torch.uint8, device=pts.device) if nb else None
         # in the forward's arithmetic mode: where it interpolated the float16 grid copies, the re-gather of the backward reads them too
         prec = L.PREC[ctx.precision] if ctx.precision is not None else L.PREC["f32"]

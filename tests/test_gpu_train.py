@@ -1,7 +1,5 @@
 """NeRF-mode training path on the GPU: the forward that keeps its activations and the backward of the fused MLP, against a
 float64 torch restatement of NeRF.mlpforward (networks/nerf.py:46-72) differentiated by torch autograd."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -865,9 +863,9 @@ def test_awp_feature_integration_backward_matches_torch_autograd(S, Cc):
         assert rel < 1e-5, name
 
 
-def test_binned_scatter_equals_the_direct_scatter():
-    """evd_voxel_sample_bwd_ws with scratch (taps binned by plane tile, summed in LDS, one global atomic per touched cell and tile run)
-    vs evd_voxel_sample_bwd (one atomic per tap and channel): the same gradients to the rounding of the summation order, incl. points
+def test_hybrid_scatter_equals_the_direct_scatter():
+    """evd_voxel_sample_bwd_ws with scratch (the hybrid form: plane taps by direct atomics, line taps summed per chunk in fixed-point LDS
+    slices) vs evd_voxel_sample_bwd (one atomic per tap and channel): the same gradients to the rounding of the summation order, incl. points
     outside the box (zero-weight, clamped taps) and a ragged sample count."""
     import ctypes as C
     from evdeblurnerf_amd import _lib as L
@@ -940,9 +938,7 @@ def test_scatter_on_the_float16_grid_copies_is_the_scatter_of_the_rounded_grids(
     assert max(errs) < 2e-6, errs
     c, d = run(sd0, "f16"), run(sd0, "f16x3")
     errs = [rel_l2(x, y) for x, y in zip(c, d)]
-    # (developer switches that take the float32 re-gather in every mode: then the two calls are the same kernel)
-    off = os.environ.get("EVD_SCATTER_HALF") == "0" or os.environ.get("EVD_SCATTER_ISSUER") == "1" or os.environ.get("EVD_SCATTER_FORM") == "block"
-    assert (0.0 if off else 1e-5) <= max(errs[:6]) < 1e-3, errs          # the float16 rounding of the grid values (2^-11 per value, averaged over taps), nothing more
+    assert 1e-5 <= max(errs[:6]) < 1e-3, errs          # the float16 rounding of the grid values (2^-11 per value, averaged over taps), nothing more
 
 
 @pytest.mark.parametrize("prec,tol", [("f16", 5e-5), ("f16x3", 5e-6)])
@@ -984,11 +980,11 @@ def test_hybrid_scatter_propagates_non_finite_gradients():
     assert all(torch.isnan(t).any().item() for t in grads[:6]), [torch.isnan(t).any().item() for t in grads]
 
 
-@pytest.mark.gpu
-def test_xy_window_scatter_equals_the_hybrid_scatter(monkeypatch):
-    """The opt-in form of the hybrid scatter that sums the x-y plane's taps through k_scatter_xy's 8 x 8-cell window (EVD_SCATTER_WIN=1)
-    gives the gradients of the default form: on rays along z (tiles fit the window: the GEMM path), on oblique rays (tiles overflow: its
-    tap-by-tap path), with a ragged last tile, and a NaN in the incoming gradient lands on the cells of its sample only."""
+@pytest.mark.parametrize("prec", ["f32", "f16"])
+def test_scatter_without_the_basis_gradient_gives_the_same_grid_and_point_gradients(prec):
+    """A null basis_mat gradient (evd_voxel_grid_grads.basis = NULL) only drops that gradient: the _ws entry (f32) and the _prec entry on the
+    float16 grid copies (f16) return the six plane / line gradients and d pts of the call that asks for it, to the rounding of the summation
+    order -- incl. points outside the box and a ragged sample count."""
     import ctypes as C
     from evdeblurnerf_amd import _lib as L
     from evdeblurnerf_amd.voxnerf import VoxelNeRFSampleFeatures, _grid_grads
@@ -996,30 +992,27 @@ def test_xy_window_scatter_equals_the_hybrid_scatter(monkeypatch):
     g = W.pdrf_grid_size(AABB[0], AABB[1], nvox)
     net = VoxelNeRFSampleFeatures(W.make_pdrf_state_dict(32, g, input_ch=127, hidden_dim=256, geo_feat_dim=128), "", AABB, num_layers=2, hidden_dim=256,
                                   geo_feat_dim=128, num_layers_color=3, input_ch=127, app_dim=32, app_n_comp=(64, 16, 16), n_voxels=nvox)
-    grads, gs = _grid_grads(net, net.grid_params())
-    rs = np.random.RandomState(3)
-    R, S = 301, 64
-    for spread, bad in ((0.01, False), (0.7, False), (0.01, True)):
-        o = rs.uniform(-1.2, 1.2, (R, 1, 3)) * np.array([1, 1, 0]) + np.array([0, 0, 0.95])
-        d = rs.normal(size=(R, 1, 3)) * spread + np.array([0, 0, -1.0])
-        z = np.sort(rs.uniform(0.0, 2.1, (R, S, 1)), 1)                   # some samples leave the box
-        pts = torch.as_tensor((o + d * z).astype(np.float32), device="cuda").reshape(-1, 3)[:R * S - 13].contiguous()
-        n = pts.shape[0]
-        d_out = torch.randn((n, 32), device="cuda")
-        if bad:
-            d_out[777, 5] = float("nan")
-        d_pts = torch.empty((n, 3), device="cuda")
-        nb = int(L.lib().evd_voxel_sample_bwd_workspace_bytes(net._h, n))
-        ws = torch.empty((nb,), dtype=torch.uint8, device="cuda")
-        outs = []
-        for win in ("0", "1"):
-            monkeypatch.setenv("EVD_SCATTER_WIN", win)
-            for t in grads:
-                t.zero_()
-            L.check(L.lib().evd_voxel_sample_bwd_ws(net._h, L.ptr(pts), n, L.ptr(d_out), 32, 0, C.byref(gs), L.ptr(d_pts), L.ptr(ws), nb, L.stream_ptr()), "bwd_ws")
-            outs.append([t.clone() for t in grads] + [d_pts.clone()])
-        for a, b in zip(outs[1], outs[0]):
-            if bad:
-                assert torch.equal(torch.isnan(a), torch.isnan(b))
-                a, b = torch.nan_to_num(a), torch.nan_to_num(b)
-            assert ((a - b).norm() / b.norm().clamp_min(1e-30)).item() < 1e-5
+    rs = np.random.RandomState(11)
+    n = 30000 - 5
+    pts = torch.tensor(rs.uniform(-1.7, 1.7, (n, 3)).astype(np.float32) * np.array([1.0, 1.0, 0.7], np.float32), device="cuda")
+    d_out = torch.randn((n, 32), device="cuda")
+    nb = int(L.lib().evd_voxel_sample_bwd_workspace_bytes(net._h, n))
+    ws = torch.empty((nb,), dtype=torch.uint8, device="cuda")
+    outs = []
+    for with_basis in (True, False):
+        grads, gs = _grid_grads(net, net.grid_params())
+        if not with_basis:
+            gs.basis = None
+        d_pts = torch.empty_like(pts)
+        if prec == "f32":
+            rc = L.lib().evd_voxel_sample_bwd_ws(net._h, L.ptr(pts), n, L.ptr(d_out), 32, 0, C.byref(gs), L.ptr(d_pts), L.ptr(ws), nb, L.stream_ptr())
+        else:
+            rc = L.lib().evd_voxel_sample_bwd_prec(net._h, L.PREC[prec], L.ptr(pts), n, L.ptr(d_out), 32, 0, C.byref(gs), L.ptr(d_pts), L.ptr(ws), nb,
+                                                   L.stream_ptr())
+        L.check(rc, "bwd")
+        torch.cuda.synchronize()
+        outs.append([t.double() for t in grads[:6]] + [d_pts.double()])
+        if with_basis:
+            assert float(grads[6].abs().max()) > 0.0
+    errs = [rel_l2(a, b) for a, b in zip(outs[1], outs[0])]
+    assert max(errs) < 1e-5, errs

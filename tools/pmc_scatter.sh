@@ -20,13 +20,13 @@ root = "$ROOT/$OUT"
 agg = collections.defaultdict(list)
 for f in glob.glob(root + "/*/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
-        for key in ("k_voxel_sample_bwd<0", "k_voxel_sample_bwd_w", "k_scatter_lines", "k_basis_grad"):
+        for key in ("k_voxel_sample_bwd<false", "k_voxel_sample_bwd_w", "k_scatter_lines"):
             if key in r["Kernel_Name"].replace(" ", ""):
                 agg[(key, r["Counter_Name"])].append(float(r["Counter_Value"]))
-print("fine level 586 x 586 x 390, 524 288 samples, slope $SLOPE, per launch (k_voxel_sample_bwd<0 = all 302 M taps by float atomics):")
+print("fine level 586 x 586 x 390, 524 288 samples, slope $SLOPE, per launch (k_voxel_sample_bwd<false = all 302 M taps by float atomics):")
 for (k, c), v in sorted(agg.items()):
     print(f"    {k:24s} {c:36s} {sorted(v)[len(v) // 2]:18.1f}  (median of {len(v)} dispatches)")
 for f in glob.glob(root + "/trace/**/*kernel_stats.csv", recursive=True):
     for r in csv.DictReader(open(f)):
-        if any(k in r["Name"] for k in ("k_voxel_sample_bwd", "k_scatter_lines", "k_basis_grad")): print("duration:", r["Name"][:60], r["Calls"], "calls avg", float(r["AverageNs"]) / 1e3, "us  min", float(r["MinNs"]) / 1e3)
+        if any(k in r["Name"] for k in ("k_voxel_sample_bwd", "k_scatter_lines")): print("duration:", r["Name"][:60], r["Calls"], "calls avg", float(r["AverageNs"]) / 1e3, "us  min", float(r["MinNs"]) / 1e3)
 PY
