@@ -60,6 +60,11 @@ void evd_voxel_destroy(evd_voxel* v) {
     delete v;
 }
 
+// The float16 copy of one grid value, as evd_voxel_create and k_load_grids make it: round to nearest, SATURATED to +-65504 (NaN stays NaN).
+// The half-precision gathers skip no tap: an outside tap reads a clamped cell with weight 0, and 0 x inf would be NaN where the reference's
+// zero padding gives 0.
+__host__ __device__ static inline _Float16 f16_sat(float x) { return (_Float16)(x > 65504.f ? 65504.f : (x < -65504.f ? -65504.f : x)); }
+
 int evd_voxel_create(const evd_voxel_desc* d, evd_voxel** out) {
     EVD_REQUIRE(d && out, "evd_voxel_create: null argument");
     // frequency counts other than (PE_L, PE_LV) run in the generic kernel only (inference; no pipelined / f16c / training streams)
@@ -96,7 +101,7 @@ int evd_voxel_create(const evd_voxel_desc* d, evd_voxel** out) {
         if (rc) break;
         {   // float16 copy for the half-precision arithmetic modes
             std::vector<_Float16> ch(cl.size());
-            for (size_t k = 0; k < cl.size(); ++k) ch[k] = (_Float16)cl[k];
+            for (size_t k = 0; k < cl.size(); ++k) ch[k] = f16_sat(cl[k]);
             rc = v->plane_h[i].upload(ch.data(), ch.size() * sizeof(_Float16));
             if (rc) break;
         }
@@ -106,7 +111,7 @@ int evd_voxel_create(const evd_voxel_desc* d, evd_voxel** out) {
         rc = v->line[i].upload(ll.data(), ll.size() * sizeof(float));
         if (rc) break;
         std::vector<_Float16> lh(ll.size());
-        for (size_t k = 0; k < ll.size(); ++k) lh[k] = (_Float16)ll[k];
+        for (size_t k = 0; k < ll.size(); ++k) lh[k] = f16_sat(ll[k]);
         rc = v->line_h[i].upload(lh.data(), lh.size() * sizeof(_Float16));
     }
     if (!rc) rc = v->basis.upload(d->basis, sizeof(float) * (size_t)d->app_dim * ctot);
@@ -803,13 +808,13 @@ static __global__ __launch_bounds__(256) void k_load_grids(const GridLoadSegs se
         reinterpret_cast<f32x4*>(s.dst)[i] = v;
         if (s.dst_h) {
             typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-            const h4 h = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+            const h4 h = {f16_sat(v[0]), f16_sat(v[1]), f16_sat(v[2]), f16_sat(v[3])};
             reinterpret_cast<h4*>(s.dst_h)[i] = h;
         }
     }
     for (long i = s.tail0 + (long)blockIdx.x * 256 + threadIdx.x; i < s.n; i += stride) {
         s.dst[i] = s.src[i];
-        if (s.dst_h) s.dst_h[i] = (_Float16)s.src[i];
+        if (s.dst_h) s.dst_h[i] = f16_sat(s.src[i]);
     }
 }
 

@@ -78,6 +78,7 @@ struct VsItem {
     float fw, fn, fl;       // fractional positions inside the cell (x, y of the plane; the line)
     float kx, ky, kl;       // d (pixel coordinate) / d (point coordinate) of the three axes the component reads
     int ax, ay, al;         // ... and which point axes those are
+    int vm;                 // taps inside the grid: bits 0-3 the plane taps, 4-5 the line taps (a tap can be inside with weight 0)
 };
 
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -143,6 +144,7 @@ __device__ __forceinline__ void vs_issue(const GridParams& g, const float (&pt)[
     it.l[1] = vs_load<HALF>(li, lih, it.il[1] - c4);
     it.wl[0] = (l0 >= 0 && l0 < Lp) ? ls : 0.f;
     it.wl[1] = (l1 >= 0 && l1 < Lp) ? ln : 0.f;
+    it.vm = (vy0 && vx0) | (vy0 && vx1) << 1 | (vy1 && vx0) << 2 | (vy1 && vx1) << 3 | (l0 >= 0 && l0 < Lp) << 4 | (l1 >= 0 && l1 < Lp) << 5;
 }
 
 // invalid taps contribute exactly nothing (the reference skips them): a zero weight times a finite grid value is 0,
@@ -647,11 +649,16 @@ __device__ __forceinline__ float vbw_mul_legacy(float a, float b) {          // 
 //     operand, nothing goes through LDS;
 //   * out^T[f, sample] = sum_k basis[f, k] coef[sample, k] on the float16 matrix core in the split form the float32-grade modes use everywhere
 //     (hi = f16(x), lo = f16(x - hi); A_hi B_hi + A_hi B_lo + A_lo B_hi, float32 accumulate: 2^-21 relative per product): 18 MFMAs of 16 cycles
-//     instead of 48 of 32; the split basis_mat operands are made once per workgroup in LDS (12 KiB), the workgroups are persistent;
+//     instead of 48 of 32; the split basis_mat operands are made once per workgroup in LDS (12 KiB), the workgroups are persistent.  As in
+//     the backward's phase 1, both operands are brought to [2^13, 2^14) by powers of two before the split -- one per basis row (feature) and
+//     one per sample, taken over ALL of the sample's coefficients (the three k steps add into one tile) -- and the product is scaled back
+//     exactly: without them a grid at 2^-10 put the coefficients into float16 subnormals (2^-7 of the feature lost) and one at 2^10 made
+//     them inf;
 //   * the D layout (feature 4 (lane / 16) + r of sample lane % 16) is four consecutive floats of a sample's output row: stored straight from the
 //     accumulators, no transposition;
-//   * 32-bit tap offsets; HALF: weight x float16 value + sum as ONE v_fma_mix_f32 (no conversion, no separate multiply; the float16 grids are
-//     finite, so a zero weight needs no guard); float32 grids: v_mul_legacy_f32 + add (the guarded sum of rounds 1-5, exactly).
+//   * 32-bit tap offsets; HALF: float16 value converted to float32, then one fused multiply-add with the weight (the float16 copies are
+//     saturated to the finite range when they are made, so a zero weight needs no guard); float32 grids: v_mul_legacy_f32 + add (the
+//     guarded sum of rounds 1-5, exactly).
 struct VmTaps { int ip[4], il[2]; float wp[4], wl[2]; };          // 48 bytes: element offsets of channel 0 (clamped) and weights (0 = outside)
 constexpr int VM_WAVES = 4;
 typedef _Float16 vm_h8 __attribute__((ext_vector_type(8)));
@@ -672,20 +679,39 @@ __global__ __launch_bounds__(64 * VM_WAVES, OCC) void k_voxel_sample_m(const Gri
                                                                        float* __restrict__ out, int out_stride, int out_col) {
     __shared__ __attribute__((aligned(16))) vm_h8 a_hi[2 * 3 * 64], a_lo[2 * 3 * 64];        // [feature tile][k step][lane]
     __shared__ __attribute__((aligned(16))) VmTaps taps_all[VM_WAVES][16 * 3];
+    __shared__ float a_inv[32];                                                                // 1 / the power-of-two scale of each A row
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int c0n = g.n_comp[0], c1n = g.n_comp[1], ctot = c0n + c1n + g.n_comp[2], steps = ctot / 32, F = g.app_dim;
-    // the split A operands: entry (tile, step, lane) = basis[16 tile + lane % 16][32 step + 8 (lane / 16) .. + 7]
-    for (int e = threadIdx.x; e < 2 * 3 * 64; e += 64 * VM_WAVES) {
-        const int l = e & 63, st = (e >> 6) % 3, tl = e / 192, f = 16 * tl + (l & 15), k0 = 32 * st + 8 * (l >> 4);
-        vm_h8 hi, lo;
+    // the split A operands, made by the first two wavefronts: entry (tile, step, lane) = basis[16 tile + lane % 16][32 step + 8 (lane / 16) .. + 7]
+    // x a power of two per basis row (feature) that brings the row's largest magnitude into [2^13, 2^14) (vbw_pow2_scale); a lane holds all
+    // three steps of its (tile, lane), the four lanes of a row meet by two shuffles
+    if (threadIdx.x < 128) {
+        const int l = threadIdx.x & 63, tl = threadIdx.x >> 6, f = 16 * tl + (l & 15);
+        float v[3][8], m = 0.f;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float v = (f < F && st < steps) ? g.basis[(long)f * ctot + k0 + j] : 0.f;
-            hi[j] = (_Float16)v;
-            lo[j] = (_Float16)(v - (float)hi[j]);
+        for (int st = 0; st < 3; ++st)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                v[st][j] = (f < F && st < steps) ? g.basis[(long)f * ctot + 32 * st + 8 * (l >> 4) + j] : 0.f;
+                m = fmaxf(m, fabsf(v[st][j]));
+            }
+        m = fmaxf(m, __shfl_xor(m, 16));
+        m = fmaxf(m, __shfl_xor(m, 32));
+        float inv;
+        const float sc = vbw_pow2_scale(m, &inv);
+#pragma unroll
+        for (int st = 0; st < 3; ++st) {
+            vm_h8 hi, lo;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float x = v[st][j] * sc;
+                hi[j] = (_Float16)x;
+                lo[j] = (_Float16)(x - (float)hi[j]);
+            }
+            a_hi[(tl * 3 + st) * 64 + l] = hi;
+            a_lo[(tl * 3 + st) * 64 + l] = lo;
         }
-        a_hi[e] = hi;
-        a_lo[e] = lo;
+        if (l < 16) a_inv[f] = inv;
     }
     __syncthreads();
     VmTaps* taps = taps_all[wv];
@@ -742,7 +768,12 @@ __global__ __launch_bounds__(64 * VM_WAVES, OCC) void k_voxel_sample_m(const Gri
             }
         }
         VS_STAMP(2);
+        // The B operand's scale: a power of two that brings the sample's largest |coefficient| (over the four lanes of its column) into
+        // [2^13, 2^14), so that the hi / lo split keeps 2^-22 of it -- unscaled, small coefficients fell into float16 subnormals and ones
+        // above 65504 became inf (and the lo term NaN).  The three k steps add into one tile, so the scale is that of the running maximum
+        // over the steps so far: when a step raises it, the tile is first multiplied by the ratio of the two powers of two (<= 1: exact).
         f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        float bm = 0.f, b_inv = 0.f;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             if (q < steps) {
@@ -784,11 +815,26 @@ __global__ __launch_bounds__(64 * VM_WAVES, OCC) void k_voxel_sample_m(const Gri
                         for (int e = 0; e < 4; ++e) cf[4 * v + e] = __fmul_rn(pv[e], lv[e]);
                     }
                 }
+                float m = bm;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(cf[e]));
+                m = fmaxf(m, __shfl_xor(m, 16));
+                m = fmaxf(m, __shfl_xor(m, 32));
+                float inv;
+                const float sc = vbw_pow2_scale(m, &inv);
+                if (q > 0) {
+                    const float ratio = sc * b_inv;   // new scale / old scale
+#pragma unroll
+                    for (int tl = 0; tl < 2; ++tl) acc[tl] *= ratio;
+                }
+                bm = m;
+                b_inv = inv;
                 vm_h8 bh, bl;
 #pragma unroll
                 for (int e = 0; e < 8; e += 2) {
-                    const vm_h2 h2 = __builtin_convertvector(vm_f2{cf[e], cf[e + 1]}, vm_h2);
-                    const vm_h2 l2 = __builtin_convertvector(vm_f2{cf[e] - (float)h2[0], cf[e + 1] - (float)h2[1]}, vm_h2);
+                    const float x0 = cf[e] * sc, x1 = cf[e + 1] * sc;
+                    const vm_h2 h2 = __builtin_convertvector(vm_f2{x0, x1}, vm_h2);
+                    const vm_h2 l2 = __builtin_convertvector(vm_f2{x0 - (float)h2[0], x1 - (float)h2[1]}, vm_h2);
                     bh[e] = h2[0]; bh[e + 1] = h2[1];
                     bl[e] = l2[0]; bl[e + 1] = l2[1];
                 }
@@ -812,10 +858,12 @@ __global__ __launch_bounds__(64 * VM_WAVES, OCC) void k_voxel_sample_m(const Gri
 #pragma unroll
             for (int tl = 0; tl < 2; ++tl) {
                 const int f0 = 16 * tl + 4 * kb;
-                f32x4 v = acc[tl];
+                f32x4 v;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = (acc[tl][r] * b_inv) * a_inv[f0 + r];       // both scales are powers of two: exact
                 if (g.app_act != EVD_ACT_NONE) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = act(g.app_act, acc[tl][r]);
+                    for (int r = 0; r < 4; ++r) v[r] = act(g.app_act, v[r]);
                 }
                 if (f0 + 3 < F) *reinterpret_cast<f32x4u*>(o + f0) = v;
                 else
@@ -888,7 +936,7 @@ __global__ __launch_bounds__(256, MM ? (CT <= 96 ? 3 : 2) : 1) void k_voxel_samp
     constexpr int STRD = CT + 1, FSTR = MM ? 33 : VSB_MAXF + 1;      // odd row strides (conflict-free column access)
 
     __shared__ float tfr[VS_SAMPLES * 3 * 6], dpt[VS_SAMPLES * 3];
-    __shared__ int tax[VS_SAMPLES * 3 * 3];
+    __shared__ int tax[VS_SAMPLES * 3 * 4];           // axes of the component's three coordinates + the tap validity mask
     __shared__ __attribute__((aligned(16))) float pvs[VS_SAMPLES * STRD], lvs[VS_SAMPLES * STRD], dco[VS_SAMPLES * STRD],
         dout[VS_SAMPLES * FSTR], tw[VS_SAMPLES * VSB_TAPS];
     __shared__ int tix[VS_SAMPLES * VSB_TAPS];
@@ -960,8 +1008,8 @@ __global__ __launch_bounds__(256, MM ? (CT <= 96 ? 3 : 2) : 1) void k_voxel_samp
             }
             float* fr = tfr + (sl * 3 + i) * 6;
             fr[0] = it.fw; fr[1] = it.fn; fr[2] = it.fl; fr[3] = it.kx; fr[4] = it.ky; fr[5] = it.kl;
-            int* ta = tax + (sl * 3 + i) * 3;
-            ta[0] = it.ax; ta[1] = it.ay; ta[2] = it.al;
+            int* ta = tax + (sl * 3 + i) * 4;
+            ta[0] = it.ax; ta[1] = it.ay; ta[2] = it.al; ta[3] = live ? it.vm : 0;
             if constexpr (HYBRID) {
                 if (live) {                         // the line taps of this (sample, component), for k_scatter_lines
                     const int C = sel3(i, g.n_comp[0], g.n_comp[1], g.n_comp[2]);
@@ -1019,21 +1067,24 @@ __global__ __launch_bounds__(256, MM ? (CT <= 96 ? 3 : 2) : 1) void k_voxel_samp
                 pvs[sl * STRD + ql] = pv;
                 lvs[sl * STRD + ql] = lv;
                 if (d_pts) {
-                    // d feature / d point through the interpolation weights (the ATen grid_sample backward: taps outside the grid
-                    // contribute nothing), chained with d coef; summed over the channels of the wavefront, then over wavefronts in LDS
+                    // d feature / d point through the interpolation weights (the ATen grid_sample backward: a tap outside the grid is a zero
+                    // VALUE -- decided by the validity mask, not by the weight: at an exact integer index the upper tap is inside with weight 0
+                    // and its value enters the derivative), chained with d coef; summed over the channels of the wavefront, then over
+                    // wavefronts in LDS
                     const float* fr = tfr + (sl * 3 + cg) * 6;
                     const float ww = fr[0], nn = fr[1], ee = 1.f - ww, sn = 1.f - nn;
+                    const int vm = tax[(sl * 3 + cg) * 4 + 3];
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) P[t] = w[4 * cg + t] != 0.f ? P[t] : 0.f;
+                    for (int t = 0; t < 4; ++t) P[t] = (vm >> t) & 1 ? P[t] : 0.f;
                     const float dpx = (P[1] - P[0]) * sn + (P[3] - P[2]) * nn, dpy = (P[2] - P[0]) * ee + (P[3] - P[1]) * ww;
-                    const float dl = (w[12 + 2 * cg + 1] != 0.f ? Lt[1] : 0.f) - (w[12 + 2 * cg] != 0.f ? Lt[0] : 0.f);
+                    const float dl = ((vm >> 5) & 1 ? Lt[1] : 0.f) - ((vm >> 4) & 1 ? Lt[0] : 0.f);
                     const float dc = dco[sl * STRD + ql];
                     float gx = dc * lv * dpx * fr[3], gy = dc * lv * dpy * fr[4], gl = dc * pv * dl * fr[5];
                     // sum over the component's channels.  When every component is a whole number of 16-lane rows (the shipped 64 / 16 / 16)
                     // the rows are summed in registers (DPP) and ONE lane per row adds to LDS: 18 LDS float atomics per sample instead of
                     // 288 -- ds_add_f32 runs at ~0.4 lane-operations per clock and CU on this chip (kernel_voxel_scatter.hip), so the
                     // 9216 of a tile cost more than everything else the tile does
-                    const int* ta = tax + (sl * 3 + cg) * 3;
+                    const int* ta = tax + (sl * 3 + cg) * 4;
                     if (rows16) {
                         gx = row_sum_dpp(gx); gy = row_sum_dpp(gy); gl = row_sum_dpp(gl);
                         if ((tid & 15) == 0) {
@@ -1134,7 +1185,7 @@ struct VbwTaps {
     int ip[4], il[2];                           // element offsets of channel 0 of the taps (clamped)
     float wp[4], wl[2];                         // interpolation weights, 0 = outside (zero padding) or dead sample
     float fw, fn, kx, ky, kl;                   // fractional position in the plane cell; d (pixel coordinate) / d (point coordinate)
-    int pad;
+    int vm;                                     // taps inside the grid (VsItem::vm; 0 for a dead sample): the point gradient's zero padding
 };
 // a wavefront's slice: tap tables | d coef -> plane rows [16][CSTR] | point-gradient partial sums [16][3 quads][3] | the coefficient rows
 // pv lv [16][96] of the in-kernel basis gradient.  16 KiB per wavefront: two workgroups of four per CU (2 x 78 KiB of the 160 KiB)
@@ -1180,7 +1231,7 @@ __device__ __forceinline__ void vbw_geometry(const GridParams& g, const float (&
     tp.kx = 0.5f * (float)(Wp - 1) * sel3(i, g.inv[0], g.inv[0], g.inv[1]);
     tp.ky = 0.5f * (float)(Hp - 1) * sel3(i, g.inv[1], g.inv[2], g.inv[2]);
     tp.kl = 0.5f * (float)(Lp - 1) * sel3(i, g.inv[2], g.inv[1], g.inv[0]);
-    tp.pad = 0;
+    tp.vm = live ? ((vy0 && vx0) | (vy0 && vx1) << 1 | (vy1 && vx0) << 2 | (vy1 && vx1) << 3 | (l0 >= 0 && l0 < Lp) << 4 | (l1 >= 0 && l1 < Lp) << 5) : 0;
 }
 
 // The basis_mat gradient d out^T . coef INSIDE this kernel (round 4).  The workgroups are persistent (a wavefront walks tiles
@@ -1496,14 +1547,16 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
                     for (int k = 0; k < 4; ++k) drow[4 * v + k] = rp[k];
                 }
                 if (DPTS) {
-                    // d feature / d point through the interpolation weights (the ATen grid_sample backward: taps outside the grid contribute
-                    // nothing), chained with d coef
+                    // d feature / d point through the interpolation weights (the ATen grid_sample backward: a tap outside the grid is a zero
+                    // VALUE; inside-ness from the mask, not the weight -- at an exact integer index the upper tap is inside with weight 0),
+                    // chained with d coef
+                    const int vm = tp.vm;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const float P0 = tp.wp[0] != 0.f ? plane_val(0, k) : 0.f, P1 = tp.wp[1] != 0.f ? plane_val(1, k) : 0.f;
-                        const float P2 = tp.wp[2] != 0.f ? plane_val(2, k) : 0.f, P3 = tp.wp[3] != 0.f ? plane_val(3, k) : 0.f;
+                        const float P0 = vm & 1 ? plane_val(0, k) : 0.f, P1 = vm & 2 ? plane_val(1, k) : 0.f;
+                        const float P2 = vm & 4 ? plane_val(2, k) : 0.f, P3 = vm & 8 ? plane_val(3, k) : 0.f;
                         const float dpx = (P1 - P0) * sn + (P3 - P2) * nn, dpy = (P2 - P0) * ee + (P3 - P1) * ww;
-                        const float dl = (tp.wl[1] != 0.f ? line_val(1, k) : 0.f) - (tp.wl[0] != 0.f ? line_val(0, k) : 0.f);
+                        const float dl = (vm & 32 ? line_val(1, k) : 0.f) - (vm & 16 ? line_val(0, k) : 0.f);
                         gx += dc[k] * lv[k] * dpx;
                         gy += dc[k] * lv[k] * dpy;
                         gl += dc[k] * pv[k] * dl;
@@ -1911,7 +1964,7 @@ int launch_voxel_sample(const GridParams& g, bool half_grids, const float* pts, 
 #ifndef EVD_VM_OCC
 #define EVD_VM_OCC 3
 #endif
-            // (three wavefronts per SIMD, 164 registers, no spills; compiled for four -- 128 registers, 34 spilled -- it runs 70 instead of 57 us)
+            // (three wavefronts per SIMD, 168 registers with the operand scaling, no spills; compiled for four -- 128 registers, 34 spilled -- it runs 70 instead of 57 us)
             k_voxel_sample_m<true, EVD_VM_OCC><<<mb, 64 * VM_WAVES, 0, st>>>(g, pts, n, out, out_stride, out_col);
             EVD_LAUNCH_CHECK();
             return EVD_OK;

@@ -350,7 +350,9 @@ int evd_voxel_load_grids(evd_voxel* v, const float* const* plane, const float* c
  * d_out dev rows of d_stride floats, the app_dim gradient columns start at d_col -> gradients ADDED into g (caller zeroes;
  * NULL = not wanted) with float32 hardware atomics; like the reference's grid_sample backward (voxnerf.py:144) the summation
  * order is not deterministic.  d_pts dev [n,3] (NULL = not wanted) is OVERWRITTEN with d loss / d pts through the bilinear /
- * linear interpolation weights (ATen grid_sample backward semantics: taps outside the grid contribute nothing). */
+ * linear interpolation weights (ATen grid_sample backward semantics: taps outside the grid contribute nothing).
+ * Arithmetic: d coef = d out . basis_mat is a split-float16 product (operands scaled by powers of two, hi + lo, ~2^-21 per product) in
+ * EVERY precision mode, EVD_PREC_F32 included; the rest (weights, re-gathered values, the sums into the gradients) is float32. */
 int evd_voxel_sample_bwd(const evd_voxel* v, const float* pts, long n, const float* d_out, int d_stride, int d_col,
                          const evd_voxel_grid_grads* g, float* d_pts, void* stream);
 /* The same with caller scratch (evd_voxel_sample_bwd_workspace_bytes(v, n): 4 x (sum of n_comp) + 48 B per sample, 432 B at the
