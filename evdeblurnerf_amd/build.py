@@ -64,15 +64,20 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def _compile(src, obj, extra):
-    cmd = [hipcc(), *FLAGS, *PER_FILE.get(os.path.basename(src), []), *extra, "-c", src, "-o", obj]
+def unit_flags(src):
+    """hipcc flags of one translation unit (tools/build_variant.sh compiles its variants with them)."""
+    return FLAGS + PER_FILE.get(os.path.basename(src), [])
+
+
+def _compile(src, obj):
+    cmd = [hipcc(), *unit_flags(src), "-c", src, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed for {os.path.basename(src)}:\n{r.stdout}\n{r.stderr}")
     return r.stderr
 
 
-def build(force: bool = False, verbose: bool = False, extra=()) -> str:
+def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     hs = headers()
     jobs = []
@@ -84,7 +89,7 @@ def build(force: bool = False, verbose: bool = False, extra=()) -> str:
             jobs.append((src, obj))
     if jobs:
         with cf.ThreadPoolExecutor(max_workers=min(4, len(jobs))) as ex:
-            for (src, _), warn in zip(jobs, ex.map(lambda j: _compile(j[0], j[1], list(extra)), jobs)):
+            for (src, _), warn in zip(jobs, ex.map(lambda j: _compile(*j), jobs)):
                 if verbose and warn.strip():
                     print(f"[{os.path.basename(src)}]\n{warn}", file=sys.stderr)
     if jobs or _stale(LIB, objs):

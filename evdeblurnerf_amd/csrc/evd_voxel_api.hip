@@ -434,12 +434,11 @@ static int voxel_pass(const evd_voxel* v, int precision, const float* pts, const
         feature = crows;
     }
     VoxMlpParams p;
-    static const bool no_pipe = env_flag("EVD_NO_PIPE");
     const bool comp = precision == EVD_PREC_F16C && v->pipe_c_chunks > 0;
     const bool coarse_of_f16c = precision == EVD_PREC_F16C && !comp;
     if (coarse_of_f16c) precision = EVD_PREC_F16X3;      // the 64-wide coarse level: float32-grade arithmetic (a few % of the render)
     if (comp && feature) return fail(EVD_E_INVALID, "evd_voxel: per-sample feature rows are not built in EVD_PREC_F16C (use EVD_PREC_F16X3)");
-    const bool piped = v->pipe_chunks[precision] > 0 && !no_pipe;
+    const bool piped = v->pipe_chunks[precision] > 0;
     p.wstream = (const char*)(piped ? v->pipe[precision].data.p : v->stream[precision].data.p);
     p.bias = (const float*)v->bias.p;
     p.pts = pts; p.viewdirs = viewdirs; p.fts = fts; p.nsamp = R * (long)S; p.S = S; p.vd_stride = vd_stride; p.ft_stride = ft_stride;
@@ -456,7 +455,7 @@ static int voxel_pass(const evd_voxel* v, int precision, const float* pts, const
         p.nchunks = v->pipe_c_chunks;
     }
     // the 64-wide coarse level on the software pipeline (its training forward's stream and layer table), where that is built
-    const bool coarse_pipe = !comp && !piped && !no_pipe && !feature && v->hidden_dim == 64 && v->geo == 15 && v->ft_dim == 32 &&
+    const bool coarse_pipe = !comp && !piped && !feature && v->hidden_dim == 64 && v->geo == 15 && v->ft_dim == 32 &&
                              is_train_prec(precision) && v->train_chunks[precision] > 0;
     if (coarse_pipe) {
         p.wstream = (const char*)v->train[precision].data.p;

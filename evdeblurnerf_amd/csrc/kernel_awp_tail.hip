@@ -109,31 +109,6 @@ struct TailKParams {
     int nblkB, partB_stride;
     long partA_stride;                 // floats between the workgroups' partial rows (a multiple of 4: the rows are 16-byte aligned)
     float *d_h, *d_vf, *d_rays, *d_hi, *d_hs, *partA;
-    long long* stamps;                 // developer build (-DEVD_AT_STAMP): per-phase shader-clock sums of workgroup 0
-};
-
-// developer build (-DEVD_AT_STAMP, tools/dev/stamp_awp_tail.py): thread 0 of workgroup 0 sums the shader-clock cycles between marks
-struct AtClock {
-#ifdef EVD_AT_STAMP
-    long long t[32], last;
-    __device__ __forceinline__ void start() {
-        for (int i = 0; i < 32; ++i) t[i] = 0;
-        last = __builtin_readcyclecounter();
-    }
-    __device__ __forceinline__ void mark(int i) {
-        const long long now = __builtin_readcyclecounter();
-        t[i] += now - last;
-        last = now;
-    }
-    __device__ __forceinline__ void flush(long long* out) const {
-        if (out && blockIdx.x == 0 && threadIdx.x == 0)
-            for (int i = 0; i < 32; ++i) out[i] = t[i];
-    }
-#else
-    __device__ __forceinline__ void start() {}
-    __device__ __forceinline__ void mark(int) {}
-    __device__ __forceinline__ void flush(long long*) const {}
-#endif
 };
 
 // threadIdx.x behind an opaque barrier: hipcc otherwise hoists every helper's per-thread index arithmetic (i / N, n % K, the strided
@@ -424,7 +399,7 @@ __device__ __forceinline__ void tail_stage_weights(const TailKParams& p, const T
 
 // The forward of one ray into LDS (both the forward kernel and the backward, which recomputes it).  On return (after the final
 // barrier): x0, xs[], hi, li, kP, nP, q, aP, ls, kI, nI, aS, f, yb (= convd f, the BatchNorm's input).
-__device__ __forceinline__ void tail_forward_ray(const TailKParams& p, const TailLds& L, long r, AtClock& clk) {
+__device__ __forceinline__ void tail_forward_ray(const TailKParams& p, const TailLds& L, long r) {
     const TailDims& d = p.d;
     const int tid = at_tid(), P = d.P, S = d.S;
     TileJobs jobs{0};
@@ -451,7 +426,6 @@ __device__ __forceinline__ void tail_forward_ray(const TailKParams& p, const Tai
         L.x0[pp * d.IN0 + AT_WS + j] = v;
     }
     __syncthreads();
-    clk.mark(1);
     // awp.py:107-109 (layer 0) and mam.py:72-74 applied to the per-sample part's inter sums
     lin<1>(jobs, L.xs(0), AT_CM, L.x0, d.IN0, L.mw(0), L.mb(0), P, AT_CM, d.IN0);
     lin<0>(jobs, L.li, AT_CM, L.hi, AT_WS, L.lin_w, L.lin_b, P, AT_CM, AT_WS);
@@ -487,17 +461,14 @@ __device__ __forceinline__ void tail_forward_ray(const TailKParams& p, const Tai
     }
     const int sl = tid / AT_LPS, hf = tid % AT_LPS;
     __syncthreads();
-    clk.mark(2);
     for (int l = 1; l < d.n_mot; ++l) {
         lin<1>(jobs, L.xs(l), AT_CM, L.xs(l - 1), AT_CM, L.mw(l), L.mb(l), P, AT_CM, AT_CM);
         if (l == 1) lin<0>(jobs, L.kP, AT_MID, L.li, AT_CM, L.conva, nullptr, P, AT_MID, AT_CM);            // mam.py:38
         __syncthreads();
-        clk.mark(3);
     }
     if (d.n_mot == 1) {
         lin<0>(jobs, L.kP, AT_MID, L.li, AT_CM, L.conva, nullptr, P, AT_MID, AT_CM);
         __syncthreads();
-        clk.mark(3);
     }
     const float* xg = L.xs(d.n_mot - 1);
     lin<0>(jobs, L.q, AT_MID, xg, AT_CM, L.convc, nullptr, P, AT_MID, AT_CM);                               // mam.py:41
@@ -515,7 +486,6 @@ __device__ __forceinline__ void tail_forward_ray(const TailKParams& p, const Tai
         }
     }
     __syncthreads();
-    clk.mark(5);
     mm<0, false>(jobs, L.aP, P, L.q, AT_MID, 1, L.kP, AT_MID, 1, nullptr, P, P, AT_MID);                   // mam.py:42: logits over the sub-exposures
     for (int s0 = 0; s0 < S; s0 += AT_NT / AT_LPS) {                                                       // mam.py:47 (convl), :43 (logits over the samples)
         const int s = s0 + sl;
@@ -531,11 +501,9 @@ __device__ __forceinline__ void tail_forward_ray(const TailKParams& p, const Tai
         }
     }
     __syncthreads();
-    clk.mark(6);
     for (int row = tid >> 6; row < P; row += AT_NT / 64) softmax_row(L.aS + row * d.SA, S);          // mam.py:42-43: the softmaxes
     if (tid >= AT_NT - 64 && tid - (AT_NT - 64) < P) softmax_small(L.aP + (tid - (AT_NT - 64)) * P, P);
     __syncthreads();
-    clk.mark(7);
     mm<0, false>(jobs, L.f, AT_CM, L.aP, P, 1, L.nP, 1, AT_MID, nullptr, P, AT_MID, P);                     // mam.py:49
     if ((tid >> 6) == AT_NT / 64 - 1) {                                                               // mam.py:50 (:52: the concatenation)
         const f32x4v acc = tile16(zero4(), L.aS, d.SA, 1, P, L.nI, AT_LK, 1, AT_MID, S);
@@ -545,25 +513,20 @@ __device__ __forceinline__ void tail_forward_ray(const TailKParams& p, const Tai
             if (4 * (lane >> 4) + i < P) L.f[(4 * (lane >> 4) + i) * AT_CM + AT_MID + (lane & 15)] = acc[i];
     }
     __syncthreads();
-    clk.mark(8);
     lin<0>(jobs, L.yb, AT_CM, L.f, AT_CM, L.convd, nullptr, P, AT_CM, AT_CM);                               // mam.py:53: convd[0]
     __syncthreads();
-    clk.mark(9);
 }
 
 __global__ __launch_bounds__(AT_NT) void k_awp_tail_fwd(TailKParams p) {
     extern __shared__ float lds[];
     TailLds L;
     tail_lds_layout(lds, p.d, false, L);
-    AtClock clk;
-    clk.start();
     tail_stage_weights(p, L);
     __syncthreads();
-    clk.mark(0);
     const int tid = threadIdx.x, P = p.d.P;
     double s1 = 0.0, s2 = 0.0;                                   // lanes 0..31: the sums of this workgroup's y, y^2 of channel tid
     for (long r = blockIdx.x; r < p.R; r += gridDim.x) {
-        tail_forward_ray(p, L, r, clk);
+        tail_forward_ray(p, L, r);
         if (p.saved) {                                           // the ray's forward state for the backward: 55 KB instead of a second forward
             float4* dst = reinterpret_cast<float4*>(p.saved + r * L.ray_floats);
             const float4* src = reinterpret_cast<const float4*>(L.x0);
@@ -586,9 +549,7 @@ __global__ __launch_bounds__(AT_NT) void k_awp_tail_fwd(TailKParams p) {
             s2 += (double)b;
         }
         __syncthreads();
-        clk.mark(10);
     }
-    clk.flush(p.stamps);
     if (tid < AT_CM) {
         p.bn_part[(long)blockIdx.x * 2 * AT_CM + tid] = s1;
         p.bn_part[(long)blockIdx.x * 2 * AT_CM + AT_CM + tid] = s2;
@@ -749,8 +710,6 @@ __global__ __launch_bounds__(AT_NT) void k_awp_tail_bwd(TailKParams p) {
     __shared__ float sums[2 * AT_CM], stat[2 * AT_CM];
     TailLds L;
     tail_lds_layout(lds, p.d, true, L);
-    AtClock clk;
-    clk.start();
     tail_stage_weights(p, L);
     const TailDims& d = p.d;
     const int tid0 = threadIdx.x, P = d.P, S = d.S, nm = d.n_mot;
@@ -794,9 +753,8 @@ __global__ __launch_bounds__(AT_NT) void k_awp_tail_bwd(TailKParams p) {
                 }
             }
             __syncthreads();
-            clk.mark(1);
         } else {
-            tail_forward_ray(p, L, r, clk);
+            tail_forward_ray(p, L, r);
         }
         const float* xg = L.xs(nm - 1);
         // BatchNorm backward (mam.py:24-27 in training: batch statistics; eval: the running estimates are constants), and the residual
@@ -809,11 +767,9 @@ __global__ __launch_bounds__(AT_NT) void k_awp_tail_bwd(TailKParams p) {
             L.dxa[i] = dzv;                                                                         // d x_global, the residual's share
         }
         __syncthreads();
-        clk.mark(11);
         wacc(jobs, part + off[wb + TW_CONVD], L.yb, AT_CM, L.f, AT_CM, P, AT_CM, AT_CM);
         mm<0, false>(jobs, L.df, AT_CM, L.yb, AT_CM, 1, L.convd, 1, AT_CM, nullptr, P, AT_CM, AT_CM);      // d f = d y convd
         __syncthreads();
-        clk.mark(12);
         // attention over the sub-exposures (mam.py:42, 46, 49) and over the samples (:43, 47, 50)
         mm<0, false>(jobs, L.daP, P, L.df, AT_CM, 1, L.nP, AT_MID, 1, nullptr, P, P, AT_MID);              // d aP[p][p'] = d fP[p] . nP[p']
         mm<0, false>(jobs, L.dnP, AT_MID, L.aP, 1, P, L.df, 1, AT_CM, nullptr, P, AT_MID, P);              // d nP[p'][m] = sum_p aP[p][p'] d fP[p][m]
@@ -827,7 +783,6 @@ __global__ __launch_bounds__(AT_NT) void k_awp_tail_bwd(TailKParams p) {
             }
         }
         __syncthreads();
-        clk.mark(13);
         for (int s0 = 0; s0 < S; s0 += AT_NT / AT_LPS) {                                                  // d nI[s][m] = sum_p aS[p][s] d fI[p][m]  (into nI's place)
             const int s = s0 + sl;
             if (s < S) {
@@ -840,7 +795,6 @@ __global__ __launch_bounds__(AT_NT) void k_awp_tail_bwd(TailKParams p) {
         for (int row = tid >> 6; row < P; row += AT_NT / 64) softmax_row_bwd(L.aS + row * d.SA, L.daS + row * d.SA, S);
         if (tid >= AT_NT - 64 && tid - (AT_NT - 64) < P) softmax_small_bwd(L.aP + (tid - (AT_NT - 64)) * P, L.daP + (tid - (AT_NT - 64)) * P, P);
         __syncthreads();
-        clk.mark(14);
         float* dnI = L.nI;
         // d q = d lgP kP + d lgS kI;  d kP = d lgP^T q + d nP convn;  d kI = d lgS^T q + d nI convl
         const int wave = tid >> 6, lane = tid & 63, tr = 4 * (lane >> 4), tc = lane & 15;       // a tile16 result: rows tr .. tr + 3, column tc
@@ -877,7 +831,6 @@ __global__ __launch_bounds__(AT_NT) void k_awp_tail_bwd(TailKParams p) {
             }
         }
         __syncthreads();
-        clk.mark(15);
         // conva / convb / convc, and back through MAM.linear
         wacc(jobs, part + off[wb + TW_CONVA], L.dkP, AT_MID, L.li, AT_CM, P, AT_MID, AT_CM);
         if (wave == 2 || wave == 3) {                                                                 // d convb[m][c] = sum_s d kI[s][m] ls[s][c]
@@ -901,7 +854,6 @@ __global__ __launch_bounds__(AT_NT) void k_awp_tail_bwd(TailKParams p) {
             }
         }
         __syncthreads();
-        clk.mark(16);
         {   // d MAM.linear.weight [32][64] += d ls^T h_intra + d li^T h_inter: eight 16 x 16 tiles, one per wavefront (AT_NT / 64 == 8)
             const int ct = wave & 1, kt = wave >> 1;
             float* dst = part + off[wb + TW_LIN_W] + (16 * ct + tr) * AT_WS + 16 * kt + tc;
@@ -954,10 +906,8 @@ __global__ __launch_bounds__(AT_NT) void k_awp_tail_bwd(TailKParams p) {
         float *dx = L.dxa, *dprev = L.dxb;
         for (int l = nm - 1; l >= 0; --l) {
             __syncthreads();
-            clk.mark(l == nm - 1 ? 17 : 19);
             for (int i = tid; i < P * AT_CM; i += AT_NT) dx[i] = L.xs(l)[i] > 0.f ? dx[i] : 0.f;
             __syncthreads();
-            clk.mark(18);
             const int K = l == 0 ? d.IN0 : AT_CM;
             const float* xin = l == 0 ? L.x0 : L.xs(l - 1);
             wacc(jobs, part + off[2 * l], dx, AT_CM, xin, K, P, AT_CM, K);
@@ -966,7 +916,6 @@ __global__ __launch_bounds__(AT_NT) void k_awp_tail_bwd(TailKParams p) {
             float* t = dx; dx = dprev; dprev = t;
         }
         __syncthreads();
-        clk.mark(19);
         // dx: d [integrated features | view_feature | direction encoding] of every sub-exposure, [P][IN0]
         for (int i = tid; i < P * AT_WS; i += AT_NT) p.d_h[r * P * AT_WS + i] = dx[(i >> 6) * d.IN0 + (i & 63)];
         for (int j = tid; j < d.VC; j += AT_NT) {
@@ -976,7 +925,6 @@ __global__ __launch_bounds__(AT_NT) void k_awp_tail_bwd(TailKParams p) {
             else L.tmp[j - d.VF] = a;
         }
         __syncthreads();
-        clk.mark(20);
         if (tid < 3 * P) {
             float out = 0.f;
             if (tid < 3 && d.F >= 0) {                                 // awp.py:89-92: d (d / |d|) of the first sub-exposure's ray
@@ -1000,9 +948,7 @@ __global__ __launch_bounds__(AT_NT) void k_awp_tail_bwd(TailKParams p) {
             p.d_rays[r * P * 3 + tid] = out;
         }
         __syncthreads();
-        clk.mark(21);
     }
-    clk.flush(p.stamps);
 }
 
 struct TailReduceParams {
@@ -1106,9 +1052,9 @@ long evd_awp_tail_saved_floats(const evd_awp_tail_desc* d) {
 size_t evd_awp_tail_workspace_bytes(const evd_awp_tail_desc* d, long R, int backward) {
     if (!d || R < 0) return 0;
     const int grid = tail_grid(R > 0 ? R : 1);
-    if (!backward) return sizeof(double) * 2 * AT_CM * (size_t)grid + 1024;
+    if (!backward) return sizeof(double) * 2 * AT_CM * (size_t)grid + 512;
     const long total = evd_awp_tail_param_count(d);
-    return sizeof(float) * ((size_t)R * d->P * AT_CM + (size_t)tail_nblk(R) * tail_partB_stride(d->P) + (size_t)grid * (size_t)((total + 3) & ~3L)) + 2048;
+    return sizeof(float) * ((size_t)R * d->P * AT_CM + (size_t)tail_nblk(R) * tail_partB_stride(d->P) + (size_t)grid * (size_t)((total + 3) & ~3L)) + 1536;
 }
 
 int evd_awp_tail_forward(const evd_awp_tail_desc* d, const float* const* params, const float* h, const float* view_feature,
@@ -1134,7 +1080,6 @@ int evd_awp_tail_forward(const evd_awp_tail_desc* d, const float* const* params,
     k.h = h; k.vf = view_feature; k.rays_d = rays_d; k.h_inter = h_inter; k.h_intra = h_intra;
     k.y = saved_y; k.xg = saved_xg; k.saved = saved_rays;
     k.bn_part = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(workspace) + 63) & ~(uintptr_t)63);
-    k.stamps = reinterpret_cast<long long*>(static_cast<char*>(workspace) + evd_awp_tail_workspace_bytes(d, R, 0) - 512);
     const int grid = tail_grid(R);
     EVD_SET_MAX_LDS(k_awp_tail_fwd, 160 * 1024);
     k_awp_tail_fwd<<<grid, AT_NT, lds, as_stream(stream)>>>(k);
@@ -1186,7 +1131,6 @@ int evd_awp_tail_backward(const evd_awp_tail_desc* d, const float* const* params
     k.y = const_cast<float*>(saved_y); k.xg = const_cast<float*>(saved_xg); k.saved = const_cast<float*>(saved_rays);
     k.dz = dz; k.stats = saved_stats; k.partB = partB; k.nblkB = nblk; k.partB_stride = strideB;
     k.partA_stride = (total + 3) & ~3L;
-    k.stamps = reinterpret_cast<long long*>(static_cast<char*>(workspace) + evd_awp_tail_workspace_bytes(d, R, 1) - 512);
     k.d_h = d_h; k.d_vf = d_view_feature; k.d_rays = d_rays_d; k.d_hi = d_h_inter; k.d_hs = d_h_intra; k.partA = partA;
     EVD_SET_MAX_LDS(k_awp_tail_bwd, 160 * 1024 - (AT_NT / 64) * 64 * sizeof(double) - 1024);
     k_awp_tail_bwd<<<grid, AT_NT, lds, as_stream(stream)>>>(k);

@@ -448,8 +448,7 @@ int evd_mam_local_forward(const float* h_local, const float* u, long R, int P, i
     const size_t lds = sizeof(float) * ((size_t)2 * P * S + 2 * MAM_MAXP + (size_t)4 * P * MAM_C);
     constexpr size_t lds_max = sizeof(float) * ((size_t)2 * MAM_MAXP * MAM_MAXS + 2 * MAM_MAXP + (size_t)4 * MAM_MAXP * MAM_C);
     EVD_SET_MAX_LDS(k_mam_local_fwd, lds_max);
-    static const bool two_pass = getenv("EVD_MAM_TWO_PASS") != nullptr;       // developer switch: round 3's kernel
-    if (!two_pass && P <= 10 && S <= 128) {
+    if (P <= 10 && S <= 128) {
         EVD_SET_MAX_LDS((k_mam_local_fwd_r<10, 8>), lds_max);
         k_mam_local_fwd_r<10, 8><<<(unsigned)R, 256, lds, as_stream(stream)>>>(h_local, u, P, S, h_inter, h_intra, alpha, beta);
     } else

@@ -211,18 +211,8 @@ __device__ __forceinline__ void vs_geometry(const GridParams& g, const float (&p
 // GC channels per work item (4, or 8 when every n_comp is a multiple of 8): the gather is bound by the rate at which the texture
 // path takes lane addresses (PMC: TCP_TOTAL_CACHE_ACCESSES = one per lane and load; 1171 per wavefront, 300 k cycles per CU), so
 // the wider the per-lane load, the fewer of them: 8 float16 channels = one 16-byte load per tap.
-#ifdef EVD_VS_TRACE
-__device__ long long evd_vs_trace[8 * 8192];
-#define VS_STAMP(k) if (threadIdx.x == 0 && blockIdx.x < 8192) evd_vs_trace[blockIdx.x * 8 + (k)] = (long long)__builtin_readcyclecounter()
-extern "C" int evd_debug_vs_trace(long long* host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(evd_vs_trace), sizeof(evd_vs_trace)); }
-#else
-#define VS_STAMP(k)
-#endif
-#ifndef EVD_VS_WAVES
-#define EVD_VS_WAVES 4
-#endif
 template <bool HALF, int GC>
-__global__ __launch_bounds__(256, EVD_VS_WAVES) void k_voxel_sample(const GridParams g, const float* __restrict__ pts, long n,
+__global__ __launch_bounds__(256, 4) void k_voxel_sample(const GridParams g, const float* __restrict__ pts, long n,
                                                       float* __restrict__ out, int out_stride, int out_col) {
     __shared__ __attribute__((aligned(16))) float coef[VS_SAMPLES * VS_STRIDE];
     __shared__ __attribute__((aligned(16))) VsTaps taps[VS_SAMPLES * 3];
@@ -231,7 +221,6 @@ __global__ __launch_bounds__(256, EVD_VS_WAVES) void k_voxel_sample(const GridPa
     const int ng = ctot / GC;
     const long s0 = blockIdx.x * (long)VS_SAMPLES;
     const int items = VS_SAMPLES * ng;
-    VS_STAMP(0);
     // phase 2's operand, fetched first so that its latency hides behind the gather: the basis_mat GEMM of the block's 32 samples is
     // split along k over the four wavefronts (a quarter of the components each), every lane keeps its <= 16 basis values in registers
     const bool ksplit = g.app_dim <= 32 && ctot % 8 == 0;
@@ -252,7 +241,6 @@ __global__ __launch_bounds__(256, EVD_VS_WAVES) void k_voxel_sample(const GridPa
         taps[threadIdx.x] = tp;
     }
     __syncthreads();
-    VS_STAMP(1);
     constexpr int UNR = GC == 8 ? 2 : 3;         // n_comp (64,16,16): 32 samples x 12 (24) groups = 1.5 (3) items per thread
     for (int base = threadIdx.x; base < items; base += UNR * 256) {
         VsItem it[UNR][NV];
@@ -271,23 +259,17 @@ __global__ __launch_bounds__(256, EVD_VS_WAVES) void k_voxel_sample(const GridPa
             const _Float16* plh = sel3(i, g.plane_h[0], g.plane_h[1], g.plane_h[2]) + c4;
             const float* li = sel3(i, g.line[0], g.line[1], g.line[2]) + c4;
             const _Float16* lih = sel3(i, g.line_h[0], g.line_h[1], g.line_h[2]) + c4;
-#ifdef EVD_VS_ABL_NOLOAD
-            const long zero_ = (long)(threadIdx.x & 0);
-#define VS_IDX(x) (zero_ + ((x) & 0))
-#else
-#define VS_IDX(x) (x)
-#endif
             if (HALF && GC == 8) {                  // one 16-byte load per tap
                 typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const f16x8v v = *reinterpret_cast<const f16x8v*>(plh + VS_IDX(tp.ip[k]));
+                    const f16x8v v = *reinterpret_cast<const f16x8v*>(plh + tp.ip[k]);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) it[q][e >> 2].p[k][e & 3] = (float)v[e];
                 }
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
-                    const f16x8v v = *reinterpret_cast<const f16x8v*>(lih + VS_IDX(tp.il[k]));
+                    const f16x8v v = *reinterpret_cast<const f16x8v*>(lih + tp.il[k]);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) it[q][e >> 2].l[k][e & 3] = (float)v[e];
                 }
@@ -321,13 +303,7 @@ __global__ __launch_bounds__(256, EVD_VS_WAVES) void k_voxel_sample(const GridPa
             }
         }
     }
-    VS_STAMP(2);
     __syncthreads();
-    VS_STAMP(3);
-#ifdef EVD_VS_ABL_NOPHASE2
-    if (threadIdx.x < 32 && s0 + threadIdx.x < n) out[(s0 + threadIdx.x) * (long)out_stride + out_col] = coef[threadIdx.x * VS_STRIDE];
-    return;
-#endif
     if (ksplit) {
         const int lane = threadIdx.x & 63, col = lane & 31, hh = lane >> 5;
         f32x16 acc;
@@ -337,7 +313,6 @@ __global__ __launch_bounds__(256, EVD_VS_WAVES) void k_voxel_sample(const GridPa
 #pragma unroll
         for (int j = 0; j < VS_MAXC / 8; ++j)
             if (2 * j < kq) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bq[j], cf[2 * j], acc, 0, 0, 0);
-        VS_STAMP(4);
         __syncthreads();                         // every wavefront has read its coefficients: the array becomes the reduction buffer
         if (wv > 0) {
 #pragma unroll
@@ -356,14 +331,11 @@ __global__ __launch_bounds__(256, EVD_VS_WAVES) void k_voxel_sample(const GridPa
 #pragma unroll
             for (int r = 0; r < 16; ++r) ot[col * 33 + (r & 3) + 8 * (r >> 2) + 4 * hh] = act(g.app_act, acc[r]);
         }
-        VS_STAMP(5);
         __syncthreads();
-        VS_STAMP(6);
         for (int t = threadIdx.x; t < VS_SAMPLES * 32; t += 256) {
             const int sl = t >> 5, f = t & 31;
             if (s0 + sl < n && f < g.app_dim) out[(s0 + sl) * (long)out_stride + out_col + f] = ot[sl * 33 + f];
         }
-        VS_STAMP(7);
         return;
     }
     if (threadIdx.x >= 64) return;
@@ -436,7 +408,6 @@ __global__ __launch_bounds__(64 * VW_WAVES, OCC) void k_voxel_sample_w(const Gri
         const int i4 = threadIdx.x + q * 64 * VW_WAVES;
         bv[q] = i4 < nb4 ? *reinterpret_cast<const f32x4*>(g.basis + 4 * i4) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    VS_STAMP(0);
     if (s0 < n && lane < VW_SAMPLES * 3) {       // geometry of this wavefront's (sample, component) pairs
         const int sl = lane / 3, i = lane % 3;
         const long s = s0 + sl < n ? s0 + sl : n - 1;
@@ -456,7 +427,6 @@ __global__ __launch_bounds__(64 * VW_WAVES, OCC) void k_voxel_sample_w(const Gri
     }
     __syncthreads();                             // the only block-wide barrier: basis_mat visible (also orders the tap tables)
     if (s0 >= n) return;
-    VS_STAMP(1);
     const int items = VW_SAMPLES * ng;
     typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
     constexpr int UNR = 3;                       // 16 samples x 12 groups = 3 items per lane
@@ -475,18 +445,6 @@ __global__ __launch_bounds__(64 * VW_WAVES, OCC) void k_voxel_sample_w(const Gri
             if (c8 >= g.n_comp[0]) { c8 -= g.n_comp[0]; i = 1; if (c8 >= g.n_comp[1]) { c8 -= g.n_comp[1]; i = 2; } }
             comp[q] = i;
             const VsTaps& tp = taps[sl[q] * 3 + i];
-#ifdef EVD_VS_NO_LOADS        // developer ablation (tools/dev/gather_ablation.sh): everything but the grid loads (values made from the tap offsets)
-            if (true) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-#pragma unroll
-                    for (int v = 0; v < NRAW; ++v) rawp[q][k][v] = f32x4{(float)tp.ip[k], 1.f, 2.f, (float)c8};
-#pragma unroll
-                for (int k = 0; k < 2; ++k)
-#pragma unroll
-                    for (int v = 0; v < NRAW; ++v) rawl[q][k][v] = f32x4{(float)tp.il[k], 1.f, 2.f, (float)c8};
-            } else
-#endif
             if (HALF) {
                 const _Float16* plh = sel3(i, g.plane_h[0], g.plane_h[1], g.plane_h[2]) + c8;
                 const _Float16* lih = sel3(i, g.line_h[0], g.line_h[1], g.line_h[2]) + c8;
@@ -546,7 +504,6 @@ __global__ __launch_bounds__(64 * VW_WAVES, OCC) void k_voxel_sample_w(const Gri
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // this wavefront's LDS writes before its own reads: program order
     __builtin_amdgcn_wave_barrier();
-    VS_STAMP(2);
     // out^T[f, sample] = sum_k basis[f, k] coef[sample, k]:  D lane l, reg r = feature 16 tile + 4 (l / 16) + r, sample l % 16
     const int col = lane & 15, kh = lane >> 4;
     f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -584,7 +541,6 @@ __global__ __launch_bounds__(64 * VW_WAVES, OCC) void k_voxel_sample_w(const Gri
                 acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(pb1[j], pc[j], acc[1], 0, 0, 0);
             }
     }
-    VS_STAMP(3);
     __builtin_amdgcn_wave_barrier();             // every lane has read its coefficients: the slice becomes the output tile [16][VW_OS]
 #pragma unroll
     for (int tile = 0; tile < 2; ++tile) {
@@ -610,8 +566,6 @@ __global__ __launch_bounds__(64 * VW_WAVES, OCC) void k_voxel_sample_w(const Gri
             if (s0 + sl < n && f < g.app_dim) out[(s0 + sl) * (long)out_stride + out_col + f] = coef[sl * VW_OS + f];
         }
     }
-    VS_STAMP(4);
-    VS_STAMP(5); VS_STAMP(6); VS_STAMP(7);
 }
 
 typedef float vbw_f32x2 __attribute__((ext_vector_type(2)));
@@ -719,7 +673,6 @@ __global__ __launch_bounds__(64 * VM_WAVES, OCC) void k_voxel_sample_m(const Gri
     const long tiles = (n + 15) / 16;
     for (long tile = (long)blockIdx.x * VM_WAVES + wv; tile < tiles; tile += (long)gridDim.x * VM_WAVES) {
         const long s0 = tile * 16;
-        VS_STAMP(0);
         // (measured and dropped: the NEXT tile's points fetched here, one tile ahead -- 57.8 vs 56.7 us: their latency is not what the tile waits for)
         if (lane < 48) {                              // geometry of this wavefront's (sample, component) pairs, once each
             const int sl = lane / 3, i = lane % 3;
@@ -731,7 +684,6 @@ __global__ __launch_bounds__(64 * VM_WAVES, OCC) void k_voxel_sample_m(const Gri
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        VS_STAMP(1);
         constexpr int NRAW = HALF ? 1 : 2;
         f32x4 rawp[3][4][NRAW], rawl[3][2][NRAW];
         int tix[3];                                   // the item's row of the tap table: the weights are read again when the values have landed
@@ -767,7 +719,6 @@ __global__ __launch_bounds__(64 * VM_WAVES, OCC) void k_voxel_sample_m(const Gri
                 }
             }
         }
-        VS_STAMP(2);
         // The B operand's scale: a power of two that brings the sample's largest |coefficient| (over the four lanes of its column) into
         // [2^13, 2^14), so that the hi / lo split keeps 2^-22 of it -- unscaled, small coefficients fell into float16 subnormals and ones
         // above 65504 became inf (and the lo term NaN).  The three k steps add into one tile, so the scale is that of the running maximum
@@ -845,12 +796,8 @@ __global__ __launch_bounds__(64 * VM_WAVES, OCC) void k_voxel_sample_m(const Gri
                     acc[tl] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc[tl], 0, 0, 0);
                     acc[tl] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[tl], 0, 0, 0);
                 }
-#ifdef EVD_VM_SERIAL
-                __builtin_amdgcn_sched_barrier(0);        // one item after the other: the next item's values stay in their load registers
-#endif
             }
         }
-        VS_STAMP(3);
         // D: lane (col = sample, kb), register r = feature 16 tl + 4 kb + r: four consecutive floats of the sample's output row
         if (s0 + col < n) {
             typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
@@ -871,7 +818,6 @@ __global__ __launch_bounds__(64 * VM_WAVES, OCC) void k_voxel_sample_m(const Gri
                     for (int r = 0; r < 4; ++r) if (f0 + r < F) o[f0 + r] = v[r];
             }
         }
-        VS_STAMP(4);
         __builtin_amdgcn_wave_barrier();              // the tap table is rewritten by the next tile
     }
 }
@@ -903,11 +849,7 @@ __global__ __launch_bounds__(64 * VM_WAVES, OCC) void k_voxel_sample_m(const Gri
 // the box of the benchmark's NDC rays is 42-60 cells, 22-28 of them touched by the 128 taps): correct, and 0.92 -> 1.43 ms per 2^19
 // samples, iteration 22.6 -> 30.3 ms -- the walk is a chain of dependent LDS read-modify-writes, again.
 constexpr int VSB_MAXF = 64, VSB_TAPS = 18;
-#ifdef EVD_VSB_BATCH
-constexpr int VSB_BATCH = EVD_VSB_BATCH;
-#else
 constexpr int VSB_BATCH = 4;            // samples whose taps are in flight together in the gather phase of k_voxel_sample_bwd (divides 16)
-#endif
 // CT: the channel capacity the LDS rows are laid out for (MM: ctot <= CT, a multiple of 32).  With the shipped 96 channels and
 // app_dim 32 the block needs 50 KB of LDS and 168 VGPRs = three blocks per CU.  (Measured: three blocks run at the speed of two,
 // 1.21 ms = 249 G adds/s; a bare kernel of coalesced float atomics on random 64-byte runs sustains 318 - 328 G adds/s = 20 G requests/s
@@ -1357,19 +1299,10 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
     for (int c = 0; c < NCT; ++c)
 #pragma unroll
         for (int r = 0; r < 16; ++r) bacc[c][r] = 0.f;
-#ifdef EVD_VBW_STAMP    // developer build (tools/dev/stamp_scatter_w.py): shader-clock cycles of this wavefront's phases, summed over its tiles
-    long long tph[7] = {0, 0, 0, 0, 0, 0, 0}, tq0, tq1;
-#define EVD_VBW_T0() tq0 = __builtin_readcyclecounter()
-#define EVD_VBW_T(i) { tq1 = __builtin_readcyclecounter(); tph[i] += tq1 - tq0; tq0 = tq1; }
-#else
-#define EVD_VBW_T0()
-#define EVD_VBW_T(i)
-#endif
     float rmaxv = 0.f;                            // max |line row value| this lane wrote (k_scatter_lines' fixed-point scale: saves it a pass over the rows)
     const long wtiles = (n + VBW_SAMPLES - 1) / VBW_SAMPLES;
     for (long wt = (long)blockIdx.x * VBW_WAVES + wv; wt < wtiles; wt += (long)gridDim.x * VBW_WAVES) {
     const long s0 = wt * VBW_SAMPLES;
-    EVD_VBW_T0();
     // d out as the MFMA B operand: lane (col = sample, kh) holds d out[sample][4 step + kh]
     const int col = lane & 15, kh = lane >> 4;
     float dv[8];                                  // lane (col = sample, kh): d out[sample][8 kh .. 8 kh + 7]
@@ -1395,7 +1328,6 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
         }
     }
     wave_sync();                                  // the tap tables are the wavefront's own
-    EVD_VBW_T(0);
     // phase 1: D[channel 16 ct + 4 kh + r][sample col] = sum_f basis[f][channel] d out[sample][f]
     {
         float m = 0.f, binv;
@@ -1425,7 +1357,6 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
         }
     }
     wave_sync();
-    EVD_VBW_T(1);
     // phase 2: gather, 3 items per lane in flight
     const int items = VBW_SAMPLES * ng;
     // items in flight per lane and trip: three (144 registers of raw taps) -- two where the wavefront also carries the basis accumulators
@@ -1580,7 +1511,6 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
         }
     }
     wave_sync();
-    EVD_VBW_T(2);
     // the A operand of the basis gradient's MFMAs (d out[sample 2 u + kb][f = lane & 31]) is fetched HERE, in front of the plane taps'
     // atomics: the VM counter retires in order, a load issued behind them waits for every one of them (stamps: the 24 MFMAs of phase 5 took
     // 14 k cycles with their eight loads issued one by one behind the atomics, a fifth of the tile)
@@ -1625,7 +1555,6 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
         }
         coff += C;
     }
-    EVD_VBW_T(3);
     // phase 4: the point gradient of (sample, axis): the three quads' partial sums
     if (DPTS && lane < VBW_SAMPLES * 3) {
         const int sl = lane / 3, a = lane % 3;
@@ -1633,7 +1562,6 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
         for (int qd = 0; qd < (ng + 3) / 4; ++qd) sum += dpart[(sl * 3 + qd) * 3 + a];
         if (s0 + sl < n) d_pts[(s0 + sl) * 3 + a] = sum;
     }
-    EVD_VBW_T(4);
     {
         // phase 5: d basis_mat += d out^T . coef over the tile's 16 samples (coefficient rows: written to the slice by phase 2)
         const int mn = lane & 31, kb = lane >> 5;
@@ -1648,15 +1576,7 @@ __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const 
         }
     }
     wave_sync();                                  // the slice is rewritten by the next tile
-    EVD_VBW_T(5);
     }
-#ifdef EVD_VBW_STAMP
-    if (lane == 0 && rows_l) {
-        float* o = rows_l + ((long)blockIdx.x * VBW_WAVES + wv) * 8;
-        for (int i = 0; i < 6; ++i) o[i] = (float)tph[i];
-        o[6] = -7.f; o[7] = (float)((wtiles - ((long)blockIdx.x * VBW_WAVES + wv) + (long)gridDim.x * VBW_WAVES - 1) / ((long)gridDim.x * VBW_WAVES));
-    }
-#endif
     if (lmax) {
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) rmaxv = fmaxf(rmaxv, __shfl_xor(rmaxv, o));
@@ -1940,15 +1860,14 @@ int launch_merge_features_bwd(const float* d_out, int d_stride, const int* order
 
 int launch_voxel_sample(const GridParams& g, bool half_grids, const float* pts, long n, float* out, int out_stride, int out_col, hipStream_t st) {
     const bool wide = (g.n_comp[0] % 8 == 0) && (g.n_comp[1] % 8 == 0) && (g.n_comp[2] % 8 == 0);
-    static const bool no_w = env_flag("EVD_VS_BLOCK");      // developer switch: the block-cooperative kernel
-    if (wide && g.app_dim <= 32 && !no_w) {
+    if (wide && g.app_dim <= 32) {
         const unsigned blocks = (unsigned)cdiv(n, (long)VW_SAMPLES * VW_WAVES);
         const int ct = g.n_comp[0] + g.n_comp[1] + g.n_comp[2];
         const size_t lds = vw_basis_bytes(ct) + VW_WAVES * vw_slice_bytes(ct);
-        // float32 grids: 174 registers by default = two blocks per CU; compiled for three (168 registers, 5 spilled) -- EVD_VW_F32_OCC=2 selects the former
-        static const bool occ2 = []{ const char* e = getenv("EVD_VW_F32_OCC"); return e && e[0] == '2'; }();
-        // round 6: k_voxel_sample_m (coefficients straight into the float16 matrix core's operand layout); EVD_GATHER_FORM=w: rounds 3-5's kernel
-        static const bool form_w = []{ const char* e = getenv("EVD_GATHER_FORM"); return e && e[0] == 'w'; }();
+        // float32 grids: compiled for three blocks per CU (168 registers, 5 spilled); by default 174 registers = two (that instance since
+        // removed; see 807b468)
+        // round 6: k_voxel_sample_m (coefficients straight into the float16 matrix core's operand layout); rounds 3-5's kernel stays the
+        // float16 fallback
         long pmax_h = 0;
         for (int i = 0; i < 3; ++i) {
             const long pe = (long)g.grid[i == 2 ? 1 : 0] * g.grid[i == 0 ? 1 : 2] * g.n_comp[i];
@@ -1956,21 +1875,17 @@ int launch_voxel_sample(const GridParams& g, bool half_grids, const float* pts, 
         }
         // float16 grids only: on float32 grids (the float32-grade levels) the new form measures equal (67.1 vs 67.0 us) and the old kernel's
         // float32 matrix product is exact -- it stays
-        if (half_grids && !form_w && ct % 32 == 0 && ct <= 96 && pmax_h < (1L << 31)) {
+        if (half_grids && ct % 32 == 0 && ct <= 96 && pmax_h < (1L << 31)) {
             int cus = 256;
             { int dev = 0, v = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
             const long tiles = cdiv(n, 16L * VM_WAVES), cap = 8L * cus;
             const unsigned mb = (unsigned)(tiles < cap ? tiles : cap);
-#ifndef EVD_VM_OCC
-#define EVD_VM_OCC 3
-#endif
             // (three wavefronts per SIMD, 168 registers with the operand scaling, no spills; compiled for four -- 128 registers, 34 spilled -- it runs 70 instead of 57 us)
-            k_voxel_sample_m<true, EVD_VM_OCC><<<mb, 64 * VM_WAVES, 0, st>>>(g, pts, n, out, out_stride, out_col);
+            k_voxel_sample_m<true, 3><<<mb, 64 * VM_WAVES, 0, st>>>(g, pts, n, out, out_stride, out_col);
             EVD_LAUNCH_CHECK();
             return EVD_OK;
         }
         if (half_grids) k_voxel_sample_w<true, 4><<<blocks, 64 * VW_WAVES, lds, st>>>(g, pts, n, out, out_stride, out_col);
-        else if (occ2) k_voxel_sample_w<false, 2><<<blocks, 64 * VW_WAVES, lds, st>>>(g, pts, n, out, out_stride, out_col);
         else k_voxel_sample_w<false, 3><<<blocks, 64 * VW_WAVES, lds, st>>>(g, pts, n, out, out_stride, out_col);
         EVD_LAUNCH_CHECK();
         return EVD_OK;

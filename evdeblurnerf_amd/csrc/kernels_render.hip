@@ -1037,23 +1037,18 @@ int evd_raw2outputs(const float* raw, const float* z, const float* rays_d, int r
     if (R == 0) return EVD_OK;
     hipStream_t st = as_stream(stream);
     // interleaved form: the two channel layouts / activation sets the renderer produces (NeRF: rgb sigmoid, sigma last; PDRF levels: sigma
-    // first, colour already sigmoided -> relu (coarse) / none (fine)), with the training node's raw noise / density output (not rmnear).  EVD_COMPOSITE_FORM=rows:
-    // round 4's kernel; EVD_COMPOSITE_NT=0: plain loads / stores; EVD_COMPOSITE_RPW=1|2|4: rays per wavefront (default by R)
-    static const bool il_form = [] { const char* e = getenv("EVD_COMPOSITE_FORM"); return !e || e[0] == 'i'; }();
-    static const bool il_nt = [] { const char* e = getenv("EVD_COMPOSITE_NT"); return !e || e[0] != '0'; }();
-    static const int il_rpw_env = [] { const char* e = getenv("EVD_COMPOSITE_RPW"); return e ? atoi(e) : 0; }();
-    const int il_rpw = il_rpw_env ? il_rpw_env : (R >= (1L << 17) ? 4 : R >= (1L << 14) ? 2 : 1);     // >= 4 workgroups per CU before rays share a wavefront
-    if (il_form && n_rgb == 3 && C == 4 && S <= 256 && !(rmnear_thresh > 0.f) && sigma_act == EVD_ACT_RELU &&
+    // first, colour already sigmoided -> relu (coarse) / none (fine)), with the training node's raw noise / density output (not rmnear);
+    // non-temporal loads / stores, rays per wavefront by R
+    const int il_rpw = R >= (1L << 17) ? 4 : R >= (1L << 14) ? 2 : 1;     // >= 4 workgroups per CU before rays share a wavefront
+    if (n_rgb == 3 && C == 4 && S <= 256 && !(rmnear_thresh > 0.f) && sigma_act == EVD_ACT_RELU &&
         ((sigma_ch == 3 && rgb_ch0 == 0 && rgb_act == EVD_ACT_SIGMOID) ||
          (sigma_ch == 0 && rgb_ch0 == 1 && (rgb_act == EVD_ACT_RELU || rgb_act == EVD_ACT_NONE)))) {
-#define EVD_IL3(NCH, RPW, SC, RA, NT) k_composite_il<NCH, RPW, SC, RA, EVD_ACT_RELU, NT><<<(unsigned)cdiv(R, 4 * RPW), 256, 0, st>>>(raw, z, rays_d, rays_d_stride, R, S, white_bkgd, out_map, acc, weights, depth, noise, density)
-#define EVD_IL2(NCH, SC, RA, NT) do { if (il_rpw == 4) EVD_IL3(NCH, 4, SC, RA, NT); else if (il_rpw == 1) EVD_IL3(NCH, 1, SC, RA, NT); else EVD_IL3(NCH, 2, SC, RA, NT); } while (0)
-#define EVD_IL1(SC, RA, NT) do { if (S <= 64) EVD_IL2(1, SC, RA, NT); else if (S <= 128) EVD_IL2(2, SC, RA, NT); else if (S <= 192) EVD_IL2(3, SC, RA, NT); else EVD_IL2(4, SC, RA, NT); } while (0)
-#define EVD_IL0(SC, RA) do { if (il_nt) EVD_IL1(SC, RA, true); else EVD_IL1(SC, RA, false); } while (0)
-        if (sigma_ch == 3) EVD_IL0(3, EVD_ACT_SIGMOID);
-        else if (rgb_act == EVD_ACT_RELU) EVD_IL0(0, EVD_ACT_RELU);
-        else EVD_IL0(0, EVD_ACT_NONE);
-#undef EVD_IL0
+#define EVD_IL3(NCH, RPW, SC, RA) k_composite_il<NCH, RPW, SC, RA, EVD_ACT_RELU, true><<<(unsigned)cdiv(R, 4 * RPW), 256, 0, st>>>(raw, z, rays_d, rays_d_stride, R, S, white_bkgd, out_map, acc, weights, depth, noise, density)
+#define EVD_IL2(NCH, SC, RA) do { if (il_rpw == 4) EVD_IL3(NCH, 4, SC, RA); else if (il_rpw == 1) EVD_IL3(NCH, 1, SC, RA); else EVD_IL3(NCH, 2, SC, RA); } while (0)
+#define EVD_IL1(SC, RA) do { if (S <= 64) EVD_IL2(1, SC, RA); else if (S <= 128) EVD_IL2(2, SC, RA); else if (S <= 192) EVD_IL2(3, SC, RA); else EVD_IL2(4, SC, RA); } while (0)
+        if (sigma_ch == 3) EVD_IL1(3, EVD_ACT_SIGMOID);
+        else if (rgb_act == EVD_ACT_RELU) EVD_IL1(0, EVD_ACT_RELU);
+        else EVD_IL1(0, EVD_ACT_NONE);
 #undef EVD_IL1
 #undef EVD_IL2
 #undef EVD_IL3
@@ -1065,14 +1060,9 @@ int evd_raw2outputs(const float* raw, const float* z, const float* rays_d, int r
         return EVD_OK;
     }
     if (n_rgb == 3 && C == 4 && S <= 256) {
-        // bandwidth form: every lane owns SPL consecutive samples
-        static const int rpw = [] { const char* e = getenv("EVD_COMPOSITE_RPW"); return e ? atoi(e) : 2; }();
-#define EVD_ROWS(SPL) if (rpw == 4) k_composite_rows<SPL, 4><<<cdiv(R, 16), 256, 0, st>>>(raw, z, rays_d, rays_d_stride, R, S, sigma_ch, rgb_ch0, rgb_act, sigma_act, \
-                                                                      white_bkgd, rmnear_thresh, noise, out_map, density, acc, weights, depth); \
-                      else if (rpw == 2) k_composite_rows<SPL, 2><<<cdiv(R, 8), 256, 0, st>>>(raw, z, rays_d, rays_d_stride, R, S, sigma_ch, rgb_ch0, rgb_act, sigma_act, \
-                                                                      white_bkgd, rmnear_thresh, noise, out_map, density, acc, weights, depth); \
-                      else k_composite_rows<SPL, 1><<<cdiv(R, 4), 256, 0, st>>>(raw, z, rays_d, rays_d_stride, R, S, sigma_ch, rgb_ch0, rgb_act, sigma_act, \
-                                                                      white_bkgd, rmnear_thresh, noise, out_map, density, acc, weights, depth)
+        // bandwidth form: every lane owns SPL consecutive samples, two rays per wavefront
+#define EVD_ROWS(SPL) k_composite_rows<SPL, 2><<<cdiv(R, 8), 256, 0, st>>>(raw, z, rays_d, rays_d_stride, R, S, sigma_ch, rgb_ch0, rgb_act, sigma_act, \
+                                                                   white_bkgd, rmnear_thresh, noise, out_map, density, acc, weights, depth)
         if (S <= 64) EVD_ROWS(1);
         else if (S <= 128) EVD_ROWS(2);
         else if (S <= 192) EVD_ROWS(3);

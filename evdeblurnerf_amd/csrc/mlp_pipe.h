@@ -31,13 +31,9 @@ constexpr int pipe_fpc(int prec) { return PIPE_CB / frag_bytes(prec); }
 // max(x, 0) as ONE v_max_f32 (fmaxf() costs two: hipcc first canonicalises the operand, a signalling-NaN nicety;
 // here NaN in -> 0 out, where torch's relu propagates the NaN -- activations are finite)
 __device__ __forceinline__ float relu_f32(float x) {
-#ifdef EVD_PIPE_RELU_C
-    return fmaxf(x, 0.f);
-#else
     float y;
     asm("v_max_f32_e32 %0, 0, %1" : "=v"(y) : "v"(x));
     return y;
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -192,11 +188,7 @@ template <int PREC, int NS_, int NT_, int CB_ = PIPE_CB, bool HI_ONLY_ = false> 
     static constexpr int FPC = CB / FB;
     static constexpr int NSLOT = 4;
     static constexpr int PIECES = CB / 1024 / NW;        // 1 KiB DMA pieces per wavefront per chunk
-#ifdef EVD_PIPE_PD
-    static constexpr int PD = EVD_PIPE_PD;
-#else
     static constexpr int PD = PREC == EVD_PREC_F32 ? 2 : 4;   // A-fragment prefetch depth
-#endif
     static constexpr int SAMPLES = NW * NS_ * 32;        // samples per workgroup
     static constexpr int RING = NSLOT * CB;
     static constexpr int BIAS_FLOATS = 4096;
@@ -273,19 +265,11 @@ template <class C, bool STORES, int NCH> struct PStream {
     }
     // fragment fc of chunk c, this lane's 16 bytes
     __device__ __forceinline__ const char* frag(int c, int fc) const { return rd_base + (c & 3) * C::CB + fc * C::FB; }
-#ifdef EVD_ABL_DMA
-    __device__ __forceinline__ void chunk_begin(int c) {}
-#else
     __device__ __forceinline__ void chunk_begin(int c) { if (c + 3 < NCH) issue(c + 3); }
-#endif
     __device__ __forceinline__ void chunk_end(int c) {
-#ifndef EVD_ABL_DMA
         if (c + 3 < NCH && !STORES) wait_vmcnt<C::PIECES>();
         else wait_vmcnt<0>();
-#endif
-#ifndef EVD_ABL_BARRIER
         __builtin_amdgcn_s_barrier();
-#endif
         asm volatile("" ::: "memory");
     }
 };
@@ -391,14 +375,9 @@ template <class C, class L, bool FIRST, bool LAST> struct GroupSched {
 // The fragment stores of the training kernels are NON-TEMPORAL (round 6): the store is written once and read again by the backward a
 // millisecond later, from HBM either way (2.36 M fine-level samples x 66 KiB per 32 = 4.9 GB per iteration against 32 MB of L2); without the
 // cache allocation the fine level's training forward runs 1.446 -> 1.259 ms per iteration, the coarse one 0.231 -> 0.190, the backward
-// kernels that read the fragments unchanged (profiles/r06_act_nt_ab.log).  -DEVD_ACT_NO_NT restores the plain stores.
-#ifndef EVD_ACT_NO_NT
+// kernels that read the fragments unchanged (profiles/r06_act_nt_ab.log; the plain-store build since removed; see 807b468).
 #define EVD_ACT_ST(ptr, val) __builtin_nontemporal_store((val), (ptr))
 #define EVD_ACT_NT_ASM " nt"
-#else
-#define EVD_ACT_ST(ptr, val) (*(ptr) = (val))
-#define EVD_ACT_NT_ASM ""
-#endif
 template <int FB = 1024, class F> __device__ __forceinline__ void act_store(char* act_lane, int slot, const F& frag) {
     static_assert(sizeof(F) == 16 || (sizeof(F) == 32 && FB == 2048), "16-byte fragments, or hi / lo pairs in 2 KiB slots");
     if constexpr (sizeof(F) == 16) {
@@ -473,16 +452,9 @@ __device__ __forceinline__ void pipe_group(ST& st, Pipe<C>& pp, typename C::O::B
         for (int t = 0; t < G; ++t) {
             const int f = (P * KTOT + j) * G + t;        // fragment index inside the layer
             const int fc = (L::FOFF + f) % FPC, c = L::CHUNK0 + (L::FOFF + f) / FPC;
-#ifdef EVD_PIPE_DMA_EARLY
-            if (fc == 0) st.chunk_begin(c);
-#endif
             {   // prefetch fragment f + PD - 1 (possibly the next layer's) into the register set freed by step f - 1
                 const int idx = f + PD - 1;
-#ifdef EVD_ABL_LDS
-                if ((idx < NF || L::NEXT_G > 0) && idx < PD) {
-#else
                 if (idx < NF || L::NEXT_G > 0) {
-#endif
                     const int v = idx < NF ? L::FOFF + idx : ENDV + (idx - NF);
                     pp.abuf[(L::AOFF + idx) % PD] = O::load_a(st.frag(L::CHUNK0 + v / FPC, v % FPC));
                 }
@@ -493,11 +465,7 @@ __device__ __forceinline__ void pipe_group(ST& st, Pipe<C>& pp, typename C::O::B
 #pragma unroll
                 for (int i = 0; i < S::drate; ++i) {         // epilogue units of the previous group
                     const int u = S::units_thru(m - 1) + i;
-#ifdef EVD_ABL_DRAIN
-                    if (u < S::units_thru(m) && u < 1) {
-#else
                     if (u < S::units_thru(m)) {
-#endif
                         const int dt = u / (NS * 8), ds = (u / 8) % NS, k = u % 8;
                         if (FIRST) {
                             float* fr = (L::PFEAT_TILE0 >= 0 && frow[ds]) ? frow[ds] + 32 * (L::PFEAT_TILE0 + dt) + 8 * (k >> 1) + 4 * h : nullptr;
@@ -546,9 +514,7 @@ __device__ __forceinline__ void pipe_group(ST& st, Pipe<C>& pp, typename C::O::B
                 O::mma(pp.acc[cur][t][s], pp.accx[cur][t][s], pp.abuf[(L::AOFF + f) % PD], in[s][j], j == 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
-#ifndef EVD_PIPE_DMA_EARLY
             if (fc == (FPC > 2 ? 1 : 0)) st.chunk_begin(c);      // after the first MFMAs of the chunk: the matrix pipe restarts right behind the barrier
-#endif
             if (fc == FPC - 1) st.chunk_end(c);
         }
     }
@@ -638,11 +604,7 @@ __device__ __forceinline__ void pipe_prime(ST& st, Pipe<C>& pp, const float* __r
 // Absolute error ~ |a| 2^-24 + 2^-20 (|a| < 800 rad here): far below the 2^-8 / 2^-11 operand rounding of the
 // bf16 / f16 modes that use it; the float32-grade modes keep sin_or_cos().
 __device__ __forceinline__ float sin_or_cos_hw(float a, int h) {
-#ifdef EVD_PIPE_EXACT_TRIG
-    return sin_or_cos(a, h);
-#else
     return __builtin_amdgcn_sinf(fmaf(a, 0.15915494309189535f, h ? 0.25f : 0.f));
-#endif
 }
 
 // ... with the compensated float16 mode's sines (mlp_pipe_c.h c_sin_rev): x / 2 pi in two floats, 2^k (hi part) exact, its fract exact, the

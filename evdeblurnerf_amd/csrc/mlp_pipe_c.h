@@ -29,15 +29,6 @@
 
 namespace evd {
 
-// developer ablations (tools/ablate_c.sh compiles variants): 1 / 2 skip the first / second fp6 product, 4 drain every chunk end fully,
-// 8 no weight DMA, 16 no barrier, 32 no epilogue, 64 no float16 fragment reads, 128 no fp6 operand reads, 256 no fp6 conversions, 512 no epilogue pairs,
-// 1024 the second fp6 operand is not read (the first one is used twice)
-#ifdef EVD_C_ABL
-constexpr int kAbl = EVD_C_ABL;
-#else
-constexpr int kAbl = 0;
-#endif
-
 // pointers into LDS that keep their address space when they are rebuilt from a (laundered) byte offset: ds_read with immediate offsets
 typedef const __attribute__((address_space(3))) float* lds_f32_p;
 typedef const __attribute__((address_space(3))) f32x4* lds_f32x4_p;
@@ -52,16 +43,8 @@ typedef _Float16 f16x32 __attribute__((ext_vector_type(32)));
 
 struct CCfg {
     static constexpr int NT = 256, NW = 4, CB = PIPE_CB, FB = 1024, UPC = CB / 1024, PIECES = CB / 1024 / NW;
-#ifdef EVD_C_NSLOT
-    static constexpr int NSLOT = EVD_C_NSLOT;
-#else
     static constexpr int NSLOT = 4;                          // ring slots: 2 chunks resident, NSLOT - 2 in flight (8 slots measured: no faster, the kernel is LDS-bandwidth-bound)
-#endif
-#ifdef EVD_C_BARP
-    static constexpr int BARP = EVD_C_BARP;
-#else
     static constexpr int BARP = 1;                           // chunks per barrier (2 needs NSLOT >= 8)
-#endif
     static constexpr int PDM = 4;                            // ring of prefetched float16 A fragments: PDM - 1 MFMAs ahead (8: no faster)
     static constexpr int SAMPLES = NW * 32;
     static constexpr int RING = NSLOT * CB;
@@ -84,7 +67,7 @@ static inline long cmin_l(long a, long b) { return a < b ? a : b; }
 
 // Weight stream of this mode: the ring protocol of mlp_pipe.h's PStream (two chunks resident, counted vmcnt, one barrier per 16 KiB
 // chunk) with a deeper ring and a cheaper issue.  NSLOT slots: at the top of chunk c (behind the barrier that ended chunk c-1) chunks
-// c and c+1 are resident, c+2 .. c+NSLOT-2 in flight, the slot of c-1 is free; chunk_begin(c) issues chunk c+NSLOT-1 into it,
+// c and c+1 are resident, c+2 .. c+NSLOT-2 in flight, the slot of c-1 is free; chunk c+NSLOT-1 is issued into it (issue_piece),
 // chunk_end(c) waits until this wavefront's pieces of chunk c+2 have landed (everything younger stays in flight) and crosses the barrier.
 // With one wavefront per SIMD nothing else hides the L2 -> LDS latency (under load well above the 2 chunk-times a 4-slot ring gives).
 // Issue: the chunk's source is  SGPR base + 32-bit lane offset  (one v_add per chunk instead of a 64-bit add per piece); M0 is set and
@@ -99,9 +82,6 @@ template <int NCH> struct CStream {
     const char* rd_base;    // ring base + 16 * lane (fragment reads)
     unsigned voff;          // this lane's byte offset of piece 0 of chunk 0
     unsigned dst0;          // LDS byte offset of this wavefront's piece 0 in slot 0 (wave-uniform)
-#ifdef EVD_C_STAMP          // developer build: shader-clock cycles this wavefront spends in the vmcnt wait / in the barrier of chunk_end
-    long long tw = 0, tb = 0;
-#endif
     static_assert(CCfg::PIECES == 4, "four 1 KiB pieces per wavefront per chunk");
     __device__ __forceinline__ void issue(int c) {          // c is a compile-time constant at every call site
         const unsigned off = voff + (unsigned)c * CCfg::CB;
@@ -114,11 +94,6 @@ template <int NCH> struct CStream {
     // one 1 KiB piece k of chunk c (the pieces of a chunk go out one at a time, three consumed units apart: the LDS takes the DMA writes in
     // four short bursts between the fragment reads instead of one long one)
     __device__ __forceinline__ void issue_piece(int c, int k) {
-#ifdef EVD_C_M0_PER_PIECE
-        const unsigned off = voff + (unsigned)c * CCfg::CB + (unsigned)k * 1024;
-        const unsigned dst = dst0 + (unsigned)(c & (NSLOT - 1)) * CCfg::CB + (unsigned)k * 1024;
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(off), "s"(gbase), "s"(dst) : "memory");
-#else
         // M0 (the LDS base of the chunk's slot) is set by the chunk's first piece and stays: nothing else in these kernels touches M0, and the
         // instruction offset moves the global and the LDS address together (as in issue()) -- 6 scalar instructions per chunk fewer in a
         // kernel whose issue slots are as full as its matrix pipe (measured on one box: 0.904 -> 0.890 ms)
@@ -130,7 +105,6 @@ template <int NCH> struct CStream {
         else if (k == 1) asm volatile("global_load_lds_dwordx4 %0, %1 offset:1024" : : "v"(off), "s"(gbase) : "memory");
         else if (k == 2) asm volatile("global_load_lds_dwordx4 %0, %1 offset:2048" : : "v"(off), "s"(gbase) : "memory");
         else asm volatile("global_load_lds_dwordx4 %0, %1 offset:3072\n\ts_mov_b32 m0, %2" : : "v"(off), "s"(gbase), "s"(dst_next) : "memory");
-#endif
     }
     __device__ __forceinline__ void set_m0_for(int c) {       // M0 = LDS base of chunk c's slot (see issue_piece)
         const unsigned dst = dst0 + (unsigned)(c & (NSLOT - 1)) * CCfg::CB;
@@ -176,22 +150,10 @@ template <int NCH> struct CStream {
         wait_chunks(cmax(0, cmin(AHEAD, NCH) - (BARP + 1)));
         __syncthreads();
     }
-    __device__ __forceinline__ void chunk_begin(int c) { if (c + AHEAD < NCH && !(kAbl & 8)) issue(c + AHEAD); }
     __device__ __forceinline__ void chunk_end(int c) {
         if ((c + 1) % BARP != 0) return;
-        if (kAbl & 4) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#ifdef EVD_C_STAMP
-        const long long t0 = __builtin_readcyclecounter();
-#endif
-        wait_chunks((kAbl & 8) ? 0 : cmax(0, cmin(c + AHEAD, NCH - 1) - (c + BARP + 1)));
-#ifdef EVD_C_STAMP
-        const long long t1 = __builtin_readcyclecounter();
-#endif
-        if (!(kAbl & 16)) __builtin_amdgcn_s_barrier();
-#ifdef EVD_C_STAMP
-        const long long t2 = __builtin_readcyclecounter();
-        tw += t1 - t0; tb += t2 - t1;
-#endif
+        wait_chunks(cmax(0, cmin(c + AHEAD, NCH - 1) - (c + BARP + 1)));
+        __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     }
 };
@@ -330,7 +292,7 @@ struct CLayer {
     static constexpr int NMAIN = KSTEPS * TILES_;
     static_assert(TILES_ % G_ == 0 && (G_ == 1 || G_ == 2), "groups of one or two tiles");
     static_assert(NMAIN % CCfg::PDM == 0, "the float16 fragment ring keeps its phase across layers");
-    static_assert(UNITS % CCfg::UPC == 0 || UNITS % CCfg::UPC >= 2, "a layer's last chunk must reach its chunk_begin");
+    static_assert(UNITS % CCfg::UPC == 0 || UNITS % CCfg::UPC >= 2, "a layer's last chunk must reach its second unit");
 };
 
 // register state that flows from layer to layer
@@ -427,15 +389,14 @@ __device__ __forceinline__ void c_group(ST& st, CPipe& pp, XBlk (&in)[NIN], XBlk
 #pragma unroll
         for (int i = 0; i < drate; ++i) {
             const int u = units_thru(s - 1) + i;
-            if (u < units_thru(s) && !(kAbl & 32)) {
+            if (u < units_thru(s)) {
                 XBlk& dst = FIRST ? in[L::PDB] : out[P > 0 ? P - 1 : 0];
                 if (u < DG * 8) {
-                    if (kAbl & 512) continue;
                     static_assert(DG == 0 || DG == 2, "blocks are drained from groups of two tiles");
                     if (u == 0) pp.m = 0u;
                     if (FIRST) c_drain_pair<L::PRELU>(pp.acc[oth][0], pp.acc[oth][1], u, dst, pp.m);
                     else c_drain_pair<L::RELU>(pp.acc[oth][0], pp.acc[oth][1], u, dst, pp.m);
-                } else if (!(kAbl & 256)) {
+                } else {
                     c_finish(dst, pp.m, pp.acc[oth][0], pp.acc[oth][1]);
                     if constexpr (TRAIN) {
                         if constexpr (FIRST) {
@@ -473,10 +434,10 @@ __device__ __forceinline__ void c_group(ST& st, CPipe& pp, XBlk (&in)[NIN], XBlk
     // of chunk c (the matrix pipe has restarted behind the barrier by then), the barrier that releases chunk c its last unit
     auto chunks = [&](int t0, int t1) __attribute__((always_inline)) {
         const int c0 = t0 / CCfg::UPC, c1 = t1 / CCfg::UPC;
-#ifndef EVD_C_NOSPREAD      // (all four pieces at the chunk's second unit: 1.4 % slower)
+        // (the four pieces issued together at the chunk's second unit measured 1.4 % slower)
         auto due = [](int t) constexpr { return cmin(CCfg::PIECES, (t + 1) / 3); };      // pieces issued once t units of the chunk are consumed: at 2, 5, 8, 11
         auto pieces = [&](int c, int k0, int k1) __attribute__((always_inline)) {
-            if (c + ST::AHEAD >= ST::kChunks || (kAbl & 8)) return;
+            if (c + ST::AHEAD >= ST::kChunks) return;
 #pragma unroll
             for (int k = 0; k < CCfg::PIECES; ++k)
                 if (k >= k0 && k < k1) st.issue_piece(c + ST::AHEAD, k);
@@ -488,14 +449,6 @@ __device__ __forceinline__ void c_group(ST& st, CPipe& pp, XBlk (&in)[NIN], XBlk
             st.chunk_end(L::CHUNK0 + c0);
             pieces(L::CHUNK0 + c1, 0, due(t1 % CCfg::UPC));
         }
-#else
-        if (c0 == c1) {
-            if (t0 % CCfg::UPC < 2 && t1 % CCfg::UPC >= 2) st.chunk_begin(L::CHUNK0 + c0);
-        } else {
-            st.chunk_end(L::CHUNK0 + c0);
-            if (t1 % CCfg::UPC >= 2) st.chunk_begin(L::CHUNK0 + c1);
-        }
-#endif
     };
 
     int s = 0, ub = ubase, mm = mbase;      // all three are compile-time constants after unrolling
@@ -529,12 +482,12 @@ __device__ __forceinline__ void c_group(ST& st, CPipe& pp, XBlk (&in)[NIN], XBlk
                             ringoff = c_ring_off<NXT>(u);
                         }
                     }
-                    if (u >= 0 && !(kAbl & 64)) pp.am[(mm + LA) % CCfg::PDM] = *reinterpret_cast<const f16x8*>(st.rd_base + ringoff);
+                    if (u >= 0) pp.am[(mm + LA) % CCfg::PDM] = *reinterpret_cast<const f16x8*>(st.rd_base + ringoff);
                 }
 #pragma unroll
                 for (int q = 0; q < per_slot; ++q) {            // fp6 parts of this block, consumed by its last 2 G slots
                     const int c = i * per_slot + q;
-                    if (c < ncl && !(kAbl & 128) && !((kAbl & 1024) && (c >> 1) / G == 1)) {      // (1024: the second fp6 operand is not read: what deriving it from the float16 fragments would save)
+                    if (c < ncl) {
                         const int kt = c >> 1, part = c & 1;    // kt = kind * G + tile
                         const int kind = kt / G, tt = kt % G;
                         if (part == 0) {
@@ -571,12 +524,10 @@ __device__ __forceinline__ void c_group(ST& st, CPipe& pp, XBlk (&in)[NIN], XBlk
                 // otherwise parks a block's scale word in an AGPR and then emits the MFMA with it -- "Operand has incorrect register class")
                 int sca = (int)pp.wsc[cur][t], scb = (int)in[b].sc;
                 if (TRAIN) asm("" : "+v"(sca), "+v"(scb));
-                if (kind == 0 && (kAbl & 1)) {}
-                else if (kind == 1 && (kAbl & 2)) {}
-                else if (kind == 0)
+                if (kind == 0)
                     pp.acc[cur][t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(pp.ac[0][t], in[b].qh, pp.acc[cur][t], 2, 2, 0, sca, 0, scb);
                 else
-                    pp.acc[cur][t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(pp.ac[(kAbl & 1024) ? 0 : 1][t], in[b].ql, pp.acc[cur][t], 2, 2, 1, sca, 1, scb);
+                    pp.acc[cur][t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(pp.ac[1][t], in[b].ql, pp.acc[cur][t], 2, 2, 1, sca, 1, scb);
                 __builtin_amdgcn_sched_barrier(0);
                 const int last = 2 * G - 1;
                 chunks(lo16 + i, i == last ? hi8 + G : lo16 + i + 1);
@@ -615,13 +566,11 @@ __device__ __forceinline__ void c_layer(ST& st, CPipe& pp, XBlk (&in)[NIN], XBlk
     static_assert(NIN >= L::NBLK, "input blocks");
     CGroupLoop<L, NXT, ST, NIN, NOUT, 0, TRAIN>::run(st, pp, in, out, bias, lane, act);
     if (L::UNITS % CCfg::UPC != 0) {             // the zero-padded tail of the layer's last chunk
-#ifndef EVD_C_NOSPREAD
         constexpr int c = L::CHUNK0 + L::UNITS / CCfg::UPC, k0 = cmin(CCfg::PIECES, (L::UNITS % CCfg::UPC + 1) / 3);
-        if (c + ST::AHEAD < ST::kChunks && !(kAbl & 8)) {
+        if (c + ST::AHEAD < ST::kChunks) {
 #pragma unroll
             for (int k = k0; k < CCfg::PIECES; ++k) st.issue_piece(c + ST::AHEAD, k);
         }
-#endif
         st.chunk_end(L::CHUNK0 + L::UNITS / CCfg::UPC);
     }
     if constexpr (!std::is_void<NXT>::value) {       // first fragments of the next layer that the last group could not prefetch (c_group)

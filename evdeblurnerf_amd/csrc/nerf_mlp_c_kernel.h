@@ -112,9 +112,6 @@ __global__ __launch_bounds__(CCfg::NT, 1) void k_nerf_mlp_c(const MlpParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     pipe_fp16_saturate<EVD_PREC_F16>();
-#ifdef EVD_C_STAMP
-    const long long t_start = __builtin_readcyclecounter();
-#endif
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = lane & 31, h = lane >> 5;
     ST st0;
@@ -219,9 +216,6 @@ __global__ __launch_bounds__(CCfg::NT, 1) void k_nerf_mlp_c(const MlpParams p) {
 
     if (h == 0 && valid && (!FUSE || p.raw)) {
         f32x4 o = {rraw[0], rraw[1], rraw[2], araw[0]};   // cat([rgb, alpha]) nerf.py:157
-#ifdef EVD_C_STAMP      // lane 0 of every wavefront reports (cycles in the vmcnt waits, in the barriers, in the kernel) instead of its sample
-        if (lane == 0) o = f32x4{(float)cx.st.tw, (float)cx.st.tb, (float)(__builtin_readcyclecounter() - t_start), -1.f};
-#endif
         *reinterpret_cast<f32x4*>(p.raw + sidx * 4) = o;
     }
     if constexpr (FUSE) {
@@ -270,9 +264,6 @@ __global__ __launch_bounds__(CCfg::NT, 1) void k_nerf_mlp_c(const MlpParams p) {
             }
         }
     }
-#ifdef EVD_C_STAMP
-    st0.tw = cx.st.tw; st0.tb = cx.st.tb;
-#endif
     if (!more) break;
     tile += gridDim.x;
     }

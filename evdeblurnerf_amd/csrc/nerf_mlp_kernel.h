@@ -179,10 +179,6 @@ __global__ __launch_bounds__(NT, NT / 256) void k_nerf_mlp(const MlpParams p) {
     cx.nofrow = nofrow;
 
     cx.st.start_wait();
-#ifdef EVD_PIPE_SHIFT
-#pragma unroll
-    for (int i = 0; i < EVD_PIPE_SHIFT; ++i) asm volatile("s_nop 0");
-#endif
     pipe_prime<C, typename N::L0>(cx.st, cx.pp, bias, lane);
     {
         B in_pe[NS][PE_KS];

@@ -277,7 +277,7 @@ template <int PREC> __device__ __forceinline__ unsigned half_one_pair() { return
 // which it publishes through LDS for the others.  The stored fragments arrive by LDS-DMA (one global_load_lds_dwordx4 = one
 // 1 KiB fragment, no registers in flight) into a ring of WG_RING tiles per wavefront, WG_RING - 1 tiles ahead of their use,
 // with counted vmcnt waits; only the owning wavefront reads its slots, so the ring needs no barrier.  (Measured: a ring of 4 with a
-// single-buffered exchange runs at the same speed; with the products or the barrier ablated, EVD_ABL_WG_*, the kernel is no faster:
+// single-buffered exchange runs at the same speed; with the products or the barrier ablated (a developer build since removed; see 807b468) the kernel is no faster:
 // it is bound by its stream of fragment loads at ~3.7 TB/s.)
 constexpr int WG_RING = 3;
 constexpr int wgrad_lds_bytes(int CT) { return WG_RING * 8 * 4 * 1024 + 2 * CT * 2 * 1024; }
@@ -317,9 +317,6 @@ __global__ __launch_bounds__(WGRAD_NT) void k_wgrad(const WgradParams p) {
     const long ox0 = xown ? (long)(p.x_slot + 2 * wave) * 1024 : oy0, ox1 = xown ? ox0 + 1024 : oy0;
     const unsigned ring0 = lds_offset_of(raw) + wave * 4096;
     auto issue = [&](long t, int stage) {
-#ifdef EVD_ABL_WG_NODMA
-        return;
-#endif
         if (t >= p.tiles) return;
         const char* g = p.store + t * p.tile_bytes + lane * 16;
         const unsigned dst = __builtin_amdgcn_readfirstlane(ring0 + stage * (8 * 4096));
@@ -353,10 +350,7 @@ __global__ __launch_bounds__(WGRAD_NT) void k_wgrad(const WgradParams p) {
 #pragma unroll
             for (int q = 0; q < 2; ++q) *reinterpret_cast<W4*>(xb + (wave * 2 + q) * 1024 + lane * 16) = xt[q];
         }
-#ifndef EVD_ABL_WG_NOBAR
         __syncthreads();
-#endif
-#ifndef EVD_ABL_WG_NOPROD
 #pragma unroll
         for (int c = 0; c < CPG; ++c) {
             if (c0 + c < CT) {
@@ -371,9 +365,6 @@ __global__ __launch_bounds__(WGRAD_NT) void k_wgrad(const WgradParams p) {
 #pragma unroll
             for (int q = 0; q < 2; ++q) accb = mfma_half<PREC>(yt[q], ones, accb);
         }
-#else
-        acc[0] = mfma_half<PREC>(yt[0], yt[1], acc[0]);
-#endif
     }
     float* out = p.partial + (((long)blockIdx.x * RT + rt) * NC) * 1024 + lane * 16;
     auto put = [&](int c, const f32x16& a) {
@@ -413,9 +404,6 @@ struct WgradFusedParams {
 };
 
 constexpr int FUSED_WL = 6;        // W^T fragments per wavefront kept in LDS instead of registers (k_wgrad_dgrad)
-#ifdef EVD_WD_STAMP
-__device__ float g_wd_stamp[32 * 2048 * 8];
-#endif
 
 // RT_ < 8 (round 5: sigma_net.1 = [geo rows | sigma row], 4 + 1 row tiles): wavefronts RT_ .. 7 own no gradient rows (no wgrad products,
 // no partial blocks), the dgrad runs over the first KD_ gradient fragments (the last row tile may be a single fragment: KD_ = 2 RT_ - 1).
@@ -491,23 +479,12 @@ __global__ __launch_bounds__(WGRAD_NT) void k_wgrad_dgrad(const WgradFusedParams
     for (int j = 0; j < KD - WL; ++j) asm volatile("" : "+v"(wt[j].w[0]), "+v"(wt[j].w[1]), "+v"(wt[j].w[2]), "+v"(wt[j].w[3]));
 #pragma unroll
     for (int k = 0; k < WG_RING - 1; ++k) issue(t + k * stride, k);
-#ifdef EVD_WD_STAMP     // developer build (tools/dev/stamp_wgrad_dgrad.sh): shader-clock cycles of this wavefront's phases summed over its tiles
-    long long wph[6] = {0, 0, 0, 0, 0, 0}, wq0, wq1;
-    int wtiles = 0;
-#define EVD_WD_T0() wq0 = __builtin_readcyclecounter()
-#define EVD_WD_T(i) { wq1 = __builtin_readcyclecounter(); wph[i] += wq1 - wq0; wq0 = wq1; }
-#else
-#define EVD_WD_T0()
-#define EVD_WD_T(i)
-#endif
     for (int it = 0; t < p.tiles; t += stride, ++it) {
-        EVD_WD_T0();
         issue(t + (WG_RING - 1) * stride, (it + WG_RING - 1) % WG_RING);
         const int later = (t + stride < p.tiles ? 1 : 0) + (t + 2 * stride < p.tiles ? 1 : 0);
         if (later == 2) wait_vmcnt<8>();
         else if (later == 1) wait_vmcnt<4>();
         else wait_vmcnt<0>();
-        EVD_WD_T(0);
         // the transposition selectors and the bias column are re-made per tile (a dozen VALU instructions) instead of living in 12 registers
         // next to 128 + 16 accumulators and the 64 registers of W^T: the kernel spilled into its loop, and scratch loads drain the VM counter
         W4 sel0, sel1, ones;
@@ -556,9 +533,7 @@ __global__ __launch_bounds__(WGRAD_NT) void k_wgrad_dgrad(const WgradFusedParams
 #pragma unroll
             for (int q = 0; q < 2; ++q) *reinterpret_cast<W4*>(xb + (xw * 2 + q) * 1024 + lane * 16) = xt[q];
         }
-        EVD_WD_T(1);
         __syncthreads();
-        EVD_WD_T(2);
 #pragma unroll
         for (int c = 0; c < CPG; ++c) {
             if (c0 + c < CT && (RT_ == 8 || yown)) {
@@ -573,7 +548,6 @@ __global__ __launch_bounds__(WGRAD_NT) void k_wgrad_dgrad(const WgradFusedParams
 #pragma unroll
             for (int q = 0; q < 2; ++q) accb = mfma_half<PREC>(yt[q], ones, accb);
         }
-        EVD_WD_T(3);
         // d X tile `wave` = W^T rows . G: gradient fragment j sits in wavefront j / 2's ring slot, fragment j & 1
         if (down) {
             f32x16 d = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -607,20 +581,8 @@ __global__ __launch_bounds__(WGRAD_NT) void k_wgrad_dgrad(const WgradFusedParams
                                            grad_scale(*fp.maxbits, true));
             }
         }
-        EVD_WD_T(4);
         __syncthreads();            // every wavefront is done with this tile's ring slots before any of them issues into the oldest one
-        EVD_WD_T(5);
-#ifdef EVD_WD_STAMP
-        ++wtiles;
-#endif
     }
-#ifdef EVD_WD_STAMP
-    if (lane == 0) {                // [kind = CT + 8 YGEN ...][block][wavefront][8] floats, read back by evd_debug_wd_stamps
-        float* sp = g_wd_stamp + ((long)(CT + (YGEN ? 8 : 0) + (RT_ < 8 ? 16 : 0)) * 2048 + (long)blockIdx.x * 8 + wave) * 8;
-        for (int i = 0; i < 6; ++i) sp[i] = (float)wph[i];
-        sp[6] = (float)wtiles; sp[7] = -7.f;
-    }
-#endif
     if (RT_ < 8 && !yown) return;           // (the reduce reads RT_ row tiles of every workgroup's 8-tile set: WreduceParams::part_stride)
     float* out = p.partial + (((long)blockIdx.x * RT + rt) * NC) * 1024 + lane * 16;
     auto put = [&](int c, const f32x16& a) {
@@ -844,9 +806,8 @@ __global__ __launch_bounds__(WGRAD_NT) void k_wgrad_dgrad_p(const WgradFusedPara
 template <int PREC, int CT, int TO, int OMASK, int RT_ = 8, int KD_ = 16, bool YGEN = false, bool ROWS = false>
 static int launch_wgrad_dgrad(const WgradFusedParams& p, int blocks, hipStream_t st) {
     if (ROWS != (p.rows != nullptr)) return fail(EVD_E_INVALID, "k_wgrad_dgrad: the row output goes with the ROWS instantiation");
-    // a layer without a bias gradient: the pipelined one-barrier form (EVD_BWD_PIPE=0: the two-barrier kernel for every layer)
-    static const bool pipe_on = [] { const char* e = getenv("EVD_BWD_PIPE"); return !(e && e[0] == '0'); }();
-    if (pipe_on && !p.w.bias && CT <= 5) {
+    // a layer without a bias gradient: the pipelined one-barrier form; the two-barrier kernel otherwise
+    if (!p.w.bias && CT <= 5) {
         const size_t ldsp = (size_t)WG_RING * 8 * 4 * 1024 + (size_t)2 * CT * 2048 + (size_t)8 * FUSED_WL_P * 1024;
         if constexpr (CT <= 5) {
             EVD_SET_MAX_LDS((&k_wgrad_dgrad_p<PREC, CT, TO, OMASK, RT_, KD_, YGEN, ROWS>), ldsp);

@@ -9,11 +9,10 @@
 
 #include "mlp_pipe.h"
 #include "voxel.h"
-#ifndef EVD_RES_NT
-#define EVD_RES_NT 512      // threads of k_voxel_mlp_resident: two wavefronts per SIMD (198 registers in the split-float16 mode); -DEVD_RES_NT=256: one (A/B)
-#endif
 
 namespace evd {
+
+constexpr int RES_NT = 512;      // threads of k_voxel_mlp_resident: two wavefronts per SIMD (198 registers in the split-float16 mode); 256 threads, one, was the A/B
 
 // Fragment slots of the PDRF activation / gradient store (training path), per 32-sample tile, for a level with hidden width HD,
 // G geo channels and FT feature channels in: what the forward saves, then the gradients the dgrad chain hands to wgrad.
@@ -328,7 +327,7 @@ __global__ __launch_bounds__(NT, 1) void k_voxel_mlp_resident(const VoxMlpParams
 // the level's TRAINING forward on the resident stream (HD = 64 levels; the caller falls back to k_voxel_mlp_pipe's TRAIN variant otherwise)
 template <int PREC, int HD, int G, int FT, bool HI_ONLY>
 static int launch_voxel_resident_train(const VoxMlpParams& p, hipStream_t st) {
-    constexpr int NT = EVD_RES_NT;
+    constexpr int NT = RES_NT;
     typedef PipeCfg<PREC, 1, NT, PIPE_CB, HI_ONLY> C;
     typedef VoxNet<C, HD, G, FT, false, true> N;
     typedef PResident<C, N::NCH> ST;
@@ -351,7 +350,7 @@ static int launch_voxel_resident_level(const VoxMlpParams& p, hipStream_t st) {
     static const bool pipe_form = [] { const char* e = getenv("EVD_COARSE_FORM"); return e && !strcmp(e, "pipe"); }();
     // (a launch of less than one tile group per CU and wavefront slot does not repay the 48-80 KiB copy: 333 x 17 samples 17.2 against 14.4 us)
     if (pipe_form || p.nsamp < 65536) return launch_voxel_pipe_level<PREC, HD, G, FT>(p, st);
-    constexpr int NT = EVD_RES_NT;
+    constexpr int NT = RES_NT;
     typedef PipeCfg<PREC, 1, NT> C;
     typedef VoxNet<C, HD, G, FT, false, false> N;
     typedef PResident<C, N::NCH> ST;

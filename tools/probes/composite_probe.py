@@ -1,6 +1,5 @@
-"""Timing of the compositing scan on 2^20 rays x 128 samples (GPU box): the form selected by the environment
-(EVD_COMPOSITE_FORM=rows|stream, EVD_COMPOSITE_BPC, EVD_LIB_PATH for a variant library), its outputs' checksum, and torch's copy / sum
-on the same bytes as the yardsticks.  tools/dev/composite_ab.sh runs the combinations."""
+"""Timing of the compositing scan on 2^20 rays x 128 samples (GPU box; EVD_LIB_PATH for a variant library), its outputs' checksum,
+and torch's copy / sum on the same bytes as the yardsticks (PROBE_YARDSTICKS=1).  tools/pmc_composite.sh runs it under the profiler."""
 import os, sys, ctypes as C
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import torch
@@ -18,7 +17,7 @@ def t(fn, n=20):
     for _ in range(n): fn()
     e1.record(); e1.synchronize(); return e0.elapsed_time(e1) / n
 rd_bytes = Rc * S * 20 + Rc * 12
-tag = f"form={os.environ.get('EVD_COMPOSITE_FORM', 'default')} lib={os.path.basename(os.environ.get('EVD_LIB_PATH', 'default'))}"
+tag = f"lib={os.path.basename(os.environ.get('EVD_LIB_PATH', 'default'))}"
 for name, fn, b in (("full", lambda: run(), rd_bytes + Rc * S * 4 + Rc * 20), ("no weights store", lambda: run(False), rd_bytes + Rc * 20),
                     ("pdrf layout, rgb act none", lambda: run(True, "none", 0), rd_bytes + Rc * S * 4 + Rc * 20)):
     ms = t(fn); print(f"[{tag}] {name:26s} {ms:.3f} ms  {b / ms / 1e6:.0f} GB/s = {b / ms / 1e6 / 8000:.3f} of 8 TB/s")
