@@ -60,7 +60,7 @@ inline long cdiv(long a, long b) { return (a + b - 1) / b; }
 // activations: reference networks/nerf.py:31-33, networks/pdrf/voxnerf.py:28-30
 __device__ __forceinline__ float act(int code, float x) {
     switch (code) {
-    case EVD_ACT_RELU: return fmaxf(x, 0.f);
+    case EVD_ACT_RELU: return x > 0.f ? x : (x == x ? 0.f : x);     // torch.relu: NaN stays NaN (fmaxf(NaN, 0) would be 0)
     case EVD_ACT_SIGMOID: return 1.f / (1.f + expf(-x));
     case EVD_ACT_EXP: return expf(x);
     case EVD_ACT_SIGMOID1: return 1.002f / (expf(-x) + 1.f) - 0.001f;

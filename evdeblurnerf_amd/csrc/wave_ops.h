@@ -41,7 +41,7 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 // IEEE expf + division of evd::act() made the scan VALU-bound: 3.8 instead of 5.2 TB/s)
 __device__ __forceinline__ float act_fast(int code, float x) {
     if (code == EVD_ACT_SIGMOID) return __builtin_amdgcn_rcpf(1.f + __expf(-x));
-    if (code == EVD_ACT_RELU) return fmaxf(x, 0.f);
+    if (code == EVD_ACT_RELU) return x > 0.f ? x : (x == x ? 0.f : x);     // NaN propagates, as in act() and torch.relu
     if (code == EVD_ACT_NONE) return x;
     return act(code, x);
 }
