@@ -9,8 +9,6 @@ and the state dict expect them; a module or a shape the kernels are not built fo
 from __future__ import annotations
 
 import ctypes as C
-import os
-
 import weakref
 
 import torch
@@ -157,7 +155,7 @@ class _MamLocal(torch.autograd.Function):
 
 class _LocalConsumers(torch.autograd.Function):
     """h_local's two consumers behind the embedding -- the feature integration (awp.py:102) and the MAM's per-sample part (mam.py:29-33,
-    72-74) -- as ONE autograd node: its backward lets the second kernel ADD into the d h_local the first one wrote, where two nodes hand
+    72-74) -- as ONE autograd node: its backward is one launch that reads h_local once and writes d h_local once, where two nodes hand
     autograd two [R P, S, 64] tensors to sum (a pass over 3 x 335 MB at the blurfactory shape).  -> (h [R P, 64], h_inter, h_intra)"""
 
     @staticmethod
@@ -182,23 +180,16 @@ class _LocalConsumers(torch.autograd.Function):
     def backward(ctx, g_h, g_inter, g_intra):
         f, zz, dd, uu, alpha, beta, h_inter, h_intra = ctx.saved_tensors
         R, P, S, Cc = ctx.dims
-        N, lib = R * P, L.lib()
+        lib = L.lib()
         d_f = torch.empty_like(f)
         d_z = torch.empty_like(zz) if ctx.needs_input_grad[1] else None
         d_d = torch.empty_like(dd) if ctx.needs_input_grad[2] else None
         d_u = torch.empty((R, Cc), dtype=torch.float32, device=f.device)
         amax = torch.zeros((1,), dtype=torch.int32, device=f.device)
-        if os.environ.get("EVD_AWP_LOCAL_BWD") == "separate":      # developer switch: the two kernels, the second adding into the first one's result
-            L.check(lib.evd_awp_feature_integration_bwd(L.ptr(f), L.ptr(zz), L.ptr(dd), L.ptr(g_h.contiguous().float()), N, S, Cc, L.ptr(d_f), L.ptr(d_z),
-                                                        L.ptr(d_d), L.stream_ptr()), "evd_awp_feature_integration_bwd")
-            L.check(lib.evd_mam_local_backward(L.ptr(f), L.ptr(uu), L.ptr(alpha), L.ptr(beta), L.ptr(h_inter), L.ptr(h_intra),
-                                               L.ptr(g_inter.contiguous().float()), L.ptr(g_intra.contiguous().float()), R, P, S, Cc, L.ptr(d_f), L.ptr(d_u),
-                                               1, L.ptr(amax), L.stream_ptr()), "evd_mam_local_backward")
-        else:                                                       # one launch: h_local read once, d h_local written once
-            L.check(lib.evd_awp_local_consumers_backward(L.ptr(f), L.ptr(uu), L.ptr(alpha), L.ptr(beta), L.ptr(h_inter), L.ptr(h_intra),
-                                                         L.ptr(g_inter.contiguous().float()), L.ptr(g_intra.contiguous().float()), L.ptr(zz), L.ptr(dd),
-                                                         L.ptr(g_h.contiguous().float()), R, P, S, Cc, L.ptr(d_f), L.ptr(d_u), L.ptr(d_z), L.ptr(d_d),
-                                                         L.ptr(amax), L.stream_ptr()), "evd_awp_local_consumers_backward")
+        L.check(lib.evd_awp_local_consumers_backward(L.ptr(f), L.ptr(uu), L.ptr(alpha), L.ptr(beta), L.ptr(h_inter), L.ptr(h_intra),
+                                                     L.ptr(g_inter.contiguous().float()), L.ptr(g_intra.contiguous().float()), L.ptr(zz), L.ptr(dd),
+                                                     L.ptr(g_h.contiguous().float()), R, P, S, Cc, L.ptr(d_f), L.ptr(d_u), L.ptr(d_z), L.ptr(d_d),
+                                                     L.ptr(amax), L.stream_ptr()), "evd_awp_local_consumers_backward")
         _DH_ABSMAX.clear()
         _DH_ABSMAX[d_f.data_ptr()] = (amax, weakref.ref(d_f), d_f._version)
         sh = ctx.shapes
@@ -392,7 +383,7 @@ class FusedAWP(torch.nn.Module):
         self.output_ch = awpnet.output_ch
         self.graph_per_ray = bool(graph_per_ray)
         self._graphed = {}
-        self.tail_kernels = bool(tail_kernels) and not self.graph_per_ray and os.environ.get("EVD_AWP_TAIL", "1") != "0" and self._tail_structure()
+        self.tail_kernels = bool(tail_kernels) and not self.graph_per_ray and self._tail_structure()
         self._F = _dir_freqs(awpnet.ray_dirs_embed_fn) if self.tail_kernels else None
         self._tail_refused = set()
 

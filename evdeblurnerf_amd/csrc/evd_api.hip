@@ -420,26 +420,6 @@ static int render_rays_impl(const evd_nerf* coarse, const evd_nerf* fine, const 
     float* zs = take(r * (Ni ? Ni : 1) * 4);
     int rc;
     float* zc = (Ni ? (out->z_vals0 ? out->z_vals0 : z0) : (out->z_vals ? out->z_vals : z0));
-    // the whole step in ONE launch where the compensated float16 kernel can take it: z stratification in its prologue, raw2outputs in
-    // its epilogue (nerf_mlp_c_kernel.h FUSE); z / raw / weights reach HBM only where the caller asked for them
-    // Measured (4096 x 128): 0.869 ms per step against 0.864 with the separate kernels -- at one wavefront per SIMD the serial prologue /
-    // epilogue costs more than the two small launches it saves, so it is opt-in (EVD_FUSE_STEP=1); tests/test_gpu_fullsize.py covers it.
-    const bool no_fuse = !env_flag("EVD_FUSE_STEP") || z_done;
-    if (!Ni && cfg->precision == EVD_PREC_F16C && coarse->pipe_chunks[EVD_PREC_F16C] > 0 && (S == 32 || S == 64 || S == 128) && !noise0 &&
-        !out->feature && !no_fuse && !(!cfg->is_train && coarse->rmnear > 0.f)) {
-        MlpParams p{};
-        p.wstream = (const char*)coarse->pipe_c.data.p;
-        p.nchunks = coarse->pipe_chunks[EVD_PREC_F16C];
-        p.wscale = (const unsigned*)coarse->pipe_c.scales.p;
-        p.bias = (const float*)coarse->bias.p;
-        p.nbias = (int)(coarse->bias.bytes / sizeof(float));
-        p.ray_batch = rb; p.z = nullptr; p.nsamp = R * (long)S; p.S = S; p.ncol = 11; p.D = coarse->D; p.skip = coarse->skip;
-        p.raw = out->raw; p.feature = nullptr; p.feature_kind = 0; p.act = nullptr;
-        p.fuse = 1; p.lindisp = cfg->lindisp; p.perturb = cfg->perturb > 0.f; p.t_rand = t_rand;
-        p.rgb_act = coarse->rgb_act; p.sigma_act = coarse->sigma_act; p.white_bkgd = cfg->white_bkgd;
-        p.z_out = out->z_vals; p.rgb_map = out->rgb; p.depth_map = out->depth; p.acc_map = out->acc; p.weights = out->weights;
-        return nerf_mlp_c_dispatch(coarse->W, coarse->D, coarse->skip, p, as_stream(stream));
-    }
     if (!z_done && (rc = evd_sample_z(cfg, rb, nc, R, t_rand, zc, stream))) return rc;
     auto pass = [&](const evd_nerf* net, const float* z, int Sp, const float* noise, float* rgb, float* depth, float* acc,
                     float* weights, float* raw_out, float* feat) -> int {
@@ -479,8 +459,8 @@ int evd_nerf_render(const evd_nerf* coarse, const evd_nerf* fine, const evd_rend
     if (!workspace || workspace_bytes < need)
         return fail(EVD_E_WORKSPACE, "evd_nerf_render: workspace %zu < %zu bytes", workspace_bytes, need);
     float* rb = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    // ray packing and z stratification in ONE launch (they are 44 B per ray and 4 B per sample), unless the step-fusing kernel wants z itself
-    const bool fused_z = cfg->use_viewdirs && cfg->N_samples >= 1 && !env_flag("EVD_FUSE_STEP");
+    // ray packing and z stratification in ONE launch (they are 44 B per ray and 4 B per sample)
+    const bool fused_z = cfg->use_viewdirs && cfg->N_samples >= 1;
     int rc = fused_z ? evd_ray_batch_z(cfg, rays, R, t_rand, rb, render_z_slot(cfg, R, out, workspace), stream) : evd_ray_batch(cfg, rays, R, rb, stream);
     if (rc) return rc;
     return render_rays_impl(coarse, fine, cfg, rb, R, t_rand, u, noise0, noise1, out, workspace, workspace_bytes, stream, fused_z);

@@ -5,6 +5,6 @@
 
 namespace evd {
 
-int launch_nerf_train_fwd_f16c(const MlpParams& p, hipStream_t st) { return launch_nerf_c<256, 8, 4, false, true>(p, st); }
+int launch_nerf_train_fwd_f16c(const MlpParams& p, hipStream_t st) { return launch_nerf_c<256, 8, 4, true>(p, st); }
 
 }  // namespace evd

@@ -53,10 +53,9 @@ struct CCfg {
     static_assert((NSLOT & (NSLOT - 1)) == 0 && NSLOT >= 4 && NSLOT - BARP >= BARP + 1 && NSLOT - BARP >= 3 && TOTAL <= 160 * 1024, "ring geometry");
 };
 
-// workgroups of a persistent launch of the f16c kernels: one per CU (one wavefront per SIMD; EVD_C_BLOCKS overrides, 0 = one per tile)
+// workgroups of a persistent launch of the f16c kernels: one per CU (one wavefront per SIMD)
 static inline int c_persistent_blocks() {
     static const int n = [] {
-        if (const char* e = getenv("EVD_C_BLOCKS")) { const int v = atoi(e); return v > 0 ? v : 0x7fffffff; }
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
         return cus;

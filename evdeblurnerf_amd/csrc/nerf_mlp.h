@@ -65,11 +65,6 @@ struct MlpParams {
     int pe_l, pe_lv;        // multires / multires_views (generic kernels; the pipelined ones are built for PE_L / PE_LV)
     int no_views;           // use_viewdirs=False network: one output_linear head tile after the hidden layers, no view direction columns
     const unsigned* wscale; // compensated float16 mode: row-scale words, 32 per output tile in bias order (pack.h StreamBuilderC), else null
-    // fused render step of the compensated float16 kernel (nerf_mlp_c_kernel.h, FUSE): z stratification in the prologue (renderer.py:163-178),
-    // raw2outputs in the epilogue (nerf.py:74-129); z / raw / weights are written only where a pointer is given
-    int fuse, lindisp, perturb, rgb_act, sigma_act, white_bkgd;
-    const float* t_rand;    // [R, S] or null
-    float *z_out, *rgb_map, *depth_map, *acc_map, *weights;
 };
 
 // Activation / gradient store of the training path, in 1 KiB fragments per 32-sample tile (W = 256, D = 8):

@@ -195,10 +195,9 @@ template <int PREC, int HD, int G, int FT, bool FEAT = false, bool HI_ONLY = fal
 static int launch_voxel_train_fwd(const VoxMlpParams& p, hipStream_t st) {
     // the 64-wide level in the split-float16 arithmetic (the coarse level of the f16c / f16m / f16x3 training modes): weight stream resident in
     // LDS, persistent workgroups -- iteration f16c 11.37 -> 11.24 ms, f16m 12.93 -> 12.81; in the single-product modes this kernel already runs two
-    // workgroups per CU and the resident form measures 197 against 189 us: not used there (profiles/r06_coarse_train_ab.log).  EVD_COARSE_FORM=pipe: this kernel
+    // workgroups per CU and the resident form measures 197 against 189 us: not used there (profiles/r06_coarse_train_ab.log)
     if constexpr (HD == 64 && !FEAT && PREC == EVD_PREC_F16X3) {
-        static const bool pipe_form = [] { const char* e = getenv("EVD_COARSE_FORM"); return e && !strcmp(e, "pipe"); }();
-        if (!pipe_form && p.nsamp >= 65536) return launch_voxel_resident_train<PREC, HD, G, FT, HI_ONLY>(p, st);
+        if (p.nsamp >= 65536) return launch_voxel_resident_train<PREC, HD, G, FT, HI_ONLY>(p, st);
     }
     constexpr int NT = is_half_prec(PREC) ? 512 : 256, OCC = is_half_prec(PREC) ? 2 : 1;     // split-float16: one wavefront per SIMD
     typedef PipeCfg<PREC, 1, NT, PIPE_CB, HI_ONLY> C;
@@ -346,10 +345,8 @@ static int launch_voxel_resident_train(const VoxMlpParams& p, hipStream_t st) {
 
 template <int PREC, int HD, int G, int FT>
 static int launch_voxel_resident_level(const VoxMlpParams& p, hipStream_t st) {
-    // EVD_COARSE_FORM=pipe (developer switch): the streaming kernel of rounds 3-5 (A/B)
-    static const bool pipe_form = [] { const char* e = getenv("EVD_COARSE_FORM"); return e && !strcmp(e, "pipe"); }();
     // (a launch of less than one tile group per CU and wavefront slot does not repay the 48-80 KiB copy: 333 x 17 samples 17.2 against 14.4 us)
-    if (pipe_form || p.nsamp < 65536) return launch_voxel_pipe_level<PREC, HD, G, FT>(p, st);
+    if (p.nsamp < 65536) return launch_voxel_pipe_level<PREC, HD, G, FT>(p, st);
     constexpr int NT = RES_NT;
     typedef PipeCfg<PREC, 1, NT> C;
     typedef VoxNet<C, HD, G, FT, false, false> N;

@@ -1,5 +1,5 @@
-// Wave-level DPP primitives and the fast activations of the compositing scan, shared by kernels_render.hip (k_composite_rows) and the
-// fused step of the compensated-float16 NeRF kernel (nerf_mlp_c_kernel.h).
+// Wave-level DPP primitives and the fast activations of the compositing scan (kernels_render.hip); the MAM, AWP-tail and voxel kernels
+// share the DPP sums.
 #pragma once
 
 #include "evd_common.h"

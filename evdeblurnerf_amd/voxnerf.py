@@ -3,7 +3,6 @@ VoxelNeRFSampleFeatures :284) on libevdnerf.so: tri-plane feature gather, sigma/
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -20,10 +19,10 @@ def _np32(v):
 
 # Grid gradients of the training path.  DEFAULT: plain autograd returns (torch.autograd.grad, backward(inputs=...), tensor hooks and
 # post-accumulate-grad hooks all work on the grid leaves).  OPT-IN (set_grads_in_place(True), or NeRFAll.enable_training(...,
-# grads_in_place=True), or EVD_GRADS_IN_PLACE=1): the scatter / TV backward kernels add straight into the leaves' .grad and return
+# grads_in_place=True)): the scatter / TV backward kernels add straight into the leaves' .grad and return
 # None to autograd -- valid ONLY for a plain loss.backward() followed by optimizer.step() (what run_nerf.py:593-601 does); it saves
 # zeroing and re-adding 165 MB of gradient tensors eleven times per blurfactory iteration.
-_GRADS_IN_PLACE = os.environ.get("EVD_GRADS_IN_PLACE", "0") == "1"
+_GRADS_IN_PLACE = False
 
 
 def set_grads_in_place(on: bool):

@@ -184,22 +184,38 @@ def test_gather_into_a_row_window_and_merge_in_place():
 
 
 @pytest.mark.parametrize("prec", ["f16x3", "f16"])
-def test_resident_coarse_level_equals_the_streaming_kernel(prec, tmp_path):
+def test_resident_coarse_level_equals_the_streaming_kernel_on_slices(prec):
     """The 64-wide level's render pass on the weight stream resident in LDS (k_voxel_mlp_resident, round 6: persistent workgroups, no ring, no
     barrier) keeps the streaming kernel's layer table, arithmetic and order of operations: colour, depth, acc and weights of 4096 x 64 samples are
-    BIT FOR BIT those of k_voxel_mlp_pipe (EVD_COARSE_FORM=pipe; the switch is read once per process, hence the two subprocesses)."""
-    import subprocess
-    outs = []
-    for form in ("resident", "pipe"):
-        env = dict(os.environ)
-        env.pop("EVD_COARSE_FORM", None)
-        if form == "pipe":
-            env["EVD_COARSE_FORM"] = "pipe"
-        out = tmp_path / f"{form}.npy"
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "dev", "coarse_form_check.py"), str(out), prec], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        assert f"[{form}, {prec}] 4096 x 64" in r.stdout, r.stdout
-        outs.append(np.load(out))
-    a, b = outs
-    assert a.size == b.size == 4096 * (3 + 1 + 1 + 64) and np.isfinite(a).all()
+    BIT FOR BIT those of k_voxel_mlp_pipe.  The form is picked by size (the resident kernel from 65536 samples on), so the same rays go through
+    evd_voxel_forward once whole and once in slices of at most 1023 rays; the compositing kernel behind the networks takes the same form for
+    both (one ray per wavefront below 16384 rays), and the C entry is called with feature = NULL, as the c2f render calls the coarse level."""
+    from evdeblurnerf_amd import _lib as L
+    from evdeblurnerf_amd.voxnerf import VoxelNeRFRayFeatures
+    nvox = W.BLURFACTORY_COARSE_VOXELS
+    sd = W.make_pdrf_state_dict(61, W.pdrf_grid_size(AABB[0], AABB[1], nvox), input_ch=95, hidden_dim=64, geo_feat_dim=15)
+    net = VoxelNeRFRayFeatures(sd, "", AABB, num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, input_ch=95, app_dim=32,
+                               app_n_comp=(64, 16, 16), n_voxels=nvox, precision=prec)
+    R, S = 4096, 64
+    rs = np.random.RandomState(3)
+    pts = T(rs.uniform(-1, 1, (R, S, 3)).astype(np.float32))
+    d = rs.normal(size=(R, 3))
+    vd = T((d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32))
+    fts = T((0.3 * rs.normal(size=(R, S, 32))).astype(np.float32))
+    z = torch.linspace(0, 1, S, device="cuda").expand(R, S).contiguous()
+    rd = T(d.astype(np.float32))
+    need = int(L.lib().evd_voxel_forward_workspace_bytes(net._h, R, S))
+    ws = torch.empty((need,), dtype=torch.uint8, device="cuda")
+
+    def forward(step):
+        out = [torch.full(sh, float("nan"), device="cuda") for sh in ((R, 3), (R,), (R,), (R, S))]
+        for r0 in range(0, R, step):
+            n = min(step, R - r0)
+            color, depth, acc, wts = (t[r0:r0 + n] for t in out)
+            L.check(L.lib().evd_voxel_forward(net._h, L.PREC[prec], L.ptr(pts[r0:r0 + n]), L.ptr(vd[r0:r0 + n]), 3, L.ptr(fts[r0:r0 + n]), 32,
+                                              L.ptr(z[r0:r0 + n]), L.ptr(rd[r0:r0 + n]), 3, n, S, 0, L.ptr(color), L.ptr(depth), L.ptr(acc),
+                                              L.ptr(wts), None, L.ptr(ws), need, L.stream_ptr()), "evd_voxel_forward")
+        return np.concatenate([N(t).reshape(-1) for t in out])
+    a, b = forward(R), forward(1023)         # k_voxel_mlp_resident (262144 samples), k_voxel_mlp_pipe (<= 65472 per launch)
+    assert a.size == b.size == R * (3 + 1 + 1 + S) and np.isfinite(a).all()
     assert (a.view(np.uint32) == b.view(np.uint32)).all(), float(np.abs(a - b).max())

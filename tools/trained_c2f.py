@@ -87,9 +87,8 @@ def train_c2f(iters=3000, rays_per_iter=4096, seed=31, precision="f16", lr_net=1
     return sd, report
 
 
-def c2f_parity(O, sd, precisions=("f32", "f16x3", "f16", "bf16"), n_rays=4096, n_oracle=256, Ni=64, rays=None, env=None):
-    """RGB L-inf (fine, coarse) of each mode vs the oracle on n_oracle rays spread over the batch.  env: {precision: {VAR: value}} set while
-    that mode's model is built and rendered (developer switches such as EVD_F32_GRIDS)."""
+def c2f_parity(O, sd, precisions=("f32", "f16x3", "f16", "bf16"), n_rays=4096, n_oracle=256, Ni=64, rays=None):
+    """RGB L-inf (fine, coarse) of each mode vs the oracle on n_oracle rays spread over the batch."""
     from evdeblurnerf_amd.renderer import NeRFAll
     lo, hi = W.BLURFACTORY_AABB
     gc, gf = W.pdrf_grid_size(lo, hi, W.BLURFACTORY_COARSE_VOXELS), W.pdrf_grid_size(lo, hi, W.BLURFACTORY_FINE_VOXELS)
