@@ -983,6 +983,7 @@ static int event_loss_bwd(const evd_crf* crf_ev, int skip_learn, int add_bii_fea
                           float* d_start, float* d_end, float* d_start0, float* d_end0, float* d_params, void* stream) {
     EVD_REQUIRE(crf_ev && start && end && cum_neg && cum_pos && d_start && d_end && N >= 0, "evd_event_loss_bwd: bad arguments");
     EVD_REQUIRE(add_bii_feat >= 0 && add_bii_feat <= 2, "evd_event_loss_bwd: add_bii_feat %d", add_bii_feat);
+    EVD_REQUIRE(add_bii_feat == 0 || crf_ev->p.map_type != 2 || crf_ev->p.E == 2, "evd_event_loss_bwd: bii features need extra_features == 2");
     EVD_REQUIRE(!color_mask || tonemap_only, "evd_event_loss_bwd: a colour mask needs tonemap_only");
     EVD_REQUIRE(add_bii_feat != 2 || color_mask, "evd_event_loss_bwd: color-pos-neg features need the colour mask");
     hipStream_t st = as_stream(stream);
