@@ -45,15 +45,10 @@ struct AwpFwdParams {
 
 struct AwpBwdGrads { float *w[AWP_D], *b[AWP_D]; };     // device float32, nn.Linear layouts; null = not wanted
 
-struct AwpBwdPlan {
+struct AwpBwdPlan : BwdPlanBase {   // no side stream, no accumulation; the loss-scale word is the first of the store's trailer
     const float* d_h_local;     // [n, 64]
     const unsigned* d_h_absmax; // float bits of max |d_h_local| when the producer took it, or null
-    long nsamp, tiles;
-    char* store;
     const char* wt[AWP_D];      // W_l^T fragment streams
-    const int* maps;
-    float* partial;
-    int wgrad_blocks;
     float* d_geo_rows;          // [n, 128] float32 out, or null
     AwpBwdGrads grads;
 };

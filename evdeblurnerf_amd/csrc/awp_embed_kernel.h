@@ -175,6 +175,7 @@ __global__ __launch_bounds__(256) void k_frag_absmax(const char* __restrict__ st
     }
 }
 
+// (every wgrad with min(tiles, wgrad_blocks) workgroups: BwdChain::tile_grid; no side stream, the parameter gradients are overwritten)
 template <int PREC> static int run_awp_backward(const AwpBwdPlan& b, hipStream_t st) {
     using namespace awpstore;
     constexpr int KW = AWP_W / 16, T = AWP_W / 32;
@@ -187,10 +188,12 @@ template <int PREC> static int run_awp_backward(const AwpBwdPlan& b, hipStream_t
         hipLaunchKernelGGL(k_absmax, dim3(512), dim3(256), 0, st, b.d_h_local, b.nsamp * AWP_W, words);
         EVD_LAUNCH_CHECK();
     }
-    // round 5: the whole chain in one launch with the tile's gradient resident in registers (awp_bwd_fused.h); EVD_AWP_BWD_FUSE=0: the
-    // per-layer chain below (A/B, and what the fused kernel is tested against)
-    static const bool fuse = [] { const char* e = getenv("EVD_AWP_BWD_FUSE"); return !(e && e[0] == '0'); }();
-    if (fuse) {
+    BwdChain c(b, TILE_BYTES, st);
+    c.maxbits = words;
+    const AwpBwdGrads& g = b.grads;
+    // the whole chain in one launch with the tile's gradient resident in registers (awp_bwd_fused.h); EVD_AWP_BWD_FUSE=0: the per-layer
+    // chain below (A/B, and what the fused kernel is tested against)
+    if (bwd_switches().awp_fuse) {
         const int blocks = (int)(cdiv(b.tiles, 4L) < b.wgrad_blocks ? cdiv(b.tiles, 4L) : b.wgrad_blocks);
         AwpBwdFusedParams fp;
         fp.d_h_local = b.d_h_local; fp.nsamp = b.nsamp; fp.tiles = b.tiles; fp.store = b.store; fp.words = words; fp.partial = b.partial;
@@ -198,7 +201,6 @@ template <int PREC> static int run_awp_backward(const AwpBwdPlan& b, hipStream_t
         EVD_SET_MAX_LDS((&k_awp_bwd_fused<PREC>), (size_t)awpf::LDS_BYTES);
         hipLaunchKernelGGL((k_awp_bwd_fused<PREC>), dim3((unsigned)blocks), dim3(256), (size_t)awpf::LDS_BYTES, st, fp);
         EVD_LAUNCH_CHECK();
-        const AwpBwdGrads& g = b.grads;
         WreduceJobs jobs;
         for (int i = 0; i < WREDUCE_MAX_JOBS; ++i) {
             const int l = i < 3 ? 3 - i : 1;            // jobs 0, 1, 2: layers 3, 2, 1; the rest empty
@@ -217,67 +219,24 @@ template <int PREC> static int run_awp_backward(const AwpBwdPlan& b, hipStream_t
         hipLaunchKernelGGL(k_bias_cols_reduce, dim3(6 * 32 / 4), dim3(256), 0, st, bp);
         EVD_LAUNCH_CHECK();
         // layer 0's weight gradient from the stored (d e0, geo) fragments: the per-layer kernel (behind the reduces above: they share `partial`)
-        {
-            if (g.w[0]) {
-                const int wb = (int)(b.tiles < b.wgrad_blocks ? b.tiles : b.wgrad_blocks);
-                WgradParams wp;
-                wp.store = b.store; wp.tiles = b.tiles; wp.tile_bytes = TILE_BYTES; wp.y_slot = D_E0; wp.x_slot = GEO; wp.bias = 1; wp.partial = b.partial;
-                int r = launch_wgrad<PREC, T, AWP_IN / 32, false>(wp, wb, st);
-                if (r) return r;
-                WreduceParams q;
-                q.partial = b.partial; q.nparts = wb; q.RT = T; q.CT = AWP_IN / 32; q.NC = q.CT + 1;
-                q.rowmap = b.maps + AMAP_H; q.colmap = b.maps + AMAP_GEO; q.dW = g.w[0]; q.ld = AWP_IN; q.db = g.b[0]; q.maxbits = words;
-                hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((long)T * q.NC * 4)), dim3(256), 0, st, q);
-                EVD_LAUNCH_CHECK();
-            }
-        }
-        if (b.d_geo_rows) {
-            hipLaunchKernelGGL((k_frags_to_rows<PREC>), dim3((unsigned)cdiv(b.tiles * 64 * (AWP_IN / 16), 256L)), dim3(256), 0, st, (const char*)b.store, TILE_BYTES,
-                               D_GEO, AWP_IN / 16, b.nsamp, words, b.d_geo_rows, AWP_IN);
-            EVD_LAUNCH_CHECK();
-        }
-        return EVD_OK;
+        if ((rc = c.wgrad(launch_wgrad<PREC, T, AWP_IN / 32, false>, c.tile_grid(), T, AWP_IN / 32, true, D_E0, GEO, AMAP_H, AMAP_GEO, g.w[0], AWP_IN, g.b[0]))) return rc;
+        return b.d_geo_rows ? c.template frags_to_rows<PREC>(D_GEO, AWP_IN / 16, b.d_geo_rows, AWP_IN) : EVD_OK;
     }
     hipLaunchKernelGGL((k_awp_rows_to_frags<PREC>), dim3((unsigned)cdiv(b.tiles * 64 * KW, 256L)), dim3(256), 0, st, b.d_h_local, b.nsamp, b.tiles, words, b.store);
     EVD_LAUNCH_CHECK();
-    auto dgrad = [&](int l, int in_slot, int mask_slot, int out_slot) {
-        DgradParams p;
-        p.wstream = b.wt[l]; p.store = b.store; p.tile_bytes = TILE_BYTES; p.in_slot = in_slot; p.extra_slot = -1; p.mask_slot = mask_slot; p.out_slot = out_slot;
-        return p;
-    };
-    auto wgrad = [&](auto launch, int RT, int CT, int y_slot, int x_slot, int xmap, float* dW, int ld, float* db) -> int {
-        if (!dW) return EVD_OK;
-        const int blocks = (int)(b.tiles < b.wgrad_blocks ? b.tiles : b.wgrad_blocks);
-        WgradParams p;
-        p.store = b.store; p.tiles = b.tiles; p.tile_bytes = TILE_BYTES; p.y_slot = y_slot; p.x_slot = x_slot; p.bias = 1; p.partial = b.partial;
-        int r = launch(p, blocks, st);
-        if (r) return r;
-        WreduceParams q;
-        q.partial = b.partial; q.nparts = blocks; q.RT = RT; q.CT = CT; q.NC = CT + 1;
-        q.rowmap = b.maps + AMAP_H; q.colmap = b.maps + xmap; q.dW = dW; q.ld = ld; q.db = db; q.maxbits = words;
-        hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((long)RT * q.NC * 4)), dim3(256), 0, st, q);
-        EVD_LAUNCH_CHECK();
-        return EVD_OK;
-    };
-    const AwpBwdGrads& g = b.grads;
     for (int l = AWP_D - 1; l >= 1; --l) {
-        if ((rc = wgrad(launch_wgrad<PREC, T, T, false>, T, T, D_E0 + KW * l, E0 + KW * (l - 1), AMAP_H, g.w[l], AWP_W, g.b[l]))) return rc;
+        if ((rc = c.wgrad(launch_wgrad<PREC, T, T, false>, c.tile_grid(), T, T, true, D_E0 + KW * l, E0 + KW * (l - 1), AMAP_H, AMAP_H, g.w[l], AWP_W, g.b[l]))) return rc;
         // d e_{l-1} = (W_l^T d e_l) . [e_{l-1} > 0]: the ReLU pattern from the saved activation fragments
-        if ((rc = launch_dgrad<PREC, KW, T, KW, false, 1>(dgrad(l, D_E0 + KW * l, E0 + KW * (l - 1), D_E0 + KW * (l - 1)), b.tiles, st))) return rc;
+        if ((rc = launch_dgrad<PREC, KW, T, KW, false, 1>(c.dgrad_params(b.wt[l], D_E0 + KW * l, -1, E0 + KW * (l - 1), D_E0 + KW * (l - 1)), b.tiles, st))) return rc;
     }
-    if ((rc = wgrad(launch_wgrad<PREC, T, AWP_IN / 32, false>, T, AWP_IN / 32, D_E0, GEO, AMAP_GEO, g.w[0], AWP_IN, g.b[0]))) return rc;
+    if ((rc = c.wgrad(launch_wgrad<PREC, T, AWP_IN / 32, false>, c.tile_grid(), T, AWP_IN / 32, true, D_E0, GEO, AMAP_H, AMAP_GEO, g.w[0], AWP_IN, g.b[0]))) return rc;
     {   // d geo (no activation); its maximum (true units, for the fine level's rescaling) is taken by the kernel that forms it
-        DgradParams dp = dgrad(0, D_E0, -1, D_GEO);
+        DgradParams dp = c.dgrad_params(b.wt[0], D_E0, -1, -1, D_GEO);
         dp.absmax_out = words + 1;
         dp.maxbits = words;
         if ((rc = launch_dgrad<PREC, KW, AWP_IN / 32, KW, false, 0>(dp, b.tiles, st))) return rc;
     }
-    if (b.d_geo_rows) {
-        hipLaunchKernelGGL((k_frags_to_rows<PREC>), dim3((unsigned)cdiv(b.tiles * 64 * (AWP_IN / 16), 256L)), dim3(256), 0, st, (const char*)b.store, TILE_BYTES,
-                           D_GEO, AWP_IN / 16, b.nsamp, words, b.d_geo_rows, AWP_IN);
-        EVD_LAUNCH_CHECK();
-    }
-    return EVD_OK;
+    return b.d_geo_rows ? c.template frags_to_rows<PREC>(D_GEO, AWP_IN / 16, b.d_geo_rows, AWP_IN) : EVD_OK;
 }
 
 }  // namespace evd

@@ -55,7 +55,18 @@ inline bool env_flag(const char* name) {
     return e && e[0] && e[0] != '0';
 }
 
+inline bool env_flag_on(const char* name) {         // a switch that is on unless the variable's first character is '0'
+    const char* e = getenv(name);
+    return !(e && e[0] == '0');
+}
+
 inline long cdiv(long a, long b) { return (a + b - 1) / b; }
+
+// compute units of the current device (`fallback` when the query fails)
+inline int device_cus(int fallback = 256) {
+    int dev = 0, v = 0;
+    return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0 ? v : fallback;
+}
 
 // activations: reference networks/nerf.py:31-33, networks/pdrf/voxnerf.py:28-30
 __device__ __forceinline__ float act(int code, float x) {
@@ -142,6 +153,35 @@ inline int bwd_overlap_blocks(int cap) {
     static const int want = [] { const char* e = getenv("EVD_BWD_OVERLAP"); return e ? atoi(e) : 192; }();
     return want <= 0 ? 0 : (want > cap ? cap : want);
 }
+
+// Developer switches of the backward forms, read once per process: each fused form is on unless its variable is 0, which selects the
+// per-layer chain it replaced (the A/B, and the reference tests/test_gpu_bwd_fusion.py compares the fused kernels with).
+struct BwdSwitches {
+    bool fuse64;        // EVD_BWD_FUSE64: the 64-wide level's whole chain in one launch (voxel_bwd_fused64.h)
+    bool fuse_sg;       // EVD_BWD_FUSE_SG: sigma_net.1's two wgrads and its dgrad in one launch
+    bool ygen;          // EVD_BWD_YGEN: color_net.2's dgrad formed inside color_net.1's fused launch
+    bool rows;          // EVD_BWD_ROWS: d fts written as float32 rows by the kernel that forms them
+    bool awp_fuse;      // EVD_AWP_BWD_FUSE: the AWP embedding's whole chain in one launch (awp_bwd_fused.h)
+};
+inline const BwdSwitches& bwd_switches() {
+    static const BwdSwitches s = {env_flag_on("EVD_BWD_FUSE64"), env_flag_on("EVD_BWD_FUSE_SG"), env_flag_on("EVD_BWD_YGEN"), env_flag_on("EVD_BWD_ROWS"),
+                                  env_flag_on("EVD_AWP_BWD_FUSE")};
+    return s;
+}
+
+// What the plans of the three training backwards share (nerf_train.h BwdPlan, voxel_train.h VoxBwdPlan, awp_embed.h AwpBwdPlan), and
+// what their launch helper is built from (bwd_launch.h BwdChain)
+struct BwdPlanBase {
+    long nsamp, tiles;
+    char* store;                        // activation / gradient fragments, one tile per 32 samples
+    const int* maps;                    // index maps of the wgrad reduction
+    float* partial;                     // the wgrad workgroups' partial sums
+    unsigned* maxbits = nullptr;        // loss-scale word
+    int wgrad_blocks;
+    hipStream_t side = nullptr;         // second stream for the wgrad launches (null: everything on the caller's stream)
+    hipEvent_t ev = nullptr;
+    int accumulate = 0;                 // 1: the parameter gradients are ADDED into the caller's buffers
+};
 
 // TEST HOOK (tests/test_gpu_dist.py), defined once in evd_api.hip: EVD_TEST_SIDE_SPIN_US=N makes every wgrad launch on a handle's side
 // stream start N microseconds late (a spin kernel in front of it), so that a missing join of the side stream into the caller's stream --

@@ -1876,9 +1876,7 @@ int launch_voxel_sample(const GridParams& g, bool half_grids, const float* pts, 
         // float16 grids only: on float32 grids (the float32-grade levels) the new form measures equal (67.1 vs 67.0 us) and the old kernel's
         // float32 matrix product is exact -- it stays
         if (half_grids && ct % 32 == 0 && ct <= 96 && pmax_h < (1L << 31)) {
-            int cus = 256;
-            { int dev = 0, v = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
-            const long tiles = cdiv(n, 16L * VM_WAVES), cap = 8L * cus;
+            const long tiles = cdiv(n, 16L * VM_WAVES), cap = 8L * device_cus();
             const unsigned mb = (unsigned)(tiles < cap ? tiles : cap);
             // (three wavefronts per SIMD, 168 registers with the operand scaling, no spills; compiled for four -- 128 registers, 34 spilled -- it runs 70 instead of 57 us)
             k_voxel_sample_m<true, 3><<<mb, 64 * VM_WAVES, 0, st>>>(g, pts, n, out, out_stride, out_col);
@@ -1904,9 +1902,8 @@ int launch_voxel_sample(const GridParams& g, bool half_grids, const float* pts, 
 // for its basis_mat column and flushes its basis_mat gradient (192 atomic requests) once.
 static long scatter_blocks_cap(bool three_per_cu) {
     if (!three_per_cu) return 3072;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 3072;
-    return 3L * cus;
+    const int cus = device_cus(0);
+    return cus ? 3L * cus : 3072;
 }
 
 // HYBRID: plane taps by direct atomics here, line taps left as rows + tap records (rows_l, ltap) for k_scatter_lines; else every tap here
@@ -1948,8 +1945,7 @@ bool voxel_sample_bwd_w_ok(const GridParams& g) {
 }
 int launch_voxel_sample_bwd_w(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
                               float* d_pts, float* rows_l, LTap* ltap, unsigned* lmax, bool half_grids, hipStream_t st) {
-    int cus = 256;
-    { int dev = 0, v = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
+    const int cus = device_cus();
     const long tiles = cdiv(n, (long)VBW_SAMPLES * VBW_WAVES);
     // persistent workgroups with the basis gradient in registers: two per CU (the LDS slices allow no more)
     const unsigned blocks = (unsigned)(tiles < 2L * cus ? tiles : 2L * cus);

@@ -27,19 +27,11 @@ struct BwdGrads {                       // device float32, reference nn.Linear l
     float *views_w, *views_b, *feature_w, *feature_b, *alpha_w, *alpha_b, *rgb_w, *rgb_b;
 };
 
-struct BwdPlan {
+struct BwdPlan : BwdPlanBase {          // accumulate: evd_nerf_grads.accumulate
     const float* d_raw;                 // [nsamp, 4]
-    long nsamp, tiles;
-    char* store;
     const char* wt[EVD_BWD_NSTREAMS];   // W^T fragment streams
-    const int* maps;
-    float* partial;
-    unsigned* maxbits;
-    int wgrad_blocks, skip;
-    hipStream_t side;                   // second stream for the wgrad launches (null: everything on the caller's stream)
-    hipEvent_t ev;
+    int skip;
     BwdGrads grads;
-    int accumulate = 0;                 // 1: the parameter gradients are ADDED into the caller's buffers (evd_nerf_grads.accumulate)
     const float *pts, *viewdirs;        // [nsamp,3] sample positions / rows of vd_stride floats per ray (the encodings' derivatives)
     int vd_stride, S;
     float *d_pts, *d_dirs;              // [nsamp,3] float32 out (through the positional encodings), or null

@@ -1036,6 +1036,12 @@ __global__ __launch_bounds__(256) void k_pe_bwd(const char* __restrict__ store, 
     }
 }
 
+}  // namespace evd
+
+#include "bwd_launch.h"
+
+namespace evd {
+
 // ------------------------------------------------------------------------------------------------
 // The whole backward of one network, in the order the gradients become available.
 template <int PREC> static int run_nerf_backward(const BwdPlan& b, hipStream_t st) {
@@ -1048,111 +1054,55 @@ template <int PREC> static int run_nerf_backward(const BwdPlan& b, hipStream_t s
     hipLaunchKernelGGL((k_grad_frags<PREC>), dim3((unsigned)cdiv(b.tiles * 64, 256L)), dim3(256), 0, st, b.d_raw, b.nsamp, b.maxbits, b.store, b.tiles);
     EVD_LAUNCH_CHECK();
 
-    auto dgrad = [&](int stream, int in_slot, int extra_slot, int mask_slot, int out_slot) {
-        DgradParams p;
-        p.wstream = b.wt[stream]; p.store = b.store; p.tile_bytes = astore::tile_bytes(PREC); p.in_slot = in_slot; p.extra_slot = extra_slot; p.mask_slot = mask_slot; p.out_slot = out_slot;
-        return p;
-    };
-    // wgrad + reduce of one parameter block: rows from `ymap`, columns from `xmap` (offset into b.maps)
-    auto wgrad = [&](auto launch, int RT, int CT, bool bias, int y_slot, int x_slot, int ymap, int xmap, float* dW, int ld, float* db) -> int {
-        if (!dW) return EVD_OK;
-        const int blocks = (int)(cdiv(b.tiles, (long)WGRAD_TPI) < b.wgrad_blocks ? cdiv(b.tiles, (long)WGRAD_TPI) : b.wgrad_blocks);
-        WgradParams p;
-        p.store = b.store; p.tiles = b.tiles; p.tile_bytes = astore::tile_bytes(PREC); p.y_slot = y_slot; p.x_slot = x_slot; p.bias = bias ? 1 : 0; p.partial = b.partial;
-        hipStream_t ws = st;
-        if (b.side) {                           // everything issued so far on the main stream (the producer of this wgrad's operands) first
-            EVD_HIP(hipEventRecord(b.ev, st));
-            EVD_HIP(hipStreamWaitEvent(b.side, b.ev, 0));
-            ws = b.side;
-            if (int rcs = test_side_spin(ws)) return rcs;
-        }
-        int r = launch(p, blocks, ws);
-        if (r) return r;
-        WreduceParams q;
-        q.partial = b.partial; q.nparts = blocks; q.RT = RT; q.CT = CT; q.NC = CT + (bias ? 1 : 0);
-        q.rowmap = b.maps + ymap; q.colmap = b.maps + xmap; q.dW = dW; q.ld = ld; q.db = bias ? db : nullptr; q.maxbits = b.maxbits; q.accum = b.accumulate;
-        hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((long)RT * q.NC * 4)), dim3(256), 0, ws, q);
-        EVD_LAUNCH_CHECK();
-        return EVD_OK;
-    };
-    // wgrad(l) with dgrad(l) in one launch (k_wgrad_dgrad above): the seven 256 x 256 trunk layers in the half-precision modes;
-    // EVD_BWD_FUSE=0 keeps the separate launches (A/B)
-    static const bool fuse_on = [] { const char* e = getenv("EVD_BWD_FUSE"); return !(e && e[0] == '0'); }();
-    auto fused = [&](auto launch, int CT, bool bias, int y_slot, int x_slot, int ymap, int xmap, float* dW, int ld, float* db, int stream, int out_slot) -> int {
-        const int blocks = (int)(b.tiles < b.wgrad_blocks ? b.tiles : b.wgrad_blocks);
-        WgradFusedParams p;
-        p.w.store = b.store; p.w.tiles = b.tiles; p.w.tile_bytes = astore::tile_bytes(PREC); p.w.y_slot = y_slot; p.w.x_slot = x_slot; p.w.bias = bias ? 1 : 0; p.w.partial = b.partial;
-        p.wt = b.wt[stream]; p.out_store = b.store; p.mask_slot = -1; p.out_slot = out_slot;
-        if (b.side && !test_skip_side_join()) { // wgrad launches in flight on the side stream use the partial scratch (and read what this one writes next): join
-            EVD_HIP(hipEventRecord(b.ev, b.side));
-            EVD_HIP(hipStreamWaitEvent(st, b.ev, 0));
-        }
-        int r = launch(p, blocks, st);
-        if (r) return r;
-        WreduceParams q;
-        q.partial = b.partial; q.nparts = blocks; q.RT = 8; q.CT = CT; q.NC = CT + (bias ? 1 : 0);
-        q.rowmap = b.maps + ymap; q.colmap = b.maps + xmap; q.dW = dW; q.ld = ld; q.db = bias ? db : nullptr; q.maxbits = b.maxbits; q.accum = b.accumulate;
-        hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((long)8 * q.NC * 4)), dim3(256), 0, st, q);
-        EVD_LAUNCH_CHECK();
-        return EVD_OK;
-    };
+    const BwdChain c(b, astore::tile_bytes(PREC), st);
+    const int wb = c.wgrad_grid();
+    auto dgrad = [&](int stream, int in_slot, int extra_slot, int mask_slot, int out_slot) { return c.dgrad_params(b.wt[stream], in_slot, extra_slot, mask_slot, out_slot); };
     const BwdGrads& g = b.grads;
-    // Every wgrad is issued BEFORE the dgrad layer that reads the same two arrays (incoming gradient, saved activation): the two are
-    // independent, and with a side stream (b.side: developer switch EVD_BWD_OVERLAP) they run concurrently and share those reads in
-    // the Infinity Cache.
+    // Every wgrad is issued BEFORE the dgrad layer that reads the same two arrays (BwdChain::wgrad; the side stream is b.side: developer
+    // switch EVD_BWD_OVERLAP).
     // rgb_linear: d hv = Wr^T d rgb;  dWr = d rgb . hv^T
-    if ((rc = wgrad(launch_wgrad<PREC, 1, 4, true>, 1, 4, true, G_RGB, HV, MAP_RGB, MAP_HID, g.rgb_w, 128, g.rgb_b))) return rc;
+    if ((rc = c.wgrad(launch_wgrad<PREC, 1, 4, true>, wb, 1, 4, true, G_RGB, HV, MAP_RGB, MAP_HID, g.rgb_w, 128, g.rgb_b))) return rc;
     if ((rc = launch_dgrad<PREC, 1, 4, 1, false, 2>(dgrad(EVD_BWD_RGB, G_RGB, -1, M_HV, D_HV), b.tiles, st))) return rc;
     // views_linears.0 on cat([feature, PE(dir)])
-    if ((rc = wgrad(launch_wgrad<PREC, 4, 8, false>, 4, 8, true, D_HV, F, MAP_HID, MAP_HID, g.views_w, 256 + 27, g.views_b))) return rc;
-    if ((rc = wgrad(launch_wgrad<PREC, 4, 1, false>, 4, 1, false, D_HV, DIR, MAP_HID, MAP_DIR, g.views_w, 256 + 27, nullptr))) return rc;
+    if ((rc = c.wgrad(launch_wgrad<PREC, 4, 8, false>, wb, 4, 8, true, D_HV, F, MAP_HID, MAP_HID, g.views_w, 256 + 27, g.views_b))) return rc;
+    if ((rc = c.wgrad(launch_wgrad<PREC, 4, 1, false>, wb, 4, 1, false, D_HV, DIR, MAP_HID, MAP_DIR, g.views_w, 256 + 27, nullptr))) return rc;
     if ((rc = launch_dgrad<PREC, 8, 8, 8, false, 0>(dgrad(EVD_BWD_VIEWS, D_HV, -1, -1, D_F), b.tiles, st))) return rc;
     // feature_linear and alpha_linear both read h_7
-    if ((rc = wgrad(launch_wgrad<PREC, 8, 8, false>, 8, 8, true, D_F, H0 + 16 * (D - 1), MAP_HID, MAP_HID, g.feature_w, 256, g.feature_b))) return rc;
-    if ((rc = wgrad(launch_wgrad<PREC, 1, 8, true>, 1, 8, true, G_ALPHA, H0 + 16 * (D - 1), MAP_ALPHA, MAP_HID, g.alpha_w, 256, g.alpha_b))) return rc;
+    if ((rc = c.wgrad(launch_wgrad<PREC, 8, 8, false>, wb, 8, 8, true, D_F, H0 + 16 * (D - 1), MAP_HID, MAP_HID, g.feature_w, 256, g.feature_b))) return rc;
+    if ((rc = c.wgrad(launch_wgrad<PREC, 1, 8, true>, wb, 1, 8, true, G_ALPHA, H0 + 16 * (D - 1), MAP_ALPHA, MAP_HID, g.alpha_w, 256, g.alpha_b))) return rc;
     if ((rc = launch_dgrad<PREC, 17, 8, 16, true, 2>(dgrad(EVD_BWD_HEAD, D_F, G_ALPHA, M_H0 + D - 1, D_H0 + 16 * (D - 1)), b.tiles, st))) return rc;
     // pts_linears[l], l = 7 .. 1
     for (int l = D - 1; l >= 1; --l) {
         const bool wide = l - 1 == b.skip;
         if constexpr (is_half_prec(PREC)) {
-            if (fuse_on && g.pts_w[l]) {
-                if (wide && (rc = wgrad(launch_wgrad<PREC, 8, 2, false>, 8, 2, false, D_H0 + 16 * l, PE, MAP_HID, MAP_PE, g.pts_w[l], 256 + 63, nullptr))) return rc;
-                if ((rc = fused(launch_wgrad_dgrad<PREC, 8, 8, 1>, 8, true, D_H0 + 16 * l, H0 + 16 * (l - 1), MAP_HID, wide ? MAP_HID_SKIP : MAP_HID, g.pts_w[l],
-                                wide ? 256 + 63 : 256, g.pts_b[l], EVD_BWD_HIDDEN1 + l - 1, D_H0 + 16 * (l - 1)))) return rc;
+            if (g.pts_w[l]) {           // wgrad(l) with dgrad(l) in one launch (k_wgrad_dgrad above): the seven 256 x 256 trunk layers in the half-precision modes
+                if (wide && (rc = c.wgrad(launch_wgrad<PREC, 8, 2, false>, wb, 8, 2, false, D_H0 + 16 * l, PE, MAP_HID, MAP_PE, g.pts_w[l], 256 + 63, nullptr))) return rc;
+                if ((rc = c.fused(launch_wgrad_dgrad<PREC, 8, 8, 1>, 8, true, D_H0 + 16 * l, H0 + 16 * (l - 1), MAP_HID, wide ? MAP_HID_SKIP : MAP_HID, g.pts_w[l],
+                                  wide ? 256 + 63 : 256, g.pts_b[l], b.wt[EVD_BWD_HIDDEN1 + l - 1], D_H0 + 16 * (l - 1)))) return rc;
                 continue;
             }
         }
-        if ((rc = wgrad(launch_wgrad<PREC, 8, 8, false>, 8, 8, true, D_H0 + 16 * l, H0 + 16 * (l - 1), MAP_HID, wide ? MAP_HID_SKIP : MAP_HID,
-                        g.pts_w[l], wide ? 256 + 63 : 256, g.pts_b[l]))) return rc;
-        if (wide && (rc = wgrad(launch_wgrad<PREC, 8, 2, false>, 8, 2, false, D_H0 + 16 * l, PE, MAP_HID, MAP_PE, g.pts_w[l], 256 + 63, nullptr))) return rc;
+        if ((rc = c.wgrad(launch_wgrad<PREC, 8, 8, false>, wb, 8, 8, true, D_H0 + 16 * l, H0 + 16 * (l - 1), MAP_HID, wide ? MAP_HID_SKIP : MAP_HID,
+                          g.pts_w[l], wide ? 256 + 63 : 256, g.pts_b[l]))) return rc;
+        if (wide && (rc = c.wgrad(launch_wgrad<PREC, 8, 2, false>, wb, 8, 2, false, D_H0 + 16 * l, PE, MAP_HID, MAP_PE, g.pts_w[l], 256 + 63, nullptr))) return rc;
         if ((rc = launch_dgrad<PREC, 16, 8, 16, false, 2>(dgrad(EVD_BWD_HIDDEN1 + l - 1, D_H0 + 16 * l, -1, M_H0 + l - 1, D_H0 + 16 * (l - 1)), b.tiles, st))) return rc;
     }
     // gradient w.r.t. the rays: the encoding rows of pts_linears[0], of the skip layer and of views_linears.0, then through sin / cos
     if (b.d_pts) {
         if ((rc = launch_dgrad<PREC, 16, 2, 16, false, 0>(dgrad(EVD_BWD_PE0, D_H0, -1, -1, D_PE0), b.tiles, st))) return rc;
-        hipLaunchKernelGGL((k_pe_bwd<PREC, PE_L, PE_KS>), dim3((unsigned)cdiv(b.tiles * 64, 256L)), dim3(256), 0, st, (const char*)b.store, astore::tile_bytes(PREC), D_PE0,
-                           b.nsamp, b.pts, 3, 1, b.maxbits, b.d_pts, 0);
-        EVD_LAUNCH_CHECK();
+        if ((rc = c.template pe_bwd<PREC, PE_L, PE_KS>(D_PE0, b.pts, 3, 1, b.d_pts, 0))) return rc;
         if (b.skip >= 0 && b.skip + 1 < D) {
             if ((rc = launch_dgrad<PREC, 16, 2, 16, false, 0>(dgrad(EVD_BWD_PESKIP, D_H0 + 16 * (b.skip + 1), -1, -1, D_PE5), b.tiles, st))) return rc;
-            hipLaunchKernelGGL((k_pe_bwd<PREC, PE_L, PE_KS>), dim3((unsigned)cdiv(b.tiles * 64, 256L)), dim3(256), 0, st, (const char*)b.store, astore::tile_bytes(PREC), D_PE5,
-                               b.nsamp, b.pts, 3, 1, b.maxbits, b.d_pts, 1);
-            EVD_LAUNCH_CHECK();
+            if ((rc = c.template pe_bwd<PREC, PE_L, PE_KS>(D_PE5, b.pts, 3, 1, b.d_pts, 1))) return rc;
         }
     }
     if (b.d_dirs) {
         if ((rc = launch_dgrad<PREC, 8, 1, 8, false, 0>(dgrad(EVD_BWD_DIR, D_HV, -1, -1, D_DIRG), b.tiles, st))) return rc;
-        hipLaunchKernelGGL((k_pe_bwd<PREC, PE_LV, PEV_KS>), dim3((unsigned)cdiv(b.tiles * 64, 256L)), dim3(256), 0, st, (const char*)b.store, astore::tile_bytes(PREC), D_DIRG,
-                           b.nsamp, b.viewdirs, b.vd_stride, b.S, b.maxbits, b.d_dirs, 0);
-        EVD_LAUNCH_CHECK();
+        if ((rc = c.template pe_bwd<PREC, PE_LV, PEV_KS>(D_DIRG, b.viewdirs, b.vd_stride, b.S, b.d_dirs, 0))) return rc;
     }
     // pts_linears[0] on PE(pts) (no dgrad beyond the inputs)
-    if ((rc = wgrad(launch_wgrad<PREC, 8, 2, false>, 8, 2, true, D_H0, PE, MAP_HID, MAP_PE, g.pts_w[0], 63, g.pts_b[0]))) return rc;
-    if (b.side && !test_skip_side_join()) {     // join the side stream
-        EVD_HIP(hipEventRecord(b.ev, b.side));
-        EVD_HIP(hipStreamWaitEvent(st, b.ev, 0));
-    }
-    return EVD_OK;
+    if ((rc = c.wgrad(launch_wgrad<PREC, 8, 2, false>, wb, 8, 2, true, D_H0, PE, MAP_HID, MAP_PE, g.pts_w[0], 63, g.pts_b[0]))) return rc;
+    return c.join();
 }
 
 }  // namespace evd

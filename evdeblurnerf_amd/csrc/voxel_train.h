@@ -29,29 +29,20 @@ struct VoxBwdGrads {                    // device float32, reference nn.Linear l
     float *sigma_w[2], *color_w[3], *color_b[3];
 };
 
-struct VoxBwdPlan {
+struct VoxBwdPlan : BwdPlanBase {       // side: nerf_train.h; accumulate: evd_voxel_grads.accumulate
     const float *d_raw, *raw;           // [nsamp, 4]
     const float* d_feature;             // [nsamp, G] gradient of the geo-feature output, or null
     const char* awp_store;              // the AWP embedding's store after ITS backward (awp_embed.h): d geo fragments to add, or null
     long awp_tile_bytes;
     int awp_slot;
     const unsigned* awp_words;          // its trailer: loss-scale word, max |d geo| in true units
-    long nsamp, tiles;
-    char* store;
     const char* wt[VBWD_NSTREAMS];
-    const int* maps;
-    float* partial;
-    unsigned* maxbits;
-    int wgrad_blocks;
-    hipStream_t side;                   // second stream for the wgrad launches (null: none), nerf_train.h
-    hipEvent_t ev;
     float* d_fts;                       // [nsamp, d_fts_stride] float32 out, or null
     int d_fts_stride;
     const float *pts, *viewdirs;        // the forward's inputs (for the encodings' derivatives)
     int vd_stride, S;
     float *d_pts, *d_dirs;              // [nsamp, 3] float32 out (through PE(pts) / PE(dirs) only), or null
     VoxBwdGrads grads;
-    int accumulate = 0;                 // 1: the parameter gradients are ADDED into the caller's buffers (evd_voxel_grads.accumulate)
 };
 
 int launch_voxel_train_fwd_f16(int HD, const VoxMlpParams& p, hipStream_t st);

@@ -60,6 +60,12 @@ __global__ __launch_bounds__(256) void k_frags_to_rows(const char* __restrict__ 
 #pragma unroll
     for (int e = 0; e < 8; ++e) rows[smp * (long)stride + 16 * j + phi(8 * h + e)] = fv[e] * inv;
 }
+template <int PREC> int BwdChain::frags_to_rows(int slot, int nfrag, float* rows, int stride) const {
+    hipLaunchKernelGGL((k_frags_to_rows<PREC>), dim3((unsigned)cdiv(tiles * 64 * nfrag, 256L)), dim3(256), 0, st, (const char*)store, tile_bytes, slot, nfrag, nsamp,
+                       maxbits, rows, stride);
+    EVD_LAUNCH_CHECK();
+    return EVD_OK;
+}
 
 // float32 gradient rows (the per-sample geo features' gradient, from the AWP consumer) added into gradient fragments: fragment j,
 // position kk <-> channel 16 j + phi(kk); rows are scaled by the loss scale first
@@ -112,10 +118,9 @@ __global__ __launch_bounds__(256) void k_frags_add_scaled(char* __restrict__ sto
     act_store(a, slot + j, b);
 }
 
-template <int PREC, int HD, int G, int FT> static int run_voxel_backward(const VoxBwdPlan& b, hipStream_t st) {
-    typedef VStore<HD, G, FT> VS;
-    constexpr int T = HD / 32, KS = HD / 16, KF = FT / 16, GT = VS::GT, FTT = (FT + 31) / 32, IC = 3 * (1 + 2 * PE_L), ICV = 3 * (1 + 2 * PE_LV);
-    int rc;
+// ---- the backward of one level -----------------------------------------------------------------------------------------------
+// the loss-scale word: the maximum over every gradient that enters the level
+static int voxel_backward_scale(const VoxBwdPlan& b, int G, hipStream_t st) {
     EVD_HIP(hipMemsetAsync(b.maxbits, 0, sizeof(unsigned), st));
     hipLaunchKernelGGL(k_absmax, dim3(512), dim3(256), 0, st, b.d_raw, b.nsamp * 4, b.maxbits);
     EVD_LAUNCH_CHECK();
@@ -127,164 +132,122 @@ template <int PREC, int HD, int G, int FT> static int run_voxel_backward(const V
         hipLaunchKernelGGL(k_max_word, dim3(1), dim3(1), 0, st, b.maxbits, b.awp_words + 1);
         EVD_LAUNCH_CHECK();
     }
-    // the 64-wide level: the whole chain in one launch, the tile's gradient resident in registers (voxel_bwd_fused64.h); EVD_BWD_FUSE64=0
-    // keeps the per-layer chain below (A/B, and the reference the fused kernel is tested against)
-    if constexpr (is_half_prec(PREC) && HD == 64 && G == 15 && FT == 32) {
-        static const bool fuse64 = [] { const char* e = getenv("EVD_BWD_FUSE64"); return !(e && e[0] == '0'); }();
-        if (fuse64 && !b.d_feature && !b.awp_store) {
-            const int blocks = (int)(cdiv(b.tiles, 4L) < 256 ? cdiv(b.tiles, 4L) : 256);
-            VoxBwdFusedParams fp;
-            fp.d_raw = b.d_raw; fp.raw = b.raw; fp.nsamp = b.nsamp; fp.tiles = b.tiles; fp.store = b.store; fp.maxbits = b.maxbits; fp.partial = b.partial;
-            for (int k = 0; k < VBWD_NSTREAMS; ++k) fp.wt[k] = b.wt[k];
-            // d fts straight as rows when they can be written with 16-byte stores (EVD_BWD_ROWS=0: fragments + k_frags_to_rows)
-            static const bool rows_on = [] { const char* e = getenv("EVD_BWD_ROWS"); return !(e && e[0] == '0'); }();
-            const bool rows_direct = rows_on && b.d_fts && b.d_fts_stride % 4 == 0 && ((uintptr_t)b.d_fts & 15) == 0;
-            fp.d_fts = rows_direct ? b.d_fts : nullptr; fp.d_fts_stride = b.d_fts_stride;
-            EVD_SET_MAX_LDS((&k_voxel_bwd_fused64<PREC>), (size_t)f64::LDS_BYTES);
-            hipLaunchKernelGGL((k_voxel_bwd_fused64<PREC>), dim3((unsigned)blocks), dim3(256), (size_t)f64::LDS_BYTES, st, fp);
-            EVD_LAUNCH_CHECK();
-            const VoxBwdGrads& g = b.grads;
-            WreduceJobs jobs;
-            auto job = [&](int i, int a0, int RT, int CT, bool bias, int ymap, int xmap, float* dW, int ld, float* db) {
-                WreduceParams& q = jobs.j[i];
-                q.partial = b.partial + (long)a0 * 1024; q.nparts = blocks; q.RT = dW ? RT : 0; q.CT = CT; q.NC = CT + (bias ? 1 : 0);
-                q.rowmap = b.maps + ymap; q.colmap = b.maps + xmap; q.dW = dW; q.ld = ld; q.db = bias ? db : nullptr; q.maxbits = b.maxbits;
-                q.accum = b.accumulate; q.part_stride = (long)f64::NBLK * 1024;
-            };
-            job(0, f64::A_C2, 1, 2, false, VMAP_COL, VMAP_HID, g.color_w[2], HD, nullptr);
-            job(1, f64::A_C1, 2, 2, false, VMAP_HID, VMAP_HID, g.color_w[1], HD, nullptr);
-            job(2, f64::A_C0, 2, 2, false, VMAP_HID, VMAP_F64_C0, g.color_w[0], G + ICV, nullptr);
-            job(3, f64::A_SG, 1, 2, false, VMAP_F64_SG, VMAP_HID, g.sigma_w[1], HD, nullptr);
-            job(4, f64::A_L0, 2, 3, false, VMAP_HID, VMAP_F64_L0, g.sigma_w[0], FT + IC, nullptr);
-            hipLaunchKernelGGL(k_wgrad_reduce_jobs, dim3(2 * 3 * 4, WREDUCE_MAX_JOBS), dim3(256), 0, st, jobs);
-            EVD_LAUNCH_CHECK();
-            if (g.color_b[0] || g.color_b[1] || g.color_b[2]) {        // the shared bias block (columns: colour_net.2, .1 x 2 row tiles, .0 x 2)
-                BiasColsParams bp;
-                bp.partial = b.partial + (long)f64::A_BIAS * 1024; bp.nparts = blocks; bp.part_stride = (long)f64::NBLK * 1024; bp.ncols = 5;
-                bp.rowmap[f64::B_C2] = b.maps + VMAP_COL; bp.db[f64::B_C2] = g.color_b[2];
-                for (int yb = 0; yb < 2; ++yb) {
-                    bp.rowmap[f64::B_C1 + yb] = b.maps + VMAP_HID + 32 * yb; bp.db[f64::B_C1 + yb] = g.color_b[1];
-                    bp.rowmap[f64::B_C0 + yb] = b.maps + VMAP_HID + 32 * yb; bp.db[f64::B_C0 + yb] = g.color_b[0];
-                }
-                bp.maxbits = b.maxbits; bp.accum = b.accumulate;
-                hipLaunchKernelGGL(k_bias_cols_reduce, dim3(5 * 32 / 4), dim3(256), 0, st, bp);
-                EVD_LAUNCH_CHECK();
-            }
-            if (b.d_dirs) {
-                hipLaunchKernelGGL((k_pe_bwd<PREC, PE_LV, PEV_KS>), dim3((unsigned)cdiv(b.tiles * 64, 256L)), dim3(256), 0, st, (const char*)b.store, VS::tile_bytes(PREC),
-                                   VS::D_DIRPE, b.nsamp, b.viewdirs, b.vd_stride, b.S, b.maxbits, b.d_dirs, 0);
-                EVD_LAUNCH_CHECK();
-            }
-            if (b.d_fts && !rows_direct) {
-                hipLaunchKernelGGL((k_frags_to_rows<PREC>), dim3((unsigned)cdiv(b.tiles * 64 * KF, 256L)), dim3(256), 0, st, (const char*)b.store, VS::tile_bytes(PREC),
-                                   VS::D_FTS, KF, b.nsamp, b.maxbits, b.d_fts, b.d_fts_stride);
-                EVD_LAUNCH_CHECK();
-            }
-            if (b.d_pts) {
-                hipLaunchKernelGGL((k_pe_bwd<PREC, PE_L, PE_KS>), dim3((unsigned)cdiv(b.tiles * 64, 256L)), dim3(256), 0, st, (const char*)b.store, VS::tile_bytes(PREC),
-                                   VS::D_PE, b.nsamp, b.pts, 3, 1, b.maxbits, b.d_pts, 0);
-                EVD_LAUNCH_CHECK();
-            }
-            return EVD_OK;
+    return EVD_OK;
+}
+
+// d fts leave the kernel that forms them as the float32 rows the scatter reads when they can be written with 16-byte stores
+// (EVD_BWD_ROWS=0: fragments + k_frags_to_rows)
+static bool voxel_rows_direct(const VoxBwdPlan& b) { return bwd_switches().rows && b.d_fts && b.d_fts_stride % 4 == 0 && ((uintptr_t)b.d_fts & 15) == 0; }
+
+// The gradients of the level's inputs from their gradient fragments: d dirs through PE(dirs), d fts as rows, d pts through PE(pts).
+// `which`: the ones whose fragments are complete at the point of the call.
+enum { VOUT_DIRS = 1, VOUT_FTS = 2, VOUT_PTS = 4 };
+template <int PREC, class VS, int FT> static int voxel_backward_inputs(const BwdChain& c, const VoxBwdPlan& b, int which) {
+    int rc;
+    if ((which & VOUT_DIRS) && b.d_dirs && (rc = c.template pe_bwd<PREC, PE_LV, PEV_KS>(VS::D_DIRPE, b.viewdirs, b.vd_stride, b.S, b.d_dirs, 0))) return rc;
+    if ((which & VOUT_FTS) && b.d_fts && (rc = c.template frags_to_rows<PREC>(VS::D_FTS, FT / 16, b.d_fts, b.d_fts_stride))) return rc;
+    if ((which & VOUT_PTS) && b.d_pts && (rc = c.template pe_bwd<PREC, PE_L, PE_KS>(VS::D_PE, b.pts, 3, 1, b.d_pts, 0))) return rc;
+    return EVD_OK;
+}
+
+// The 64-wide level: the whole chain in one launch, the tile's gradient resident in registers (voxel_bwd_fused64.h), then the reduces of
+// its partial blocks
+template <int PREC> static int voxel_backward_fused64(const BwdChain& c, const VoxBwdPlan& b) {
+    constexpr int HD = 64, G = 15, FT = 32, IC = 3 * (1 + 2 * PE_L), ICV = 3 * (1 + 2 * PE_LV);
+    typedef VStore<HD, G, FT> VS;
+    hipStream_t st = c.st;
+    const int blocks = (int)(cdiv(b.tiles, 4L) < 256 ? cdiv(b.tiles, 4L) : 256);
+    VoxBwdFusedParams fp;
+    fp.d_raw = b.d_raw; fp.raw = b.raw; fp.nsamp = b.nsamp; fp.tiles = b.tiles; fp.store = b.store; fp.maxbits = b.maxbits; fp.partial = b.partial;
+    for (int k = 0; k < VBWD_NSTREAMS; ++k) fp.wt[k] = b.wt[k];
+    const bool rows_direct = voxel_rows_direct(b);
+    fp.d_fts = rows_direct ? b.d_fts : nullptr; fp.d_fts_stride = b.d_fts_stride;
+    EVD_SET_MAX_LDS((&k_voxel_bwd_fused64<PREC>), (size_t)f64::LDS_BYTES);
+    hipLaunchKernelGGL((k_voxel_bwd_fused64<PREC>), dim3((unsigned)blocks), dim3(256), (size_t)f64::LDS_BYTES, st, fp);
+    EVD_LAUNCH_CHECK();
+    const VoxBwdGrads& g = b.grads;
+    WreduceJobs jobs;
+    auto job = [&](int i, int a0, int RT, int CT, bool bias, int ymap, int xmap, float* dW, int ld, float* db) {
+        WreduceParams& q = jobs.j[i];
+        q.partial = b.partial + (long)a0 * 1024; q.nparts = blocks; q.RT = dW ? RT : 0; q.CT = CT; q.NC = CT + (bias ? 1 : 0);
+        q.rowmap = b.maps + ymap; q.colmap = b.maps + xmap; q.dW = dW; q.ld = ld; q.db = bias ? db : nullptr; q.maxbits = b.maxbits;
+        q.accum = b.accumulate; q.part_stride = (long)f64::NBLK * 1024;
+    };
+    job(0, f64::A_C2, 1, 2, false, VMAP_COL, VMAP_HID, g.color_w[2], HD, nullptr);
+    job(1, f64::A_C1, 2, 2, false, VMAP_HID, VMAP_HID, g.color_w[1], HD, nullptr);
+    job(2, f64::A_C0, 2, 2, false, VMAP_HID, VMAP_F64_C0, g.color_w[0], G + ICV, nullptr);
+    job(3, f64::A_SG, 1, 2, false, VMAP_F64_SG, VMAP_HID, g.sigma_w[1], HD, nullptr);
+    job(4, f64::A_L0, 2, 3, false, VMAP_HID, VMAP_F64_L0, g.sigma_w[0], FT + IC, nullptr);
+    hipLaunchKernelGGL(k_wgrad_reduce_jobs, dim3(2 * 3 * 4, WREDUCE_MAX_JOBS), dim3(256), 0, st, jobs);
+    EVD_LAUNCH_CHECK();
+    if (g.color_b[0] || g.color_b[1] || g.color_b[2]) {        // the shared bias block (columns: colour_net.2, .1 x 2 row tiles, .0 x 2)
+        BiasColsParams bp;
+        bp.partial = b.partial + (long)f64::A_BIAS * 1024; bp.nparts = blocks; bp.part_stride = (long)f64::NBLK * 1024; bp.ncols = 5;
+        bp.rowmap[f64::B_C2] = b.maps + VMAP_COL; bp.db[f64::B_C2] = g.color_b[2];
+        for (int yb = 0; yb < 2; ++yb) {
+            bp.rowmap[f64::B_C1 + yb] = b.maps + VMAP_HID + 32 * yb; bp.db[f64::B_C1 + yb] = g.color_b[1];
+            bp.rowmap[f64::B_C0 + yb] = b.maps + VMAP_HID + 32 * yb; bp.db[f64::B_C0 + yb] = g.color_b[0];
         }
+        bp.maxbits = b.maxbits; bp.accum = b.accumulate;
+        hipLaunchKernelGGL(k_bias_cols_reduce, dim3(5 * 32 / 4), dim3(256), 0, st, bp);
+        EVD_LAUNCH_CHECK();
     }
+    return voxel_backward_inputs<PREC, VS, FT>(c, b, VOUT_DIRS | (rows_direct ? 0 : VOUT_FTS) | VOUT_PTS);
+}
+
+// The per-layer sequence.  The 256-wide layers of the fine level run wgrad(l) and dgrad(l) in one launch in the half-precision modes
+// (FUSABLE; nerf_train_kernel.h k_wgrad_dgrad) when the layer's weight gradient is wanted; every other layer issues its wgrad before the
+// dgrad that reads the same arrays (BwdChain::wgrad).
+template <int PREC, int HD, int G, int FT> static int voxel_backward_layers(const BwdChain& c, const VoxBwdPlan& b) {
+    typedef VStore<HD, G, FT> VS;
+    constexpr int T = HD / 32, KS = HD / 16, KF = FT / 16, GT = VS::GT, FTT = (FT + 31) / 32, IC = 3 * (1 + 2 * PE_L), ICV = 3 * (1 + 2 * PE_LV);
+    constexpr bool FUSABLE = is_half_prec(PREC) && T == 8;
+    hipStream_t st = c.st;
+    const BwdSwitches& sw = bwd_switches();
+    const VoxBwdGrads& g = b.grads;
+    const int wb = c.wgrad_grid();
+    auto dgrad = [&](int stream, int in_slot, int extra_slot, int mask_slot, int out_slot) { return c.dgrad_params(b.wt[stream], in_slot, extra_slot, mask_slot, out_slot); };
+    int rc;
     hipLaunchKernelGGL((k_voxel_grad_frags<PREC>), dim3((unsigned)cdiv(b.tiles * 64, 256L)), dim3(256), 0, st, b.d_raw, b.raw, b.nsamp, b.maxbits, b.store,
                        b.tiles, VS::tile_bytes(PREC), VS::G_COL, VS::G_SIG);
     EVD_LAUNCH_CHECK();
-    auto dgrad = [&](int stream, int in_slot, int extra_slot, int mask_slot, int out_slot) {
-        DgradParams p;
-        p.wstream = b.wt[stream]; p.store = b.store; p.tile_bytes = VS::tile_bytes(PREC);
-        p.in_slot = in_slot; p.extra_slot = extra_slot; p.mask_slot = mask_slot; p.out_slot = out_slot;
-        return p;
-    };
-    auto wgrad = [&](auto launch, int RT, int CT, bool bias, int y_slot, int x_slot, int ymap, int xmap, float* dW, int ld, float* db) -> int {
-        if (!dW) return EVD_OK;
-        const int blocks = (int)(cdiv(b.tiles, (long)WGRAD_TPI) < b.wgrad_blocks ? cdiv(b.tiles, (long)WGRAD_TPI) : b.wgrad_blocks);
-        WgradParams p;
-        p.store = b.store; p.tiles = b.tiles; p.tile_bytes = VS::tile_bytes(PREC); p.y_slot = y_slot; p.x_slot = x_slot; p.bias = bias ? 1 : 0; p.partial = b.partial;
-        hipStream_t ws = st;
-        if (b.side) {                           // fork: everything issued so far on the caller's stream first (nerf_train_kernel.h)
-            EVD_HIP(hipEventRecord(b.ev, st));
-            EVD_HIP(hipStreamWaitEvent(b.side, b.ev, 0));
-            ws = b.side;
-            if (int rcs = test_side_spin(ws)) return rcs;
-        }
-        int r = launch(p, blocks, ws);
-        if (r) return r;
-        WreduceParams q;
-        q.partial = b.partial; q.nparts = blocks; q.RT = RT; q.CT = CT; q.NC = CT + (bias ? 1 : 0);
-        q.rowmap = b.maps + ymap; q.colmap = b.maps + xmap; q.dW = dW; q.ld = ld; q.db = bias ? db : nullptr; q.maxbits = b.maxbits; q.accum = b.accumulate;
-        hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((long)RT * q.NC * 4)), dim3(256), 0, ws, q);
-        EVD_LAUNCH_CHECK();
-        return EVD_OK;
-    };
-    // wgrad(l) with dgrad(l) in one launch (nerf_train_kernel.h k_wgrad_dgrad): the 256-wide layers of the fine level in the
-    // half-precision modes; EVD_BWD_FUSE=0 keeps the separate launches (A/B)
-    static const bool fuse_on = [] { const char* e = getenv("EVD_BWD_FUSE"); return !(e && e[0] == '0'); }();
-    constexpr bool FUSABLE = is_half_prec(PREC) && T == 8;
-    auto fused = [&](auto launch, int CT, bool bias, int y_slot, int x_slot, int ymap, int xmap, float* dW, int ld, float* db, int stream, int mask_slot, int out_slot,
-                     int RTr = 8, int y_last_slot = -1, const char* ygen_wt = nullptr, float* rows = nullptr, int rows_tiles = 0) -> int {
-        const int blocks = (int)(b.tiles < b.wgrad_blocks ? b.tiles : b.wgrad_blocks);
-        WgradFusedParams p;
-        p.w.store = b.store; p.w.tiles = b.tiles; p.w.tile_bytes = VS::tile_bytes(PREC); p.w.y_slot = y_slot; p.w.x_slot = x_slot; p.w.bias = bias ? 1 : 0; p.w.partial = b.partial;
-        p.wt = b.wt[stream]; p.out_store = b.store; p.mask_slot = mask_slot; p.out_slot = out_slot; p.y_last_slot = y_last_slot; p.ygen_wt = ygen_wt;
-        p.rows = rows; p.rows_stride = b.d_fts_stride; p.rows_tiles = rows_tiles; p.nsamp = b.nsamp; p.maxbits = b.maxbits;
-        if (b.side && !test_skip_side_join()) { // the wgrad launches in flight on the side stream use the partial scratch: join first
-            EVD_HIP(hipEventRecord(b.ev, b.side));
-            EVD_HIP(hipStreamWaitEvent(st, b.ev, 0));
-        }
-        int r = launch(p, blocks, st);
-        if (r) return r;
-        if (!dW) return EVD_OK;
-        WreduceParams q;
-        q.partial = b.partial; q.nparts = blocks; q.RT = RTr; q.CT = CT; q.NC = CT + (bias ? 1 : 0);
-        q.rowmap = b.maps + ymap; q.colmap = b.maps + xmap; q.dW = dW; q.ld = ld; q.db = bias ? db : nullptr; q.maxbits = b.maxbits; q.accum = b.accumulate;
-        q.part_stride = RTr < 8 ? (long)8 * q.NC * 1024 : 0;       // the kernel lays every workgroup's set out as 8 row tiles
-        hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((long)RTr * q.NC * 4)), dim3(256), 0, st, q);
-        EVD_LAUNCH_CHECK();
-        return EVD_OK;
-    };
-    const VoxBwdGrads& g = b.grads;
-    // (each wgrad is issued before the dgrad layer that reads the same arrays: independent, concurrent on the side stream)
     // color_net.2 (+ sigmoid, folded into the gradient fragment)
-    if ((rc = wgrad(launch_wgrad<PREC, 1, T, true>, 1, T, g.color_b[2] != nullptr, VS::G_COL, VS::C1, VMAP_COL, VMAP_HID, g.color_w[2], HD, g.color_b[2]))) return rc;
+    if ((rc = c.wgrad(launch_wgrad<PREC, 1, T, true>, wb, 1, T, g.color_b[2] != nullptr, VS::G_COL, VS::C1, VMAP_COL, VMAP_HID, g.color_w[2], HD, g.color_b[2]))) return rc;
     // color_net.1; in the fused form d c1 = (W2^T d colour) . [c1 > 0] is formed inside the launch from the pair [G_COL | M_C1]
     // (k_wgrad_dgrad YGEN: color_net.2's dgrad launch and the D_C1 round trip are gone; EVD_BWD_YGEN=0: the separate launch)
-    static const bool ygen_on = [] { const char* e = getenv("EVD_BWD_YGEN"); return !(e && e[0] == '0'); }();
-    const bool ygen = FUSABLE && fuse_on && ygen_on && g.color_w[1];
+    const bool c1_fused = FUSABLE && g.color_w[1], ygen = c1_fused && sw.ygen;
     static_assert(VS::M_C1 == VS::G_COL + 1, "the formed gradient's two inputs are one fragment pair");
     if (!ygen && (rc = launch_dgrad<PREC, 1, T, 1, false, 2>(dgrad(VBWD_C2, VS::G_COL, -1, VS::M_C1, VS::D_C1), b.tiles, st))) return rc;
     if constexpr (FUSABLE) {
-        if (ygen) {
-            if ((rc = fused(launch_wgrad_dgrad<PREC, 8, 8, 1, 8, 16, true>, 8, g.color_b[1] != nullptr, VS::G_COL, VS::C1 - KS, VMAP_HID, VMAP_HID, g.color_w[1], HD, g.color_b[1], VBWD_C1, VS::M_C0,
-                            VS::D_C0, 8, -1, b.wt[VBWD_C2]))) return rc;
-        } else if (fuse_on && g.color_w[1]) {
-            if ((rc = fused(launch_wgrad_dgrad<PREC, 8, 8, 1>, 8, g.color_b[1] != nullptr, VS::D_C1, VS::C1 - KS, VMAP_HID, VMAP_HID, g.color_w[1], HD, g.color_b[1], VBWD_C1, VS::M_C0, VS::D_C0))) return rc;
-        } else {
-            if ((rc = wgrad(launch_wgrad<PREC, T, T, false>, T, T, g.color_b[1] != nullptr, VS::D_C1, VS::C1 - KS, VMAP_HID, VMAP_HID, g.color_w[1], HD, g.color_b[1]))) return rc;
-            if ((rc = launch_dgrad<PREC, KS, T, KS, false, 2>(dgrad(VBWD_C1, VS::D_C1, -1, VS::M_C0, VS::D_C0), b.tiles, st))) return rc;
+        if (c1_fused) {
+            FusedExtra x;
+            x.mask_slot = VS::M_C0;
+            x.ygen_wt = ygen ? b.wt[VBWD_C2] : nullptr;
+            rc = ygen ? c.fused(launch_wgrad_dgrad<PREC, 8, 8, 1, 8, 16, true>, 8, g.color_b[1] != nullptr, VS::G_COL, VS::C1 - KS, VMAP_HID, VMAP_HID, g.color_w[1], HD, g.color_b[1],
+                                b.wt[VBWD_C1], VS::D_C0, x)
+                      : c.fused(launch_wgrad_dgrad<PREC, 8, 8, 1>, 8, g.color_b[1] != nullptr, VS::D_C1, VS::C1 - KS, VMAP_HID, VMAP_HID, g.color_w[1], HD, g.color_b[1],
+                                b.wt[VBWD_C1], VS::D_C0, x);
+            if (rc) return rc;
         }
-    } else {
-        if ((rc = wgrad(launch_wgrad<PREC, T, T, false>, T, T, g.color_b[1] != nullptr, VS::D_C1, VS::C1 - KS, VMAP_HID, VMAP_HID, g.color_w[1], HD, g.color_b[1]))) return rc;
+    }
+    if (!c1_fused) {
+        if ((rc = c.wgrad(launch_wgrad<PREC, T, T, false>, wb, T, T, g.color_b[1] != nullptr, VS::D_C1, VS::C1 - KS, VMAP_HID, VMAP_HID, g.color_w[1], HD, g.color_b[1]))) return rc;
         if ((rc = launch_dgrad<PREC, KS, T, KS, false, 2>(dgrad(VBWD_C1, VS::D_C1, -1, VS::M_C0, VS::D_C0), b.tiles, st))) return rc;
     }
     // color_net.0 on cat([geo, PE(dirs)])
     bool c0_fused = false;
     if constexpr (FUSABLE && G == 32 * GT) {
-        if (fuse_on && g.color_w[0]) {     // wgrad + dgrad of color_net.0 in one launch: d c0 read once; writes d geo | d PE(dirs) (no ReLU on geo)
+        if (g.color_w[0]) {     // wgrad + dgrad in one launch: d c0 read once; writes d geo | d PE(dirs) (no ReLU on geo)
             static_assert(VS::D_DIRPE == VS::D_GEO + 2 * GT, "d PE(dirs) behind d geo");
-            if ((rc = fused(launch_wgrad_dgrad<PREC, GT + 1, GT + 1, 0>, GT + 1, g.color_b[0] != nullptr, VS::D_C0, VS::GEO, VMAP_HID, VMAP_GEO_X, g.color_w[0], G + ICV, g.color_b[0], VBWD_C0, -1, VS::D_GEO))) return rc;
+            // the geo and the direction-encoding columns are ONE operand of GT + 1 tiles
+            static_assert(VS::DIRPE == VS::GEO + 2 * GT && VMAP_DIR == VMAP_GEO_X + 128 && (G == 128), "adjacent fragments and column maps");
+            if ((rc = c.fused(launch_wgrad_dgrad<PREC, GT + 1, GT + 1, 0>, GT + 1, g.color_b[0] != nullptr, VS::D_C0, VS::GEO, VMAP_HID, VMAP_GEO_X, g.color_w[0], G + ICV, g.color_b[0],
+                              b.wt[VBWD_C0], VS::D_GEO))) return rc;
             c0_fused = true;
-        }
-    }
-    if (c0_fused) {
-    } else if constexpr (is_half_prec(PREC) && G == 32 * GT) {
-        // geo and direction-encoding columns in ONE launch (adjacent fragments, adjacent index maps): d c0 is read once
-        static_assert(VS::DIRPE == VS::GEO + 2 * GT && VMAP_DIR == VMAP_GEO_X + 128 && (G == 128), "adjacent fragments and column maps");
-        if ((rc = wgrad(launch_wgrad<PREC, T, GT + 1, false>, T, GT + 1, g.color_b[0] != nullptr, VS::D_C0, VS::GEO, VMAP_HID, VMAP_GEO_X, g.color_w[0], G + ICV, g.color_b[0]))) return rc;
+        }                       // (not wanted: no wgrad, the dgrad below)
     } else {
-        if ((rc = wgrad(launch_wgrad<PREC, T, GT, false>, T, GT, g.color_b[0] != nullptr, VS::D_C0, VS::GEO, VMAP_HID, VMAP_GEO_X, g.color_w[0], G + ICV, g.color_b[0]))) return rc;
-        if ((rc = wgrad(launch_wgrad<PREC, T, 1, false>, T, 1, false, VS::D_C0, VS::DIRPE, VMAP_HID, VMAP_DIR, g.color_w[0], G + ICV, nullptr))) return rc;
+        if ((rc = c.wgrad(launch_wgrad<PREC, T, GT, false>, wb, T, GT, g.color_b[0] != nullptr, VS::D_C0, VS::GEO, VMAP_HID, VMAP_GEO_X, g.color_w[0], G + ICV, g.color_b[0]))) return rc;
+        if ((rc = c.wgrad(launch_wgrad<PREC, T, 1, false>, wb, T, 1, false, VS::D_C0, VS::DIRPE, VMAP_HID, VMAP_DIR, g.color_w[0], G + ICV, nullptr))) return rc;
     }
     if (!c0_fused && (rc = launch_dgrad<PREC, KS, GT + 1, KS, false, 0>(dgrad(VBWD_C0, VS::D_C0, -1, -1, VS::D_GEO), b.tiles, st))) return rc;   // d geo | d PE(dirs)
     if (b.d_feature) {          // + the gradient of the geo features as an output of the level (voxnerf.py:221, consumed by AWP)
@@ -300,39 +263,36 @@ template <int PREC, int HD, int G, int FT> static int run_voxel_backward(const V
                            b.awp_store, b.awp_tile_bytes, b.awp_slot, G / 16, b.tiles, b.maxbits, b.awp_words);
         EVD_LAUNCH_CHECK();
     }
-    if (b.d_dirs) {
-        hipLaunchKernelGGL((k_pe_bwd<PREC, PE_LV, PEV_KS>), dim3((unsigned)cdiv(b.tiles * 64, 256L)), dim3(256), 0, st, (const char*)b.store, VS::tile_bytes(PREC),
-                           VS::D_DIRPE, b.nsamp, b.viewdirs, b.vd_stride, b.S, b.maxbits, b.d_dirs, 0);
-        EVD_LAUNCH_CHECK();
-    }
+    if ((rc = voxel_backward_inputs<PREC, VS, FT>(c, b, VOUT_DIRS))) return rc;
     // sigma_net.1 = [sigma row | geo rows] on hid
     bool sg_fused = false;
     if constexpr (FUSABLE && GT == 4) {
-        // round 5: both wgrads and the dgrad in one launch -- the gradient as 4 geo row tiles + the d sigma fragment (k_wgrad_dgrad RT_ = 5,
-        // 9 k-steps): hid and d geo are read once instead of three / two times (42 KiB per tile instead of 67); EVD_BWD_FUSE_SG=0: the three launches
-        static const bool sg_on = [] { const char* e = getenv("EVD_BWD_FUSE_SG"); return !(e && e[0] == '0'); }();
-        if (fuse_on && sg_on && g.sigma_w[1]) {
-            if ((rc = fused(launch_wgrad_dgrad<PREC, 8, 8, 1, GT + 1, 2 * GT + 1>, T, false, VS::D_GEO, VS::HID, VMAP_SG5, VMAP_HID, g.sigma_w[1], HD, nullptr, VBWD_SIGGEO,
-                            VS::M_HID, VS::D_HID, GT + 1, VS::G_SIG))) return rc;
+        // both wgrads and the dgrad in one launch -- the gradient as 4 geo row tiles + the d sigma fragment (k_wgrad_dgrad RT_ = 5, 9 k-steps): hid
+        // and d geo are read once instead of three / two times (42 KiB per tile instead of 67); EVD_BWD_FUSE_SG=0: the three launches
+        if (sw.fuse_sg && g.sigma_w[1]) {
+            FusedExtra x;
+            x.mask_slot = VS::M_HID; x.RTr = GT + 1; x.y_last_slot = VS::G_SIG;
+            if ((rc = c.fused(launch_wgrad_dgrad<PREC, 8, 8, 1, GT + 1, 2 * GT + 1>, T, false, VS::D_GEO, VS::HID, VMAP_SG5, VMAP_HID, g.sigma_w[1], HD, nullptr, b.wt[VBWD_SIGGEO],
+                              VS::D_HID, x))) return rc;
             sg_fused = true;
         }
     }
     if (!sg_fused) {
-        if ((rc = wgrad(launch_wgrad<PREC, GT, T, false>, GT, T, false, VS::D_GEO, VS::HID, VMAP_GEO_Y, VMAP_HID, g.sigma_w[1], HD, nullptr))) return rc;
-        if ((rc = wgrad(launch_wgrad<PREC, 1, T, true>, 1, T, false, VS::G_SIG, VS::HID, VMAP_SIG, VMAP_HID, g.sigma_w[1], HD, nullptr))) return rc;
+        if ((rc = c.wgrad(launch_wgrad<PREC, GT, T, false>, wb, GT, T, false, VS::D_GEO, VS::HID, VMAP_GEO_Y, VMAP_HID, g.sigma_w[1], HD, nullptr))) return rc;
+        if ((rc = c.wgrad(launch_wgrad<PREC, 1, T, true>, wb, 1, T, false, VS::G_SIG, VS::HID, VMAP_SIG, VMAP_HID, g.sigma_w[1], HD, nullptr))) return rc;
         if ((rc = launch_dgrad<PREC, 2 * GT + 1, T, 2 * GT, true, 2>(dgrad(VBWD_SIGGEO, VS::D_GEO, VS::G_SIG, VS::M_HID, VS::D_HID), b.tiles, st))) return rc;
     }
     // sigma_net.0 on cat([fts, PE(pts)])
     bool l0_fused = false, l0_rows = false;
     if constexpr (FUSABLE && FTT == 2) {
-        if (fuse_on && g.sigma_w[0] && (b.d_fts || b.d_pts)) {     // ... with its dgrad (d fts | d PE(pts)) in one launch
+        if (g.sigma_w[0] && (b.d_fts || b.d_pts)) {     // ... with its dgrad (d fts | d PE(pts)) in one launch
             static_assert(VS::D_PE == VS::D_FTS + 2 * FTT, "d PE(pts) behind d fts");
-            // round 5: the feature tiles of d X leave as the float32 rows the scatter reads (EVD_BWD_ROWS=0: fragments + k_frags_to_rows)
-            static const bool rows_on = [] { const char* e = getenv("EVD_BWD_ROWS"); return !(e && e[0] == '0'); }();
-            l0_rows = rows_on && b.d_fts && b.d_fts_stride % 4 == 0 && ((uintptr_t)b.d_fts & 15) == 0;
-            if (l0_rows) rc = fused(launch_wgrad_dgrad<PREC, FTT + 2, FTT + 2, 0, 8, 16, false, true>, FTT + 2, false, VS::D_HID, VS::IN0, VMAP_HID, VMAP_FTS, g.sigma_w[0], FT + IC, nullptr,
-                                    VBWD_L0, -1, VS::D_FTS, 8, -1, nullptr, b.d_fts, FTT);
-            else rc = fused(launch_wgrad_dgrad<PREC, FTT + 2, FTT + 2, 0>, FTT + 2, false, VS::D_HID, VS::IN0, VMAP_HID, VMAP_FTS, g.sigma_w[0], FT + IC, nullptr, VBWD_L0, -1, VS::D_FTS);
+            l0_rows = voxel_rows_direct(b);
+            FusedExtra x;
+            x.rows = b.d_fts; x.rows_stride = b.d_fts_stride; x.rows_tiles = FTT;
+            rc = l0_rows ? c.fused(launch_wgrad_dgrad<PREC, FTT + 2, FTT + 2, 0, 8, 16, false, true>, FTT + 2, false, VS::D_HID, VS::IN0, VMAP_HID, VMAP_FTS, g.sigma_w[0], FT + IC, nullptr,
+                                   b.wt[VBWD_L0], VS::D_FTS, x)
+                         : c.fused(launch_wgrad_dgrad<PREC, FTT + 2, FTT + 2, 0>, FTT + 2, false, VS::D_HID, VS::IN0, VMAP_HID, VMAP_FTS, g.sigma_w[0], FT + IC, nullptr, b.wt[VBWD_L0], VS::D_FTS);
             if (rc) return rc;
             l0_fused = true;
         }
@@ -341,29 +301,28 @@ template <int PREC, int HD, int G, int FT> static int run_voxel_backward(const V
     } else if constexpr (FTT == 2) {
         // the feature and encoding columns in ONE launch (their fragments and their index maps are adjacent): d hid is read once, not twice
         static_assert(VMAP_PE == VMAP_FTS + 32 * FTT, "adjacent column maps");
-        if ((rc = wgrad(launch_wgrad<PREC, T, FTT + 2, false>, T, FTT + 2, false, VS::D_HID, VS::IN0, VMAP_HID, VMAP_FTS, g.sigma_w[0], FT + IC, nullptr))) return rc;
+        if ((rc = c.wgrad(launch_wgrad<PREC, T, FTT + 2, false>, wb, T, FTT + 2, false, VS::D_HID, VS::IN0, VMAP_HID, VMAP_FTS, g.sigma_w[0], FT + IC, nullptr))) return rc;
     } else {
-        if ((rc = wgrad(launch_wgrad<PREC, T, FTT, false>, T, FTT, false, VS::D_HID, VS::IN0, VMAP_HID, VMAP_FTS, g.sigma_w[0], FT + IC, nullptr))) return rc;
-        if ((rc = wgrad(launch_wgrad<PREC, T, 2, false>, T, 2, false, VS::D_HID, VS::IN0 + KF, VMAP_HID, VMAP_PE, g.sigma_w[0], FT + IC, nullptr))) return rc;
+        if ((rc = c.wgrad(launch_wgrad<PREC, T, FTT, false>, wb, T, FTT, false, VS::D_HID, VS::IN0, VMAP_HID, VMAP_FTS, g.sigma_w[0], FT + IC, nullptr))) return rc;
+        if ((rc = c.wgrad(launch_wgrad<PREC, T, 2, false>, wb, T, 2, false, VS::D_HID, VS::IN0 + KF, VMAP_HID, VMAP_PE, g.sigma_w[0], FT + IC, nullptr))) return rc;
     }
     if (b.d_fts || b.d_pts) {
         if (!l0_fused && (rc = launch_dgrad<PREC, KS, FTT + 2, KS, false, 0>(dgrad(VBWD_L0, VS::D_HID, -1, -1, VS::D_FTS), b.tiles, st))) return rc;       // d fts | d PE(pts)
-        if (b.d_fts && !l0_rows) {
-            hipLaunchKernelGGL((k_frags_to_rows<PREC>), dim3((unsigned)cdiv(b.tiles * 64 * KF, 256L)), dim3(256), 0, st, (const char*)b.store, VS::tile_bytes(PREC),
-                               VS::D_FTS, KF, b.nsamp, b.maxbits, b.d_fts, b.d_fts_stride);
-            EVD_LAUNCH_CHECK();
-        }
-        if (b.d_pts) {
-            hipLaunchKernelGGL((k_pe_bwd<PREC, PE_L, PE_KS>), dim3((unsigned)cdiv(b.tiles * 64, 256L)), dim3(256), 0, st, (const char*)b.store, VS::tile_bytes(PREC),
-                               VS::D_PE, b.nsamp, b.pts, 3, 1, b.maxbits, b.d_pts, 0);
-            EVD_LAUNCH_CHECK();
-        }
+        if ((rc = voxel_backward_inputs<PREC, VS, FT>(c, b, (l0_rows ? 0 : VOUT_FTS) | VOUT_PTS))) return rc;
     }
-    if (b.side && !test_skip_side_join()) {     // join
-        EVD_HIP(hipEventRecord(b.ev, b.side));
-        EVD_HIP(hipStreamWaitEvent(st, b.ev, 0));
+    return c.join();
+}
+
+template <int PREC, int HD, int G, int FT> static int run_voxel_backward(const VoxBwdPlan& b, hipStream_t st) {
+    typedef VStore<HD, G, FT> VS;
+    int rc;
+    if ((rc = voxel_backward_scale(b, G, st))) return rc;
+    const BwdChain c(b, VS::tile_bytes(PREC), st);
+    // EVD_BWD_FUSE64=0 keeps the per-layer chain for the 64-wide level too (A/B, and the reference the fused kernel is tested against)
+    if constexpr (is_half_prec(PREC) && HD == 64 && G == 15 && FT == 32) {
+        if (bwd_switches().fuse64 && !b.d_feature && !b.awp_store) return voxel_backward_fused64<PREC>(c, b);
     }
-    return EVD_OK;
+    return voxel_backward_layers<PREC, HD, G, FT>(c, b);
 }
 
 }  // namespace evd

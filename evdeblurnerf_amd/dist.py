@@ -132,7 +132,7 @@ class GradReducer:
           networks, TV).  A torch-side term on those leaves (e.g. a weight-decay loss written as (p ** 2).sum()) reaches .grad through
           AccumulateGrad, possibly after the level's last library node: use no_sync() for such a step, or do not attach.
         * ordering against the backward entries' side streams: evd_*_mlp_backward joins its per-handle side stream into the caller's
-          stream before it returns (csrc/voxel_train_kernel.h, nerf_train_kernel.h: hipEventRecord(side) + hipStreamWaitEvent(stream)),
+          stream before it returns (csrc/bwd_launch.h BwdChain::join: hipEventRecord(side) + hipStreamWaitEvent(stream)),
           and the process group orders the collective behind the work already enqueued on the current stream, so a collective started
           here sees the complete buffers.  tests/test_gpu_dist.py delays every side-stream launch by 2 ms (with the voxel levels' side
           stream switched on, asserting that the delay kernels ran) and has a negative control with the join disabled, whose gradients
