@@ -208,6 +208,8 @@ SIGNATURES = {
     "evd_numerics_flags": (_I, [C.POINTER(_vp), C.POINTER(C.c_long), _I, _vp, _vp]),
     "evd_edi_deblur": (_I, [_vp, _vp, _I, _L, _vp, _vp]),
     "evd_edi_bii_image": (_I, [_vp, _vp, _vp, _L, _I, _I, _F, _F, _vp, _vp]),
+    "evd_edi_prior_workspace_bytes": (_S, [_I, _I, _I, _I]),
+    "evd_edi_prior": (_I, [_vp, _L, _vp, _L, _vp, _vp, _I, _I, _I, _I, _F, _F, _vp, _vp, _vp, _vp, _S, _vp]),
 }
 
 _lib = None

@@ -818,7 +818,8 @@ __global__ void k_edi_splat(const float* __restrict__ x, const float* __restrict
 #pragma unroll
         for (int yr = 0; yr < 2; ++yr) {
             const float xf = xr ? ceilf(xv) : floorf(xv), yf = yr ? ceilf(yv) : floorf(yv);
-            if (!((xf != xv || xr == 0) && (yf != yv || yr == 0) && xf < (float)w && yf < (float)h)) continue;
+            // (a tap left of / above the frame is dropped: the reference's negative index wraps to the opposite edge, an indexing artefact)
+            if (!((xf != xv || xr == 0) && (yf != yv || yr == 0) && xf < (float)w && yf < (float)h && xf >= 0.f && yf >= 0.f)) continue;
             const float kx = fmaxf(0.f, 1.f - fabsf(xf - xv)), ky = fmaxf(0.f, 1.f - fabsf(yf - yv));
             atomicAdd(image + (long)yf * w + (long)xf, sc * (kx * ky));
         }

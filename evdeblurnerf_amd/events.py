@@ -162,7 +162,8 @@ class EventTables:
     None: ``id_to_coords`` is in the byte order the ids were assigned in and is searched directly), ``id_to_color_map`` [Ncoords, 3] bool or
     None, ``events_num_successors`` [N'] int32, ``events_with_successor_idx`` int64, ``intcoords``, ``noev_coord_ids`` (the ids of the pixels
     no event rounds to), ``allknown_poses`` [M, 3, 4], ``allknown_poses_timestamps``, ``images_*`` timestamps, ``pose_track`` (poses.PoseTrack: the
-    reference's ``events_pose_bspl`` inside ``interpolate_poses``).  ``sampler(K)`` returns the ready ``EventSampler``."""
+    reference's ``events_pose_bspl`` inside ``interpolate_poses``).  ``sampler(K)`` returns the ready ``EventSampler``,
+    ``compute_edi_prior(i_images, images, steps, cpos, cneg)`` the table ``ImageBatcher.set_pts0_prior`` takes."""
 
     @classmethod
     def from_arrays(cls, x, y, t, p, h, w, all_timestamps, all_poses_bounds, img_timestamps=None, img_timestamps_start=None, img_timestamps_end=None,
@@ -263,6 +264,19 @@ class EventTables:
         if self.pose_track is None:
             raise L.EvdError("EventTables.interpolate_poses: built with recenter=True but without the image dataset's recenter_partial")
         return self.pose_track.interpolate_poses(t)
+
+    def compute_edi_prior(self, i_images, images, steps, cpos, cneg):
+        """LLFFEventsDataset.compute_edi_prior (data/loader_events.py:99-131): the sharpened image of every blurry image ``images[k]`` =
+        image ``i_images[k]`` of the dataset, from the events of its exposure: float32 [len(i_images), H, W, 3] on the device, what
+        ``ImageBatcher.set_pts0_prior`` takes.  Raises where the reference asserts (:103) or fails for want of the timestamps."""
+        from .edi import compute_edi_prior
+        if self.images_timestamps_start is None or self.images_timestamps_end is None:
+            raise L.EvdError("EventTables.compute_edi_prior: built without img_timestamps_start / img_timestamps_end")
+        idx = np.asarray(i_images.detach().cpu() if isinstance(i_images, torch.Tensor) else i_images).astype(np.int64).reshape(-1)
+        start, end = self.images_timestamps_start[idx], self.images_timestamps_end[idx]
+        if not (bool((start < end).all()) and bool((start > 0).all())):
+            raise L.EvdError("EventTables.compute_edi_prior: every exposure needs 0 < start < end (loader_events.py:103)")
+        return compute_edi_prior(self.events, self.id_to_coords, start, end, images, steps, cpos, cneg)
 
     def sampler(self, K, step_end=0, scheduler="constant"):
         """-> the EventSampler of this dataset (integer_coords, colour map, pose track, hop schedule when an accumulation range was given)"""

@@ -565,6 +565,30 @@ int evd_edi_deblur(const float* blurry, const float* bii, int steps, long npix, 
  * x,y dev [n] float, p dev int8 [n] -> image dev [h,w] (overwritten) */
 int evd_edi_bii_image(const float* x, const float* y, const signed char* p, long n, int w, int h,
                       float c_pos, float c_neg, float* image, void* stream);
+/* The whole prior table, LLFFEventsDataset.compute_edi_prior (data/loader_events.py:99-131), on the resident event tables: per image the
+ * event windows between `steps` boundary timestamps, the bilinear splat of every window and the double integral.
+ *   events        dev float64 [N, 4] (coordinate id, timestamp, polarity, successor: the table of evd_event_filter + the successor column),
+ *                 timestamps ascending
+ *   id_to_coords  dev float64 [Ncoords, 2] (x, y)
+ *   boundaries    dev float64 [n_img, steps]: np.linspace(start, end, steps) of every image, made on the host in float64 (:107)
+ *   images        dev float32 [n_img, h, w, 3], the blurry images     prior_out  dev float32 [n_img, h, w, 3]
+ *   windows_out   dev int64 [2, n_img, steps] or NULL: left[i, j] / right[i, j] = the lower / upper bound of boundary j in the timestamp
+ *                 column (torch.searchsorted side left / right, :111-112)
+ *   bad_id        dev int32 [1] or NULL: set to 1 when an event's coordinate id lies outside [0, Ncoords); such an event is skipped
+ * Window j of image i holds the events left[i, j] <= e < right[i, j + 1] (:119-121): an event exactly on an interior boundary counts in
+ * both neighbouring windows.  Taps as evd_edi_bii_image (utils/edi.py:7-41) on the float64 coordinates, with ONE deviation: a tap with
+ * xf < 0 or yf < 0 is dropped (numpy's negative index wraps it to the opposite edge in the reference); the event's other taps land.
+ * The tap weights are summed as 64-bit integers in units of 2^-40 (integer atomics: the table is bit-reproducible; a pixel takes 2^23 unit
+ * taps per window and polarity before overflow; a stored weight is the float64 product rounded to the nearest unit: off by <= 2^-41).
+ * bii = float(pos) c_pos - float(neg) c_neg and the double integral in float32 as evd_edi_deblur; one bii feeds the three channels.
+ * steps odd, 3 <= steps <= 65.  Workspace: evd_edi_prior_workspace_bytes(c, steps, h, w) = the windows of c images + their accumulator
+ * planes, c (steps - 1) h w 16 bytes (11.5 MB per image at 260 x 346, steps 9); c is capped at 16 images (the figure no longer grows
+ * beyond).  The entry takes any workspace >= the figure for ONE image and works through the images in chunks of as many as fit
+ * (<= 16); the result does not depend on the chunk.  No device-to-host read-back; asynchronous on `stream`. */
+size_t evd_edi_prior_workspace_bytes(int n_img, int steps, int h, int w);
+int evd_edi_prior(const double* events, long N, const double* id_to_coords, long n_coords, const double* boundaries, const float* images,
+                  int n_img, int steps, int h, int w, float c_pos, float c_neg, float* prior_out, long long* windows_out, int* bad_id,
+                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- event preprocessing
  * compute_successor, utils/events.py:72-120 (flat_xy = True): pixel_ids dev int32 [N] (y * w + x of every event, in stream

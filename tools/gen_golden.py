@@ -1554,13 +1554,70 @@ def G35_llff_poses():
                     f"{tag}_recentered": np.asarray(rec), f"{tag}_c2w": np.asarray(c2w).astype(np.float64)})
     save64("G35_llff_poses", **out)
 
+def g36_int_inputs():
+    """G36 'int': integer pixel coordinates on a 48 x 64 frame, 3 exposures of 8 x 40 microseconds, steps 9 (every boundary an integer microsecond),
+    integer timestamps drawn 20 microseconds around each exposure -- many of them ON a boundary --, plus events placed on purpose, each kind on pixels
+    of its own: exactly on the start boundary, on interior boundaries, on the end boundary, and 1 microsecond outside the start and the end."""
+    rs = np.random.RandomState(3602)
+    h, w, steps, span = 48, 64, 9, 320
+    start = np.array([50_000.0, 50_700.0, 51_900.0])
+    end = start + span
+    x, y, tt, pp = [], [], [], []
+    for i in range(3):
+        n_ev = 1500
+        x.append(rs.randint(0, w, n_ev)); y.append(rs.randint(8, h, n_ev))
+        tt.append(rs.randint(int(start[i]) - 20, int(end[i]) + 21, n_ev)); pp.append(rs.choice([-1, 1], n_ev))
+        # the placed events: rows 0 .. 4 of the frame belong to them (the random part stays on rows >= 8)
+        step = span // (steps - 1)
+        kinds = {0: [start[i]] * 6, 1: [start[i] + step * j for j in (1, 2, 4, 5, 7, 7)], 2: [end[i]] * 6, 3: [start[i] - 1] * 4, 4: [end[i] + 1] * 4}
+        for row, ts in kinds.items():
+            for k, tv in enumerate(ts):
+                x.append([10 * i + k]); y.append([row]); tt.append([int(tv)]); pp.append([1 if k % 2 == 0 else -1])
+    x, y, tt, pp = (np.concatenate(a) for a in (x, y, tt, pp))
+    order = np.argsort(tt, kind="stable")
+    x, y, tt, pp = x[order], y[order], tt[order], pp[order]
+    gx, gy = np.meshgrid(np.arange(w), np.arange(h))
+    i2c = np.stack([gx.reshape(-1), gy.reshape(-1)], -1).astype(np.float64)            # id = y w + x
+    events = np.stack([(y * w + x).astype(np.float64), tt.astype(np.float64), pp.astype(np.float64), np.zeros(len(tt))], -1)
+    images = rs.uniform(0.05, 1.0, (3, h, w, 3)).astype(np.float32)
+    return {"events": events, "id_to_coords": i2c, "tms_start": start, "tms_end": end, "images": images, "steps": steps, "cpos": 0.2, "cneg": 0.25}
+
+
+def G36_edi_prior():
+    """LLFFEventsDataset.compute_edi_prior (data/loader_events.py:99-131) called UNBOUND on an object with the attributes it reads
+    (images_tms_start, images_tms_end, events, id_to_coords, device).  'int': inputs and the full result stored.  'flt': the inputs are
+    tests/edi_prior_ref.g36_flt_inputs() (seeded; the tests derive them again), stored is what the reference returned: channel 0 in
+    full, channels 1 and 2 on every 8th row (the three channels share every factor but the blurry pixel)."""
+    import types
+    import data.loader_events as LE
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from edi_prior_ref import G36_FLT_ROWS, g36_flt_inputs
+    out = {}
+    for tag, d in (("int", g36_int_inputs()), ("flt", g36_flt_inputs())):
+        n_img = d["images"].shape[0]
+        # i_images out of order, a dataset with more exposures than are asked for
+        pad = np.array([1.0, 2.0])
+        i_images = np.arange(n_img)[::-1] + 1
+        fake = types.SimpleNamespace(images_tms_start=np.concatenate([pad[:1], d["tms_start"][::-1], pad[1:]]),
+                                     images_tms_end=np.concatenate([pad[:1] + 1, d["tms_end"][::-1], pad[1:] + 1]),
+                                     events=t(d["events"]), id_to_coords=t(d["id_to_coords"]), device="cpu")
+        prior = n(LE.LLFFEventsDataset.compute_edi_prior(fake, i_images, t(d["images"]), d["steps"], d["cpos"], d["cneg"]))
+        assert prior.dtype == np.float32 and prior.shape == d["images"].shape
+        if tag == "int":
+            out.update({"int_events": d["events"][:, :3], "int_tms_start": d["tms_start"], "int_tms_end": d["tms_end"], "int_images": d["images"],
+                        "int_args": np.array([d["steps"], d["cpos"], d["cneg"]]), "int_prior": prior})
+        else:
+            out.update({"flt_prior_c0": prior[..., 0], "flt_prior_c12_rows": prior[:, ::G36_FLT_ROWS, :, 1:]})
+        print(f"   {tag}: prior {prior.shape}, {d['events'].shape[0]} events")
+    save64("G36_edi_prior", **out)
+
 
 ALL = [G1_embedder, G2_nerf_mlp, G3_nerf_raw2outputs, G4_voxel_raw2outputs, G5_sample_pdf, G6_rays,
        G7_render_nerf, G8_appfeature, G9_render_c2f, G10_rbk_weighted_sum, G11_crf, G12_egm_loss, G13_edi,
        G14_loss_assembly, G15_awp_feature_integration, G16_rbk_warp, G17_compute_successor, G18_nerf_grads, G19_c2f_grads, G20_loss_grads,
        G21_awp_sample_embed, G22_mam, G23_render_nerf_no_viewdirs, G24_render_other_multires, G25_pbe_composite_feature,
        G26_sample_events, G27_awp_per_ray, G28_image_batch, G29_pose_track, G30_c2f_grads_16k, G31_event_hops, G32_train_forward,
-       G33_train_trajectory, G34_event_tables, G35_llff_poses]
+       G33_train_trajectory, G34_event_tables, G35_llff_poses, G36_edi_prior]
 
 if __name__ == "__main__":
     want = set(sys.argv[1:])
