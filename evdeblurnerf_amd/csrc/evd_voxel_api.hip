@@ -12,8 +12,8 @@
 #include <cstdint>
 #include <cstdlib>
 
-// the PDRF level networks keep generic / pipelined / training streams for the first four arithmetic modes; EVD_PREC_F16C (compensated
-// float16) is an INFERENCE mode with its own stream (pipe_c) on the fine level; the 64-wide coarse level runs EVD_PREC_F16X3 next to it
+// the PDRF level networks keep packed streams for the first four arithmetic modes; EVD_PREC_F16C (compensated float16) has its own
+// stream (pipe_c) on the fine level; the 64-wide coarse level runs EVD_PREC_F16X3 next to it
 #define EVD_VOX_NUM_PREC EVD_PREC_F16C
 
 using namespace evd;
@@ -24,11 +24,11 @@ struct evd_voxel {
     float aabb[6], rmnear;
     int multires = PE_L, multires_views = PE_LV;
     DevBuf plane[3], line[3], plane_h[3], line_h[3], basis, bias, bias_src, tv_acc, wmaps;
-    PackedStream stream[EVD_VOX_NUM_PREC], pipe[EVD_VOX_NUM_PREC];    // pipe: stream of the software-pipelined kernel, where built
-    int nchunks[EVD_VOX_NUM_PREC], pipe_chunks[EVD_VOX_NUM_PREC];
-    // training path (bf16 / f16): the level's network on the software pipeline (the fine level shares `pipe`) and its W^T streams
-    PackedStream train[EVD_VOX_NUM_PREC], bwd[EVD_VOX_NUM_PREC][VBWD_NSTREAMS];
-    int train_chunks[EVD_VOX_NUM_PREC];
+    // fwd: the level's network in the layer table of voxel_mlp_kernel.h, ONE stream per mode of a standard level (is_train_prec): the
+    // render pass and the training forward both read it.  stream: the generic kernel's layout (kernel_voxel.hip), built only where
+    // voxel_level_forward can select it (has_generic_stream).  bwd: the W^T streams of the training backward.
+    PackedStream stream[EVD_VOX_NUM_PREC], fwd[EVD_VOX_NUM_PREC], bwd[EVD_VOX_NUM_PREC][VBWD_NSTREAMS];
+    int nchunks[EVD_VOX_NUM_PREC], fwd_chunks[EVD_VOX_NUM_PREC];
     mutable PackedStreamC pipe_c; // compensated float16 mode (voxel_mlp_c_kernel.h): float16 + fp6 fragments and row scales; fine level only
     int pipe_c_chunks = 0;
     // its re-pack after evd_voxel_load_params is LAZY (a training loop re-loads every iteration and never renders in this mode): the new
@@ -44,13 +44,18 @@ struct evd_voxel {
 
 static const int kMat0[3] = {0, 0, 1}, kMat1[3] = {1, 2, 2}, kVec[3] = {2, 1, 0};
 
+// Where voxel_level_forward can take the generic kernel, i.e. which levels and modes need `stream`: a mode or an encoding without a pipelined
+// stream (EVD_PREC_F32, non-standard multires / multires_views), and the 64-wide level in every mode: for per-sample feature rows (also
+// the geo rows of a composite_feature level) it has no other kernel.  The fine level's pipelined kernels write those rows themselves.
+static bool has_generic_stream(bool piped, int hidden_dim) { return !piped || hidden_dim == 64; }
+
 extern "C" {
 
 void evd_voxel_destroy(evd_voxel* v) {
     if (!v) return;
     for (int i = 0; i < 3; ++i) { v->plane[i].release(); v->line[i].release(); v->plane_h[i].release(); v->line_h[i].release(); }
     for (int i = 0; i < EVD_VOX_NUM_PREC; ++i) {
-        v->stream[i].release(); v->pipe[i].release(); v->train[i].release();
+        v->stream[i].release(); v->fwd[i].release();
         for (int k = 0; k < VBWD_NSTREAMS; ++k) v->bwd[i][k].release();
     }
     v->basis.release(); v->bias.release(); v->bias_src.release(); v->tv_acc.release(); v->wmaps.release();
@@ -193,33 +198,25 @@ int evd_voxel_create(const evd_voxel_desc* d, evd_voxel** out) {
         sb.layer(color_w2, 3, HD, 1, KS, true, hid_col);
     };
     for (int prec = 0; prec < EVD_VOX_NUM_PREC; ++prec) {
-        StreamBuilder sb(prec);
-        sb.arena = A;
-        build(sb);
-        v->nchunks[prec] = (int)(sb.bytes.size() / chunk_bytes(prec));
-        rc = v->stream[prec].upload(sb);
-        if (rc) { evd_voxel_destroy(v); return rc; }
-        v->pipe_chunks[prec] = 0;
-        v->train_chunks[prec] = 0;
-        if (standard && voxel_pipe_built(prec, HD, G, FT)) {        // same layers, single-tile groups, 16 KiB chunks (voxel_mlp_kernel.h)
+        const bool piped = standard && is_train_prec(prec);
+        v->nchunks[prec] = v->fwd_chunks[prec] = 0;
+        if (has_generic_stream(piped, HD)) {
+            StreamBuilder sb(prec);
+            sb.arena = A;
+            build(sb);
+            v->nchunks[prec] = (int)(sb.bytes.size() / chunk_bytes(prec));
+            if ((rc = v->stream[prec].upload(sb))) { evd_voxel_destroy(v); return rc; }
+        }
+        if (!piped) continue;
+        {   // same layers, single-tile groups, 16 KiB chunks (voxel_mlp_kernel.h): render and training forward
             StreamBuilder sp(prec, PIPE_CB);
             sp.arena = A;
             sp.group = 1;
             build_pipe(sp);
-            v->pipe_chunks[prec] = (int)(sp.bytes.size() / PIPE_CB);
-            rc = v->pipe[prec].upload(sp);
-            if (rc) { evd_voxel_destroy(v); return rc; }
+            v->fwd_chunks[prec] = (int)(sp.bytes.size() / PIPE_CB);
+            if ((rc = v->fwd[prec].upload(sp))) { evd_voxel_destroy(v); return rc; }
         }
-        if (!is_train_prec(prec) || !standard) continue;
-        {   // training: forward stream of the level (the coarse level has no pipelined inference kernel: its own copy) ...
-            StreamBuilder sp(prec, PIPE_CB);
-            sp.arena = A;
-            sp.group = 1;
-            build_pipe(sp);
-            v->train_chunks[prec] = (int)(sp.bytes.size() / PIPE_CB);
-            if ((rc = v->train[prec].upload(sp))) { evd_voxel_destroy(v); return rc; }
-        }
-        // ... and the W^T streams of the dgrad chain (voxel_train_kernel.h)
+        // the W^T streams of the dgrad chain (voxel_train_kernel.h)
         auto put = [&](int which, auto fill) {
             StreamBuilder sb2(prec, PIPE_CB);
             sb2.arena = A;
@@ -409,6 +406,52 @@ static __global__ __launch_bounds__(256) void k_color_rows(const float* __restri
     }
 }
 
+// the compensated mode's stream into p, re-packed first if evd_voxel_load_params has run since its last use
+static int use_pipe_c(const evd_voxel* v, VoxMlpParams& p, hipStream_t st) {
+    if (v->pipe_c_stale) {
+        int rc = repack_stream_c(v->pipe_c, (const float*)v->arena_dev.p, st);
+        if (rc) return rc;
+        v->pipe_c_stale = false;
+    }
+    p.wstream = (const char*)v->pipe_c.data.p;
+    p.wscale = (const unsigned*)v->pipe_c.scales.p;
+    p.nchunks = v->pipe_c_chunks;
+    return EVD_OK;
+}
+
+// The network of a level's inference pass: picks the kernel and, with it, the stream of the handle it reads (p.wstream / p.nchunks).
+static int voxel_level_forward(const evd_voxel* v, int precision, VoxMlpParams& p, hipStream_t st) {
+    const bool coarse = v->hidden_dim == 64;
+    bool coarse_of_f16c = false;
+    if (precision == EVD_PREC_F16C) {
+        if (v->pipe_c_chunks > 0) {     // the level's compensated kernel (fine level)
+            if (p.feature) return fail(EVD_E_INVALID, "evd_voxel: per-sample feature rows are not built in EVD_PREC_F16C (use EVD_PREC_F16X3)");
+            int rc = use_pipe_c(v, p, st);
+            return rc ? rc : launch_voxel_pipe_f16c(p, st);
+        }
+        precision = EVD_PREC_F16X3;     // the 64-wide coarse level: float32-grade arithmetic (a few % of the render)
+        coarse_of_f16c = coarse;
+    }
+    // the pipelined stream of a standard level; the 64-wide level's kernels on it write no per-sample feature rows
+    if (v->fwd_chunks[precision] > 0 && !(coarse && p.feature)) {
+        p.wstream = (const char*)v->fwd[precision].data.p;
+        p.nchunks = v->fwd_chunks[precision];
+        p.rev_trig = coarse_of_f16c ? 1 : 0;       // an f16c render: this level's encodings as the fine level's kernel computes them (voxel_mlp_kernel.h)
+        switch (precision) {
+        case EVD_PREC_BF16: return launch_voxel_fwd_bf16(v->hidden_dim, p, st);
+        case EVD_PREC_F16: return launch_voxel_fwd_f16(v->hidden_dim, p, st);
+        case EVD_PREC_F16X3: return launch_voxel_fwd_f16x3(v->hidden_dim, p, st);
+        }
+    }
+    // the generic kernel, any frequency counts: has_generic_stream() names exactly the levels and modes that arrive here
+    if (!v->stream[precision].data.p)
+        return fail(EVD_E_INVALID, "evd_voxel: no generic-layout stream for precision %d on this level (hidden %d, multires %d / %d)", precision,
+                    v->hidden_dim, v->multires, v->multires_views);
+    p.wstream = (const char*)v->stream[precision].data.p;
+    p.nchunks = v->nchunks[precision];
+    return voxel_mlp_dispatch(precision, v->hidden_dim, v->geo, v->ft_dim, p, st);
+}
+
 static int voxel_pass(const evd_voxel* v, int precision, const float* pts, const float* viewdirs, int vd_stride, const float* fts,
                       int ft_stride, const float* z, const float* rays_d, int rd_stride, long R, int S, int is_train,
                       const float* noise, float* color, float* depth, float* acc, float* weights, float* feature, float* raw,
@@ -424,41 +467,11 @@ static int voxel_pass(const evd_voxel* v, int precision, const float* pts, const
         feature = crows;
     }
     VoxMlpParams p;
-    const bool comp = precision == EVD_PREC_F16C && v->pipe_c_chunks > 0;
-    const bool coarse_of_f16c = precision == EVD_PREC_F16C && !comp;
-    if (coarse_of_f16c) precision = EVD_PREC_F16X3;      // the 64-wide coarse level: float32-grade arithmetic (a few % of the render)
-    if (comp && feature) return fail(EVD_E_INVALID, "evd_voxel: per-sample feature rows are not built in EVD_PREC_F16C (use EVD_PREC_F16X3)");
-    const bool piped = v->pipe_chunks[precision] > 0;
-    p.wstream = (const char*)(piped ? v->pipe[precision].data.p : v->stream[precision].data.p);
     p.bias = (const float*)v->bias.p;
     p.pts = pts; p.viewdirs = viewdirs; p.fts = fts; p.nsamp = R * (long)S; p.S = S; p.vd_stride = vd_stride; p.ft_stride = ft_stride;
-    p.nchunks = piped ? v->pipe_chunks[precision] : v->nchunks[precision]; p.nbias = (int)(v->bias.bytes / sizeof(float)); p.raw = raw; p.feature = feature; p.act = nullptr;
+    p.nbias = (int)(v->bias.bytes / sizeof(float)); p.raw = raw; p.feature = feature; p.act = nullptr;
     p.pe_l = v->multires; p.pe_lv = v->multires_views;
-    if (comp) {
-        if (v->pipe_c_stale) {
-            int rcc = repack_stream_c(v->pipe_c, (const float*)v->arena_dev.p, as_stream(stream));
-            if (rcc) return rcc;
-            v->pipe_c_stale = false;
-        }
-        p.wstream = (const char*)v->pipe_c.data.p;
-        p.wscale = (const unsigned*)v->pipe_c.scales.p;
-        p.nchunks = v->pipe_c_chunks;
-    }
-    // the 64-wide coarse level on the software pipeline (its training forward's stream and layer table), where that is built
-    const bool coarse_pipe = !comp && !piped && !feature && v->hidden_dim == 64 && v->geo == 15 && v->ft_dim == 32 &&
-                             is_train_prec(precision) && v->train_chunks[precision] > 0;
-    if (coarse_pipe) {
-        p.wstream = (const char*)v->train[precision].data.p;
-        p.nchunks = v->train_chunks[precision];
-        p.rev_trig = coarse_of_f16c ? 1 : 0;       // an f16c render: this level's encodings as the fine level's kernel computes them (voxel_mlp_kernel.h)
-    }
-    int rc = comp ? launch_voxel_pipe_f16c(p, as_stream(stream))
-             : coarse_pipe ? (precision == EVD_PREC_BF16 ? launch_voxel_coarse_pipe_bf16(p, as_stream(stream))
-                              : precision == EVD_PREC_F16 ? launch_voxel_coarse_pipe_f16(p, as_stream(stream)) : launch_voxel_coarse_pipe_f16x3(p, as_stream(stream)))
-             : piped ? (precision == EVD_PREC_BF16 ? launch_voxel_pipe_bf16(feature != nullptr, p, as_stream(stream))
-                      : precision == EVD_PREC_F16 ? launch_voxel_pipe_f16(feature != nullptr, p, as_stream(stream))
-                                                  : launch_voxel_pipe_f16x3(feature != nullptr, p, as_stream(stream)))
-                   : voxel_mlp_dispatch(precision, v->hidden_dim, v->geo, v->ft_dim, p, as_stream(stream));
+    int rc = voxel_level_forward(v, precision, p, as_stream(stream));
     if (rc) return rc;
     const float thr = (!is_train && v->rmnear > 0.f) ? (float)((double)v->rmnear / 128.0) : 0.f;
     if (v->composite_feature) {
@@ -627,9 +640,9 @@ static long vox_tiles(long nsamp) { return cdiv(nsamp, 256L) * 8; }
 // that is built (fine level), else the split-float16 forward writing the float16 store (coarse level)
 // EVD_PREC_F16M: the split-float16 forward on every level, same store and backward
 static bool vox_train_built(const evd_voxel* v, int prec) {
-    if (prec == EVD_PREC_F16C) return v->train_chunks[EVD_PREC_F16] > 0 && (v->pipe_c_chunks > 0 || v->train_chunks[EVD_PREC_F16X3] > 0);
-    if (prec == EVD_PREC_F16M) return v->train_chunks[EVD_PREC_F16] > 0 && v->train_chunks[EVD_PREC_F16X3] > 0;
-    return prec >= 0 && prec < EVD_VOX_NUM_PREC && is_train_prec(prec) && v->train_chunks[prec] > 0;
+    if (prec == EVD_PREC_F16C) return v->fwd_chunks[EVD_PREC_F16] > 0 && (v->pipe_c_chunks > 0 || v->fwd_chunks[EVD_PREC_F16X3] > 0);
+    if (prec == EVD_PREC_F16M) return v->fwd_chunks[EVD_PREC_F16] > 0 && v->fwd_chunks[EVD_PREC_F16X3] > 0;
+    return prec >= 0 && prec < EVD_VOX_NUM_PREC && v->fwd_chunks[prec] > 0;
 }
 static int vox_store_prec(int prec) { return (prec == EVD_PREC_F16C || prec == EVD_PREC_F16M) ? EVD_PREC_F16 : prec; }
 
@@ -649,8 +662,7 @@ int evd_voxel_load_params(evd_voxel* v, const float* params, void* stream) {
     std::vector<PackedStream*> all;
     for (int i = 0; i < EVD_VOX_NUM_PREC; ++i) {
         all.push_back(&v->stream[i]);
-        all.push_back(&v->pipe[i]);
-        all.push_back(&v->train[i]);
+        all.push_back(&v->fwd[i]);
         for (int k = 0; k < VBWD_NSTREAMS; ++k) all.push_back(&v->bwd[i][k]);
     }
     if ((rc = repack_batch(v->batch, all, params, st))) return rc;
@@ -691,26 +703,17 @@ int evd_voxel_mlp_train(const evd_voxel* v, int precision, const float* pts, con
     p.bias = (const float*)v->bias.p;
     p.pts = pts; p.viewdirs = viewdirs; p.fts = fts; p.nsamp = nsamp; p.S = S; p.vd_stride = vd_stride; p.ft_stride = ft_stride;
     p.nbias = (int)(v->bias.bytes / sizeof(float)); p.raw = raw; p.feature = feature; p.act = (char*)store;
-    if (precision == EVD_PREC_F16C || precision == EVD_PREC_F16M) {
-        if (feature) return fail(EVD_E_INVALID, "evd_voxel_mlp_train: float32 feature rows are not built in EVD_PREC_F16C / EVD_PREC_F16M (the geo features stay fragments in the store)");
-        if (precision == EVD_PREC_F16C && v->pipe_c_chunks > 0) {        // the level's compensated kernel (fine level)
-            if (v->pipe_c_stale) {
-                int rcc = repack_stream_c(v->pipe_c, (const float*)v->arena_dev.p, as_stream(stream));
-                if (rcc) return rcc;
-                v->pipe_c_stale = false;
-            }
-            p.wstream = (const char*)v->pipe_c.data.p;
-            p.wscale = (const unsigned*)v->pipe_c.scales.p;
-            p.nchunks = v->pipe_c_chunks;
-            return launch_voxel_train_fwd_f16c(p, as_stream(stream));
-        }
-        p.wstream = (const char*)v->train[EVD_PREC_F16X3].data.p;
-        p.nchunks = v->train_chunks[EVD_PREC_F16X3];
-        return launch_voxel_train_fwd_f16x3_hi(v->hidden_dim, p, as_stream(stream));
+    const bool mixed = precision == EVD_PREC_F16C || precision == EVD_PREC_F16M;      // a float32-grade forward writing the float16 mode's store
+    if (mixed && feature) return fail(EVD_E_INVALID, "evd_voxel_mlp_train: float32 feature rows are not built in EVD_PREC_F16C / EVD_PREC_F16M (the geo features stay fragments in the store)");
+    if (precision == EVD_PREC_F16C && v->pipe_c_chunks > 0) {        // the level's compensated kernel (fine level)
+        int rc = use_pipe_c(v, p, as_stream(stream));
+        return rc ? rc : launch_voxel_train_fwd_f16c(p, as_stream(stream));
     }
-    p.wstream = (const char*)v->train[precision].data.p;
-    p.nchunks = v->train_chunks[precision];
-    return launch_voxel_train_fwd_dispatch(precision, v->hidden_dim, p, as_stream(stream));
+    const int arith = mixed ? EVD_PREC_F16X3 : precision;             // (vox_train_built: that stream exists)
+    p.wstream = (const char*)v->fwd[arith].data.p;
+    p.nchunks = v->fwd_chunks[arith];
+    return mixed ? launch_voxel_train_fwd_f16x3_hi(v->hidden_dim, p, as_stream(stream))
+                 : launch_voxel_train_fwd_dispatch(precision, v->hidden_dim, p, as_stream(stream));
 }
 
 int evd_voxel_geo_feat_dim(const evd_voxel* v) { return v ? v->geo : 0; }

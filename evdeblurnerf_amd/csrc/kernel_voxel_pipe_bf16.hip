@@ -1,10 +1,8 @@
-// bf16 instantiations of the software-pipelined PDRF fine-level network (voxel_mlp_kernel.h).
+// bf16 instantiations of the PDRF level networks' inference kernels, both levels (voxel_mlp_kernel.h).
 #include "voxel_mlp_kernel.h"
 
 namespace evd {
 
-int launch_voxel_pipe_bf16(bool feat, const VoxMlpParams& p, hipStream_t st) {
-    return feat ? launch_voxel_pipe<EVD_PREC_BF16, true>(p, st) : launch_voxel_pipe<EVD_PREC_BF16, false>(p, st);
-}
+int launch_voxel_fwd_bf16(int HD, const VoxMlpParams& p, hipStream_t st) { return launch_voxel_fwd<EVD_PREC_BF16>(HD, p, st); }
 
 }  // namespace evd

@@ -1,10 +1,8 @@
-// f16 instantiations of the software-pipelined PDRF fine-level network (voxel_mlp_kernel.h).
+// f16 instantiations of the PDRF level networks' inference kernels, both levels (voxel_mlp_kernel.h).
 #include "voxel_mlp_kernel.h"
 
 namespace evd {
 
-int launch_voxel_pipe_f16(bool feat, const VoxMlpParams& p, hipStream_t st) {
-    return feat ? launch_voxel_pipe<EVD_PREC_F16, true>(p, st) : launch_voxel_pipe<EVD_PREC_F16, false>(p, st);
-}
+int launch_voxel_fwd_f16(int HD, const VoxMlpParams& p, hipStream_t st) { return launch_voxel_fwd<EVD_PREC_F16>(HD, p, st); }
 
 }  // namespace evd

@@ -13,6 +13,4 @@ int run_voxel_backward_bf16(int HD, const VoxBwdPlan& b, hipStream_t st) {
     return HD == 256 ? run_voxel_backward<EVD_PREC_BF16, 256, 128, 64>(b, st) : run_voxel_backward<EVD_PREC_BF16, 64, 15, 32>(b, st);
 }
 
-int launch_voxel_coarse_pipe_bf16(const VoxMlpParams& p, hipStream_t st) { return launch_voxel_resident_level<EVD_PREC_BF16, 64, 15, 32>(p, st); }
-
 }  // namespace evd

@@ -73,9 +73,14 @@ int launch_tv_bwd(const float* x, int H, int W, int C, const float* d_loss, floa
 int launch_f32_to_f16(const float* x, long n, _Float16* y, hipStream_t st);
 int launch_tv(const float* x, int H, int W, int C, double* partials, int* blocks, hipStream_t st);
 int launch_tv_finish(const double* acc, const TvShape& s, float* out, hipStream_t st);
-int voxel_mlp_dispatch(int prec, int HD, int G, int FT, const VoxMlpParams& p, hipStream_t st);
+int voxel_mlp_dispatch(int prec, int HD, int G, int FT, const VoxMlpParams& p, hipStream_t st);     // generic kernel, its own stream layout
+// inference on the level's pipelined forward stream, one entry per mode (kernel_voxel_pipe_<mode>.hip): the fine level (HD 256; with
+// the float32 feature rows where p.feature is set) and the coarse level (HD 64; raw only)
+int launch_voxel_fwd_bf16(int HD, const VoxMlpParams& p, hipStream_t st);
+int launch_voxel_fwd_f16(int HD, const VoxMlpParams& p, hipStream_t st);
+int launch_voxel_fwd_f16x3(int HD, const VoxMlpParams& p, hipStream_t st);
 int voxel_mlp_c_chunks(int HD, int G, int FT);              // compensated float16 mode (voxel_mlp_c_kernel.h): chunks of its stream, 0 = not built for this level
-int launch_voxel_pipe_f16c(const VoxMlpParams& p, hipStream_t st);
+int launch_voxel_pipe_f16c(const VoxMlpParams& p, hipStream_t st);        // fine level, its own stream (PackedStreamC)
 int launch_voxel_train_fwd_f16c(const VoxMlpParams& p, hipStream_t st);   // fine level; writes the float16 mode's activation store
 
 }  // namespace evd

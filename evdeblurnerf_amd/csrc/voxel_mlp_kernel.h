@@ -1,10 +1,15 @@
-// Software-pipelined PDRF level network (fine: hidden 256, geo 128, 64 feature channels in; the training path also builds the
-// coarse 64 / 15 / 32 level on it; reference
+// Software-pipelined PDRF level network (fine: hidden 256, geo 128, 64 feature channels in; coarse: 64 / 15 / 32; reference
 // networks/pdrf/voxnerf.py:210-221,240-254 with the blurfactory dimensions): sigma net 127 -> 256 -> 1 + 128,
 // colour net 155 -> 256 -> 256 -> 3 (sigmoid), on the machinery of mlp_pipe.h.  One straight-line stream of 368
-// MFMAs per wavefront; layer table below.  The coarse level (64-wide) runs the same table: its training forward on k_voxel_mlp_pipe (TRAIN), its
-// render pass -- and its training forward in the split-float16 modes -- on k_voxel_mlp_resident (round 6: the whole weight stream resident in LDS,
-// persistent workgroups, no barrier); with per-sample feature rows wanted it takes kernel_voxel.hip's generic kernel.
+// MFMAs per wavefront; layer table below.  Both levels read ONE packed stream per arithmetic mode (evd_voxel_api.hip `fwd`), in render
+// and in training.  Which kernel walks it:
+//   fine level     k_voxel_mlp_pipe: render (launch_voxel_pipe, FEAT with feature rows) and training forward (TRAIN)
+//   coarse level   render: k_voxel_mlp_resident from 65536 samples (round 6: the whole weight stream resident in LDS, persistent
+//                  workgroups, no barrier), k_voxel_mlp_pipe below; with per-sample feature rows wanted, kernel_voxel.hip's generic
+//                  kernel on its own stream layout
+//                  training forward: k_voxel_mlp_pipe (TRAIN); k_voxel_mlp_resident (TRAIN) in the split-float16 arithmetic from 65536 samples
+// launch_voxel_fwd<PREC> is the inference entry of one mode (kernel_voxel_pipe_<mode>.hip), launch_voxel_train_fwd the training one
+// (kernel_voxel_train_<mode>.hip).
 #pragma once
 
 #include "mlp_pipe.h"
@@ -63,7 +68,6 @@ template <class C, int HD_, int G_, int FT_, bool FEAT, bool TRAIN = false> stru
     static_assert(F1 % PD == 0 && F3 % PD == 0 && F4 % PD == 0, "prefetch ring phase");
     static_assert(!FEAT || G % 32 == 0, "float32 feature rows are written 32 at a time");
 };
-template <class C, bool FEAT> using VoxFineNet = VoxNet<C, 256, 128, 64, FEAT, false>;
 
 template <int PREC, int HD, int G, int FT, int NS, int NT, bool FEAT, int CB, int OCC, bool TRAIN, bool HI_ONLY = false>
 __global__ __launch_bounds__(NT, OCC) void k_voxel_mlp_pipe(const VoxMlpParams p) {
@@ -167,26 +171,32 @@ __global__ __launch_bounds__(NT, OCC) void k_voxel_mlp_pipe(const VoxMlpParams p
     }
 }
 
+// Inference on the software pipeline, either level, on the level's one forward stream (evd_voxel_api.hip `fwd`).  FEAT: the float32
+// feature rows too (fine level).  The 64-wide coarse level comes here below 65536 samples (launch_voxel_resident_level); it is
+// prologue-bound, not MFMA-bound: 86 us per 4096 x 64 samples, the same as the generic kernel.
 // (Measured and dropped: 256-thread workgroups walking the same stream in 8 KiB chunks -- 72 KiB of LDS, two workgroups per CU
 // overlapping each other's prologue and barrier waits -- run 1 % slower: the overlap is paid back by twice the L2 -> LDS weight
 // traffic and DMA issue.  PipeCfg keeps the chunk size as a parameter.)
-template <int PREC, bool FEAT>
+template <int PREC, int HD, int G, int FT, bool FEAT>
 static int launch_voxel_pipe(const VoxMlpParams& p, hipStream_t st) {
     constexpr bool half = is_half_prec(PREC);
-    constexpr int NT = half ? 512 : 256;      // the split-float16 B fragments need the whole register file: one wavefront per SIMD
+    // the split-float16 B fragments need the whole register file: one wavefront per SIMD (and with 512 threads the ring + stash of
+    // PipeCfg exceed the 160 KiB of LDS)
+    constexpr int NT = half ? 512 : 256;
     constexpr int OCC = half ? 2 : 1;
     typedef PipeCfg<PREC, 1, NT> C;
-    typedef VoxFineNet<C, FEAT> N;
+    typedef VoxNet<C, HD, G, FT, FEAT, false> N;
     const long blocks = cdiv(p.nsamp, C::SAMPLES);
     const size_t lds = C::TOTAL;
-    EVD_SET_MAX_LDS((&k_voxel_mlp_pipe<PREC, 256, 128, 64, 1, NT, FEAT, PIPE_CB, OCC, false>), lds);
+    EVD_SET_MAX_LDS((&k_voxel_mlp_pipe<PREC, HD, G, FT, 1, NT, FEAT, PIPE_CB, OCC, false>), lds);
     if (p.nchunks != N::NCH) return fail(EVD_E_INVALID, "evd_voxel: packed stream has %d chunks, kernel expects %d", p.nchunks, N::NCH);
-    hipLaunchKernelGGL((k_voxel_mlp_pipe<PREC, 256, 128, 64, 1, NT, FEAT, PIPE_CB, OCC, false>), dim3((unsigned)blocks), dim3(NT), lds, st, p);
+    if ((!FEAT && p.feature) || p.act) return fail(EVD_E_INVALID, "evd_voxel: the level's pipelined inference pass writes raw only");
+    hipLaunchKernelGGL((k_voxel_mlp_pipe<PREC, HD, G, FT, 1, NT, FEAT, PIPE_CB, OCC, false>), dim3((unsigned)blocks), dim3(NT), lds, st, p);
     EVD_LAUNCH_CHECK();
     return EVD_OK;
 }
 
-// training variant (keeps the activations), either level; the stream is the level's pipe stream (evd_voxel_api.hip).  The store is
+// training variant (keeps the activations), either level, on the same stream.  The store is
 // tiled in groups of 8 tiles (256 samples) and the backward walks all of them: the grid covers the padding tiles too.
 // HI_ONLY (PREC = EVD_PREC_F16X3): the store is the single-product float16 mode's (mlp_pipe.h PipeCfg) -- the coarse level of a
 // training forward in EVD_PREC_F16C
@@ -212,25 +222,6 @@ static int launch_voxel_train_fwd(const VoxMlpParams& p, hipStream_t st) {
     return EVD_OK;
 }
 
-// inference on the software pipeline for ANY level, on the stream the level's training forward uses (same layer table, no activation store):
-// the 64-wide coarse level's render pass (the generic kernel took 86 us per 4096 x 64 samples in f16x3 -- 11 % of a c2f render in the
-// compensated mode, whose coarse level runs float32-grade)
-template <int PREC, int HD, int G, int FT>
-static int launch_voxel_pipe_level(const VoxMlpParams& p, hipStream_t st) {
-    // (split-float16: one wavefront per SIMD as in the fine level -- with 512 threads the ring + stash of PipeCfg exceed the 160 KiB of LDS;
-    // measured 86 us per 4096 x 64 samples either way, the same as the generic kernel: the 64-wide level is prologue-bound, not MFMA-bound)
-    constexpr int NT = is_half_prec(PREC) ? 512 : 256, OCC = is_half_prec(PREC) ? 2 : 1;
-    typedef PipeCfg<PREC, 1, NT> C;
-    typedef VoxNet<C, HD, G, FT, false, false> N;
-    const long blocks = cdiv(p.nsamp, C::SAMPLES);
-    const size_t lds = C::TOTAL;
-    EVD_SET_MAX_LDS((&k_voxel_mlp_pipe<PREC, HD, G, FT, 1, NT, false, PIPE_CB, OCC, false>), lds);
-    if (p.nchunks != N::NCH) return fail(EVD_E_INVALID, "evd_voxel: packed stream has %d chunks, kernel expects %d", p.nchunks, N::NCH);
-    if (p.feature || p.act) return fail(EVD_E_INVALID, "evd_voxel: the level's pipelined inference pass writes raw only");
-    hipLaunchKernelGGL((k_voxel_mlp_pipe<PREC, HD, G, FT, 1, NT, false, PIPE_CB, OCC, false>), dim3((unsigned)blocks), dim3(NT), lds, st, p);
-    EVD_LAUNCH_CHECK();
-    return EVD_OK;
-}
 // Round 6: the same layer table, arithmetic and order of operations (results bit for bit those of k_voxel_mlp_pipe) for a level whose whole
 // weight stream fits LDS -- the 64-wide coarse level of the shipped c2f configs.  k_voxel_mlp_pipe is built for 256-wide layers: every
 // workgroup streams the weights through a 4-slot ring with a counted wait and a barrier per 16 KiB chunk and lives for ONE group of sample
@@ -334,8 +325,7 @@ static int launch_voxel_resident_train(const VoxMlpParams& p, hipStream_t st) {
     static_assert(lds <= 160 * 1024, "the level's stream is resident in LDS");
     if (p.nchunks != N::NCH) return fail(EVD_E_INVALID, "evd_voxel: packed stream has %d chunks, kernel expects %d", p.nchunks, N::NCH);
     if (!p.act) return fail(EVD_E_INVALID, "evd_voxel: training launch without an activation store");
-    int cus = 256;
-    { int dev = 0, v = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
+    const int cus = device_cus();
     const long groups = cdiv(p.nsamp, 256L) * (256 / C::SAMPLES);
     EVD_SET_MAX_LDS((&k_voxel_mlp_resident<PREC, HD, G, FT, NT, true, HI_ONLY>), lds);
     hipLaunchKernelGGL((k_voxel_mlp_resident<PREC, HD, G, FT, NT, true, HI_ONLY>), dim3((unsigned)(groups < cus ? groups : cus)), dim3(NT), lds, st, p);
@@ -346,7 +336,7 @@ static int launch_voxel_resident_train(const VoxMlpParams& p, hipStream_t st) {
 template <int PREC, int HD, int G, int FT>
 static int launch_voxel_resident_level(const VoxMlpParams& p, hipStream_t st) {
     // (a launch of less than one tile group per CU and wavefront slot does not repay the 48-80 KiB copy: 333 x 17 samples 17.2 against 14.4 us)
-    if (p.nsamp < 65536) return launch_voxel_pipe_level<PREC, HD, G, FT>(p, st);
+    if (p.nsamp < 65536) return launch_voxel_pipe<PREC, HD, G, FT, false>(p, st);
     constexpr int NT = RES_NT;
     typedef PipeCfg<PREC, 1, NT> C;
     typedef VoxNet<C, HD, G, FT, false, false> N;
@@ -355,13 +345,11 @@ static int launch_voxel_resident_level(const VoxMlpParams& p, hipStream_t st) {
     static_assert(lds <= 160 * 1024, "the level's stream is resident in LDS");
     if (p.nchunks != N::NCH) return fail(EVD_E_INVALID, "evd_voxel: packed stream has %d chunks, kernel expects %d", p.nchunks, N::NCH);
     if (p.feature || p.act) return fail(EVD_E_INVALID, "evd_voxel: the level's inference pass writes raw only");
-    int cus = 256;
-    { int dev = 0, v = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
+    const int cus = device_cus();
     const long groups = cdiv(p.nsamp, (long)C::SAMPLES);
     if constexpr (PREC == EVD_PREC_F16X3) {
-        // the coarse level of an f16c RENDER (p.rev_trig, evd_voxel_api.hip): sines as in that mode's fine-level kernel; EVD_COARSE_TRIG=exact (developer switch): the polynomial
-        static const bool exact = [] { const char* e = getenv("EVD_COARSE_TRIG"); return e && !strcmp(e, "exact"); }();
-        if (p.rev_trig && !exact) {
+        // the coarse level of an f16c RENDER (p.rev_trig, evd_voxel_api.hip): sines as in that mode's fine-level kernel
+        if (p.rev_trig) {
             EVD_SET_MAX_LDS((&k_voxel_mlp_resident<PREC, HD, G, FT, NT, false, false, true>), lds);
             hipLaunchKernelGGL((k_voxel_mlp_resident<PREC, HD, G, FT, NT, false, false, true>), dim3((unsigned)(groups < cus ? groups : cus)), dim3(NT), lds, st, p);
             EVD_LAUNCH_CHECK();
@@ -373,15 +361,13 @@ static int launch_voxel_resident_level(const VoxMlpParams& p, hipStream_t st) {
     EVD_LAUNCH_CHECK();
     return EVD_OK;
 }
-int launch_voxel_coarse_pipe_bf16(const VoxMlpParams& p, hipStream_t st);
-int launch_voxel_coarse_pipe_f16(const VoxMlpParams& p, hipStream_t st);
-int launch_voxel_coarse_pipe_f16x3(const VoxMlpParams& p, hipStream_t st);
 
-constexpr bool voxel_pipe_built(int prec, int HD, int G, int FT) {
-    return (prec == EVD_PREC_BF16 || prec == EVD_PREC_F16 || prec == EVD_PREC_F16X3) && HD == 256 && G == 128 && FT == 64;
+// one mode's inference entry (voxel.h launch_voxel_fwd_<mode>, kernel_voxel_pipe_<mode>.hip): the fine level on the streaming kernel, with
+// the float32 feature rows where p.feature asks for them; the coarse level resident in LDS
+template <int PREC>
+static int launch_voxel_fwd(int HD, const VoxMlpParams& p, hipStream_t st) {
+    if (HD == 256) return p.feature ? launch_voxel_pipe<PREC, 256, 128, 64, true>(p, st) : launch_voxel_pipe<PREC, 256, 128, 64, false>(p, st);
+    return launch_voxel_resident_level<PREC, 64, 15, 32>(p, st);
 }
-int launch_voxel_pipe_bf16(bool feat, const VoxMlpParams& p, hipStream_t st);
-int launch_voxel_pipe_f16(bool feat, const VoxMlpParams& p, hipStream_t st);
-int launch_voxel_pipe_f16x3(bool feat, const VoxMlpParams& p, hipStream_t st);
 
 }  // namespace evd

@@ -52,12 +52,14 @@ int launch_voxel_train_fwd_f16x3_hi(int HD, const VoxMlpParams& p, hipStream_t s
 int run_voxel_backward_f16(int HD, const VoxBwdPlan& b, hipStream_t st);
 int run_voxel_backward_bf16(int HD, const VoxBwdPlan& b, hipStream_t st);
 int run_voxel_backward_f16x3(int HD, const VoxBwdPlan& b, hipStream_t st);
+// prec: one of the modes the training kernels are built for (is_train_prec), checked by the callers (evd_voxel_api.hip vox_train_built)
 inline int launch_voxel_train_fwd_dispatch(int prec, int HD, const VoxMlpParams& p, hipStream_t st) {
-    return prec == 3 /*EVD_PREC_F16*/ ? launch_voxel_train_fwd_f16(HD, p, st)
-           : prec == 2 /*EVD_PREC_BF16*/ ? launch_voxel_train_fwd_bf16(HD, p, st) : launch_voxel_train_fwd_f16x3(HD, p, st);
+    return prec == EVD_PREC_F16 ? launch_voxel_train_fwd_f16(HD, p, st)
+           : prec == EVD_PREC_BF16 ? launch_voxel_train_fwd_bf16(HD, p, st) : launch_voxel_train_fwd_f16x3(HD, p, st);
 }
 inline int run_voxel_backward_dispatch(int prec, int HD, const VoxBwdPlan& b, hipStream_t st) {
-    return prec == 3 ? run_voxel_backward_f16(HD, b, st) : prec == 2 ? run_voxel_backward_bf16(HD, b, st) : run_voxel_backward_f16x3(HD, b, st);
+    return prec == EVD_PREC_F16 ? run_voxel_backward_f16(HD, b, st)
+           : prec == EVD_PREC_BF16 ? run_voxel_backward_bf16(HD, b, st) : run_voxel_backward_f16x3(HD, b, st);
 }
 int voxel_store_geo_slot(int HD);         // first of the geo fragments the training forward keeps (fine level: 8 fragments)
 long voxel_store_tile_bytes(int HD);      // fine 256 / 128 / 64 or coarse 64 / 15 / 32 (kernel_voxel_train_f16.hip); half-precision modes

@@ -130,6 +130,87 @@ def test_load_params_repacks_like_a_fresh_network():
         assert torch.equal(ga, gb), prec
 
 
+def _level_forward(net, prec, pts, vd, fts, z, rd, want_feature):
+    """evd_voxel_forward of one PDRF level -> [colour, depth, acc, weights, raw (, per-sample feature rows)]; want_feature False passes a
+    null feature pointer (the level's pass inside a c2f render), which VoxelNeRFBase.forward never does"""
+    import evdeblurnerf_amd._lib as L
+    R, S = pts.shape[:2]
+    f32 = dict(dtype=torch.float32, device=pts.device)
+    color, depth, acc, wts = torch.empty((R, 3), **f32), torch.empty((R,), **f32), torch.empty((R,), **f32), torch.empty((R, S), **f32)
+    feat = torch.zeros((R, S, net.geo_feat_dim), **f32) if want_feature else None
+    need = int(L.lib().evd_voxel_forward_workspace_bytes(net._h, R, S))
+    ws = torch.zeros((need,), dtype=torch.uint8, device=pts.device)
+    L.check(L.lib().evd_voxel_forward(net._h, L.PREC[prec], L.ptr(pts), L.ptr(vd), 3, L.ptr(fts), fts.shape[-1], L.ptr(z), L.ptr(rd), 3, R, S, 0,
+                                      L.ptr(color), L.ptr(depth), L.ptr(acc), L.ptr(wts), L.ptr(feat), L.ptr(ws), need, L.stream_ptr()), "evd_voxel_forward")
+    off = -ws.data_ptr() % 256                                  # the network's raw output opens the workspace, 256-byte aligned
+    raw = ws[off:off + R * S * 16].view(torch.float32)
+    return [color, depth, acc, wts, raw] + ([feat] if want_feature else [])
+
+
+def _level_train_forward(net, prec, pts, vd, fts):
+    """evd_voxel_mlp_train into a ZEROED store (the forward leaves the gradient slots alone) -> raw, store"""
+    import evdeblurnerf_amd._lib as L
+    R, S = pts.shape[:2]
+    raw = torch.empty((R, S, 4), dtype=torch.float32, device=pts.device)
+    nb = int(L.lib().evd_voxel_train_store_bytes_prec(net._h, L.PREC[prec], R * S))
+    assert nb > 0, prec
+    store = torch.zeros((nb,), dtype=torch.uint8, device=pts.device)
+    L.check(L.lib().evd_voxel_mlp_train(net._h, L.PREC[prec], L.ptr(pts), L.ptr(vd), 3, L.ptr(fts), fts.shape[-1], R, S, L.ptr(raw), None,
+                                        L.ptr(store), nb, L.stream_ptr()), "evd_voxel_mlp_train")
+    return raw, store
+
+
+def test_level_load_params_repacks_like_a_fresh_level():
+    """The PDRF levels' counterpart of the test above: a coarse (64 / 15 / 32) and a fine (256 / 128 / 64) level created from state dict A
+    and loaded with B's flat parameters compute, bit for bit, what fresh levels created from B compute -- in every kernel that reads a
+    weight stream of the handle: the generic one (f32; the coarse level with feature rows), the streaming one (the fine level with and
+    without feature rows; the coarse level below 65536 samples), the resident one (the coarse level from 65536 samples) and the
+    training forwards of both levels.  The render and the training forward of ONE loaded handle must both see B's values: a handle that
+    kept two copies of a stream and re-packed one would pass either check alone."""
+    sd_a = _c2f_state_dict(81, 82)
+    other = _c2f_state_dict(83, 84)
+    sd_b = {k: (other[k] if ("sigma_net" in k or "color_net" in k) else v) for k, v in sd_a.items()}      # B: other networks on A's grids
+    model, _ = _c2f_model("f16", 16, sd=sd_a)
+    fresh, _ = _c2f_model("f16", 16, sd=sd_b)
+    for lvl, prefix in ((model.mlp_coarse, "mlp_coarse."), (model.mlp_fine, "mlp_fine.")):
+        lvl.load_params(lvl.flat_params(sd_b, prefix))
+    rs = np.random.RandomState(17)
+
+    def inputs(R, S, FT):
+        pts = rs.uniform(-1, 1, (R, S, 3)).astype(np.float32)
+        d = rs.normal(size=(R, 3))
+        vd = (d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32)
+        fts = (0.3 * rs.normal(size=(R, S, FT))).astype(np.float32)
+        z = np.sort(rs.uniform(0.2, 2.0, (R, S)).astype(np.float32), -1)
+        return [torch.tensor(a, device="cuda") for a in (pts, vd, fts, z, vd)]
+
+    small, large = (70, 33), (1024, 64)             # 2310 samples, ragged; 65536 samples: the coarse level's resident kernel
+    # (level of the loaded model, of the fresh one, feature width, [(R, S), feature rows wanted])
+    cases = [("coarse", model.mlp_coarse, fresh.mlp_coarse, 32, [(small, True), (small, False), (large, False)]),
+             ("fine", model.mlp_fine, fresh.mlp_fine, 64, [(small, True), (small, False)])]
+    for name, got, want, FT, runs in cases:
+        for (R, S), feat in runs:
+            a = inputs(R, S, FT)
+            for prec in ("f32", "f16x3", "f16", "bf16"):
+                for k, (x, y) in enumerate(zip(_level_forward(got, prec, *a, feat), _level_forward(want, prec, *a, feat))):
+                    assert torch.equal(x, y), (name, R, S, feat, prec, k)
+        for R, S in (small, large):
+            a = inputs(R, S, FT)[:3]
+            for prec in ("f16", "bf16", "f16x3"):
+                (raw_a, store_a), (raw_b, store_b) = _level_train_forward(got, prec, *a), _level_train_forward(want, prec, *a)
+                assert torch.equal(raw_a, raw_b) and torch.equal(store_a, store_b), (name, R, S, prec)
+    # one loaded handle pair, f16: the c2f render (both levels' inference streams; 2731 x 24 = 65544 coarse samples) and the levels'
+    # training forwards
+    rb = torch.tensor(_c2f_rays(2731, 3), device="cuda")
+    out, ref = model.render_rays(rb, 24, N_importance=16, retraw=True), fresh.render_rays(rb, 24, N_importance=16, retraw=True)
+    for k in ("rgb_map", "depth_map", "acc_map", "rgb0", "z_vals", "weights"):
+        assert torch.equal(out[k], ref[k]), k
+    for name, got, want, FT, _ in cases:
+        a = inputs(*small, FT)[:3]
+        (raw_a, store_a), (raw_b, store_b) = _level_train_forward(got, "f16", *a), _level_train_forward(want, "f16", *a)
+        assert torch.equal(raw_a, raw_b) and torch.equal(store_a, store_b), name
+
+
 def test_training_loop_tracks_the_float64_reference():
     """Adam on raw -> target regression through the autograd Function, against the same loop on the float64 torch network:
     the loss goes down and the two trajectories stay together."""
@@ -345,12 +426,17 @@ def test_pdrf_level_networks_backward_match_torch_autograd(level, prec, tol):
     assert max(errs.values()) < tol, {k: f"{v:.1e}" for k, v in errs.items()}
 
 
-def _c2f_model(prec, N_importance=32, coarse_voxels=24 ** 3, fine_voxels=48 ** 3):
+def _c2f_state_dict(seed_coarse=81, seed_fine=82, coarse_voxels=24 ** 3, fine_voxels=48 ** 3):
+    gc, gf = W.pdrf_grid_size(AABB[0], AABB[1], coarse_voxels), W.pdrf_grid_size(AABB[0], AABB[1], fine_voxels)
+    sd = dict(W.prefixed(W.make_pdrf_state_dict(seed_coarse, gc, input_ch=95, hidden_dim=64, geo_feat_dim=15, add_bias_color=True), "mlp_coarse"))
+    sd.update(W.prefixed(W.make_pdrf_state_dict(seed_fine, gf, input_ch=127, hidden_dim=256, geo_feat_dim=128, add_bias_color=True), "mlp_fine"))
+    return sd
+
+
+def _c2f_model(prec, N_importance=32, coarse_voxels=24 ** 3, fine_voxels=48 ** 3, sd=None):
     from types import SimpleNamespace
     from evdeblurnerf_amd.renderer import NeRFAll
-    gc, gf = W.pdrf_grid_size(AABB[0], AABB[1], coarse_voxels), W.pdrf_grid_size(AABB[0], AABB[1], fine_voxels)
-    sd = dict(W.prefixed(W.make_pdrf_state_dict(81, gc, input_ch=95, hidden_dim=64, geo_feat_dim=15, add_bias_color=True), "mlp_coarse"))
-    sd.update(W.prefixed(W.make_pdrf_state_dict(82, gf, input_ch=127, hidden_dim=256, geo_feat_dim=128, add_bias_color=True), "mlp_fine"))
+    sd = sd if sd is not None else _c2f_state_dict(81, 82, coarse_voxels, fine_voxels)
     args = SimpleNamespace(mode="c2f", multires=10, multires_views=4, use_viewdirs=True, N_importance=N_importance, kernel_type="RBK",
                            kernel_use_awp=False, rgb_activate="sigmoid", sigma_activate="relu", bounding_box=AABB, coarse_num_layers=2,
                            coarse_num_layers_color=3, coarse_hidden_dim=64, coarse_hidden_dim_color=64, coarse_app_dim=32,
