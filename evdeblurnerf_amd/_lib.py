@@ -83,6 +83,15 @@ class PoseTrack(C.Structure):
                 ("bd_scale", C.c_float), ("recenter", C.c_int), ("recenter_inv", C.c_double * 12)]
 
 
+class RigidBlurDesc(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("C", "W_r", "W_v", "W_w", "D_r", "D_v", "D_w", "M", "use_origin", "n_img")] + [("rv_window", C.c_float)]
+
+
+class RigidBlurParams(C.Structure):
+    _fields_ = [(k, _vp) for k in ("table", "r_branch_w", "r_branch_b", "v_branch_w", "v_branch_b", "w_branch_w", "w_branch_b",
+                                   "r_linear_w", "r_linear_b", "v_linear_w", "v_linear_b", "w_linear_w", "w_linear_b")]
+
+
 class RenderOut(C.Structure):
     _fields_ = [(k, _vp) for k in ("rgb", "depth", "acc", "z_vals", "weights", "rgb0", "depth0", "acc0", "z_std",
                                    "z_vals0", "weights0", "feature", "raw")] + [("feature_kind", C.c_int)]
@@ -107,6 +116,10 @@ SIGNATURES = {
     "evd_interpolate_poses": (_I, [C.POINTER(PoseTrack), _vp, _L, _vp, _vp]),
     "evd_image_batch": (_I, [_vp, _L, _vp, _vp, _vp, _I, _I, _I, _fp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "evd_rbk_warp": (_I, [_vp, _vp, _vp, _L, _I, _I, _vp, _vp, _vp]),
+    "evd_rigid_blur_workspace_bytes": (_S, [C.POINTER(RigidBlurDesc), _L]),
+    "evd_rigid_blur_forward": (_I, [C.POINTER(RigidBlurDesc), C.POINTER(RigidBlurParams), _vp, _vp, _vp, _L, _vp, _vp, _vp, _vp]),
+    "evd_rigid_blur_backward": (_I, [C.POINTER(RigidBlurDesc), C.POINTER(RigidBlurParams), _vp, _vp, _vp, _L, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _S, _vp]),
     "evd_awp_feature_integration": (_I, [_vp, _vp, _vp, _L, _I, _I, _vp, _vp]),
     "evd_awp_feature_integration_bwd": (_I, [_vp, _vp, _vp, _vp, _L, _I, _I, _vp, _vp, _vp, _vp]),
     "evd_mam_local_forward": (_I, [_vp, _vp, _L, _I, _I, _I, _vp, _vp, _vp, _vp, _vp]),

@@ -87,6 +87,37 @@ int evd_ndc_rays(int H, int W, float focal, float near, const float* rays_o, con
  * transforms dev [R, M + use_origin, 4, 4] or NULL. */
 int evd_rbk_warp(const float* rays, const float* r, const float* v, long R, int M, int use_origin, float* new_rays, float* transforms,
                  void* stream);
+/* RigidBlurringModel.forward, networks/dpnerf/blurmodel.py:129-173, with ViewEmbedding.forward (networks/embedding.py:31-32) in front and
+ * rbk_warp (:51-82, utils/rigid_warping.py:18-49,72-110) behind it: the whole blur kernel network of a training iteration (the call site
+ * is networks/renderer.py:303-304, the module is built at run_nerf.py:204-215).  The parameters are the reference module's own tensors,
+ * float32 in torch layout ([out, in] weights), read in place: nothing is packed and no handle is kept.
+ *   C = width of a ray's feature row; W_r, W_v, W_w = hidden widths of the three branches (1..64); D_* = branch depths, 1 only (the
+ *   reference's loop feeds every branch layer the branch INPUT, :148-158, so a deeper branch is ill-formed or equal to its last layer);
+ *   M = num_motion (1..15); n_img = rows of the embedding table (0 without one); C <= 128.  Anything else: EVD_E_INVALID. */
+typedef struct {
+    int C, W_r, W_v, W_w, D_r, D_v, D_w, M, use_origin, n_img;
+    float rv_window;
+} evd_rigid_blur_desc;
+typedef struct {
+    const float* table;                                                           /* view_embed_module.img_embed dev [n_img, C], or NULL */
+    const float *r_branch_w, *r_branch_b, *v_branch_w, *v_branch_b, *w_branch_w, *w_branch_b;    /* *_branch.0: dev [W_*, C], [W_*] */
+    const float *r_linear_w, *r_linear_b, *v_linear_w, *v_linear_b;               /* dev [3 M, W_r / W_v], [3 M] */
+    const float *w_linear_w, *w_linear_b;                                         /* dev [M + 1, W_w], [M + 1] */
+} evd_rigid_blur_params;
+/* bytes of the backward's workspace for R rays (0 for an unsupported descriptor) */
+size_t evd_rigid_blur_workspace_bytes(const evd_rigid_blur_desc* d, long R);
+/* One launch.  rays dev [R,3,2]; a ray's feature row is table[ids[r]] (ids dev [R] int64: ViewEmbedding 'param', blurmodel.py:133-135) or,
+ * with ids == NULL, x[r] (x dev [R, C]: what the caller's param_mlp / feats concatenation produced, :139-146).
+ * -> new_rays dev [R, M + use_origin, 3, 2], weight dev [R, M + 1] (:163-164), img_embed dev [R, C] (the feature rows, bit for bit: :171). */
+int evd_rigid_blur_forward(const evd_rigid_blur_desc* d, const evd_rigid_blur_params* p, const float* rays, const long* ids, const float* x, long R,
+                           float* new_rays, float* weight, float* img_embed, void* stream);
+/* torch.autograd of the above (the reference has no explicit backward): two launches, no float atomics, the same bits on every run.
+ * d_new_rays dev [R, M + use_origin, 3, 2], d_weight dev [R, M + 1], d_img_embed dev [R, C] or NULL (what arrives at the img_embed output).
+ * -> grads dev: one flat float32 buffer in evd_rigid_blur_params' order (table [n_img, C] -- zeros in the ids == NULL form --, then the
+ * twelve network tensors), overwritten; d_rays dev [R,3,2] or NULL; d_x dev [R, C] or NULL (ids == NULL form only).  R = 0 writes zeros. */
+int evd_rigid_blur_backward(const evd_rigid_blur_desc* d, const evd_rigid_blur_params* p, const float* rays, const long* ids, const float* x, long R,
+                            const float* d_new_rays, const float* d_weight, const float* d_img_embed, float* grads, float* d_rays, float* d_x,
+                            void* workspace, size_t workspace_bytes, void* stream);
 /* The NaN / Inf guard of render_rays, networks/renderer.py:259-263 (there: isnan().any() + isinf().any() per result key = two
  * host synchronisations per key).  Here one launch: ptrs host[n_keys] (device arrays), counts host[n_keys] (floats per array),
  * n_keys <= 16 -> flags dev [n_keys] (unsigned): bit 0 = the key contains a NaN, bit 1 = an Inf.  Nothing synchronises; the caller

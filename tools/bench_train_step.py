@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """One WHOLE blurfactory training iteration (reference call stack SURVEY 3.1, run_nerf.py:423-601) on synthetic inputs, GPU only:
-    blur batch   1024 pixels -> rigid blur kernel (a small PyTorch module standing in for RigidBlurringModel: P = 10 warped rays
-                 per pixel + composition weights, learnable) -> c2f render under autograd -> fused blur-loss reduction
+    blur batch   1024 pixels -> rigid blur kernel (--kernel standin: a small PyTorch module standing in for RigidBlurringModel, P = 10
+                 warped rays per pixel + composition weights, learnable; torch: the real network as PyTorch ops, tools/rigid_blur_torch.py;
+                 device: evdeblurnerf_amd.blurmodel.RigidBlurKernel) -> c2f render under autograd -> fused blur-loss reduction
     event batch  2 x 4096 rays (start, end) -> c2f render under autograd -> fused event-loss reduction with the learnable event-CRF
     TV regulariser; backward through everything (hand-written kernels); Adam on both levels' networks and grids, the kernel and
     the CRF; parameters pushed back into the library
@@ -48,6 +49,9 @@ def main():
     ap.add_argument("--pixels", type=int, default=1024)
     ap.add_argument("--events", type=int, default=4096)
     ap.add_argument("--P", type=int, default=10)
+    ap.add_argument("--kernel", choices=["standin", "torch", "device"], default="standin",
+                    help="the blur kernel network: standin = RigidKernel above (what bench.py times), torch = RigidBlurringModel's function as PyTorch ops "
+                         "(tools/rigid_blur_torch.py), device = the library's kernels (evdeblurnerf_amd.blurmodel.RigidBlurKernel); 34 images, widths 32")
     ap.add_argument("--awp", choices=["none", "fused", "torch"], default="none",
                     help="the shipped configs' adaptive weight proposal on the blur batch (kernel_use_awp): fused = evdeblurnerf_amd.awp.FusedAWP around a "
                          "module with the reference's surface (tools/awp_standin.py), torch = that module's plain PyTorch forward on depth_feature")
@@ -61,7 +65,7 @@ def main():
                     help="the AWP module's motion aggregation: corr = the reference's MotionAggregationModule structure (MAMLike), mean = a small stand-in")
     a = ap.parse_args()
     ms, nr, loss = run(a)
-    print(f"blurfactory TRAINING iteration [{a.precision}]: {nr} rays x (64 + 64) samples, losses, TV, backward, Adam, re-pack: {ms:.2f} ms "
+    print(f"blurfactory TRAINING iteration [{a.precision}, {a.kernel} blur kernel]: {nr} rays x (64 + 64) samples, losses, TV, backward, Adam, re-pack: {ms:.2f} ms "
           f"({nr / ms / 1e3:.2f} M rays/s); loss = {loss:.5f}")
 
 
@@ -77,13 +81,27 @@ def run(a):
                            kernel_feat_cnl=15, fine_num_layers=2, fine_num_layers_color=3, fine_hidden_dim=256, fine_hidden_dim_color=256,
                            fine_geo_feat_dim=128, fine_app_dim=32, fine_app_n_comp=[64, 16, 16], fine_n_voxels=fv)
     dev = "cuda"
-    kern = RigidKernel(a.P).to(dev)
+    kernel_kind = getattr(a, "kernel", "standin")
+    blur_info = None
+    if kernel_kind == "standin":
+        kern = RigidKernel(a.P).to(dev)
+    else:
+        from evdeblurnerf_amd.blurmodel import RigidBlurKernel
+        torch.manual_seed(0)
+        kern = RigidBlurKernel(34, embed_dim=32, embed_init="normal", num_motion=a.P - 1).to(dev)
+        if kernel_kind == "torch":
+            sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+            from rigid_blur_torch import TorchRigidBlur
+            twin = TorchRigidBlur(34, embed_dim=32, num_motion=a.P - 1).to(dev)
+            twin.load_state_dict(kern.state_dict())
+            kern = twin
+        blur_info = {"images_idx": torch.randint(0, 34, (a.pixels, 1), generator=torch.Generator().manual_seed(1)).to(dev)}
     awp_mode = getattr(a, "awp", "none")
     awpnet = None
     if awp_mode != "none":
         from awp_standin import RefLikeAWP
         from evdeblurnerf_amd.awp import FusedAWP
-        awpnet = RefLikeAWP(P=a.P, view_ch=4, mam=getattr(a, "mam", "corr")).to(dev)
+        awpnet = RefLikeAWP(P=a.P, view_ch=4 if kernel_kind == "standin" else 32, mam=getattr(a, "mam", "corr")).to(dev)
         if awp_mode == "fused":
             awpnet = FusedAWP(awpnet, precision=a.precision if a.precision in ("f16", "bf16") else "f16", graph_per_ray=bool(getattr(a, "graph", False)))
     model = NeRFAll(args, sd, kernelsnet=kern, awpnet=awpnet, precision=a.precision).enable_training(sd, grads_in_place=not getattr(a, "plain_autograd", False)).train()
@@ -121,7 +139,7 @@ def run(a):
     kw = dict(ndc=True, near=0., far=1., N_samples=64, N_importance=64, perturb=1.0, raw_noise_std=0.)
 
     def step():
-        rgb, rgb0, other, tens = model(400, 400, K, 1 << 22, rays=blur_rays, rays_info=None, force_naive=False, **kw)
+        rgb, rgb0, other, tens = model(400, 400, K, 1 << 22, rays=blur_rays, rays_info=blur_info, force_naive=False, **kw)
         # the fused blur loss takes the per-sub-exposure colours and the weights; here the composed colours with unit weights
         ones = torch.ones((R, 1), device=dev)
         pb = blur_loss_partials_autograd(crf_rgb, rgb[:, None], ones, tgt, rgb0_p=rgb0[:, None], w2=ones, target_pts0=tgt0)

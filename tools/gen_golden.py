@@ -1612,12 +1612,112 @@ def G36_edi_prior():
     save64("G36_edi_prior", **out)
 
 
+# --------------------------------------------------------------------------- G37: the rigid blur kernel network
+RIGID_BLUR_CASES = {          # constructor arguments of the three cases; R rays, n images
+    "regular": dict(C=32, W_r=32, W_v=32, W_w=32, M=9, use_origin=True, R=130, n=7, seed=3701),
+    "small": dict(C=32, W_r=32, W_v=32, W_w=32, M=9, use_origin=True, R=130, n=7, seed=3702),
+    "odd": dict(C=24, W_r=20, W_v=32, W_w=12, M=4, use_origin=False, R=67, n=7, seed=3703),
+}
+
+
+def _rigid_blur_module(c, dtype):
+    from networks.dpnerf.blurmodel import RigidBlurringModel
+    from networks.embedding import ViewEmbedding
+    torch.manual_seed(c["seed"])
+    ve = ViewEmbedding(num_embed=c["n"], embed_dim=c["C"], init_params="normal")
+    kern = RigidBlurringModel(feat_ch=0, num_motion=c["M"], D_r=1, W_r=c["W_r"], D_v=1, W_v=c["W_v"], D_w=1, W_w=c["W_w"], output_ch_r=3,
+                              output_ch_v=3, rv_window=0.1, use_origin=c["use_origin"], view_embed=ve, W=ve.out_channels)
+    return kern.to(dtype)
+
+
+def _rigid_blur_run(kern, rays, ids, proj, dtype):
+    """outputs and autograd gradients (every parameter, the rays) of the projected sum of the three outputs, in `dtype` throughout
+    (rigid_warping.py builds its identity matrices in the default dtype, and blurmodel.py:166 casts the rays with .float(): for the
+    float64 run the default dtype is switched and Tensor.float is the identity while the module runs)"""
+    old, old_float = torch.get_default_dtype(), torch.Tensor.float
+    torch.set_default_dtype(dtype)
+    if dtype == torch.float64:
+        torch.Tensor.float = lambda self, *a, **k: self
+    try:
+        with torch.enable_grad():
+            r = t(rays).to(dtype).requires_grad_(True)
+            new_rays, weight, _, extras = kern(400, 400, None, r, {"images_idx": t(ids)}, return_img_embed=True)
+            loss = ((new_rays * t(proj["new_rays"]).to(dtype)).sum() + (weight * t(proj["weight"]).to(dtype)).sum() +
+                    (extras["img_embed"] * t(proj["img_embed"]).to(dtype)).sum())
+            names = [k for k, _ in kern.named_parameters()]
+            g = torch.autograd.grad(loss, [p for _, p in kern.named_parameters()] + [r])
+        theta = torch.linalg.norm((kern.r_linear(torch.relu(kern.r_branch[0](extras["img_embed"]))) * kern.rv_window).reshape(-1, 3, kern.num_motion), dim=1)
+    finally:
+        torch.set_default_dtype(old)
+        torch.Tensor.float = old_float
+    out = dict(new_rays=n(new_rays), weight=n(weight), img_embed=n(extras["img_embed"]))
+    grads = {k: n(v) for k, v in zip(names, g[:-1])}
+    grads["rays"] = n(g[-1])
+    return out, grads, (float(theta.min()), float(theta.max()))
+
+
+def G37_rigid_blur():
+    """RigidBlurringModel.forward (dpnerf/blurmodel.py:129-173) with ViewEmbedding 'param' (embedding.py:6-32), the real modules on the CPU:
+    (a) three cases -- the shipped sizes at the default initialisation with normal embeddings (theta ~ 1e-2); the same with the two heads'
+    biases zeroed and their weights x 1e3 (theta ~ 1e-4, where float32 1 - cos(theta) is 0 or 1 ulp); an odd shape without the origin slot --
+    each with one image id absent from the batch (and, in the odd case, one holding half of it).  Recorded per case: parameters, rays, ids,
+    projections, the float32 outputs and autograd gradients of the projected sum, and the error of those float32 results against the SAME
+    module run in float64 on the same float32-valued inputs (ref_f32_err: max abs for outputs, relative L2 per gradient tensor).
+    (b) the kernel state dict of _train_call_model(P=5, seed=32), the model G32 was recorded with: replaying it must give G32's committed
+    new_rays / weight bit for bit (asserted here), so G32 itself is not regenerated."""
+    out = {}
+    for tag, c in RIGID_BLUR_CASES.items():
+        rs = np.random.RandomState(c["seed"])
+        R, P = c["R"], c["M"] + int(c["use_origin"])
+        rays = W.synthetic_rays(c["seed"] % 100, R)
+        present = [i for i in range(c["n"]) if i != 3]                      # image 3 has no ray in the batch
+        ids = rs.choice(present, size=(R, 1)).astype(np.int64)
+        if tag == "odd":
+            ids[rs.permutation(R)[:R // 2 + 1]] = 5                          # image 5 holds half of it
+        proj = dict(new_rays=rs.standard_normal((R, P, 3, 2)).astype(np.float32), weight=rs.standard_normal((R, c["M"] + 1)).astype(np.float32),
+                    img_embed=rs.standard_normal((R, c["C"])).astype(np.float32))
+        k32 = _rigid_blur_module(c, torch.float32)
+        if tag == "small":
+            for lin in (k32.r_linear, k32.v_linear):
+                lin.bias.data.zero_()
+                lin.weight.data.mul_(1e3)
+        k64 = _rigid_blur_module(c, torch.float64)
+        k64.load_state_dict({k: v.double() for k, v in k32.state_dict().items()})
+        o32, g32, th = _rigid_blur_run(k32, rays, ids, proj, torch.float32)
+        o64, g64, _ = _rigid_blur_run(k64, rays, ids, proj, torch.float64)
+        assert all(v.dtype == np.float32 for v in o32.values()) and all(v.dtype == np.float64 for v in o64.values())
+        assert np.array_equal(o32["img_embed"], n(k32.view_embed_module.img_embed)[ids[:, 0]])
+        pre = tag + "."
+        out.update({pre + "sd." + k: n(v).copy() for k, v in k32.state_dict().items()})
+        out.update({pre + "rays": rays, pre + "ids": ids, pre + "theta_range": np.array(th, np.float32),
+                    pre + "args": np.array([c["M"], int(c["use_origin"])], np.int64), pre + "rv_window": np.float64(0.1)})
+        out.update({pre + "proj." + k: v for k, v in proj.items()})
+        out.update({pre + "out." + k: v for k, v in o32.items()})
+        out.update({pre + "g." + k: v for k, v in g32.items()})
+        for k in ("new_rays", "weight"):
+            out[pre + "ref_f32_err.out." + k] = np.float64(np.abs(o32[k].astype(np.float64) - o64[k]).max())
+        for k in g32:
+            out[pre + "ref_f32_err.g." + k] = np.float64(np.linalg.norm(g32[k].astype(np.float64) - g64[k]) / np.linalg.norm(g64[k]))
+        print(f"   {tag}: theta {th[0]:.1e} ... {th[1]:.1e}; float32 error of the reference: new_rays {out[pre + 'ref_f32_err.out.new_rays']:.1e}, "
+              f"weight {out[pre + 'ref_f32_err.out.weight']:.1e}, gradients "
+              f"{max(float(out[pre + 'ref_f32_err.g.' + k]) for k in g32):.1e} (worst tensor) {min(float(out[pre + 'ref_f32_err.g.' + k]) for k in g32):.1e} (best)")
+    # (b)
+    g = np.load(os.path.join(OUT, "G32_train_forward.npz"))
+    model, kern, awp, gc, gf = _train_call_model(5, seed=32)
+    new_rays, weight, _, extras = kern(400, 400, None, t(g["rays"]), {"images_idx": t(g["images_idx"])}, return_img_embed=True)
+    assert np.array_equal(n(new_rays), g["new_rays"]) and np.array_equal(n(weight), g["weight"]) and np.array_equal(n(extras["img_embed"]), g["img_embed"])
+    out.update({"train_call.sd." + k: n(v).copy() for k, v in kern.state_dict().items()})
+    path = os.path.join(OUT, "G37_rigid_blur.npz")
+    np.savez_compressed(path, **out)                                        # (keeps the float64 error records)
+    print(f"  wrote {os.path.relpath(path, ROOT)}  ({os.path.getsize(path) / 1024:.1f} KiB)")
+
+
 ALL = [G1_embedder, G2_nerf_mlp, G3_nerf_raw2outputs, G4_voxel_raw2outputs, G5_sample_pdf, G6_rays,
        G7_render_nerf, G8_appfeature, G9_render_c2f, G10_rbk_weighted_sum, G11_crf, G12_egm_loss, G13_edi,
        G14_loss_assembly, G15_awp_feature_integration, G16_rbk_warp, G17_compute_successor, G18_nerf_grads, G19_c2f_grads, G20_loss_grads,
        G21_awp_sample_embed, G22_mam, G23_render_nerf_no_viewdirs, G24_render_other_multires, G25_pbe_composite_feature,
        G26_sample_events, G27_awp_per_ray, G28_image_batch, G29_pose_track, G30_c2f_grads_16k, G31_event_hops, G32_train_forward,
-       G33_train_trajectory, G34_event_tables, G35_llff_poses, G36_edi_prior]
+       G33_train_trajectory, G34_event_tables, G35_llff_poses, G36_edi_prior, G37_rigid_blur]
 
 if __name__ == "__main__":
     want = set(sys.argv[1:])
