@@ -223,6 +223,9 @@ SIGNATURES = {
     "evd_edi_bii_image": (_I, [_vp, _vp, _vp, _L, _I, _I, _F, _F, _vp, _vp]),
     "evd_edi_prior_workspace_bytes": (_S, [_I, _I, _I, _I]),
     "evd_edi_prior": (_I, [_vp, _L, _vp, _L, _vp, _vp, _I, _I, _I, _I, _F, _F, _vp, _vp, _vp, _vp, _S, _vp]),
+    "evd_img_metrics_workspace_bytes": (_S, [_I, _I, _I]),
+    "evd_img_metrics": (_I, [_vp, _vp, _vp, _I, _I, _I, _I, _I, _I, _vp, _vp, _S, _vp]),
+    "evd_to8b": (_I, [_vp, _L, _vp, _vp]),
 }
 
 _lib = None

@@ -731,6 +731,38 @@ int evd_image_batch(const long long* ray_ids, long n, const float* images, const
                     int W, const float* K, float* rays, float* rays_x, float* rays_y, long long* images_idx, float* rgbsf, float* poses_out,
                     float* rgbsf_pts0, int* invalid, void* stream);
 
+/* ---------------------------------------------------------------- test-set pass: image metrics, 8-bit frames
+ * compute_img_metric(im1t, im2t, 'mse' | 'psnr' | 'ssim', margin, mask), utils/metrics.py:18-100 (called at run_nerf.py:685-687,704), for a
+ * whole batch in one main launch plus a fixed-order finish launch: scikit-image 0.19.2's mean_squared_error, peak_signal_noise_ratio and
+ * structural_similarity(multichannel=True) with the reference's arguments.
+ *   pred, target  dev float32 [B, H, W, 3], values nominally in [0, 1]; mapped clamp(2 x - 1, -1, 1) in float32 (:48-49).  Everything after
+ *                 the mapping is float64 (the reference keeps float32; its SSIM then loses 1e-8 .. 4e-7 to cancellation).
+ *   mask          dev float32 [B, H, W, mask_ch], mask_ch 1 or 3, or NULL (mask_ch ignored)
+ *   margin_h / w  rows / columns dropped on every side: int(H * margin) + 1 and int(W * margin) + 1 for margin > 0, else 0 (:67-71).  The
+ *                 region (H - 2 margin_h) x (W - 2 margin_w) is a window into the frames (no copy); borders, the SSIM crop and every
+ *                 count refer to it.  A region smaller than 7 in either dimension is rejected (scikit-image raises).
+ *   out           dev float64 [3 B + 3]: mse [B], psnr [B], ssim [B], then the three means over the batch (summed image by image, :100)
+ * mse = mean((x - y)^2) over the region and the channels.  psnr = 10 log10(data_range^2 / mse), data_range 1 if the mapped PREDICTION (the
+ * first argument) has no negative value in the region, else 2: the reference's behaviour, kept; +inf for identical images; NaN inputs
+ * give NaN.  ssim: uniform 7 x 7 window, K1 0.01, K2 0.03, data_range 2, sample covariance (49 / 48),
+ * S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)), the mean of S over the region shrunk by 3 and over the channels.
+ * With a mask: x and y are multiplied by it before mse / psnr and the minimum (zeros count toward it), 10 log10(h w / sum(mask[..., 0]))
+ * is subtracted from psnr AND from mse (:83-85), and ssim = sum(S mask) / sum(mask) over the whole region and the channels, S there with
+ * scipy.ndimage.uniform_filter's default border (half-sample symmetric reflect) (:90-91).
+ * ONE deviation: every image is multiplied by its own mask; the reference multiplies the whole batch by every earlier image's mask
+ * inside its loop (:77-78), which is the same for a batch of one or identical binary masks.
+ * No floating-point atomics: workgroup partials go to the workspace (evd_img_metrics_workspace_bytes(B, H, W): 40 bytes per tile of
+ * EVD_IMG_METRICS_TILE_H x EVD_IMG_METRICS_TILE_W pixels, sized for margin 0) and are summed in a fixed order; two runs give the same
+ * bits and an image's values do not depend on the rest of the batch.  No read-back; asynchronous on `stream`. */
+#define EVD_IMG_METRICS_TILE_H 16
+#define EVD_IMG_METRICS_TILE_W 32
+size_t evd_img_metrics_workspace_bytes(int B, int H, int W);
+int evd_img_metrics(const float* pred, const float* target, const float* mask, int mask_ch, int B, int H, int W, int margin_h, int margin_w,
+                    double* out, void* workspace, size_t workspace_bytes, void* stream);
+/* to8b, utils/misc.py:6: out[i] = (uint8)(255 * clip(x[i], 0, 1)), the product in float32, truncated; NaN -> 0.  x dev float32 [n],
+ * out dev uint8 [n]. */
+int evd_to8b(const float* x, long n, unsigned char* out, void* stream);
+
 /* ---------------------------------------------------------------- measurement aid (no reference counterpart)
  * Sustained rate of back-to-back v_mfma_f32_32x32x16_bf16 issue on every SIMD of the current device, in dense
  * TFLOP/s, with constant (random_operands == 0) or random operands.  The chip clocks to its power budget, so the
