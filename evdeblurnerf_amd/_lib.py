@@ -92,6 +92,10 @@ class RigidBlurParams(C.Structure):
                                    "r_linear_w", "r_linear_b", "v_linear_w", "v_linear_b", "w_linear_w", "w_linear_b")]
 
 
+class LpipsDesc(C.Structure):
+    _fields_ = [("conv_w", _fp * 5), ("conv_b", _fp * 5), ("lin", _fp * 5), ("shift", C.c_float * 3), ("scale", C.c_float * 3)]
+
+
 class RenderOut(C.Structure):
     _fields_ = [(k, _vp) for k in ("rgb", "depth", "acc", "z_vals", "weights", "rgb0", "depth0", "acc0", "z_std",
                                    "z_vals0", "weights0", "feature", "raw")] + [("feature_kind", C.c_int)]
@@ -226,6 +230,10 @@ SIGNATURES = {
     "evd_img_metrics_workspace_bytes": (_S, [_I, _I, _I]),
     "evd_img_metrics": (_I, [_vp, _vp, _vp, _I, _I, _I, _I, _I, _I, _vp, _vp, _S, _vp]),
     "evd_to8b": (_I, [_vp, _L, _vp, _vp]),
+    "evd_lpips_create": (_I, [C.POINTER(LpipsDesc), C.POINTER(_vp)]),
+    "evd_lpips_destroy": (None, [_vp]),
+    "evd_lpips_workspace_bytes": (_S, [_I, _I, _I]),
+    "evd_lpips": (_I, [_vp, _vp, _vp, _I, _I, _I, _vp, _vp, _S, _vp]),
 }
 
 _lib = None

@@ -5,9 +5,14 @@ call (evd_img_metrics) without a host copy; scikit-image is not needed.  The ari
 One deliberate deviation: with a mask, every image is multiplied by its own mask.  The reference multiplies the whole batch by every earlier
 image's mask inside its loop (:77-78); the two agree for a batch of one and for identical binary masks.
 
-LPIPS is not built: its AlexNet backbone weights are not part of the reference checkout (torchvision downloads them)."""
+LPIPS (:92-95, networks/lpips/lpips.py) is built as the reference's ``LPIPS()`` call uses it -- AlexNet backbone, version 0.1, linear heads,
+spatial average, eval mode -- on the device in float32 (evd_lpips).  Its WEIGHTS ARE THE CALLER'S: the AlexNet backbone's pretrained
+weights are not part of the reference checkout (torchvision downloads them), so ``LPIPS`` is built from two state dicts or files the
+user already has, nothing is ever downloaded, and ``compute_img_metric(..., 'lpips')`` works once a model is installed with
+``set_lpips``.  vgg / squeeze, the spatial map, the baseline without heads and any backward are not built."""
 from __future__ import annotations
 
+import ctypes
 import math
 
 import torch
@@ -73,14 +78,99 @@ def img_metrics(pred, target, margin=0, mask=None, format=None):
             "ssim_mean": out[3 * B + 2]}
 
 
+class LPIPS:
+    """The reference's ``LPIPS()`` (net='alex', version='0.1', lpips=True, spatial=False, eval mode: dropout is the identity) on the device.
+    alexnet: torchvision's AlexNet state dict (``features.{0,3,6,8,10}.{weight,bias}``; other keys such as ``classifier.*`` are ignored);
+    lin: the linear heads (``lin{0..4}.model.1.weight``, the keys of the reference's weights/v0.1/alex.pth).  The library packs them once."""
+    CONV = ((0, 3, 64, 11), (3, 64, 192, 5), (6, 192, 384, 3), (8, 384, 256, 3), (10, 256, 256, 3))       # features index, Cin, Cout, kernel
+    SHIFT, SCALE = (-.030, -.088, -.188), (.458, .448, .450)                                             # ScalingLayer, lpips.py:245-252
+
+    def __init__(self, alexnet, lin):
+        def take(sd, key, shape, what):
+            if key not in sd:
+                raise L.EvdError(f"LPIPS: {what} state dict has no '{key}'")
+            v = torch.as_tensor(sd[key]).detach().to(device="cpu", dtype=torch.float32)
+            if v.numel() != math.prod(shape) or (v.dim() == len(shape) and tuple(v.shape) != shape):
+                raise L.EvdError(f"LPIPS: '{key}' has shape {tuple(v.shape)}, expected {shape}")
+            return v.reshape(shape).contiguous()
+
+        keep = []
+        desc = L.LpipsDesc()
+        for l, (idx, ci, co, k) in enumerate(self.CONV):
+            w = take(alexnet, f"features.{idx}.weight", (co, ci, k, k), "the AlexNet")
+            b = take(alexnet, f"features.{idx}.bias", (co,), "the AlexNet")
+            h = take(lin, f"lin{l}.model.1.weight", (1, co, 1, 1), "the linear-head")
+            keep += [w, b, h]
+            desc.conv_w[l] = ctypes.cast(w.data_ptr(), L._fp)
+            desc.conv_b[l] = ctypes.cast(b.data_ptr(), L._fp)
+            desc.lin[l] = ctypes.cast(h.data_ptr(), L._fp)
+        for c in range(3):
+            desc.shift[c], desc.scale[c] = self.SHIFT[c], self.SCALE[c]
+        self._lib = L.lib()
+        self._h = ctypes.c_void_p()
+        L.check(self._lib.evd_lpips_create(ctypes.byref(desc), ctypes.byref(self._h)), "evd_lpips_create")
+
+    @classmethod
+    def from_files(cls, alexnet_path, lin_path):
+        """Both files are read with torch.load(..., map_location='cpu', weights_only=True); nothing is downloaded."""
+        return cls(torch.load(alexnet_path, map_location="cpu", weights_only=True), torch.load(lin_path, map_location="cpu", weights_only=True))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.evd_lpips_destroy(h)
+
+    def _run(self, im1, im2, format):
+        p = _bhwc(im1, format)
+        t = _bhwc(im2, format).to(p.device)
+        if not p.is_cuda:
+            raise L.EvdError("LPIPS: the images must be on the GPU (there is no CPU fallback)")
+        if p.shape != t.shape:
+            raise L.EvdError(f"LPIPS: shapes {tuple(p.shape)} and {tuple(t.shape)} differ")
+        B, H, W = (int(v) for v in p.shape[:3])
+        need = int(self._lib.evd_lpips_workspace_bytes(B, H, W))
+        ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=p.device)
+        out = torch.empty((6 * B + 1,), dtype=torch.float64, device=p.device)
+        L.check(self._lib.evd_lpips(self._h, L.ptr(p), L.ptr(t), B, H, W, L.ptr(out), L.ptr(ws), need, L.stream_ptr()), "evd_lpips")
+        return out, B
+
+    def __call__(self, im1, im2, format=None, retPerLayer=False):
+        """im1, im2 in (0, 1), laid out as compute_img_metric takes them -> the [B] float64 device tensor of per-image values, and with
+        retPerLayer the [B, 5] per-layer terms (each layer's own term: the reference's list carries the total in slot 0 because its sum adds
+        in place).  No host copy, no synchronisation."""
+        out, B = self._run(im1, im2, format)
+        return (out[:B], out[B + 1:].view(B, 5)) if retPerLayer else out[:B]
+
+    def mean(self, im1, im2, format=None):
+        """the batch mean, summed image by image (0-dim float64 device tensor)"""
+        out, B = self._run(im1, im2, format)
+        return out[B]
+
+
+_LPIPS = [None]
+
+
+def set_lpips(model):
+    """Install the LPIPS model compute_img_metric(..., 'lpips') uses (the reference's module-level `photometric` cache, utils/metrics.py:11-16,
+    filled by hand because the weights are the caller's); None removes it."""
+    if model is not None and not isinstance(model, LPIPS):
+        raise L.EvdError(f"set_lpips: an evdeblurnerf_amd.metrics.LPIPS or None, got {type(model).__name__}")
+    _LPIPS[0] = model
+
+
 def compute_img_metric(im1t, im2t, metric="mse", margin=0, mask=None, format=None):
     """utils/metrics.py:18-100: the mean of `metric` over the batch as a Python float (one read-back).  im1t, im2t: batched images in (0, 1),
-    [H, W, 3], [3, H, W], [B, H, W, 3] or [B, 3, H, W] (`format` None, 'HWC', 'CHW', 'BHWC'; anything else means [B, 3, H, W])."""
+    [H, W, 3], [3, H, W], [B, H, W, 3] or [B, 3, H, W] (`format` None, 'HWC', 'CHW', 'BHWC'; anything else means [B, 3, H, W]).
+    'lpips' needs a model installed with set_lpips and IGNORES margin and mask, as the reference's branch does: it feeds the un-cropped,
+    un-masked im1t[i:i+1] to the network (:92-95)."""
     if metric not in PHOTOMETRIC:
         raise RuntimeError(f"img_utils:: metric {metric} not recognized")
     if metric == "lpips":
-        raise NotImplementedError("compute_img_metric: 'lpips' is not built: the LPIPS backbone's pretrained weights are not part of the "
-                                  "reference checkout and cannot be fetched; 'mse', 'psnr' and 'ssim' run on the device")
+        if _LPIPS[0] is None:
+            raise NotImplementedError("compute_img_metric: 'lpips' needs the LPIPS backbone's pretrained weights, which are not part of the "
+                                      "reference checkout and cannot be fetched: build metrics.LPIPS from the AlexNet and linear-head weights "
+                                      "you have and install it with metrics.set_lpips; 'mse', 'psnr' and 'ssim' run on the device")
+        return float(_LPIPS[0].mean(im1t, im2t, format=format))
     return float(img_metrics(im1t, im2t, margin=margin, mask=mask, format=format)[metric + "_mean"])
 
 

@@ -130,6 +130,32 @@ def make_awp_embed_state_dict(seed: int, input_ch: int = 128, W_sam: int = 64, D
     return sd
 
 
+LPIPS_ALEXNET = ((0, 3, 64, 11), (3, 64, 192, 5), (6, 192, 384, 3), (8, 384, 256, 3), (10, 256, 256, 3))   # features index, Cin, Cout, kernel
+
+
+def make_lpips_alexnet_state_dict(seed: int, gain: float = 1.4, bias_bound: float = 0.1):
+    """``features.{0,3,6,8,10}.{weight,bias}`` of torchvision's AlexNet, the LPIPS backbone (networks/lpips/pretrained_networks.py:57-95), as a
+    SYNTHETIC stand-in for the pretrained weights nobody may ship: uniform +-gain sqrt(3 / fan_in) keeps the activations O(1) through conv5
+    (per-layer LPIPS terms of 1e-3 .. 1e-2 on random frames), biases uniform +-bias_bound."""
+    rs = np.random.RandomState(seed)
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for idx, ci, co, k in LPIPS_ALEXNET:
+        sd[f"features.{idx}.weight"] = _uniform(rs, (co, ci, k, k), gain * math.sqrt(3.0 / (ci * k * k)))
+        sd[f"features.{idx}.bias"] = _uniform(rs, (co,), bias_bound)
+    return sd
+
+
+def synthetic_frame_pairs(seed: int, B: int, H: int, W: int, lo: float = 0.0, hi: float = 1.0, noise: float = 0.15):
+    """Predicted and target frames [B, H, W, 3] for the image-metric goldens: uniform [lo, hi) frames and a noisy copy, clipped to [0, 1]
+    unless the range leaves it (the case that exercises the metrics' clamp)."""
+    rs = np.random.RandomState(seed)
+    pred = rs.uniform(lo, hi, size=(B, H, W, 3))
+    target = pred + noise * rs.standard_normal((B, H, W, 3))
+    if lo >= 0.0 and hi <= 1.0:
+        target = np.clip(target, 0.0, 1.0)
+    return pred.astype(np.float32), target.astype(np.float32)
+
+
 def prefixed(sd, prefix: str):
     """``{prefix}.{name}`` view of a state dict (e.g. ``mlp_coarse``)."""
     return OrderedDict((f"{prefix}.{k}", v) for k, v in sd.items())

@@ -763,6 +763,46 @@ int evd_img_metrics(const float* pred, const float* target, const float* mask, i
  * out dev uint8 [n]. */
 int evd_to8b(const float* x, long n, unsigned char* out, void* stream);
 
+/* LPIPS, the fourth metric of the test-set pass: compute_img_metric(im1t, im2t, 'lpips'), utils/metrics.py:92-95 (called at run_nerf.py:688),
+ * i.e. networks/lpips/lpips.py LPIPS(net='alex', version='0.1', lpips=True, spatial=False) in eval mode, float32 throughout.
+ * The WEIGHTS ARE THE CALLER'S: torchvision's pretrained AlexNet `features` (not part of the reference checkout; torchvision downloads
+ * them) and the linear heads of the reference's weights/v0.1/alex.pth.  The library ships none and fetches nothing.
+ *   conv_w[l], conv_b[l]  host float32, torchvision's features.{0,3,6,8,10}.{weight,bias}: [Cout, Cin, kh, kw] / [Cout] with
+ *                         (Cout, Cin, k) = (64, 3, 11), (192, 64, 5), (384, 192, 3), (256, 384, 3), (256, 256, 3)
+ *   lin[l]                host float32 [Cout of layer l]: lin{l}.model.1.weight (a 1 x 1 convolution without bias)
+ *   shift, scale          the ScalingLayer's constants (lpips.py:245-252)
+ * Host pointers are read during evd_lpips_create only (as for every _create entry); the handle owns packed device copies ([K, Cout] with
+ * K = (ky, kx, c), the layout of the implicit-GEMM kernel) and is destroyed with evd_lpips_destroy.
+ * evd_lpips:
+ *   pred, target  dev float32 [B, H, W, 3] in (0, 1); conv1 maps them on load, clamp(2 x - 1, -1, 1) (utils/metrics.py:48-49), then
+ *                 (x - shift) / scale, and pads with zeros by predicate.  H, W >= EVD_LPIPS_MIN_SIDE: the smallest side at which the
+ *                 second 3 x 3 / stride 2 pool still has one output.
+ *   out           dev float64 [6 B + 1]: the per-image values [B], their mean over the batch (summed image by image), then the per-layer
+ *                 terms [B, 5]; value[b] = sum_l term[b, l], term[b, l] = mean over the layer's pixels of
+ *                 sum_c lin_c (f0_c / (n0 + 1e-10) - f1_c / (n1 + 1e-10))^2 with n = sqrt(sum_c f_c^2); an all-zero feature vector gives 0.
+ *   workspace     evd_lpips_workspace_bytes(B, H, W) bytes (0 for sizes the entry rejects): two activation buffers and the partials.
+ * Predicted and target frames of the whole batch go through every layer in ONE launch (M = 2 B h w rows of the implicit GEMM on
+ * v_mfma_f32_32x32x2_f32: exact float32 products).  The features are float32; the normalisation, the distance and every sum after it
+ * are float64, workgroup partials summed in a fixed order without floating-point atomics: two runs give the same bits, an image's
+ * value does not depend on the rest of the batch, and identical frames give exactly 0.  No allocation, no host copy, no
+ * synchronisation; asynchronous on `stream`.
+ * Not built: net = 'vgg' / 'squeeze', spatial maps, the baseline without heads (lpips=False), version 0.0, dropout in training mode,
+ * any backward. */
+#define EVD_LPIPS_MIN_SIDE 31
+#define EVD_LPIPS_LAYERS 5
+typedef struct evd_lpips_model evd_lpips_model;     /* opaque: packed backbone weights, heads, scaling constants (a type cannot share the
+                                                      * entry's name evd_lpips in C) */
+typedef struct {
+    const float *conv_w[EVD_LPIPS_LAYERS], *conv_b[EVD_LPIPS_LAYERS];
+    const float* lin[EVD_LPIPS_LAYERS];
+    float shift[3], scale[3];
+} evd_lpips_desc;
+int evd_lpips_create(const evd_lpips_desc* desc, evd_lpips_model** out);
+void evd_lpips_destroy(evd_lpips_model* m);
+size_t evd_lpips_workspace_bytes(int B, int H, int W);
+int evd_lpips(const evd_lpips_model* m, const float* pred, const float* target, int B, int H, int W, double* out, void* workspace, size_t workspace_bytes,
+              void* stream);
+
 /* ---------------------------------------------------------------- measurement aid (no reference counterpart)
  * Sustained rate of back-to-back v_mfma_f32_32x32x16_bf16 issue on every SIMD of the current device, in dense
  * TFLOP/s, with constant (random_operands == 0) or random operands.  The chip clocks to its power budget, so the

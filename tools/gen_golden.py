@@ -1712,12 +1712,106 @@ def G37_rigid_blur():
     print(f"  wrote {os.path.relpath(path, ROOT)}  ({os.path.getsize(path) / 1024:.1f} KiB)")
 
 
+# --------------------------------------------------------------------------- G38: LPIPS
+LPIPS_BACKBONE_SEED = 3800
+LPIPS_CASES = {               # B, H, W, seed of the frames, value range of the predicted frames
+    "min": (2, 31, 31, 3801, 0.0, 1.0),           # every map after the second pool is 1 x 1
+    "odd": (2, 35, 47, 3802, 0.0, 1.0),           # non-square; the conv1 and pool floors are both inexact
+    "one": (1, 67, 90, 3803, 0.0, 1.0),
+    "clamp": (2, 40, 33, 3804, -0.3, 1.3),        # values outside (0, 1): the clamp matters
+}
+
+
+def _lpips_reference_model():
+    """the reference's real LPIPS class (networks/lpips/lpips.py) with its own linear heads (weights/v0.1/alex.pth); torchvision is absent, so
+    a stub `torchvision.models.alexnet` hands it a `features` stack of the public AlexNet architecture built from torch.nn and loaded with
+    the seed-derived stand-in weights"""
+    import types
+    from torch import nn
+
+    def alexnet(pretrained=True, **kw):
+        feats = nn.Sequential(
+            nn.Conv2d(3, 64, kernel_size=11, stride=4, padding=2), nn.ReLU(inplace=True), nn.MaxPool2d(kernel_size=3, stride=2),
+            nn.Conv2d(64, 192, kernel_size=5, padding=2), nn.ReLU(inplace=True), nn.MaxPool2d(kernel_size=3, stride=2),
+            nn.Conv2d(192, 384, kernel_size=3, padding=1), nn.ReLU(inplace=True),
+            nn.Conv2d(384, 256, kernel_size=3, padding=1), nn.ReLU(inplace=True),
+            nn.Conv2d(256, 256, kernel_size=3, padding=1), nn.ReLU(inplace=True), nn.MaxPool2d(kernel_size=3, stride=2))
+        sd = W.make_lpips_alexnet_state_dict(LPIPS_BACKBONE_SEED)
+        feats.load_state_dict({k[len("features."):]: t(v) for k, v in sd.items()})
+        return types.SimpleNamespace(features=feats)
+
+    tv = types.ModuleType("torchvision")
+    tv.models = types.ModuleType("torchvision.models")
+    tv.models.alexnet = alexnet
+    sys.modules.setdefault("torchvision", tv)
+    sys.modules.setdefault("torchvision.models", tv.models)
+    from networks.lpips import lpips as lp
+    return lp, lp.LPIPS(verbose=False)
+
+
+def _lpips_run(lp, model, pred, target, dtype):
+    """value [B] and per-layer terms [B, 5] as compute_img_metric's 'lpips' branch forms them (utils/metrics.py:48-49, :92-95): the float32
+    mapping, then one call per image.  The reference's `val = res[0]; val += res[l]` adds IN PLACE, so its retPerLayer list carries the
+    total in slot 0: the terms are copied as spatial_average returns them, before the sum."""
+    seen = []
+    orig = lp.spatial_average
+
+    def recording(*a, **k):
+        r = orig(*a, **k)
+        seen.append(r.detach().clone())
+        return r
+
+    lp.spatial_average = recording
+    try:
+        im1 = (t(pred) * 2 - 1).clamp(-1, 1).permute(0, 3, 1, 2).to(dtype)
+        im2 = (t(target) * 2 - 1).clamp(-1, 1).permute(0, 3, 1, 2).to(dtype)
+        vals, terms = [], []
+        for i in range(im1.shape[0]):
+            del seen[:]
+            v = model(im1[i:i + 1], im2[i:i + 1])
+            assert len(seen) == 5 and v.dtype == dtype
+            vals.append(float(v.reshape(-1)[0]) if dtype == torch.float64 else np.float32(v.reshape(-1)[0].item()))
+            terms.append([x.reshape(-1)[0].item() for x in seen])
+    finally:
+        lp.spatial_average = orig
+    return np.asarray(vals, np.float64), np.asarray(terms, np.float64)
+
+
+def G38_lpips():
+    """LPIPS(net='alex', version='0.1') of the reference on the CPU, float32 and the same module in .double(), per case: value [B], per-layer
+    terms [B, 5], and ref_f32_err = |f32 - f64| / f64 of both.  Stored beside them: the reference's linear heads (1152 floats of
+    weights/v0.1/alex.pth), the scaling layer's shift and scale, and each case's (B, H, W, seed, lo, hi); the backbone weights and the frames
+    are derived from seeds on both sides (evdeblurnerf_amd.weights) and not stored."""
+    import copy
+    lp, m32 = _lpips_reference_model()
+    m64 = copy.deepcopy(m32).double()
+    out = {f"lin{l}": n(getattr(m32, f"lin{l}").model[1].weight).reshape(-1).copy() for l in range(5)}
+    assert sum(v.size for v in out.values()) == 1152 and all((v >= 0).all() for v in out.values())
+    out["shift"] = n(m32.scaling_layer.shift).reshape(3).copy()
+    out["scale"] = n(m32.scaling_layer.scale).reshape(3).copy()
+    out["backbone_seed"] = np.int64(LPIPS_BACKBONE_SEED)
+    out["cases"] = np.array(list(LPIPS_CASES))
+    for tag, (B, H, Wd, seed, lo, hi) in LPIPS_CASES.items():
+        pred, target = W.synthetic_frame_pairs(seed, B, H, Wd, lo, hi)
+        v32, t32 = _lpips_run(lp, m32, pred, target, torch.float32)
+        v64, t64 = _lpips_run(lp, m64, pred, target, torch.float64)
+        pre = tag + "."
+        out.update({pre + "args": np.array([B, H, Wd, seed], np.int64), pre + "range": np.array([lo, hi], np.float64),
+                    pre + "f32.value": v32, pre + "f32.terms": t32, pre + "f64.value": v64, pre + "f64.terms": t64,
+                    pre + "ref_f32_err.value": np.abs(v32 - v64) / v64, pre + "ref_f32_err.terms": np.abs(t32 - t64) / t64})
+        print(f"   {tag}: value {v64}, terms {t64.min():.1e} .. {t64.max():.1e}; float32 error of the reference: value "
+              f"{out[pre + 'ref_f32_err.value'].max():.1e}, terms {out[pre + 'ref_f32_err.terms'].max():.1e}")
+    path = os.path.join(OUT, "G38_lpips.npz")
+    np.savez_compressed(path, **out)                                        # (keeps the float64 records)
+    print(f"  wrote {os.path.relpath(path, ROOT)}  ({os.path.getsize(path) / 1024:.1f} KiB)")
+
+
 ALL = [G1_embedder, G2_nerf_mlp, G3_nerf_raw2outputs, G4_voxel_raw2outputs, G5_sample_pdf, G6_rays,
        G7_render_nerf, G8_appfeature, G9_render_c2f, G10_rbk_weighted_sum, G11_crf, G12_egm_loss, G13_edi,
        G14_loss_assembly, G15_awp_feature_integration, G16_rbk_warp, G17_compute_successor, G18_nerf_grads, G19_c2f_grads, G20_loss_grads,
        G21_awp_sample_embed, G22_mam, G23_render_nerf_no_viewdirs, G24_render_other_multires, G25_pbe_composite_feature,
        G26_sample_events, G27_awp_per_ray, G28_image_batch, G29_pose_track, G30_c2f_grads_16k, G31_event_hops, G32_train_forward,
-       G33_train_trajectory, G34_event_tables, G35_llff_poses, G36_edi_prior, G37_rigid_blur]
+       G33_train_trajectory, G34_event_tables, G35_llff_poses, G36_edi_prior, G37_rigid_blur, G38_lpips]
 
 if __name__ == "__main__":
     want = set(sys.argv[1:])
