@@ -31,7 +31,49 @@ int fail(int code, const char* fmt, ...) {
 int nerf_mlp_generic_dispatch(int prec, int W, const MlpParams& p, hipStream_t st);
 int nerf_mlp_pipe_dispatch(int prec, const MlpParams& p, hipStream_t st);
 int nerf_mlp_c_dispatch(int W, int D, int skip, const MlpParams& p, hipStream_t st);       // kernel_nerf_mlp.hip: compensated float16 mode
-int nerf_mlp_c_chunks(int W, int D, int skip);                                             // 0: not built for this network
+int nerf_mlp_c_chunks(int W, int D, int skip, bool train);                                 // 0: not built for this network; train: the unfolded stream
+
+// Inference in the compensated mode folds feature_linear (no activation, read by views_linears.0 only) into the views layer:
+//     Wfold = [Wv[:, :W] Wf | Wv[:, W:]]  (W/2 x (W + ICV)),   bfold = Wv[:, :W] bf + bv
+// written behind a device copy of the parameter arena (evd_nerf::fold_arena) that the folded stream's re-pack maps index.  Every
+// element is ONE float64 fma chain over k = 0 .. W-1 in that order, rounded once to float32: creation and re-pack run this kernel, so
+// their streams agree bit for bit.  thread = one element of Wfold (row-major), then of bfold.
+static __global__ void k_fold_feature(const float* __restrict__ views_w, const float* __restrict__ views_b, const float* __restrict__ feature_w,
+                                      const float* __restrict__ feature_b, int W, int ICV, float* __restrict__ wfold, float* __restrict__ bfold) {
+    const int in = W + ICV, rows = W / 2;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < (long)rows * in) {
+        const int r = (int)(i / in), c = (int)(i % in);
+        if (c >= W) { wfold[i] = views_w[i]; return; }
+        double acc = 0.0;
+        for (int k = 0; k < W; ++k) acc = fma((double)views_w[(long)r * in + k], (double)feature_w[(long)k * W + c], acc);
+        wfold[i] = (float)acc;
+    } else if (i < (long)rows * in + rows) {
+        const int r = (int)(i - (long)rows * in);
+        double acc = 0.0;
+        for (int k = 0; k < W; ++k) acc = fma((double)views_w[(long)r * in + k], (double)feature_b[k], acc);
+        bfold[r] = (float)(acc + (double)views_b[r]);
+    }
+}
+
+// the folded stream, its row scales and its bias block from the parameter values at `params` (device, canonical order): one path for
+// evd_nerf_create and evd_nerf_load_params
+static int nerf_fold_pack(evd_nerf* n, const float* params, hipStream_t st) {
+    if (!n->pipe_cf.data.p) return EVD_OK;
+    const int W = n->W, D = n->D, ICV = 3 * (1 + 2 * n->multires_views);
+    const long total = n->param_off[n->nparam_blocks], nw = (long)(W / 2) * (W + ICV), nel = nw + W / 2;
+    float* ext = (float*)n->fold_arena.p;
+    EVD_HIP(hipMemcpyAsync(ext, params, (size_t)total * sizeof(float), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_fold_feature, dim3((unsigned)cdiv(nel, 256L)), dim3(256), 0, st, ext + n->param_off[2 * D], ext + n->param_off[2 * D + 1],
+                       ext + n->param_off[2 * D + 2], ext + n->param_off[2 * D + 3], W, ICV, ext + total, ext + total + nw);
+    EVD_LAUNCH_CHECK();
+    int rc = repack_stream_c(n->pipe_cf, ext, st);
+    if (rc) return rc;
+    const long nb = (long)(n->bias_f.bytes / sizeof(float));
+    hipLaunchKernelGGL(k_gather_f32, dim3((unsigned)cdiv(nb, 256L)), dim3(256), 0, st, (const float*)ext, (const int*)n->bias_f_src.p, nb, (float*)n->bias_f.p);
+    EVD_LAUNCH_CHECK();
+    return EVD_OK;
+}
 
 // the side-stream test hook (evd_common.h): ONE copy of the spin kernel in the library, the launch checked, launches counted
 static std::atomic<long> g_side_spins{0};
@@ -171,34 +213,50 @@ int evd_nerf_create(const evd_nerf_desc* d, evd_nerf** out) {
     for (int prec = 0; prec < EVD_NUM_PREC && !rc; ++prec) {
         if (prec == EVD_PREC_F16C) {      // compensated float16 mode: its own stream (float16 + fp6 fragments) and row scales; pipelined kernel only
             n->nchunks[prec] = n->pipe_chunks[prec] = 0;
-            if (no_views || !standard || !nerf_mlp_c_chunks(W, D, d->skip)) continue;
-            StreamBuilderC sc(PIPE_CB);
-            sc.arena = A;
-            const int KB = KS / 4;
-            sc.layer(pts_w(0), W, IC, T, PE_KS, 2, pe_col);
-            for (int l = 1; l < D; ++l) {
-                if (l - 1 == d->skip) {       // blocks [h_0 .. h_{KB-2} | pe | h_{KB-1}]
-                    auto wide_col = [&](int j, int kk) {
-                        if (j < 4 * (KB - 1)) return IC + c_hid_col(j, kk);
-                        if (j < 4 * (KB - 1) + PE_KS) return pe_col(j - 4 * (KB - 1), kk);
-                        return IC + c_hid_col(j - PE_KS, kk);
-                    };
-                    sc.layer(pts_w(l), W, W + IC, T, PE_KS + KS, 2, wide_col);
-                } else {
-                    sc.layer(pts_w(l), W, W, T, KS, 2, c_hid_col);
+            if (no_views || !standard || !nerf_mlp_c_chunks(W, D, d->skip, false)) continue;
+            // fold: the inference stream -- no feature layer, views_linears.0 replaced by the folded layer, whose elements live behind the
+            // parameters in the extended arena (k_fold_feature); base: the arena the element -> source maps index
+            auto build_c = [&](StreamBuilderC& sc, const float* base, bool fold) {
+                auto Pb = [&](int i) { return base + n->param_off[i]; };
+                sc.arena = base;
+                const int KB = KS / 4;
+                sc.layer(Pb(0), W, IC, T, PE_KS, 2, pe_col);
+                for (int l = 1; l < D; ++l) {
+                    if (l - 1 == d->skip) {       // blocks [h_0 .. h_{KB-2} | pe | h_{KB-1}]
+                        auto wide_col = [&](int j, int kk) {
+                            if (j < 4 * (KB - 1)) return IC + c_hid_col(j, kk);
+                            if (j < 4 * (KB - 1) + PE_KS) return pe_col(j - 4 * (KB - 1), kk);
+                            return IC + c_hid_col(j - PE_KS, kk);
+                        };
+                        sc.layer(Pb(2 * l), W, W + IC, T, PE_KS + KS, 2, wide_col);
+                    } else {
+                        sc.layer(Pb(2 * l), W, W, T, KS, 2, c_hid_col);
+                    }
                 }
-            }
-            sc.layer(alpha_w, 1, W, 1, KS, 1, c_hid_col);
-            sc.layer(feature_w, W, W, T, KS, 2, c_hid_col);
-            sc.layer(views_w, W / 2, W + ICV, T / 2, KS + PEV_KS, 2, [&](int j, int kk) {
-                if (j < KS) return c_hid_col(j, kk);
-                const int c = pe_src_col(Lv, 8 * (j - KS) + (kk & 7), kk >> 3);
-                return c < 0 ? -1 : W + c;
-            });
-            sc.layer(rgb_w, 3, W / 2, 1, KS / 2, 1, c_hid_col);
+                sc.layer(Pb(2 * D + 4), 1, W, 1, KS, 1, c_hid_col);
+                if (!fold) sc.layer(Pb(2 * D + 2), W, W, T, KS, 2, c_hid_col);
+                sc.layer(fold ? base + total : Pb(2 * D), W / 2, W + ICV, T / 2, KS + PEV_KS, 2, [&](int j, int kk) {
+                    if (j < KS) return c_hid_col(j, kk);
+                    const int c = pe_src_col(Lv, 8 * (j - KS) + (kk & 7), kk >> 3);
+                    return c < 0 ? -1 : W + c;
+                });
+                sc.layer(Pb(2 * D + 6), 3, W / 2, 1, KS / 2, 1, c_hid_col);
+            };
+            StreamBuilderC sc(PIPE_CB);
+            build_c(sc, A, false);
             n->pipe_chunks[prec] = (int)(sc.bytes.size() / PIPE_CB);
-            if (n->pipe_chunks[prec] != nerf_mlp_c_chunks(W, D, d->skip)) rc = fail(EVD_E_INVALID, "evd_nerf_create: f16c stream has %d chunks, kernel expects %d", n->pipe_chunks[prec], nerf_mlp_c_chunks(W, D, d->skip));
+            if (n->pipe_chunks[prec] != nerf_mlp_c_chunks(W, D, d->skip, true)) rc = fail(EVD_E_INVALID, "evd_nerf_create: f16c stream has %d chunks, kernel expects %d", n->pipe_chunks[prec], nerf_mlp_c_chunks(W, D, d->skip, true));
             if (!rc) rc = n->pipe_c.upload(sc);
+            if (rc) continue;
+            // the folded stream: the builder gives the layout and the maps (over zeros); the values are always filled on the device (below)
+            const long nfold = (long)(W / 2) * (W + ICV) + W / 2;
+            std::vector<float> ext((size_t)(total + nfold), 0.f);
+            StreamBuilderC sf(PIPE_CB);
+            build_c(sf, ext.data(), true);
+            n->fold_chunks = (int)(sf.bytes.size() / PIPE_CB);
+            if (n->fold_chunks != nerf_mlp_c_chunks(W, D, d->skip, false)) rc = fail(EVD_E_INVALID, "evd_nerf_create: folded f16c stream has %d chunks, kernel expects %d", n->fold_chunks, nerf_mlp_c_chunks(W, D, d->skip, false));
+            if (!rc) rc = n->pipe_cf.upload(sf);
+            if (!rc) rc = n->fold_arena.alloc(ext.size() * sizeof(float));
             continue;
         }
         StreamBuilder sb(prec);
@@ -280,6 +338,19 @@ int evd_nerf_create(const evd_nerf_desc* d, evd_nerf** out) {
     }
     rc = n->bias.upload(b.data(), b.size() * sizeof(float));
     if (!rc) rc = n->bias_src.upload(bsrc.data(), bsrc.size() * sizeof(int32_t));
+    if (!rc && n->pipe_cf.data.p) {      // folded f16c stream: its bias block (no feature tiles, bfold as the views bias), then the device fill
+        const long nw = (long)(W / 2) * (W + ICV);
+        std::vector<int32_t> fsrc(bsrc.begin(), bsrc.begin() + (D * T + 1) * 32);
+        for (int i = 0; i < (T / 2) * 32; ++i) fsrc.push_back((int32_t)(total + nw + i));
+        fsrc.insert(fsrc.end(), bsrc.end() - 32, bsrc.end());
+        rc = n->bias_f_src.upload(fsrc.data(), fsrc.size() * sizeof(int32_t));
+        if (!rc) rc = n->bias_f.alloc(fsrc.size() * sizeof(float));
+        DevBuf dev_params;
+        if (!rc) rc = dev_params.upload(arena.data(), arena.size() * sizeof(float));
+        if (!rc) rc = nerf_fold_pack(n, (const float*)dev_params.p, nullptr);
+        if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(EVD_E_HIP, "evd_nerf_create: the folded f16c stream could not be packed");
+        dev_params.release();
+    }
     if (rc) { evd_nerf_destroy(n); return rc; }
     *out = n;
     return EVD_OK;
@@ -297,6 +368,10 @@ void evd_nerf_destroy(evd_nerf* n) {
     n->bias.release();
     n->bias_src.release();
     n->pipe_c.release();
+    n->pipe_cf.release();
+    n->bias_f.release();
+    n->bias_f_src.release();
+    n->fold_arena.release();
     n->side.release();
     delete n;
 }
@@ -325,12 +400,12 @@ int evd_nerf_load_params(evd_nerf* net, const float* params, void* stream) {
     const long nb = (long)(net->bias.bytes / sizeof(float));
     hipLaunchKernelGGL(k_gather_f32, dim3((unsigned)cdiv(nb, 256L)), dim3(256), 0, st, params, (const int*)net->bias_src.p, nb, (float*)net->bias.p);
     EVD_LAUNCH_CHECK();
-    return EVD_OK;
+    return nerf_fold_pack(net, params, st);
 }
 
 size_t evd_nerf_stream_bytes(const evd_nerf* net, int precision) {
     if (!net || precision < 0 || precision >= EVD_NUM_PREC) return 0;
-    if (precision == EVD_PREC_F16C) return net->pipe_c.data.bytes;
+    if (precision == EVD_PREC_F16C) return net->pipe_cf.data.bytes;       // the stream the inference launch reads (the training forward: pipe_c)
     return net->pipe_chunks[precision] ? net->pipe[precision].data.bytes : net->stream[precision].data.bytes;
 }
 
@@ -354,9 +429,11 @@ int evd_nerf_mlp(const evd_nerf* net, int precision, const float* ray_batch, con
     if (precision == EVD_PREC_F16C) {
         EVD_REQUIRE(net->pipe_chunks[precision] > 0, "evd_nerf_mlp: EVD_PREC_F16C is built for netdepth 8, netwidth 256, skips [4], multires 10 / 4 only");
         EVD_REQUIRE(!feature, "evd_nerf_mlp: EVD_PREC_F16C has no feature-row variant (use EVD_PREC_F16X3)");
-        p.wstream = (const char*)net->pipe_c.data.p;
-        p.nchunks = net->pipe_chunks[precision];
-        p.wscale = (const unsigned*)net->pipe_c.scales.p;
+        p.wstream = (const char*)net->pipe_cf.data.p;       // feature_linear folded into the views layer
+        p.nchunks = net->fold_chunks;
+        p.wscale = (const unsigned*)net->pipe_cf.scales.p;
+        p.bias = (const float*)net->bias_f.p;
+        p.nbias = (int)(net->bias_f.bytes / sizeof(float));
         return nerf_mlp_c_dispatch(net->W, net->D, net->skip, p, as_stream(stream));
     }
     if (piped) return nerf_mlp_pipe_dispatch(precision, p, as_stream(stream));

@@ -5,7 +5,11 @@
 
 namespace evd {
 
-int nerf_mlp_c_chunks(int W, int D, int skip) { return nerf_c_built(W, D, skip) ? nerf_c_chunks<256, 8, 4>() : 0; }
+// chunks of the stream the inference kernel reads (feature_linear folded into the views layer) / train: of the training forward's
+int nerf_mlp_c_chunks(int W, int D, int skip, bool train) {
+    if (!nerf_c_built(W, D, skip)) return 0;
+    return train ? nerf_c_chunks<256, 8, 4, true>() : nerf_c_chunks<256, 8, 4, false>();
+}
 
 int nerf_mlp_c_dispatch(int W, int D, int skip, const MlpParams& p, hipStream_t st) {
     if (nerf_c_built(W, D, skip)) return launch_nerf_c<256, 8, 4>(p, st);

@@ -3,6 +3,8 @@
 // Machinery and arithmetic: mlp_pipe_c.h.  Built for the reference network (netdepth 8, netwidth 256, skips [4]); no feature rows.
 // TRAIN variant (round 4): + the activation store of the single-product float16 mode (nerf_mlp.h astore: float16 fragments in that
 // mode's arrangement, ReLU patterns as bit masks from the COMPENSATED pre-activations); the backward is that mode's.
+// Inference variant (FOLD): feature_linear has no activation and feeds views_linears.0 only, so the two are one linear layer on
+// cat([h, PE(dir)]) whose parameters depend on the weights alone (evd_api.hip k_fold_feature); the Feature layer is not run.
 #pragma once
 
 #include "mlp_pipe_c.h"
@@ -12,6 +14,7 @@ namespace evd {
 // static layer table: width W (T tiles, KB k-blocks), depth D, skip index SKIP
 template <int W, int D, int SKIP, bool TRAIN = false> struct NerfNetC {
     static constexpr int T = W / 32, KB = W / 64;
+    static constexpr bool FOLD = !TRAIN;                           // the training forward stores the feature for the backward: not folded
     static constexpr int slot(int s) { return TRAIN ? s : -1; }
     static constexpr int oslot(int l) { return slot(astore::H0 + 16 * l); }                       // hidden layer l's output ...
     static constexpr int pslot(int l) { return slot(astore::H0 + 16 * l + 4 * (KB - 1)); }        // ... its last (pending) block
@@ -34,14 +37,17 @@ template <int W, int D, int SKIP, bool TRAIN = false> struct NerfNetC {
         CLayer<KB + 1, 4, T, 2, true, false, chunk0(l), PARH, 2, true, KB, l == D - 1 ? 1 : 2, oslot(l), pslot(l - 1), mslot(l), mslot(l - 1), 4 * (KB - 1)>,
         CLayer<KB, 4, T, 2, true, false, chunk0(l), PARH, 2, true, KB - 1, l == D - 1 ? 1 : 2, oslot(l), pslot(l - 1), mslot(l), mslot(l - 1)>>;
     // heads (nerf.py:144-157): alpha_linear, feature_linear, views_linears.0 on cat([feature, PE(dir)]), rgb_linear
-    typedef CLayer<KB, 4, 1, 1, false, true, chunk0(D), PARH, 2, true, KB - 1, 2, -1, pslot(D - 1), -1, mslot(D - 1)> Alpha;
+    // FOLD: alpha_linear, the folded views layer on cat([h, PE(dir)]) (no pending group: Alpha is a float32 head), rgb_linear
+    typedef CLayer<KB, 4, 1, 1, false, true, chunk0(D), PARH, 2, true, KB - 1, 2, -1, pslot(D - 1), -1, mslot(D - 1)> Alpha;     // NEXT_G: Feature's group size, FOLD: Views'
     typedef CLayer<KB, 4, T, 2, false, false, Alpha::CHUNK0 + Alpha::NCHUNKS, Alpha::PAR_OUT, 0, false, 0, 2, slot(astore::F)> Feature;
-    typedef CLayer<KB + 1, 2, T / 2, 2, true, false, Feature::CHUNK0 + Feature::NCHUNKS, Feature::PAR_OUT, 2, false, KB - 1, 1, slot(astore::HV),
-                   slot(astore::F + 4 * (KB - 1)), slot(astore::M_HV)> Views;
+    typedef std::conditional_t<FOLD,
+        CLayer<KB + 1, 2, T / 2, 2, true, false, Alpha::CHUNK0 + Alpha::NCHUNKS, Alpha::PAR_OUT, 0, false, 0, 1>,
+        CLayer<KB + 1, 2, T / 2, 2, true, false, Feature::CHUNK0 + Feature::NCHUNKS, Feature::PAR_OUT, 2, false, KB - 1, 1, slot(astore::HV),
+               slot(astore::F + 4 * (KB - 1)), slot(astore::M_HV)>> Views;
     typedef CLayer<KB / 2, 4, 1, 1, false, true, Views::CHUNK0 + Views::NCHUNKS, Views::PAR_OUT, 2, true, KB / 2 - 1, 0, -1, slot(astore::HV + 4 * (KB / 2 - 1)), -1,
                    slot(astore::M_HV)> Rgb;
     static constexpr int NCH = Rgb::CHUNK0 + Rgb::NCHUNKS;
-    static constexpr int NTILES = D * T + 1 + T + T / 2 + 1;
+    static constexpr int NTILES = D * T + 1 + (FOLD ? 0 : T) + T / 2 + 1;
     static_assert(D >= 2 && NTILES * 32 <= CCfg::BIAS_WORDS / 2, "bias / row-scale block");
 };
 
@@ -168,14 +174,23 @@ __global__ __launch_bounds__(CCfg::NT, 1) void k_nerf_mlp_c(const MlpParams p) {
     lds_f32_p lb = lbias + D * T * 32;
     float araw[4], rraw[4];
     XBlk none[1];
-    c_layer<typename N::Alpha, typename N::Feature, ST, KB, 1, TRAIN>(cx.st, cx.pp, hact, none, araw, lb, lane, cx.act);
+    typedef std::conditional_t<N::FOLD, typename N::Views, typename N::Feature> AfterAlpha;
+    c_layer<typename N::Alpha, AfterAlpha, ST, KB, 1, TRAIN>(cx.st, cx.pp, hact, none, araw, lb, lane, cx.act);
     lb += 32;
-    XBlk vin[KB + 1];
-    c_layer<typename N::Feature, typename N::Views, ST, KB, KB + 1, TRAIN>(cx.st, cx.pp, hact, vin, nullptr, lb, lane, cx.act);
-    lb += T * 32;
-    vin[KB] = cx.pev;
     XBlk hbuf[KB / 2];
-    c_layer<typename N::Views, typename N::Rgb, ST, KB + 1, KB / 2, TRAIN>(cx.st, cx.pp, vin, hbuf, nullptr, lb, lane, cx.act);
+    if constexpr (N::FOLD) {
+        XBlk hv[KB + 1];                            // blocks [h_0 .. h_{KB-1} | pev]
+#pragma unroll
+        for (int j = 0; j < KB; ++j) hv[j] = hact[j];
+        hv[KB] = cx.pev;
+        c_layer<typename N::Views, typename N::Rgb, ST, KB + 1, KB / 2, TRAIN>(cx.st, cx.pp, hv, hbuf, nullptr, lb, lane, cx.act);
+    } else {
+        XBlk vin[KB + 1];
+        c_layer<typename N::Feature, typename N::Views, ST, KB, KB + 1, TRAIN>(cx.st, cx.pp, hact, vin, nullptr, lb, lane, cx.act);
+        lb += T * 32;
+        vin[KB] = cx.pev;
+        c_layer<typename N::Views, typename N::Rgb, ST, KB + 1, KB / 2, TRAIN>(cx.st, cx.pp, vin, hbuf, nullptr, lb, lane, cx.act);
+    }
     lb += (T / 2) * 32;
     c_layer<typename N::Rgb, void, ST, KB / 2, 1, TRAIN>(cx.st, cx.pp, hbuf, none, rraw, lb, lane, cx.act);
     const bool more = tile + gridDim.x < ntile;
@@ -190,7 +205,7 @@ __global__ __launch_bounds__(CCfg::NT, 1) void k_nerf_mlp_c(const MlpParams p) {
     }
 }
 
-template <int W, int D, int SKIP> constexpr int nerf_c_chunks() { return NerfNetC<W, D, SKIP>::NCH; }
+template <int W, int D, int SKIP, bool TRAIN = false> constexpr int nerf_c_chunks() { return NerfNetC<W, D, SKIP, TRAIN>::NCH; }
 
 template <int W, int D, int SKIP, bool TRAIN = false>
 static int launch_nerf_c(const MlpParams& p, hipStream_t st) {

@@ -19,6 +19,11 @@ struct evd_nerf {
     int pipe_chunks[EVD_NUM_PREC];
     evd::DevBuf bias, bias_src;
     evd::PackedStreamC pipe_c;               // EVD_PREC_F16C: float16 + fp6 fragment stream, row-scale words (32 per output tile in bias order), re-pack maps
+    // EVD_PREC_F16C inference: feature_linear folded into views_linears.0 (evd_api.hip k_fold_feature) -- its own stream, row scales and
+    // bias block; the re-pack maps index fold_arena = [device copy of the parameters | Wfold | bfold].  pipe_c / bias: the training forward.
+    evd::PackedStreamC pipe_cf;
+    evd::DevBuf bias_f, bias_f_src, fold_arena;
+    int fold_chunks = 0;
     Packed bwd[EVD_NUM_PREC][EVD_BWD_NSTREAMS];   // training (bf16 / f16, 8 x 256): W^T streams; HIDDEN1 + l - 1 = pts_linears[l]
     evd::DevBuf wmaps;                       // wgrad index maps (int32), nerf_train.h
     int nparam_blocks;                       // 2 D + 8 parameter tensors, canonical order (evd_api.hip: nerf_param_sizes)

@@ -182,7 +182,8 @@ void evd_nerf_destroy(evd_nerf* net);
 long evd_nerf_param_count(const evd_nerf* net);
 int evd_nerf_param_blocks(const evd_nerf* net, long* offsets, int capacity);
 int evd_nerf_load_params(evd_nerf* net, const float* params, void* stream);
-/* bytes of the packed weight stream for a precision (what one workgroup streams per sample tile) */
+/* bytes of the packed weight stream for a precision (what one workgroup streams per sample tile); EVD_PREC_F16C: the inference
+ * stream, in which feature_linear is folded into views_linears.0 (the training forward reads an unfolded stream of its own) */
 size_t evd_nerf_stream_bytes(const evd_nerf* net, int precision);
 
 /* NeRF.mlpforward + NeRF.eval, networks/nerf.py:46-72,131-162, fused with the point computation

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """CPU emulation of the MLP arithmetic modes on the 8x256 NeRF: where does the half-precision RGB error come from, and what does a
 low-precision (fp6 e2m3, block-scaled) correction product buy?  float64 torch is the reference.  Used to choose the `f16c` mode.
-    python tools/precision_anatomy.py [--scale 1.4] [--weights file.npz] [--rays 256]"""
+    python tools/precision_anatomy.py [--scale 1.4] [--weights file.npz] [--rays 256] [--fold]
+--fold: the row-scaled fp6 mode (the f16c kernels') once more with feature_linear folded into views_linears.0, as the f16c inference
+kernel runs it (folded in float64, the folded parameters rounded to float32), printed next to the unfolded line."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -12,6 +14,7 @@ ap.add_argument("--scale", type=float, default=1.0)
 ap.add_argument("--weights", default=None)
 ap.add_argument("--rays", type=int, default=256)
 ap.add_argument("--samples", type=int, default=128)
+ap.add_argument("--fold", action="store_true")
 a = ap.parse_args()
 torch.set_num_threads(8)
 F64 = torch.float64
@@ -68,7 +71,7 @@ def embed(x, L):
         out += [torch.sin(x * 2.0 ** i), torch.cos(x * 2.0 ** i)]
     return torch.cat(out, -1)
 
-def render(sd, rb, z, mode):
+def render(sd, rb, z, mode, fold=False):
     g = lambda k: torch.as_tensor(sd["mlp_coarse." + k], dtype=F64)
     R, S = z.shape
     pts = rb[:, None, 0:3] + rb[:, None, 3:6] * z[..., None]
@@ -80,8 +83,15 @@ def render(sd, rb, z, mode):
         if i == 4:
             x = torch.cat([pe, x], -1)
     alpha = mode.lin(g("alpha_linear.weight"), g("alpha_linear.bias"), x, 8)
-    feat = mode.lin(g("feature_linear.weight"), g("feature_linear.bias"), x, 9)
-    hv = torch.relu(mode.lin(g("views_linears.0.weight"), g("views_linears.0.bias"), torch.cat([feat, ve], -1), 10))
+    Wv, bv, Wf, bf = g("views_linears.0.weight"), g("views_linears.0.bias"), g("feature_linear.weight"), g("feature_linear.bias")
+    if fold:    # views(h, d) = relu([Wv[:, :256] Wf | Wv[:, 256:]] cat([h, PE(d)]) + Wv[:, :256] bf + bv): feature_linear has no activation
+        nf = Wf.shape[0]
+        Wfold = torch.cat([Wv[:, :nf] @ Wf, Wv[:, nf:]], -1).to(torch.float32).to(F64)
+        bfold = (Wv[:, :nf] @ bf + bv).to(torch.float32).to(F64)
+        hv = torch.relu(mode.lin(Wfold, bfold, torch.cat([x, ve], -1), 10))
+    else:
+        feat = mode.lin(Wf, bf, x, 9)
+        hv = torch.relu(mode.lin(Wv, bv, torch.cat([feat, ve], -1), 10))
     rgb = mode.lin(g("rgb_linear.weight"), g("rgb_linear.bias"), hv, 11)
     raw = torch.cat([rgb, alpha], -1).reshape(R, S, 4)
     dists = torch.cat([z[:, 1:] - z[:, :-1], torch.full((R, 1), 1e10, dtype=F64)], -1) * rb[:, None, 3:6].norm(dim=-1)
@@ -121,3 +131,6 @@ modes = [Mode("f16 (Wh Xh)"),
 for m in modes:
     rgb, raw = render(sd, rb, z, m)
     print(f"{m.name:34s} rgb Linf {float((rgb - ref).abs().max()):.3e}   raw Linf {float((raw - raw_ref).abs().max()):.3e}")
+    if a.fold and m.cw == "q" and m.cx == "q" and m.wblock == 0 and m.wgrid is E2M3:
+        rgb, raw = render(sd, rb, z, m, fold=True)
+        print(f"{'  ... feature_linear folded':34s} rgb Linf {float((rgb - ref).abs().max()):.3e}   raw Linf {float((raw - raw_ref).abs().max()):.3e}")
