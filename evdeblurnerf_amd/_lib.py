@@ -155,6 +155,8 @@ SIGNATURES = {
     "evd_points": (_I, [_vp, _I, _vp, _L, _I, _vp, _vp]),
     "evd_points_bwd": (_I, [_vp, _vp, _L, _I, _I, _vp, _vp]),
     "evd_sample_z": (_I, [C.POINTER(RenderCfg), _vp, _I, _L, _vp, _vp, _vp]),
+    "evd_sample_z_pts": (_I, [C.POINTER(RenderCfg), _vp, _I, _L, _vp, _vp, _vp, _vp]),
+    "evd_ray_batch_z": (_I, [C.POINTER(RenderCfg), _vp, _L, _vp, _vp, _vp, _vp]),
     "evd_nerf_create": (_I, [C.POINTER(NerfDesc), C.POINTER(_vp)]),
     "evd_nerf_destroy": (None, [_vp]),
     "evd_nerf_param_count": (_L, [_vp]),

@@ -459,7 +459,6 @@ size_t evd_nerf_render_workspace_bytes(const evd_render_cfg* cfg, long R) {
 }
 
 }  // extern "C"
-int evd_ray_batch_z(const evd_render_cfg* cfg, const float* rays, long R, const float* t_rand, float* ray_batch, float* z, void* stream);   // kernels_render.hip
 // where the first pass's z lives (an output the caller asked for, else the workspace slot): shared by the two entries below
 static float* render_z_slot(const evd_render_cfg* cfg, long R, const evd_render_out* out, void* workspace) {
     const int S = cfg->N_samples, Ni = cfg->N_importance > 0 ? cfg->N_importance : 0, St = S + Ni;

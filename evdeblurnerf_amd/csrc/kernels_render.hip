@@ -993,12 +993,12 @@ int evd_points_bwd(const float* z, const float* d_pts, long R, int S, int accumu
     return EVD_OK;
 }
 
-}  // extern "C"
-// internal (evd_api.hip, C++ linkage: not part of the ABI): ray packing + z stratification of evd_nerf_render in one launch
+// ray packing + z stratification of evd_nerf_render in one launch
 int evd_ray_batch_z(const evd_render_cfg* cfg, const float* rays, long R, const float* t_rand, float* ray_batch, float* z, void* stream) {
     EVD_REQUIRE(cfg && R >= 0 && ray_batch && z && cfg->N_samples > 0 && cfg->use_viewdirs, "evd_ray_batch_z: bad arguments");
     EVD_REQUIRE(!(cfg->perturb > 0.f) || t_rand, "evd_nerf_render: perturb > 0 needs the explicit t_rand draw");
     if (R == 0) return EVD_OK;
+    EVD_REQUIRE(rays, "evd_ray_batch_z: null rays");
     float cw, ch;
     ndc_coeffs(cfg->H, cfg->W, cfg->focal, &cw, &ch);
     k_ray_batch_z<<<cdiv(R * cfg->N_samples, 256), 256, 0, as_stream(stream)>>>(rays, R, cfg->ndc, cw, ch, cfg->near, cfg->far, cfg->N_samples, cfg->lindisp,
@@ -1006,10 +1006,13 @@ int evd_ray_batch_z(const evd_render_cfg* cfg, const float* rays, long R, const 
     EVD_LAUNCH_CHECK();
     return EVD_OK;
 }
-extern "C" {
 
 int evd_sample_z(const evd_render_cfg* cfg, const float* ray_batch, int ncol, long R, const float* t_rand, float* z, void* stream) {
     return evd::launch_sample_z_pts(cfg, ray_batch, ncol, R, t_rand, z, nullptr, as_stream(stream));
+}
+int evd_sample_z_pts(const evd_render_cfg* cfg, const float* ray_batch, int ncol, long R, const float* t_rand, float* z, float* pts, void* stream) {
+    EVD_REQUIRE(pts, "evd_sample_z_pts: null pts");
+    return evd::launch_sample_z_pts(cfg, ray_batch, ncol, R, t_rand, z, pts, as_stream(stream));
 }
 }  // extern "C"
 namespace evd {
@@ -1017,8 +1020,8 @@ namespace evd {
 int launch_sample_z_pts(const evd_render_cfg* cfg, const float* ray_batch, int ncol, long R, const float* t_rand, float* z, float* pts, hipStream_t stream) {
     EVD_REQUIRE(cfg && R >= 0 && z && cfg->N_samples > 0, "evd_sample_z: bad arguments");
     EVD_REQUIRE(!(cfg->perturb > 0.f) || t_rand, "evd_sample_z: perturb > 0 needs the explicit t_rand draw");
-    EVD_REQUIRE(!pts || ncol >= 6, "evd_sample_z: sample positions need the origin and direction columns");
     if (R == 0) return EVD_OK;
+    EVD_REQUIRE(ray_batch && ncol >= 8, "evd_sample_z: the packed rays (near / far at columns 6, 7) are missing");
     k_sample_z<<<cdiv(R * cfg->N_samples, 256), 256, 0, stream>>>(ray_batch, ncol, R, cfg->N_samples, cfg->lindisp, cfg->perturb > 0.f, t_rand, z, pts);
     EVD_LAUNCH_CHECK();
     return EVD_OK;

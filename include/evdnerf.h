@@ -153,6 +153,14 @@ int evd_points_bwd(const float* z, const float* d_pts, long R, int S, int accumu
  * (required when cfg->perturb > 0).  -> z dev [R,S] */
 int evd_sample_z(const evd_render_cfg* cfg, const float* ray_batch, int ncol, long R, const float* t_rand,
                  float* z, void* stream);
+/* The same, and the sample positions pts dev [R,S,3] = o + d z with the arithmetic of evd_points, in one launch (what evd_c2f_render_rays
+ * runs; ncol >= 6). */
+int evd_sample_z_pts(const evd_render_cfg* cfg, const float* ray_batch, int ncol, long R, const float* t_rand,
+                     float* z, float* pts, void* stream);
+/* evd_ray_batch + evd_sample_z in one launch (what evd_nerf_render runs; 11-column batch, near / far from cfg): rays dev [R,3,2] ->
+ * ray_batch dev [R,11], z dev [R,S].  Both outputs carry the bits the two entries give. */
+int evd_ray_batch_z(const evd_render_cfg* cfg, const float* rays, long R, const float* t_rand, float* ray_batch, float* z,
+                    void* stream);
 
 /* ---------------------------------------------------------------- NeRF backbone (networks/nerf.py) */
 typedef struct evd_nerf evd_nerf;   /* opaque: packed MFMA-fragment weight streams on one device */
