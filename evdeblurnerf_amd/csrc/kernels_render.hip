@@ -925,6 +925,7 @@ int evd_get_rays(int H, int W, const float* K, const float* c2w, int add_halfpix
 int evd_get_rays_pix(const float* coords, const float* K, const float* c2ws, long n, int add_halfpix, float* rays_o, float* rays_d, void* stream) {
     EVD_REQUIRE(n >= 0 && K && rays_o && rays_d, "evd_get_rays_pix: bad arguments");
     if (n == 0) return EVD_OK;
+    EVD_REQUIRE(coords && c2ws, "evd_get_rays_pix: null coords or c2ws");
     k_get_rays_pix<<<cdiv(n, 256), 256, 0, as_stream(stream)>>>(coords, K[0], K[2], K[4], K[5], add_halfpix ? 0.5f : 0.f, c2ws, n, rays_o, rays_d);
     EVD_LAUNCH_CHECK();
     return EVD_OK;
@@ -940,6 +941,7 @@ int evd_ndc_rays(int H, int W, float focal, float near, const float* rays_o, con
                  float* out_o, float* out_d, void* stream) {
     EVD_REQUIRE(n >= 0 && out_o && out_d, "evd_ndc_rays: bad arguments");
     if (n == 0) return EVD_OK;
+    EVD_REQUIRE(rays_o && rays_d, "evd_ndc_rays: null rays_o or rays_d");
     float cw, ch;
     ndc_coeffs(H, W, focal, &cw, &ch);
     k_ndc<<<cdiv(n, 256), 256, 0, as_stream(stream)>>>(cw, ch, near, (float)(2.0 * (double)near), rays_o, rays_d, n, out_o, out_d);
@@ -950,6 +952,7 @@ int evd_ndc_rays(int H, int W, float focal, float near, const float* rays_o, con
 int evd_embed(const float* x, long n, int dim, int L, float* out, void* stream) {
     EVD_REQUIRE(n >= 0 && dim > 0 && L >= 0 && out, "evd_embed: bad arguments");
     if (n == 0) return EVD_OK;
+    EVD_REQUIRE(x, "evd_embed: null x");
     k_embed<<<cdiv(n * dim, 256), 256, 0, as_stream(stream)>>>(x, n, dim, L, out);
     EVD_LAUNCH_CHECK();
     return EVD_OK;
@@ -968,6 +971,7 @@ int evd_rbk_warp(const float* rays, const float* r, const float* v, long R, int 
 int evd_ray_batch(const evd_render_cfg* cfg, const float* rays, long R, float* ray_batch, void* stream) {
     EVD_REQUIRE(cfg && R >= 0 && ray_batch, "evd_ray_batch: bad arguments");
     if (R == 0) return EVD_OK;
+    EVD_REQUIRE(rays, "evd_ray_batch: null rays");
     float cw, ch;
     ndc_coeffs(cfg->H, cfg->W, cfg->focal, &cw, &ch);
     k_ray_batch<<<cdiv(R, 256), 256, 0, as_stream(stream)>>>(rays, R, cfg->ndc, cfg->use_viewdirs, cw, ch, cfg->near, cfg->far, ray_batch);

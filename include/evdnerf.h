@@ -75,10 +75,11 @@ int evd_device_count(void);
  * (:8-9; HALF_PIX = 0.5 added to the pixel index when non-zero). */
 int evd_get_rays(int H, int W, const float* K, const float* c2w, int add_halfpix, float* rays_o, float* rays_d, void* stream);
 /* get_rays_pix, utils/rays.py:25-36.  coords dev [n,2], c2ws dev [n,3,4], K host[9].  add_halfpix 0: the coordinates are already
- * sub-pixel positions (rectified event coordinates, data/loader_events.py:290-293 passes integer_coords). */
+ * sub-pixel positions (rectified event coordinates, data/loader_events.py:290-293 passes integer_coords).  n == 0 is a no-op; with
+ * n > 0 a NULL coords or c2ws is refused (-1). */
 int evd_get_rays_pix(const float* coords, const float* K, const float* c2ws, long n, int add_halfpix,
                      float* rays_o, float* rays_d, void* stream);
-/* get_ndc_rays, utils/rays.py:104-145 */
+/* get_ndc_rays, utils/rays.py:104-145.  n == 0 is a no-op; with n > 0 a NULL rays_o or rays_d is refused (-1). */
 int evd_ndc_rays(int H, int W, float focal, float near, const float* rays_o, const float* rays_d, long n,
                  float* out_o, float* out_d, void* stream);
 /* RigidBlurringModel.rbk_warp, networks/dpnerf/blurmodel.py:51-82 (SE3Field / RigidBody of utils/rigid_warping.py): the
@@ -123,7 +124,8 @@ int evd_rigid_blur_backward(const evd_rigid_blur_desc* d, const evd_rigid_blur_p
  * n_keys <= 16 -> flags dev [n_keys] (unsigned): bit 0 = the key contains a NaN, bit 1 = an Inf.  Nothing synchronises; the caller
  * reads the words when (if) it wants the answer. */
 int evd_numerics_flags(const float* const* ptrs, const long* counts, int n_keys, unsigned* flags, void* stream);
-/* Embedder.forward, networks/embedding.py:88-98.  x dev [n,dim] -> out dev [n, dim*(1+2L)] */
+/* Embedder.forward, networks/embedding.py:88-98.  x dev [n,dim] -> out dev [n, dim*(1+2L)].  n == 0 is a no-op; with n > 0 a NULL x is
+ * refused (-1). */
 int evd_embed(const float* x, long n, int dim, int L, float* out, void* stream);
 
 /* ---------------------------------------------------------------- render configuration
@@ -138,7 +140,8 @@ typedef struct {
 } evd_render_cfg;
 
 /* NeRFAll.render ray packing, networks/renderer.py:423-446: rays dev [R,3,2] -> ray_batch dev [R,11]
- * = o(3) d(3) near far viewdir(3); viewdir = d/|d| before the NDC warp.  (8 columns when !use_viewdirs) */
+ * = o(3) d(3) near far viewdir(3); viewdir = d/|d| before the NDC warp.  (8 columns when !use_viewdirs)  R == 0 is a no-op; with
+ * R > 0 a NULL rays is refused (-1). */
 int evd_ray_batch(const evd_render_cfg* cfg, const float* rays, long R, float* ray_batch, void* stream);
 /* Backward of evd_ray_batch (the training branch of NeRFAll.forward, renderer.py:303-308: the loss reaches the blur kernel's warped
  * rays through the packing, viewdirs normalisation :431 and the NDC warp utils/rays.py:104-145; the reference gets it from autograd):
