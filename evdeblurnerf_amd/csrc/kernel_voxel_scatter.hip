@@ -1,7 +1,7 @@
 // The line taps of the tri-plane scatter, and the hybrid scatter that evd_voxel_sample_bwd_ws / _prec run (reference: the backward of
 // F.grid_sample in VoxelNeRFBase.compute_appfeature, networks/pdrf/voxnerf.py:132-151, under run_nerf.py:593-601).
 //
-// The direct kernel (kernel_voxel.hip k_voxel_sample_bwd<false>) issues 576 float atomics per sample; they run at the L2's rate of one
+// The direct kernel (kernel_voxel_sample_bwd.hip k_voxel_sample_bwd<false>) issues 576 float atomics per sample; they run at the L2's rate of one
 // dword per clock and channel (~250 G adds/s).  In the hybrid form the plane taps stay direct float atomics (k_voxel_sample_bwd_w, or
 // k_voxel_sample_bwd<true> for the shapes the wavefront-autonomous kernel is not built for); the line taps -- a third of the requests, onto
 // <= 586 cells -- are left as one row of per-channel contributions per sample plus the tap records, and k_scatter_lines adds them through

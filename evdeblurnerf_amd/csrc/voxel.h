@@ -1,4 +1,4 @@
-// Shared between kernel_voxel.hip (kernels + launchers) and evd_voxel_api.hip (C ABI).
+// Shared between the tri-plane level's kernel units (kernel_voxel*.hip: kernels + launchers) and evd_voxel_api.hip (C ABI).
 #pragma once
 
 #include "evd_common.h"
@@ -38,7 +38,7 @@ struct VoxMlpParams {
 struct LTap { int c0, c1; float w0, w1; };                          // the 2 taps of one line
 bool voxel_scatter_hybrid_ok(const GridParams& g, long n);
 size_t voxel_scatter_hybrid_workspace_bytes(const GridParams& g, long n);
-// half_grids: the re-gather of the grid values reads the float16 copies (the forward of the half-precision modes did: kernel_voxel.hip HALF)
+// half_grids: the re-gather of the grid values reads the float16 copies (the forward of the half-precision modes did: kernel_voxel_sample_bwd.hip HALF)
 int launch_voxel_sample_bwd_hybrid(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
                                    float* d_pts, void* workspace, size_t workspace_bytes, hipStream_t st, bool half_grids = false);
 int launch_voxel_sample_bwd_planes(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,

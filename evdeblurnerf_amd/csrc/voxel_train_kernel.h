@@ -3,7 +3,7 @@
 //
 //   raw = (sigma, sigmoid(colour)):  d colour_pre = d raw_c . s (1 - s) is folded into the gradient fragments
 //   C2^T -> d c1 . [c1 > 0];  C1^T -> d c0 . [c0 > 0];  C0^T (geo rows) -> d geo;  [Geo^T | Sigma^T] -> d hid . [hid > 0];
-//   L0^T (feature rows) -> d fts, written out as float32 rows for the tri-plane scatter (kernel_voxel.hip k_voxel_sample_bwd)
+//   L0^T (feature rows) -> d fts, written out as float32 rows for the tri-plane scatter (kernel_voxel_sample_bwd.hip k_voxel_sample_bwd)
 #pragma once
 
 #include "nerf_train_kernel.h"

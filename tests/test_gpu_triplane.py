@@ -44,7 +44,7 @@ def fwd_kernel(shape, half):
     ct = sum(nc)
     if all(c % 8 == 0 for c in nc):
         if half and ct % 32 == 0 and ct <= 96:
-            return "k_voxel_sample_m<true,3>"
+            return "k_voxel_sample_m"
         return "k_voxel_sample_w<true,4>" if half else "k_voxel_sample_w<false,3>"
     return f"k_voxel_sample<{'true' if half else 'false'},4>"
 
