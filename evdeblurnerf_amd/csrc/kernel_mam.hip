@@ -14,6 +14,7 @@
 //
 // HBM-bound: the forward reads h_local twice (logits, then sums: the softmax needs every logit of the ray first; a ray's 64 P S floats
 // -- 320 KiB at P = 10, S = 128 -- do not fit the LDS), the backward reads it once and writes d h_local once.
+#include "awp_integrate.h"
 #include "evd_common.h"
 #include "wave_ops.h"
 
@@ -21,14 +22,6 @@ namespace evd {
 
 constexpr int MAM_C = 64, MAM_MAXP = 16, MAM_MAXS = 512;
 
-// sum over the 16 lanes of a DPP row, left in every lane of the row
-__device__ __forceinline__ float row_sum16(float v) {
-    v += dpp_f32<0xb1>(0.f, v);
-    v += dpp_f32<0x4e>(0.f, v);
-    v += dpp_f32<0x141>(0.f, v);
-    v += dpp_f32<0x140>(0.f, v);
-    return v;
-}
 __device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 __device__ __forceinline__ void fma4(float4& acc, float s, float4 v) {
     acc.x = fmaf(s, v.x, acc.x); acc.y = fmaf(s, v.y, acc.y); acc.z = fmaf(s, v.z, acc.z); acc.w = fmaf(s, v.w, acc.w);
@@ -55,7 +48,7 @@ __global__ __launch_bounds__(256) void k_mam_local_fwd(const float* __restrict__
 #pragma unroll
         for (int p = 0; p < MAM_MAXP; ++p)
             if (p < P) {
-                const float d = row_sum16(dot4(h4[((long)p * S + s) * 16 + l], u4));
+                const float d = row_sum_dpp(dot4(h4[((long)p * S + s) * 16 + l], u4));
                 if (l == 0) A[p * S + s] = d;
             }
     }
@@ -144,7 +137,7 @@ __global__ __launch_bounds__(256) void k_mam_local_fwd_r(const float* __restrict
     for (int j = 0; j < NSR; ++j)
 #pragma unroll
         for (int p = 0; p < PR; ++p) {
-            const float d = row_sum16(dot4(hr[p][j], u4));
+            const float d = row_sum_dpp(dot4(hr[p][j], u4));
             if (l == 0 && p < P && g + 16 * j < S) A[p * S + g + 16 * j] = d;
         }
     __syncthreads();
@@ -206,6 +199,74 @@ __global__ __launch_bounds__(256) void k_mam_local_fwd_r(const float* __restrict
 // Backward.  With gA[p,s] = d_inter[p] . h[p,s], gB[p,s] = d_intra[s] . h[p,s] the two softmax backwards need sum_s alpha gA = d_inter[p] .
 // h_inter[p] and sum_p beta gB = d_intra[s] . h_intra[s]: dots of the SAVED outputs, so h_local is read once:
 //      d logit = alpha (gA - cP[p]) + beta (gB - cI[s]);   d h = alpha d_inter[p] + beta d_intra[s] + d logit u;   d u = sum d logit h
+// The pieces below are shared by k_mam_local_bwd and the fused k_local_consumers_bwd.
+struct MamBwdLds {
+    float *dP, *cP, *red;                   // [MAXP][64] d_inter of the ray, [MAXP] d_inter[p] . h_inter[p], [4][64] reduction scratch
+    float* end;                             // first float past the three
+    __device__ explicit MamBwdLds(float* lds) : dP(lds), cP(dP + MAM_MAXP * MAM_C), red(cP + MAM_MAXP), end(red + 4 * MAM_C) {}
+};
+constexpr int MAM_BWD_LDS_FLOATS = MAM_MAXP * MAM_C + MAM_MAXP + 4 * MAM_C;
+
+// dP <- d_inter of ray b (a barrier has to follow), then cP[p] <- d_inter[p] . h_inter[p] (ends behind a barrier)
+__device__ __forceinline__ void mam_bwd_stage_dP(const MamBwdLds& m, const float* d_inter, long b, int P) {
+    for (int i = threadIdx.x; i < P * MAM_C; i += 256) m.dP[i] = d_inter[b * P * MAM_C + i];
+}
+__device__ __forceinline__ void mam_bwd_cP(const MamBwdLds& m, const float* h_inter, long b, int P) {
+    const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
+    for (int p = g; p < P; p += 16) {
+        const float c = row_sum_dpp(dot4(reinterpret_cast<const float4*>(m.dP)[p * 16 + l],
+                                         reinterpret_cast<const float4*>(h_inter)[(b * P + p) * 16 + l]));
+        if (l == 0) m.cP[p] = c;
+    }
+    __syncthreads();
+}
+// d_intra[s] of the lane's four channels and cI[s] = d_intra[s] . h_intra[s]
+__device__ __forceinline__ float4 mam_bwd_sample(const float* d_intra, const float* h_intra, long b, int S, int s, float& cI) {
+    const int l = threadIdx.x & 15;
+    const float4 dI = reinterpret_cast<const float4*>(d_intra)[(b * S + s) * 16 + l];
+    cI = row_sum_dpp(dot4(dI, reinterpret_cast<const float4*>(h_intra)[(b * S + s) * 16 + l]));
+    return dI;
+}
+// the MAM's share of d h[p,s] (the lane's four channels) and d logit[p,s] (the caller adds d logit h to its d u)
+__device__ __forceinline__ float4 mam_bwd_row(float4 v, float4 dp, float4 dI, float4 u4, float al, float be, float cP, float cI, float& da) {
+    const float gA = row_sum_dpp(dot4(dp, v)), gB = row_sum_dpp(dot4(dI, v));
+    da = al * (gA - cP) + be * (gB - cI);
+    float4 o;
+    o.x = al * dp.x + be * dI.x + da * u4.x;
+    o.y = al * dp.y + be * dI.y + da * u4.y;
+    o.z = al * dp.z + be * dI.z + da * u4.z;
+    o.w = al * dp.w + be * dI.w + da * u4.w;
+    return o;
+}
+// running max |d h_local|; fmaxf drops a NaN (or inf - inf): record it as +inf like the scatter's maximum does, not a finite scale word
+__device__ __forceinline__ float mam_absmax_row(float amax, float4 o) {
+    amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+    const float nan_probe = (o.x + o.y) + (o.z + o.w);
+    return nan_probe != nan_probe ? __builtin_huge_valf() : amax;
+}
+// d_u_partial[b] <- the workgroup's du: the wavefront's four groups by lane exchange, the four wavefronts through LDS (one barrier inside)
+__device__ __forceinline__ void mam_bwd_fold_du(const MamBwdLds& m, float4 du, float* d_u_partial, long b) {
+    const int tid = threadIdx.x, l = tid & 15, wave = tid >> 6, lane = tid & 63;
+    du.x += __shfl_xor(du.x, 16); du.y += __shfl_xor(du.y, 16); du.z += __shfl_xor(du.z, 16); du.w += __shfl_xor(du.w, 16);
+    du.x += __shfl_xor(du.x, 32); du.y += __shfl_xor(du.y, 32); du.z += __shfl_xor(du.z, 32); du.w += __shfl_xor(du.w, 32);
+    if (lane < 16) reinterpret_cast<float4*>(m.red)[wave * 16 + l] = du;
+    __syncthreads();
+    if (tid < MAM_C) d_u_partial[b * MAM_C + tid] = m.red[tid] + m.red[MAM_C + tid] + m.red[2 * MAM_C + tid] + m.red[3 * MAM_C + tid];
+}
+// max |d h_local| of this ray -> the caller's word (guarded: one atomic per raising workgroup, not per ray)
+__device__ __forceinline__ void mam_bwd_fold_absmax(const MamBwdLds& m, float amax, unsigned* absmax) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    if (!absmax) return;
+    for (int o = 32; o; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+    __syncthreads();
+    if (lane == 0) m.red[wave] = amax;
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned mb = __float_as_uint(fmaxf(fmaxf(m.red[0], m.red[1]), fmaxf(m.red[2], m.red[3])));
+        if (mb > *reinterpret_cast<volatile unsigned*>(absmax)) atomicMax(absmax, mb);
+    }
+}
+
 template <bool ACC>
 __global__ __launch_bounds__(256) void k_mam_local_bwd(const float* __restrict__ h, const float* __restrict__ u,
                                                        const float* __restrict__ alpha, const float* __restrict__ beta,
@@ -213,77 +274,50 @@ __global__ __launch_bounds__(256) void k_mam_local_bwd(const float* __restrict__
                                                        const float* __restrict__ d_inter, const float* __restrict__ d_intra, int P, int S,
                                                        float* __restrict__ d_h, float* __restrict__ d_u_partial, unsigned* __restrict__ absmax) {
     extern __shared__ float lds[];
-    float* dP = lds;                        // [P][64]
-    float* cP = dP + MAM_MAXP * MAM_C;      // [P]
-    float* red = cP + MAM_MAXP;             // [4][64]
+    const MamBwdLds m(lds);
     const long b = blockIdx.x;
-    const int tid = threadIdx.x, g = tid >> 4, l = tid & 15, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x, g = tid >> 4, l = tid & 15;
     const float4* h4 = reinterpret_cast<const float4*>(h) + b * (long)P * S * 16;
     float4* dh4 = reinterpret_cast<float4*>(d_h) + b * (long)P * S * 16;
     const float4 u4 = reinterpret_cast<const float4*>(u)[l];
-    for (int i = tid; i < P * MAM_C; i += 256) dP[i] = d_inter[b * P * MAM_C + i];
+    mam_bwd_stage_dP(m, d_inter, b, P);
     __syncthreads();
-    for (int p = g; p < P; p += 16) {
-        const float c = row_sum16(dot4(reinterpret_cast<const float4*>(dP)[p * 16 + l],
-                                       reinterpret_cast<const float4*>(h_inter)[(b * P + p) * 16 + l]));
-        if (l == 0) cP[p] = c;
-    }
-    __syncthreads();
+    mam_bwd_cP(m, h_inter, b, P);
     float4 du = make_float4(0.f, 0.f, 0.f, 0.f);
     float amax = 0.f;
     for (int s = g; s < S; s += 16) {
-        const float4 dI = reinterpret_cast<const float4*>(d_intra)[(b * S + s) * 16 + l];
-        const float cI = row_sum16(dot4(dI, reinterpret_cast<const float4*>(h_intra)[(b * S + s) * 16 + l]));
+        float cI;
+        const float4 dI = mam_bwd_sample(d_intra, h_intra, b, S, s, cI);
 #pragma unroll
         for (int p = 0; p < MAM_MAXP; ++p)
             if (p < P) {
                 const long at = ((long)p * S + s) * 16 + l;
+                const float4 dp = reinterpret_cast<const float4*>(m.dP)[p * 16 + l];
                 const float4 v = h4[at];
-                const float4 dp = reinterpret_cast<const float4*>(dP)[p * 16 + l];
-                const float al = alpha[(b * P + p) * S + s], be = beta[(b * P + p) * S + s];
-                const float gA = row_sum16(dot4(dp, v)), gB = row_sum16(dot4(dI, v));
-                const float da = al * (gA - cP[p]) + be * (gB - cI);
-                float4 o;
-                o.x = al * dp.x + be * dI.x + da * u4.x;
-                o.y = al * dp.y + be * dI.y + da * u4.y;
-                o.z = al * dp.z + be * dI.z + da * u4.z;
-                o.w = al * dp.w + be * dI.w + da * u4.w;
+                float da;
+                float4 o = mam_bwd_row(v, dp, dI, u4, alpha[(b * P + p) * S + s], beta[(b * P + p) * S + s], m.cP[p], cI, da);
                 if (ACC) {                   // d h_local already holds another consumer's share (the feature integration's): add to it here
                     const float4 prev = dh4[at];  // instead of in a separate pass over 2 x 335 MB
                     o.x += prev.x; o.y += prev.y; o.z += prev.z; o.w += prev.w;
                 }
                 dh4[at] = o;
-                amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-                const float nan_probe = (o.x + o.y) + (o.z + o.w);      // fmaxf drops a NaN: record it as +inf like the scatter's maximum does
-                amax = nan_probe != nan_probe ? __builtin_huge_valf() : amax;
+                amax = mam_absmax_row(amax, o);
                 fma4(du, da, v);
             }
     }
-    du.x += __shfl_xor(du.x, 16); du.y += __shfl_xor(du.y, 16); du.z += __shfl_xor(du.z, 16); du.w += __shfl_xor(du.w, 16);
-    du.x += __shfl_xor(du.x, 32); du.y += __shfl_xor(du.y, 32); du.z += __shfl_xor(du.z, 32); du.w += __shfl_xor(du.w, 32);
-    if (lane < 16) reinterpret_cast<float4*>(red)[wave * 16 + l] = du;
-    __syncthreads();
-    if (tid < MAM_C) d_u_partial[b * MAM_C + tid] = red[tid] + red[MAM_C + tid] + red[2 * MAM_C + tid] + red[3 * MAM_C + tid];
-    if (absmax) {                        // max |d h_local| of this ray -> the caller's word (guarded: one atomic per raising workgroup, not per ray)
-        for (int o = 32; o; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-        __syncthreads();
-        if (lane == 0) red[wave] = amax;
-        __syncthreads();
-        if (tid == 0) {
-            const unsigned mb = __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
-            if (mb > *reinterpret_cast<volatile unsigned*>(absmax)) atomicMax(absmax, mb);
-        }
-    }
+    mam_bwd_fold_du(m, du, d_u_partial, b);
+    mam_bwd_fold_absmax(m, amax, absmax);
 }
 
 // ---- h_local's two consumers in ONE backward pass ----------------------------------------------------------------------------------------
-// k_awp_integrate_bwd_c64 (kernels_loss.hip) and k_mam_local_bwd above both read h_local [R P, S, 64] and produce a d h_local of that
-// size; as two launches the second reads the first one's result back and adds to it (1.67 GB of traffic at the blurfactory shape).  Here
+// k_awp_integrate_bwd_c64 (kernel_awp_integrate.hip) and k_mam_local_bwd above both read h_local [R P, S, 64] and produce a d h_local of
+// that size; as two launches the second reads the first one's result back and adds to it (1.67 GB of traffic at the blurfactory shape).  Here
 // the MAM backward's 16-lane group that owns row (p, s) also evaluates the integration's gradient of that row -- its formulas need rows
 // s - 1 and s + 1 of the same sub-exposure, which the neighbouring groups of the workgroup load anyway (cache hits) -- and writes the sum:
 // h_local is fetched from HBM once, d h_local written once.  The integration's d z_vals / d rays_d need per-ray sums of d dist: the rows'
-// values go through LDS ([P][S]) and are folded after the tile loop.  Same arithmetic as the two kernels (awp.py:58-75 as written:
-// Q[s] is the cumulative product over the CHANNELS of row s - 1's 1 - alpha + 1e-10).
+// values go through LDS ([P][S]) and are folded after the tile loop.  The two shares are the two kernels' own functions (mam_bwd_row above,
+// awp_bwd_row of awp_integrate.h), added in the order of the two-launch path; only Q is obtained differently: a group does not walk the
+// samples in order, so it rebuilds row s's Q from row s - 1's exponentials instead of carrying it.
 struct LocalBwdParams {
     const float *h, *u, *alpha, *beta, *h_inter, *h_intra, *d_inter, *d_intra;     // the MAM part (k_mam_local_bwd)
     const float *z, *rays_d, *d_int;                                                 // the integration part: z [R P, S], rays_d [R P, 3], d out [R P, 64]
@@ -291,26 +325,12 @@ struct LocalBwdParams {
     float *d_h, *d_u_partial, *d_z, *d_rays_d;                                       // d_z, d_rays_d: may be null
     unsigned* absmax;
 };
-__device__ __forceinline__ float lc_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-template <int CTRL> __device__ __forceinline__ float lc_dpp(float old, float src) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, src), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float lc_scan_mul(float v) {          // inclusive product over the lanes <= this one of the 16-lane row
-    v *= lc_dpp<0x111>(1.f, v); v *= lc_dpp<0x112>(1.f, v); v *= lc_dpp<0x114>(1.f, v); v *= lc_dpp<0x118>(1.f, v);
-    return v;
-}
-__device__ __forceinline__ float lc_scan_add_right(float v) {    // inclusive sum over the lanes >= this one
-    v += lc_dpp<0x101>(0.f, v); v += lc_dpp<0x102>(0.f, v); v += lc_dpp<0x104>(0.f, v); v += lc_dpp<0x108>(0.f, v);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void k_local_consumers_bwd(const LocalBwdParams q) {
     extern __shared__ float lds[];
     const int P = q.P, S = q.S;
-    float* dP = lds;                        // [MAXP][64]
-    float* cP = dP + MAM_MAXP * MAM_C;      // [MAXP]
-    float* red = cP + MAM_MAXP;             // [4][64]
-    float* nrm = red + 4 * MAM_C;           // [MAXP] |rays_d| of the sub-exposures
+    const MamBwdLds m(lds);
+    float* nrm = m.end;                     // [MAXP] |rays_d| of the sub-exposures
     float* zl = nrm + MAM_MAXP;             // [P][S] z_vals of the ray's sub-exposures
     float* dd = zl + P * S;                 // [P][S] d dist of every row
     const long b = blockIdx.x;
@@ -318,24 +338,16 @@ __global__ __launch_bounds__(256) void k_local_consumers_bwd(const LocalBwdParam
     const float4* h4 = reinterpret_cast<const float4*>(q.h) + b * (long)P * S * 16;
     float4* dh4 = reinterpret_cast<float4*>(q.d_h) + b * (long)P * S * 16;
     const float4 u4 = reinterpret_cast<const float4*>(q.u)[l];
-    for (int i = tid; i < P * MAM_C; i += 256) dP[i] = q.d_inter[b * P * MAM_C + i];
+    mam_bwd_stage_dP(m, q.d_inter, b, P);
     for (int i = tid; i < P * S; i += 256) zl[i] = q.z[b * P * S + i];
-    if (tid < P) {
-        const float* d = q.rays_d + (b * P + tid) * 3;
-        nrm[tid] = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d[0], d[0]), __fmul_rn(d[1], d[1])), __fmul_rn(d[2], d[2])));
-    }
+    if (tid < P) nrm[tid] = awp_ray_norm(q.rays_d + (b * P + tid) * 3);
     __syncthreads();
-    for (int p = g; p < P; p += 16) {
-        const float c = row_sum16(dot4(reinterpret_cast<const float4*>(dP)[p * 16 + l],
-                                       reinterpret_cast<const float4*>(q.h_inter)[(b * P + p) * 16 + l]));
-        if (l == 0) cP[p] = c;
-    }
-    __syncthreads();
+    mam_bwd_cP(m, q.h_inter, b, P);
     float4 du = make_float4(0.f, 0.f, 0.f, 0.f);
     float amax = 0.f;
     for (int s = g; s < S; s += 16) {
-        const float4 dI = reinterpret_cast<const float4*>(q.d_intra)[(b * S + s) * 16 + l];
-        const float cI = row_sum16(dot4(dI, reinterpret_cast<const float4*>(q.h_intra)[(b * S + s) * 16 + l]));
+        float cI;
+        const float4 dI = mam_bwd_sample(q.d_intra, q.h_intra, b, S, s, cI);
         const bool last = s == S - 1;
 #pragma unroll 2
         for (int p = 0; p < P; ++p) {
@@ -343,64 +355,56 @@ __global__ __launch_bounds__(256) void k_local_consumers_bwd(const LocalBwdParam
             const float4 v = h4[at];
             const float4 vm = h4[s > 0 ? at - 16 : at], vn = h4[last ? at : at + 16];
             const float4 gi = reinterpret_cast<const float4*>(q.d_int)[(b * P + p) * 16 + l];
-            const float4 dp = reinterpret_cast<const float4*>(dP)[p * 16 + l];
-            const float al = q.alpha[(b * P + p) * S + s], be = q.beta[(b * P + p) * S + s];
-            // ---- the MAM's share (k_mam_local_bwd)
-            const float gA = row_sum16(dot4(dp, v)), gB = row_sum16(dot4(dI, v));
-            const float da = al * (gA - cP[p]) + be * (gB - cI);
-            float o[4] = {al * dp.x + be * dI.x + da * u4.x, al * dp.y + be * dI.y + da * u4.y, al * dp.z + be * dI.z + da * u4.z,
-                          al * dp.w + be * dI.w + da * u4.w};
+            const float4 dp = reinterpret_cast<const float4*>(m.dP)[p * 16 + l];
+            float da;
+            const float4 om4 = mam_bwd_row(v, dp, dI, u4, q.alpha[(b * P + p) * S + s], q.beta[(b * P + p) * S + s], m.cP[p], cI, da);
+            float o[4] = {om4.x, om4.y, om4.z, om4.w};
             fma4(du, da, v);
-            // ---- the integration's share (k_awp_integrate_bwd_c64, row s of sub-exposure p)
+            // ---- the integration's share (row s of sub-exposure p)
             const float* zz = zl + p * S;
             const float norm = nrm[p];
-            const float dz = last ? 0.f : __fsub_rn(zz[s + 1], zz[s]);
-            const float dist = __fmul_rn(dz, norm);
-            const float dist_m = s > 0 ? __fmul_rn(__fsub_rn(zz[s], zz[s - 1]), norm) : 0.f;
-            const float dist_n = s + 2 < S ? __fmul_rn(__fsub_rn(zz[s + 2], zz[s + 1]), norm) : 0.f;
+            const float dist = __fmul_rn(awp_dz(zz, s, last), norm), dist_m = s > 0 ? awp_dist(zz, s - 1, S, norm) : 0.f;
+            const float dist_n = awp_dist(zz, s + 1, S, norm);
             const float fc[4] = {v.x, v.y, v.z, v.w}, fm[4] = {vm.x, vm.y, vm.z, vm.w}, fn[4] = {vn.x, vn.y, vn.z, vn.w}, gg[4] = {gi.x, gi.y, gi.z, gi.w};
+            // awp_bwd_row's steps, written out: wrapped in a function of array arguments hipcc allocates 88 - 96 registers for this loop instead
+            // of 79 (one occupancy step); the formulas themselves are awp_integrate.h's
             float Q[4], e[4], om[4], Qn[4], G[4], lsum = 0.f, localm = 1.f, local = 1.f;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                Q[k] = s > 0 ? __fadd_rn(lc_exp(-__fmul_rn(fm[k], dist_m)), 1e-10f) : 1.f;      // om of row s - 1 (never the last row)
+                Q[k] = s > 0 ? awp_om(awp_e(fm[k], dist_m)) : 1.f;       // om of row s - 1 (never the last row)
                 localm *= Q[k];
-                e[k] = last ? 1.f : lc_exp(-__fmul_rn(fc[k], dist));
-                om[k] = __fadd_rn(e[k], 1e-10f);
+                e[k] = last ? 1.f : awp_e(fc[k], dist);
+                om[k] = awp_om(e[k]);
                 local *= om[k];
             }
-            float exm = lc_dpp<0x111>(1.f, lc_scan_mul(localm)), ex = lc_dpp<0x111>(1.f, lc_scan_mul(local));
+            float exm = AwpRowGroup::excl_mul(localm), ex = AwpRowGroup::excl_mul(local);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                exm *= Q[k]; Q[k] = s > 0 ? exm : 1.f;            // Q of this row: the cumulative product of row s - 1's om over the channels
+                exm *= Q[k]; Q[k] = s > 0 ? exm : 1.f;                   // Q of this row: the cumulative product of row s - 1's om over the channels
                 ex *= om[k]; Qn[k] = ex;
-                const float en = s + 2 < S ? lc_exp(-__fmul_rn(fn[k], dist_n)) : 1.f;
+                const float en = s + 2 < S ? awp_e(fn[k], dist_n) : 1.f;
                 const float an = s + 2 < S ? __fadd_rn(-en, 1.f) : 0.f;
                 G[k] = last ? 0.f : gg[k] * an * fn[k] * Qn[k];
                 lsum += G[k];
             }
-            float sfx = lc_scan_add_right(lsum) - lsum, ddist = 0.f;
+            float sfx = AwpRowGroup::sum_right(lsum), ddist = 0.f;
 #pragma unroll
             for (int k = 3; k >= 0; --k) {
                 sfx += G[k];
                 const float a = last ? 0.f : __fadd_rn(-e[k], 1.f);
                 const float through = last ? 0.f : sfx * __builtin_amdgcn_rcpf(om[k]);
                 const float ga = gg[k] * Q[k] * fc[k] - through;
-                o[k] += last ? 0.f : gg[k] * Q[k] * a + ga * dist * e[k];
+                o[k] += last ? 0.f : gg[k] * Q[k] * a + ga * dist * e[k];       // the MAM's share + the integration's
                 ddist += last ? 0.f : ga * fc[k] * e[k];
             }
-            ddist = row_sum16(ddist);
-            if (l == 0) dd[p * S + s] = ddist;
-            dh4[at] = make_float4(o[0], o[1], o[2], o[3]);
-            amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o[0]), fabsf(o[1]))), fmaxf(fabsf(o[2]), fabsf(o[3])));
-            const float nan_probe = (o[0] + o[1]) + (o[2] + o[3]);      // a NaN (or inf - inf) in d h_local: +inf, not a finite scale word
-            amax = nan_probe != nan_probe ? __builtin_huge_valf() : amax;
+            const float dds = AwpRowGroup::sum(ddist);
+            if (l == 0) dd[p * S + s] = dds;
+            const float4 o4 = make_float4(o[0], o[1], o[2], o[3]);
+            dh4[at] = o4;
+            amax = mam_absmax_row(amax, o4);
         }
     }
-    du.x += __shfl_xor(du.x, 16); du.y += __shfl_xor(du.y, 16); du.z += __shfl_xor(du.z, 16); du.w += __shfl_xor(du.w, 16);
-    du.x += __shfl_xor(du.x, 32); du.y += __shfl_xor(du.y, 32); du.z += __shfl_xor(du.z, 32); du.w += __shfl_xor(du.w, 32);
-    if (lane < 16) reinterpret_cast<float4*>(red)[wave * 16 + l] = du;
-    __syncthreads();
-    if (tid < MAM_C) q.d_u_partial[b * MAM_C + tid] = red[tid] + red[MAM_C + tid] + red[2 * MAM_C + tid] + red[3 * MAM_C + tid];
+    mam_bwd_fold_du(m, du, q.d_u_partial, b);
     // d z[s] = (d dist[s - 1] - d dist[s]) |d|;  d rays_d = (sum_s d dist[s] (z[s + 1] - z[s])) d / |d|      (awp.py:61-63)
     if (q.d_z)
         for (int i = tid; i < P * S; i += 256) {
@@ -417,16 +421,7 @@ __global__ __launch_bounds__(256) void k_local_consumers_bwd(const LocalBwdParam
                 q.d_rays_d[(b * P + p) * 3 + lane] = nrm[p] > 0.f ? a * d[lane] / nrm[p] : 0.f;
             }
         }
-    if (q.absmax) {
-        for (int o = 32; o; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-        __syncthreads();
-        if (lane == 0) red[wave] = amax;
-        __syncthreads();
-        if (tid == 0) {
-            const unsigned mb = __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
-            if (mb > *reinterpret_cast<volatile unsigned*>(q.absmax)) atomicMax(q.absmax, mb);
-        }
-    }
+    mam_bwd_fold_absmax(m, amax, q.absmax);
 }
 
 }  // namespace evd
@@ -465,7 +460,7 @@ int evd_mam_local_backward(const float* h_local, const float* u, const float* al
     if (int e = mam_check("evd_mam_local_backward", R, P, S, C)) return e;
     if (R == 0) return EVD_OK;
     if (d_h_absmax) EVD_HIP(hipMemsetAsync(d_h_absmax, 0, sizeof(unsigned), as_stream(stream)));     // the kernel raises the word; the entry owns its start value
-    const size_t lds = sizeof(float) * (MAM_MAXP * MAM_C + MAM_MAXP + 4 * MAM_C);
+    const size_t lds = sizeof(float) * MAM_BWD_LDS_FLOATS;
     if (accumulate)
         k_mam_local_bwd<true><<<(unsigned)R, 256, lds, as_stream(stream)>>>(h_local, u, alpha, beta, h_inter, h_intra, d_inter, d_intra, P, S,
                                                                             d_h_local, d_u_partial, d_h_absmax);
@@ -489,8 +484,8 @@ int evd_awp_local_consumers_backward(const float* h_local, const float* u, const
     q.h = h_local; q.u = u; q.alpha = alpha; q.beta = beta; q.h_inter = h_inter; q.h_intra = h_intra; q.d_inter = d_inter; q.d_intra = d_intra;
     q.z = z; q.rays_d = rays_d; q.d_int = d_integrated; q.P = P; q.S = S;
     q.d_h = d_h_local; q.d_u_partial = d_u_partial; q.d_z = d_z; q.d_rays_d = d_rays_d; q.absmax = d_h_absmax;
-    const size_t lds = sizeof(float) * (MAM_MAXP * MAM_C + MAM_MAXP + 4 * MAM_C + MAM_MAXP + (size_t)2 * P * S);
-    EVD_SET_MAX_LDS(k_local_consumers_bwd, sizeof(float) * (MAM_MAXP * MAM_C + 2 * MAM_MAXP + 4 * MAM_C + (size_t)2 * MAM_MAXP * MAM_MAXS));
+    const size_t lds = sizeof(float) * (MAM_BWD_LDS_FLOATS + MAM_MAXP + (size_t)2 * P * S);
+    EVD_SET_MAX_LDS(k_local_consumers_bwd, sizeof(float) * (MAM_BWD_LDS_FLOATS + MAM_MAXP + (size_t)2 * MAM_MAXP * MAM_MAXS));
     k_local_consumers_bwd<<<(unsigned)R, 256, lds, as_stream(stream)>>>(q);
     EVD_HIP(hipGetLastError());
     return EVD_OK;

@@ -40,17 +40,6 @@ constexpr int VSB_BATCH = 4;            // samples whose taps are in flight toge
 // regardless of the table size, tools/probes/atomic_probe.hip, and the counters show EVERY atomic request of this kernel travelling to
 // the memory side, TCC_EA0_ATOMIC == TCC_ATOMIC = 18.6 M 64-byte requests per 2^19 samples: device-scope float atomics are not
 // executed in the XCD's L2.  The kernel is at 78 % of that ceiling; the gap is the repeated hits on the same few line cells.)
-// sum over the 16 lanes of a DPP row, left in every lane of the row (lanes that are switched off contribute 0)
-__device__ __forceinline__ float row_sum_dpp(float v) {
-    auto d = [](float src, auto ctrl) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, src), decltype(ctrl)::value, 0xf, 0xf, false));
-    };
-    v += d(v, std::integral_constant<int, 0xb1>());      // quad_perm [1,0,3,2]
-    v += d(v, std::integral_constant<int, 0x4e>());      // quad_perm [2,3,0,1]
-    v += d(v, std::integral_constant<int, 0x141>());     // row_half_mirror
-    v += d(v, std::integral_constant<int, 0x140>());     // row_mirror
-    return v;
-}
 
 // HYBRID = false: every tap by a direct atomic.  HYBRID = true: the plane taps by direct atomics, the line taps deferred -- their rows
 // (rows_l) and tap records (ltap) are written and k_scatter_lines adds them through privatised LDS slices of the (small) line gradients:

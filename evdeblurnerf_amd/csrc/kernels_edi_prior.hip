@@ -11,7 +11,7 @@
 // window and polarity before a signed 64-bit sum overflows.  The coordinates are float32 values held as float64 (EventTables keeps the
 // float32 event coordinates): for coordinates >= 1 each factor has at most 23 significant bits and the float64 product is exact; it is
 // then rounded to the nearest unit, so a stored weight is exact (coordinates >= 256: multiples of 2^-30) or off by at most 2^-41.  Integer
-// sums do not depend on the arrival order: the table is bit-reproducible, unlike the float atomics of k_edi_splat (kernels_loss.hip).
+// sums do not depend on the arrival order: the table is bit-reproducible, unlike the float atomics of k_edi_splat below.
 // One deviation from the reference: a tap with xf < 0 or yf < 0 is dropped (numpy wraps the negative index to the opposite edge).
 // Thread-to-event mapping: one thread per event, consecutive threads on consecutive events of one image (blockIdx.y), a grid-stride loop over
 // the image's index range, so that no size has to be read back.  The four taps of an event are two 16-byte pairs on neighbouring rows;
@@ -141,6 +141,47 @@ __global__ __launch_bounds__(EDI_DEBLUR_THREADS) void k_edi_prior_deblur(const f
     for (int c = 0; c < 3; ++c) o[c] = fs * im[c] / s;
 }
 
+// ---- the per-image forms: one blurry grey image, float sums
+// utils/edi.py:73-95: E_k = -sum_{j=k}^{N-1} bii_j (k<N), 0 (k=N), +sum_{j=N}^{k-1} bii_j (k>N); sharp = (2N+1) blurry / sum exp(E_k)
+__global__ void k_edi_deblur(const float* __restrict__ blurry, const float* __restrict__ bii, int steps, long npix,
+                             float* __restrict__ sharp) {
+    const long px = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (px >= npix) return;
+    const int N = (steps - 1) / 2;
+    float s = 1.f;       // exp(0) of the frame at f
+    float run = 0.f;
+    // left part: E_i = -(bii_i + ... + bii_{N-1}); accumulate in the reference's order (i ascending inside each sum)
+    for (int i = 0; i < N; ++i) {
+        float e = 0.f;
+        for (int j = i; j < N; ++j) e += bii[(long)j * npix + px];
+        s += expf(-e);
+    }
+    for (int i = 0; i < N; ++i) {
+        run += bii[(long)(N + i) * npix + px];
+        s += expf(run);
+    }
+    sharp[px] = (float)(2 * N + 1) * blurry[px] / s;
+}
+
+// utils/edi.py:7-41,44-70: bilinear sub-pixel splat of +-1 events, grey sensor
+__global__ void k_edi_splat(const float* __restrict__ x, const float* __restrict__ y, const signed char* __restrict__ p, long n,
+                            int w, int h, float c_pos, float c_neg, float* __restrict__ image) {
+    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float xv = x[i], yv = y[i];
+    const float sc = p[i] > 0 ? c_pos : -c_neg;
+#pragma unroll
+    for (int xr = 0; xr < 2; ++xr)
+#pragma unroll
+        for (int yr = 0; yr < 2; ++yr) {
+            const float xf = xr ? ceilf(xv) : floorf(xv), yf = yr ? ceilf(yv) : floorf(yv);
+            // (a tap left of / above the frame is dropped: the reference's negative index wraps to the opposite edge, an indexing artefact)
+            if (!((xf != xv || xr == 0) && (yf != yv || yr == 0) && xf < (float)w && yf < (float)h && xf >= 0.f && yf >= 0.f)) continue;
+            const float kx = fmaxf(0.f, 1.f - fabsf(xf - xv)), ky = fmaxf(0.f, 1.f - fabsf(yf - yv));
+            atomicAdd(image + (long)yf * w + (long)xf, sc * (kx * ky));
+        }
+}
+
 static inline size_t edi_al256(size_t b) { return (b + 255) & ~(size_t)255; }
 static inline size_t edi_win_bytes(int c, int steps) { return 2 * edi_al256((size_t)c * steps * 8); }
 static inline size_t edi_plane_bytes(int steps, int h, int w) { return (size_t)(steps - 1) * h * w * 16; }
@@ -189,6 +230,24 @@ int evd_edi_prior(const double* events, long N, const double* id_to_coords, long
             images + (long)c0 * hw * 3, (const long long*)acc, steps, hw, c_pos, c_neg, prior_out + (long)c0 * hw * 3);
         EVD_LAUNCH_CHECK();
     }
+    return EVD_OK;
+}
+
+int evd_edi_deblur(const float* blurry, const float* bii, int steps, long npix, float* sharp, void* stream) {
+    EVD_REQUIRE(blurry && bii && sharp && steps >= 3 && (steps & 1) && npix >= 0, "evd_edi_deblur: steps must be odd >= 3");
+    if (npix == 0) return EVD_OK;
+    k_edi_deblur<<<cdiv(npix, 256), 256, 0, as_stream(stream)>>>(blurry, bii, steps, npix, sharp);
+    EVD_LAUNCH_CHECK();
+    return EVD_OK;
+}
+
+int evd_edi_bii_image(const float* x, const float* y, const signed char* p, long n, int w, int h,
+                      float c_pos, float c_neg, float* image, void* stream) {
+    EVD_REQUIRE(image && w > 0 && h > 0 && n >= 0, "evd_edi_bii_image: bad arguments");
+    EVD_HIP(hipMemsetAsync(image, 0, sizeof(float) * (size_t)w * h, as_stream(stream)));
+    if (n == 0) return EVD_OK;
+    k_edi_splat<<<cdiv(n, 256), 256, 0, as_stream(stream)>>>(x, y, p, n, w, h, c_pos, c_neg, image);
+    EVD_LAUNCH_CHECK();
     return EVD_OK;
 }
 

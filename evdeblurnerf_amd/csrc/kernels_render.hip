@@ -642,16 +642,6 @@ __device__ __forceinline__ float act_grad(int code, float x) {
     }
 }
 
-__device__ __forceinline__ float wave_scan_add_dpp(float v) {
-    v += dpp_f32<0x111>(0.f, v);
-    v += dpp_f32<0x112>(0.f, v);
-    v += dpp_f32<0x114>(0.f, v);
-    v += dpp_f32<0x118>(0.f, v);
-    v += dpp_f32<0x142, 0xa>(0.f, v);
-    v += dpp_f32<0x143, 0xc>(0.f, v);
-    return v;
-}
-
 // Backward of raw2outputs ("next" row f-1, first slice): d raw from the gradients of (out_map, depth, acc, weights).
 // Same decomposition as k_composite_rows (a wavefront per ray, SPL consecutive samples per lane); the forward quantities
 // are recomputed.  With G_i = dL/dw_i = g_map . rgb_i + g_depth z_i + g_acc + g_w_i (- sum g_map for a white background):

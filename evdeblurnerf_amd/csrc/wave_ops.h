@@ -1,5 +1,5 @@
-// Wave-level DPP primitives and the fast activations of the compositing scan (kernels_render.hip); the MAM, AWP-tail and voxel kernels
-// share the DPP sums.
+// Wave-level and row-level DPP primitives and the fast activations of the compositing scan (kernels_render.hip); the loss, AWP-scan,
+// MAM, AWP-tail and voxel kernels share the DPP scans and sums.
 #pragma once
 
 #include "evd_common.h"
@@ -25,17 +25,52 @@ __device__ __forceinline__ float wave_scan_mul_dpp(float v) {
     v *= dpp_f32<0x143, 0xc>(1.f, v);     // rows 2, 3 <- lane 31
     return v;
 }
-// sum over the 64 lanes, result uniform (in an SGPR-backed value)
-__device__ __forceinline__ float wave_sum_dpp(float v) {
+// inclusive sum scan over the 64 lanes
+__device__ __forceinline__ float wave_scan_add_dpp(float v) {
+    v += dpp_f32<0x111>(0.f, v);
+    v += dpp_f32<0x112>(0.f, v);
+    v += dpp_f32<0x114>(0.f, v);
+    v += dpp_f32<0x118>(0.f, v);
+    v += dpp_f32<0x142, 0xa>(0.f, v);
+    v += dpp_f32<0x143, 0xc>(0.f, v);
+    return v;
+}
+// inclusive product over the lanes <= this one of the 16-lane DPP row
+__device__ __forceinline__ float row_scan_mul_dpp(float v) {
+    v *= dpp_f32<0x111>(1.f, v);
+    v *= dpp_f32<0x112>(1.f, v);
+    v *= dpp_f32<0x114>(1.f, v);
+    v *= dpp_f32<0x118>(1.f, v);
+    return v;
+}
+// inclusive sum over the lanes >= this one of the row (row_shl:n 0x100+n)
+__device__ __forceinline__ float row_scan_add_right_dpp(float v) {
+    v += dpp_f32<0x101>(0.f, v);
+    v += dpp_f32<0x102>(0.f, v);
+    v += dpp_f32<0x104>(0.f, v);
+    v += dpp_f32<0x108>(0.f, v);
+    return v;
+}
+// sum over the 16 lanes of a row, left in every lane of the row (lanes that are switched off contribute 0)
+__device__ __forceinline__ float row_sum_dpp(float v) {
     v += dpp_f32<0xb1>(0.f, v);           // quad_perm [1,0,3,2]
     v += dpp_f32<0x4e>(0.f, v);           // quad_perm [2,3,0,1]
     v += dpp_f32<0x141>(0.f, v);          // row_half_mirror
-    v += dpp_f32<0x140>(0.f, v);          // row_mirror: every lane now holds its row's sum
+    v += dpp_f32<0x140>(0.f, v);          // row_mirror
+    return v;
+}
+// sum over the 64 lanes, result uniform (in an SGPR-backed value)
+__device__ __forceinline__ float wave_sum_dpp(float v) {
+    v = row_sum_dpp(v);
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0)) +
            __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16)) +
            __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32)) +
            __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
 }
+
+// e^x on the hardware exp2 (v_exp_f32, 1 ulp) behind one multiply: relative error <= 1e-6 for |x| <= 16 against ~20 instructions of the
+// IEEE expf -- the AWP scans evaluate one exponential per (sample, channel) and were bound by the instruction count, not by HBM
+__device__ __forceinline__ float exp_fast(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 
 // activations of the bandwidth-form scan: sigmoid with the hardware exp2 and reciprocal (relative error ~3e-7; the
 // IEEE expf + division of evd::act() made the scan VALU-bound: 3.8 instead of 5.2 TB/s)

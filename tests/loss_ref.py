@@ -1,4 +1,4 @@
-"""float64 reference of the loss-side kernels (csrc/kernels_loss.hip): the sub-exposure weighted sum (rbk_weighted_sum,
+"""float64 reference of the loss-side kernels (csrc/kernels_loss.hip; the AWP scan: csrc/kernel_awp_integrate.hip + awp_integrate.h): the sub-exposure weighted sum (rbk_weighted_sum,
 blurmodel.py:112-127), the response curves (tonemapping.py:59-93, none / gamma / learn), the blur-loss partial sums (run_nerf.py:443-497) with
 their hand-written backward for the curves the backward kernel is built for (none, gamma, learn + skip_learn), the event-loss partial sums
 (run_nerf.py:518-570, events.py:260-284) with their hand-written backward incl. the 705-float parameter gradient, and the AWP consumer's
@@ -16,7 +16,7 @@ Error model (units of u; a rounding is <= u relative; a product of k factors tak
   weighted_sum   s += x ccw, P steps (an FMA or a product and an add)         sum_p |x ccw| (1 + P)
   dist           fl(fl(z1 - z0) norm): dz 1, the float32 norm 2.5 (three __fmul_rn, two __fadd_rn: 1.5 under the root, halved, + sqrtf's
                  own + the products'), the product 1                         5 |dist|  (composite_ref.py's figure)
-  x = f dist     the product 1; awp_exp scales by float32(log2 e) (0.22 u off the real log2 e) and rounds: 1.25
+  x = f dist     the product 1; exp_fast scales by float32(log2 e) (0.22 u off the real log2 e) and rounds: 1.25
                                                                              E_x = |f| E_dist + 2.25 |x| = 7.25 |x|
   e = exp2(.)    v_exp_f32, 1 ulp = 2 u                                      E_e = e (E_x + 2)
   alpha = 1 - e  E_alpha = E_e + |alpha|;  forward om = fl(1 - alpha): E_om = E_alpha + |om| (~u ABSOLUTE once alpha -> 1, and exactly
@@ -70,7 +70,7 @@ Event loss (16 lanes per event; block_sum = 6 shuffles + 4 LDS adds; one atomicA
                           dh3 = mask ds w3;  dh2 = mask W2^T dh3, dh1 = mask W1^T dh2, d in0 = w0[:, 0] . dh1: 16 fmaf's each, as the forward layers;
                           d_x = dz + d in0
   d_params                per-lane products (dh1 in, dh2 h1, dh3 h2, ds h3, and the dh / ds themselves for the biases): both factors' bounds + 1;
-                          wave_sum_all (4 DPP adds + 3), one LDS atomic per wavefront (4), one global atomic per block, all in arbitrary order:
+                          wave_sum_dpp (4 DPP adds + 3), one LDS atomic per wavefront (4), one global atomic per block, all in arbitrary order:
                           sum E_c + (7 + 4 + nblocks) sum |c|.  Columns 3..7 of the w0 gradient are exactly 0
 POW_ULP, LOG_ULP: powf and logf have no figure in the project, so their constants are measured (tools/measure_pow_log_ulp.py: float32 torch.pow /
 torch.log on the MI355X against float64, 2^25 points per function, log-uniform and linear): pow(x, 1/2.2) 1.3128 ulp and pow(x, 1/2.2 - 1)
@@ -656,7 +656,7 @@ def event_loss_bwd(start, end, cum_neg, cum_pos, thr_neg, thr_pos, g_fine, g_coa
         E_din0 = E_dh1 @ p["w0"][:, 0].abs() + 16 * (dh1.abs() @ p["w0"][:, 0].abs())
         d_x = dz + din0
         E_d_x = E_dz + E_din0 + dz.abs() + din0.abs() + d_x.abs()
-        # parameter gradient: per-lane contributions, wave_sum_all (4 DPP adds + 3), LDS atomics of the block's 4 wavefronts, one global
+        # parameter gradient: per-lane contributions, wave_sum_dpp (4 DPP adds + 3), LDS atomics of the block's 4 wavefronts, one global
         # atomic per block -- all in arbitrary order
         n_p = 7 + 4 + q["nblocks"]
 

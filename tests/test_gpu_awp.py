@@ -355,6 +355,49 @@ def test_mam_local_backward_equals_float64_autograd(R, P, S):
         assert _rel(a.cpu().numpy().reshape(-1), b.numpy().reshape(-1)) < 2e-5, name
 
 
+def _local_consumers_both_ways(R, P, S):
+    """h_local's two backward paths on _mam_inputs: (fused, two_launch), each (d h_local, d u_partial, absmax word) as numpy arrays"""
+    from evdeblurnerf_amd import _lib as L
+    lib = L.lib()
+    x_local, Wl, bl, v = _mam_inputs(91 + S, R, P, S)
+    rs = np.random.RandomState(17 + S)
+    hl, u = _t(x_local), _t((Wl.T @ v.reshape(32)).astype(np.float32))
+    z = _t(np.sort(rs.uniform(0, 1, (R * P, S)).astype(np.float32), -1))
+    d = _t(rs.standard_normal((R * P, 3)).astype(np.float32))
+    g_h, g_inter, g_intra = (_t(rs.standard_normal(s).astype(np.float32)) for s in ((R * P, 64), (R, P, 64), (R, S, 64)))
+    f32 = dict(dtype=torch.float32, device="cuda")
+    h_inter, h_intra = torch.empty((R, P, 64), **f32), torch.empty((R, S, 64), **f32)
+    alpha, beta = torch.empty((R, P, S), **f32), torch.empty((R, P, S), **f32)
+    L.check(lib.evd_mam_local_forward(L.ptr(hl), L.ptr(u), R, P, S, 64, L.ptr(h_inter), L.ptr(h_intra), L.ptr(alpha), L.ptr(beta), L.stream_ptr()),
+            "evd_mam_local_forward")
+    new = lambda: (torch.empty_like(hl), torch.empty((R, 64), **f32), torch.full((1,), 7, dtype=torch.int32, device="cuda"))
+    d_h1, d_u1, amax1 = new()
+    d_z, d_d = torch.empty_like(z), torch.empty_like(d)
+    L.check(lib.evd_awp_local_consumers_backward(L.ptr(hl), L.ptr(u), L.ptr(alpha), L.ptr(beta), L.ptr(h_inter), L.ptr(h_intra), L.ptr(g_inter), L.ptr(g_intra),
+                                                 L.ptr(z), L.ptr(d), L.ptr(g_h), R, P, S, 64, L.ptr(d_h1), L.ptr(d_u1), L.ptr(d_z), L.ptr(d_d), L.ptr(amax1),
+                                                 L.stream_ptr()), "evd_awp_local_consumers_backward")
+    d_h2, d_u2, amax2 = new()
+    L.check(lib.evd_awp_feature_integration_bwd(L.ptr(hl), L.ptr(z), L.ptr(d), L.ptr(g_h), R * P, S, 64, L.ptr(d_h2), L.ptr(d_z), L.ptr(d_d), L.stream_ptr()),
+            "evd_awp_feature_integration_bwd")
+    L.check(lib.evd_mam_local_backward(L.ptr(hl), L.ptr(u), L.ptr(alpha), L.ptr(beta), L.ptr(h_inter), L.ptr(h_intra), L.ptr(g_inter), L.ptr(g_intra), R, P, S, 64,
+                                       L.ptr(d_h2), L.ptr(d_u2), 1, L.ptr(amax2), L.stream_ptr()), "evd_mam_local_backward")
+    torch.cuda.synchronize()
+    return tuple(tuple(t.cpu().numpy() for t in ts) for ts in ((d_h1, d_u1, amax1), (d_h2, d_u2, amax2)))
+
+
+@pytest.mark.parametrize("R,P,S", [(2, 3, 1), (3, 10, 33), (1, 16, 18)])
+def test_local_consumers_backward_has_the_bits_of_the_two_launches(R, P, S):
+    """evd_awp_local_consumers_backward against evd_awp_feature_integration_bwd (C = 64) followed by evd_mam_local_backward with
+    accumulate = 1: the same bits in d h_local, d u_partial and the absmax word.  Both paths evaluate the same float32 operations in the
+    same order per element (the MAM's share + the integration's share; no contraction), the fused kernel only obtains Q of a row from the
+    row before instead of carrying it.  (d z_vals / d rays_d are folded in another order in the fused kernel: not compared here.)
+    One sample, a partial 16-sample tile with more than one tile, the largest P."""
+    fused, two = _local_consumers_both_ways(R, P, S)
+    for a, b, name in zip(fused, two, ("d_h_local", "d_u_partial", "absmax")):
+        diff = np.flatnonzero(a.reshape(-1).view(np.uint32) != b.reshape(-1).view(np.uint32))
+        assert diff.size == 0, f"{name}: {diff.size} words differ, first at {diff[0]}: {a.reshape(-1)[diff[0]]!r} vs {b.reshape(-1)[diff[0]]!r}"
+
+
 def test_fused_awp_with_the_reference_mam_structure_equals_plain_torch():
     """FusedAWP around a module with the reference's MotionAggregationModule structure (MAMLike): output and parameter gradients
     against the same module run in plain float32 torch on the float32 depth_feature tensor.  Float16 embedding against float32 torch

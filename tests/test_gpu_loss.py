@@ -1,4 +1,4 @@
-"""The loss-side kernels (csrc/kernels_loss.hip) against the float64 reference of tests/loss_ref.py, element by element:
+"""The loss-side kernels (csrc/kernels_loss.hip; the AWP scan in csrc/kernel_awp_integrate.hip + awp_integrate.h) against the float64 reference of tests/loss_ref.py, element by element:
 |kernel - ref| <= K u E with u = 2^-24, E the reference's first-order bound for the kernel form, K = 2 for the second-order terms, an absolute
 2^-120 for float32 underflow, and isfinite(kernel) == isfinite(ref).  Every kernel form is reached by shape and mode alone through the
 public entries; each case id names the kernel it expects.  Each case prints its worst err / (u E) before it asserts (pytest -s)."""
