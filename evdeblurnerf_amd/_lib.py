@@ -92,6 +92,17 @@ class RigidBlurParams(C.Structure):
                                    "r_linear_w", "r_linear_b", "v_linear_w", "v_linear_b", "w_linear_w", "w_linear_b")]
 
 
+class SparseBlurDesc(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("kernel_type", "num_pt", "in_embed", "spatial_embed", "embed_cnl", "feat_cnl", "num_hidden", "num_wide", "short_cut",
+                                       "isglobal", "optim_trans", "optim_spatialvariant_trans", "n_img", "n_pattern", "poses_per_image", "H", "W")] + \
+               [(k, C.c_float) for k in ("kernel_hwindow", "random_hwindow", "fx", "fy", "cx", "cy")]
+
+
+class SparseBlurParams(C.Structure):
+    _fields_ = [("pattern_pos", _vp), ("pattern_trans", _vp), ("table", _vp), ("linears_w", _vp * 4), ("linears_b", _vp * 4),
+                ("linears1_w", _vp * 2), ("linears1_b", _vp * 2)]
+
+
 class LpipsDesc(C.Structure):
     _fields_ = [("conv_w", _fp * 5), ("conv_b", _fp * 5), ("lin", _fp * 5), ("shift", C.c_float * 3), ("scale", C.c_float * 3)]
 
@@ -124,6 +135,11 @@ SIGNATURES = {
     "evd_rigid_blur_forward": (_I, [C.POINTER(RigidBlurDesc), C.POINTER(RigidBlurParams), _vp, _vp, _vp, _L, _vp, _vp, _vp, _vp]),
     "evd_rigid_blur_backward": (_I, [C.POINTER(RigidBlurDesc), C.POINTER(RigidBlurParams), _vp, _vp, _vp, _L, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _S, _vp]),
+    "evd_sparse_blur_workspace_bytes": (_S, [C.POINTER(SparseBlurDesc), _L]),
+    "evd_sparse_blur_forward": (_I, [C.POINTER(SparseBlurDesc), C.POINTER(SparseBlurParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _L, _vp, _vp, _vp, _vp,
+                                     _vp, _S, _vp]),
+    "evd_sparse_blur_backward": (_I, [C.POINTER(SparseBlurDesc), C.POINTER(SparseBlurParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _L, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _S, _vp]),
     "evd_awp_feature_integration": (_I, [_vp, _vp, _vp, _L, _I, _I, _vp, _vp]),
     "evd_awp_feature_integration_bwd": (_I, [_vp, _vp, _vp, _vp, _L, _I, _I, _vp, _vp, _vp, _vp]),
     "evd_mam_local_forward": (_I, [_vp, _vp, _L, _I, _I, _I, _vp, _vp, _vp, _vp, _vp]),

@@ -1,7 +1,8 @@
-"""Mirror of the reference's rigid blur kernel network: ``RigidBlurringModel`` (networks/dpnerf/blurmodel.py:9-173) with its
-``ViewEmbedding`` (networks/embedding.py:6-32), as run_nerf.py:167-215 builds them.  The module carries the reference's parameter names,
-shapes and initialisation, so a reference checkpoint's ``kernelsnet.*`` keys load; its forward and backward are one and two launches of
-the library (evd_rigid_blur_forward / _backward) that read the parameters in place."""
+"""Mirrors of the reference's blur kernel networks, with its ``ViewEmbedding`` (networks/embedding.py:6-32), as run_nerf.py:167-215 builds
+them: ``RigidBlurKernel`` for ``RigidBlurringModel`` (networks/dpnerf/blurmodel.py:9-173, kernel_type RBK) and ``SparseBlurKernel`` for
+``BlurModel`` (networks/pdrf/blurmodel.py:9-224, kernel_type DSK and PBE).  A module carries the reference's parameter names, shapes and
+initialisation, so a reference checkpoint's ``kernelsnet.*`` keys load; its forward and backward are launches of the library
+(evd_rigid_blur_* / evd_sparse_blur_*) that read the parameters in place."""
 from __future__ import annotations
 
 import ctypes as C
@@ -176,3 +177,193 @@ class RigidBlurKernel(nn.Module):
             new_rays, weight, _ = _RigidBlurFn.apply(self._desc(x.shape[1], 0), rays, None, x, None, *net)
             img_embed = view_feature
         return new_rays, weight, None, ({"img_embed": img_embed} if return_img_embed else {})
+
+
+class _SparseBlurFn(torch.autograd.Function):
+    """(ids, x | None, rays_x, rays_y, poses, noise | None, feats | None, pattern_pos, pattern_trans | None, table | None, the linears' and
+    linears1's weights and biases) -> (new_rays, weight, align [1] | None, img_embed)"""
+
+    @staticmethod
+    def forward(ctx, desc, ids, x, rays_x, rays_y, poses, noise, feats, pattern_pos, pattern_trans, table, *net):
+        R, P, dev = ids.shape[0], desc.num_pt, rays_x.device
+        new_rays = torch.empty((R, P, 3, 2), dtype=torch.float32, device=dev)
+        weight = torch.empty((R, P), dtype=torch.float32, device=dev)
+        img_embed = torch.empty((R, desc.embed_cnl), dtype=torch.float32, device=dev)
+        align = torch.zeros((1,), dtype=torch.float32, device=dev) if desc.kernel_type == 0 else None
+        ws = torch.empty((max(2 * R, 1),), dtype=torch.float32, device=dev) if desc.kernel_type == 0 else None
+        prm = _sparse_params(pattern_pos, pattern_trans, table, net)
+        L.check(L.lib().evd_sparse_blur_forward(C.byref(desc), C.byref(prm), L.ptr(ids), L.ptr(x), L.ptr(rays_x), L.ptr(rays_y), L.ptr(poses), L.ptr(noise),
+                                                L.ptr(feats), R, L.ptr(new_rays), L.ptr(weight), L.ptr(align), L.ptr(img_embed), L.ptr(ws),
+                                                0 if ws is None else 4 * ws.numel(), L.stream_ptr()), "evd_sparse_blur_forward")
+        ctx.desc = desc
+        ctx.save_for_backward(ids, x, rays_x, rays_y, poses, noise, feats, pattern_pos, pattern_trans, table, *net)
+        ctx.set_materialize_grads(False)
+        return new_rays, weight, align, img_embed
+
+    @staticmethod
+    def backward(ctx, d_new_rays, d_weight, d_align, d_img_embed):
+        desc = ctx.desc
+        ids, x, rays_x, rays_y, poses, noise, feats, pattern_pos, pattern_trans, table, *net = ctx.saved_tensors
+        R, P, dev = ids.shape[0], desc.num_pt, rays_x.device
+        d_new_rays = torch.zeros((R, P, 3, 2), device=dev) if d_new_rays is None else d_new_rays.contiguous()
+        d_weight = torch.zeros((R, P), device=dev) if d_weight is None else d_weight.contiguous()
+        d_align = None if d_align is None else d_align.contiguous()
+        d_img_embed = None if d_img_embed is None else d_img_embed.contiguous()
+        leaves = (pattern_pos, pattern_trans, table) + tuple(net)
+        sizes = [0 if t is None else t.numel() for t in leaves]
+        flat = torch.empty((sum(sizes),), dtype=torch.float32, device=dev)
+        d_x = torch.empty_like(x) if x is not None and ctx.needs_input_grad[2] else None
+        d_feats = torch.empty_like(feats) if feats is not None and ctx.needs_input_grad[7] else None
+        lib = L.lib()
+        need = int(lib.evd_sparse_blur_workspace_bytes(C.byref(desc), R))
+        ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+        prm = _sparse_params(pattern_pos, pattern_trans, table, net)
+        L.check(lib.evd_sparse_blur_backward(C.byref(desc), C.byref(prm), L.ptr(ids), L.ptr(x), L.ptr(rays_x), L.ptr(rays_y), L.ptr(poses), L.ptr(noise),
+                                             L.ptr(feats), R, L.ptr(d_new_rays), L.ptr(d_weight), L.ptr(d_align), L.ptr(d_img_embed), L.ptr(flat),
+                                             L.ptr(d_x), L.ptr(d_feats), L.ptr(ws), need, L.stream_ptr()), "evd_sparse_blur_backward")
+        grads, o = [], 0
+        for t, n in zip(leaves, sizes):                          # the flat buffer sliced into the leaves' gradients
+            grads.append(None if t is None else flat[o:o + n].view(t.shape))
+            o += n
+        return (None, None, d_x, None, None, None, None, d_feats, *grads)
+
+
+def _sparse_params(pattern_pos, pattern_trans, table, net):
+    prm = L.SparseBlurParams()
+    for name, t in (("pattern_pos", pattern_pos), ("pattern_trans", pattern_trans), ("table", table)) + tuple((f"net[{i}]", t) for i, t in enumerate(net)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise L.EvdError(f"SparseBlurKernel: parameter {name} must be contiguous float32")
+    prm.pattern_pos, prm.pattern_trans, prm.table = (None if t is None else t.data_ptr() for t in (pattern_pos, pattern_trans, table))
+    hidden = (len(net) - 4) // 2
+    for i in range(min(hidden, 4)):                              # (a deeper network is refused by the library: num_hidden)
+        prm.linears_w[i], prm.linears_b[i] = net[2 * i].data_ptr(), net[2 * i + 1].data_ptr()
+    for i in range(2):
+        prm.linears1_w[i], prm.linears1_b[i] = net[2 * hidden + 2 * i].data_ptr(), net[2 * hidden + 2 * i + 1].data_ptr()
+    return prm
+
+
+def init_linear_weights(m):
+    """utils/misc.py:95-102: Xavier-normal (gain 0.1 for a weight of 2 or 3 output rows), biases 0"""
+    if isinstance(m, nn.Linear):
+        nn.init.xavier_normal_(m.weight, 0.1 if m.weight.shape[0] in (2, 3) else 1.0)
+        nn.init.constant_(m.bias, 0)
+
+
+class SparseBlurKernel(nn.Module):
+    """BlurModel (networks/pdrf/blurmodel.py:9-224), kernel_type 'DSK' or 'PBE', under the reference's argument names and defaults.
+    `view_embed`: None builds the 'param' ViewEmbedding of run_nerf.py:168-170 (num_img x view_embed_cnl, `embed_init`), whose rows the kernel
+    gathers itself; any other module stays PyTorch in front of the kernel and hands it per-ray rows.  `noise` of forward is the [R, P, 2]
+    standard-normal draw the reference takes with randn_like (in eval mode too); None draws it on the device when random_hwindow > 0."""
+    TILE_ROWS = 16            # a tile of the kernels holds TILE_ROWS // num_pt whole rays
+    GRID_CAP = 128            # ... and at most this many workgroups share a batch's tiles
+
+    def __init__(self, num_img, num_pt, kernel_hwindow, kernel_type, view_embed=None, img_wh=None, random_hwindow=0.25, in_embed=3, random_mode="input",
+                 view_embed_cnl=32, spatial_embed=0, depth_embed=0, num_hidden=3, num_wide=64, feat_cnl=15, short_cut=False, pattern_init_radius=0.1,
+                 isglobal=False, optim_trans=False, optim_spatialvariant_trans=False, use_pattern_pos=True, poses=None, embed_init="zero"):
+        super().__init__()
+        if kernel_type not in ("DSK", "PBE"):
+            raise L.EvdError(f"SparseBlurKernel: kernel_type {kernel_type!r} is neither 'DSK' nor 'PBE'")
+        if random_mode not in ("input", "output"):
+            raise L.EvdError(f"SparseBlurKernel: random_mode {random_mode!r} unrecognized, should be input / output")
+        if depth_embed > 0:
+            raise L.EvdError("SparseBlurKernel: depth_embed > 0 is not built (the reference calls it deprecated; nothing produces rays_info['ray_depth'])")
+        if not use_pattern_pos:
+            raise L.EvdError("SparseBlurKernel: use_pattern_pos=False is not built (run_nerf.py never passes it)")
+        self.num_pt, self.num_img, self.short_cut, self.kernel_hwindow = num_pt, num_img, short_cut, kernel_hwindow
+        self.random_hwindow, self.random_mode, self.kernel_type, self.isglobal, self.feat_cnl = random_hwindow, random_mode, kernel_type, isglobal, feat_cnl
+        self.in_embed, self.spatial_embed, self.num_hidden, self.num_wide = in_embed, spatial_embed, num_hidden, num_wide
+        self.optim_trans, self.optim_sv_trans = optim_trans, optim_spatialvariant_trans
+        pattern_num = 1 if isglobal else num_img
+        if poses is not None:
+            self.register_buffer("poses", torch.as_tensor(poses).float())
+        else:
+            self.poses = None
+        self.pattern_pos = nn.Parameter(torch.randn(pattern_num, num_pt, 2).float() * pattern_init_radius, True)
+        if optim_trans:
+            self.pattern_trans = nn.Parameter(torch.zeros(pattern_num, num_pt, 2).float(), True)
+        self.img_embed = ViewEmbedding(num_img, view_embed_cnl, embed_init) if view_embed is None else view_embed
+        self.img_embed_cnl = view_embed_cnl
+        width = lambda L_: 2 * (1 + 2 * L_) if L_ > 0 else 0
+        in_cnl = width(in_embed) + view_embed_cnl + width(spatial_embed) + (feat_cnl if kernel_type == "PBE" else 0)
+        out_cnl = 5 if optim_spatialvariant_trans else 3
+        hiddens = [nn.Linear(num_wide, num_wide) if i % 2 == 0 else nn.ReLU() for i in range((num_hidden - 1) * 2)]
+        self.linears = nn.Sequential(nn.Linear(in_cnl, num_wide), nn.ReLU(), *hiddens)
+        self.linears1 = nn.Sequential(nn.Linear((num_wide + in_cnl) if short_cut else num_wide, num_wide), nn.ReLU(), nn.Linear(num_wide, out_cnl))
+        self.linears.apply(init_linear_weights)
+        self.linears1.apply(init_linear_weights)
+
+    @classmethod
+    def from_args(cls, args, n_imgs, poses=None):
+        """the constructor call of run_nerf.py:168-170,184-203 ('param' embedding)"""
+        kind = getattr(args, "kernel_img_embed_type", "param")
+        if kind != "param":
+            raise L.EvdError(f"SparseBlurKernel.from_args: kernel_img_embed_type {kind!r}: pass the embedding module as view_embed")
+        return cls(n_imgs, args.kernel_ptnum, args.kernel_hwindow, args.kernel_type, random_hwindow=args.kernel_random_hwindow,
+                   in_embed=args.kernel_rand_embed, random_mode=args.kernel_random_mode, spatial_embed=args.kernel_spatial_embed,
+                   depth_embed=args.kernel_depth_embed, num_hidden=args.kernel_num_hidden, num_wide=args.kernel_num_wide, feat_cnl=args.kernel_feat_cnl,
+                   short_cut=args.kernel_shortcut, pattern_init_radius=args.kernel_pattern_init_radius, isglobal=args.kernel_isglobal,
+                   optim_trans=args.kernel_global_trans, optim_spatialvariant_trans=args.kernel_spatialvariant_trans,
+                   view_embed_cnl=args.kernel_img_embed, embed_init=getattr(args, "kernel_img_embed_init", "zero"), poses=poses)
+
+    @classmethod
+    def from_state_dict(cls, sd, kernel_type, kernel_hwindow, random_hwindow=0.25, in_embed=3, spatial_embed=0, isglobal=None, random_mode="input", prefix=""):
+        """the module a reference checkpoint's `kernelsnet.*` tensors (prefix 'kernelsnet.') describe, with them loaded.  The tensors fix every
+        size but the two embedding depths (and, when there is one image, isglobal): those are arguments."""
+        sd = {k[len(prefix):]: torch.as_tensor(v) for k, v in sd.items() if k.startswith(prefix)}
+        num_img, embed = sd["img_embed.img_embed"].shape
+        n_pat, num_pt, _ = sd["pattern_pos"].shape
+        isglobal = (n_pat == 1 and num_img != 1) if isglobal is None else isglobal
+        num_wide, in_cnl = sd["linears.0.weight"].shape
+        num_hidden = len([k for k in sd if k.startswith("linears.") and k.endswith(".weight")])
+        width = lambda L_: 2 * (1 + 2 * L_) if L_ > 0 else 0
+        feat_cnl = in_cnl - width(in_embed) - embed - width(spatial_embed)
+        if feat_cnl < 0 or (kernel_type == "DSK" and feat_cnl):
+            raise L.EvdError(f"SparseBlurKernel.from_state_dict: row width {in_cnl} does not fit in_embed {in_embed}, embedding {embed}, spatial_embed {spatial_embed}")
+        mod = cls(num_img, num_pt, kernel_hwindow, kernel_type, random_hwindow=random_hwindow, in_embed=in_embed, random_mode=random_mode,
+                  view_embed_cnl=embed, spatial_embed=spatial_embed, num_hidden=num_hidden, num_wide=num_wide, feat_cnl=feat_cnl if kernel_type == "PBE" else 15,
+                  short_cut=sd["linears1.0.weight"].shape[1] > num_wide, isglobal=isglobal, optim_trans="pattern_trans" in sd,
+                  optim_spatialvariant_trans=sd["linears1.2.weight"].shape[0] == 5, poses=sd.get("poses"))
+        mod.load_state_dict(sd)
+        return mod
+
+    def _net(self):
+        lins = [m for m in self.linears if isinstance(m, nn.Linear)] + [self.linears1[0], self.linears1[2]]
+        return tuple(t for m in lins for t in (m.weight, m.bias))
+
+    def _desc(self, H, W, K, Cw, n_img):
+        return L.SparseBlurDesc(kernel_type=int(self.kernel_type == "PBE"), num_pt=self.num_pt, in_embed=self.in_embed, spatial_embed=self.spatial_embed,
+                                embed_cnl=Cw, feat_cnl=self.feat_cnl if self.kernel_type == "PBE" else 0, num_hidden=self.num_hidden, num_wide=self.num_wide,
+                                short_cut=int(bool(self.short_cut)), isglobal=int(bool(self.isglobal)), optim_trans=int(bool(self.optim_trans)),
+                                optim_spatialvariant_trans=int(bool(self.optim_sv_trans)), n_img=n_img, n_pattern=self.pattern_pos.shape[0],
+                                poses_per_image=0 if self.poses is None else self.poses.shape[0], H=int(H), W=int(W),
+                                kernel_hwindow=float(self.kernel_hwindow), random_hwindow=float(self.random_hwindow), fx=float(K[0][0]), fy=float(K[1][1]),
+                                cx=float(K[0][2]), cy=float(K[1][2]))
+
+    def forward(self, H, W, K, rays, rays_info, feats=None, return_img_embed=False, noise=None, **kwargs):
+        if self.random_hwindow > 0 and self.random_mode == "output":
+            raise NotImplementedError(f"{self.random_mode} for self.random_mode is not implemented")
+        ids = rays_info["images_idx"].reshape(-1).to(torch.int64).contiguous()
+        R, dev = ids.shape[0], ids.device
+        flat = lambda a: a.reshape(-1).float().contiguous()
+        rays_x, rays_y = flat(rays_info["rays_x"]), flat(rays_info["rays_y"])
+        poses = (rays_info["poses"].float() if self.poses is None else self.poses).contiguous()
+        if self.random_hwindow > 0:
+            noise = torch.randn((R, self.num_pt, 2), device=dev) if noise is None else noise.reshape(R, self.num_pt, 2).float().contiguous()
+        else:
+            noise = None
+        if self.kernel_type == "PBE" and feats is not None:
+            feats = feats.reshape(R * self.num_pt, self.feat_cnl).float().contiguous()
+        else:
+            feats = None
+        trans = self.pattern_trans if self.optim_trans else None
+        if type(self.img_embed) is ViewEmbedding:
+            table = self.img_embed.img_embed
+            out = _SparseBlurFn.apply(self._desc(H, W, K, table.shape[1], table.shape[0]), ids, None, rays_x, rays_y, poses, noise, feats, self.pattern_pos,
+                                      trans, table, *self._net())
+            new_rays, weight, align, img_embed = out
+        else:
+            x = self.img_embed(ids).float().contiguous()
+            new_rays, weight, align, _ = _SparseBlurFn.apply(self._desc(H, W, K, x.shape[1], 0), ids, x, rays_x, rays_y, poses, noise, feats, self.pattern_pos,
+                                                             trans, None, *self._net())
+            img_embed = x
+        return new_rays, weight, (None if align is None else align.reshape(())), ({"img_embed": img_embed} if return_img_embed else {})

@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "evd_common.h"
+#include "mfma_f32_tile.h"
 #include "rigid_blur_se3.h"
 
 namespace evd {
@@ -29,8 +30,6 @@ constexpr int RB_WS = 17;             // weight-head row (M + 1 <= 16)
 constexpr int RB_MAX_TILES = 3 * 4 * 9 + 2 * 3 * 5 + 5;        // weight-gradient tiles at the largest shape
 constexpr int RB_TPW = (RB_MAX_TILES + RB_NW - 1) / RB_NW;     // ... of one wavefront
 constexpr int RB_MAX_BLOCKS = 64;
-
-typedef float rb_f4 __attribute__((ext_vector_type(4)));
 
 struct RbK {
     evd_rigid_blur_params p;
@@ -56,34 +55,6 @@ struct RbSmem {
     float dp[3][RB_TR][RB_PS];
     float dray[RB_TR][RB_MAXM + 1][6];
 };
-
-// One wavefront, one 16 x 16 tile: acc[i] (row 4 (lane / 16) + i, column lane % 16) += sum_k A[m sa_m + k sa_k] B[n sb_n + k sb_k], m < Mv,
-// k < K (A is guarded: parameters are read in place; B is a zero-padded LDS array).
-__device__ __forceinline__ rb_f4 rb_tile(rb_f4 acc, const float* A, int sa_m, int sa_k, int Mv, int K, const float* B, int sb_n, int sb_k) {
-    const int lane = threadIdx.x & 63, mn = lane & 15, kq = lane >> 4;
-    const bool am = mn < Mv;
-    const float* a = A + (am ? mn : 0) * sa_m;
-    const float* b = B + mn * sb_n;
-    for (int k0 = 0; k0 < K; k0 += 16) {
-        float av[4], bv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = k0 + 4 * u + kq;
-            const bool in = am && k < K;
-            av[u] = a[(in ? k : 0) * sa_k];
-            av[u] = in ? av[u] : 0.f;
-            bv[u] = k < K ? b[k * sb_k] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
-    }
-    return acc;
-}
-__device__ __forceinline__ rb_f4 rb_zero() {
-    rb_f4 z;
-    z[0] = z[1] = z[2] = z[3] = 0.f;
-    return z;
-}
 
 __device__ __forceinline__ const float* rb_branch_w(const RbK& k, int b) { return b == 0 ? k.p.r_branch_w : b == 1 ? k.p.v_branch_w : k.p.w_branch_w; }
 __device__ __forceinline__ const float* rb_branch_b(const RbK& k, int b) { return b == 0 ? k.p.r_branch_b : b == 1 ? k.p.v_branch_b : k.p.w_branch_b; }

@@ -220,8 +220,9 @@ class NeRFAll:
         else:
             from .voxnerf import VoxelNeRFRayFeatures, VoxelNeRFSampleFeatures
             # kernel_type PBE: the coarse level composites its geo features and runs its colour network per ray (renderer.py:30-34,
-            # voxnerf.py:223-239) -- built for inference (render / coarse_render); its training forward needs the PDRF blur model
-            # (networks/pdrf/blurmodel.py, out of scope: no shipped config uses it)
+            # voxnerf.py:223-239) -- built for inference (render / coarse_render).  The blur model that consumes them is built
+            # (blurmodel.SparseBlurKernel, kernel_type PBE, takes feats and returns their gradient); the training forward still needs the
+            # differentiable composite-feature coarse render in front of it (_check_kernel_type)
             ic = 3 * (1 + 2 * args.multires)
             rm = _args_get(args, "render_rmnearplane", 0)
             self.mlp_coarse = VoxelNeRFRayFeatures(
@@ -511,18 +512,18 @@ class NeRFAll:
         return torch.cat([o, d, nf, vd], -1)
 
     def forward_train(self, H, W, K, rays, params_coarse, params_fine, rays_info=None, force_naive=True, ndc=True, near=0., far=1.,
-                      N_samples=64, N_importance=0, tv=True, **kw):
+                      N_samples=64, N_importance=0, tv=True, kernel_noise=None, **kw):
         """The training branch of NeRFAll.forward (renderer.py:266-397) under autograd: [blur kernel -> P warped rays per pixel]
         -> ray packing -> render_rays_train -> [composition with the kernel's weights] ; returns the reference's
         (rgb, rgb0, other_loss, other_tensors).  Gradients reach params_coarse / params_fine (trainable_parameters) and, through
         the rays, the kernelsnet (a PyTorch module, as in the reference).  kw: lindisp, perturb, white_bkgd, raw_noise_std and the
-        explicit random draws of render_rays_train."""
+        explicit random draws of render_rays_train; kernel_noise: the DSK kernel's explicit [R, P, 2] draw (SparseBlurKernel.forward's `noise`)."""
         other_loss, other_tensors = {}, {}
         use_kernel = self.kernelsnet is not None and not force_naive
         if use_kernel:
-            if self.kernel_type != "RBK":
-                raise NotImplementedError("only the RBK kernel of the shipped configs is supported")
-            new_rays, weight1, align_loss, extra1 = self.kernelsnet(H, W, K, rays, rays_info, feats=None, return_img_embed=self.use_awp)
+            self._check_kernel_type()
+            new_rays, weight1, align_loss, extra1 = self.kernelsnet(H, W, K, rays, rays_info, feats=None, return_img_embed=self.use_awp,
+                                                                    **({} if kernel_noise is None else {"noise": kernel_noise}))
             ray_num, pt_num = new_rays.shape[:2]
             flat_rays = new_rays.reshape(-1, 3, 2)
         else:
@@ -914,15 +915,15 @@ class NeRFAll:
             pc, pf = self._current_params()
             return self.forward_train(H, W, K, rays, pc, pf, rays_info=rays_info, force_naive=kw.pop("force_naive", True), **kw)
         force_baseline = kwargs.pop("force_naive", True)
+        kernel_noise = kwargs.pop("kernel_noise", None)
         return_pts0_rgb = kwargs.pop("return_pts0_rgb", False)
         N_importance = kwargs.get("N_importance", 0)
         other_loss, other_tensors = {}, {}
         if self.kernelsnet is not None and not force_baseline:
-            if self.kernel_type != "RBK":
-                raise NotImplementedError("only the RBK kernel of the shipped configs is supported")
+            self._check_kernel_type()
             from .losses import weighted_sum
-            new_rays, weight1, align_loss, extra1 = self.kernelsnet(H, W, K, rays, rays_info, feats=None,
-                                                                    return_img_embed=self.use_awp)
+            new_rays, weight1, align_loss, extra1 = self.kernelsnet(H, W, K, rays, rays_info, feats=None, return_img_embed=self.use_awp,
+                                                                    **({} if kernel_noise is None else {"noise": kernel_noise}))
             extra1 = {f"stage1_{k}": v for k, v in extra1.items()}
             ray_num, pt_num = new_rays.shape[:2]
             rgb, depth, acc, extras = self.render(H, W, K, chunk, new_rays.reshape(-1, 3, 2), **kwargs)
@@ -950,6 +951,16 @@ class NeRFAll:
             other_tensors["stage1_rgb1_pts0"] = extras["rgb0"]
         self._tv(other_loss, N_importance)
         return rgb, extras["rgb0"] if "rgb0" in extras else None, other_loss, other_tensors
+
+    def _check_kernel_type(self):
+        """RBK (blurmodel.RigidBlurKernel) and DSK (blurmodel.SparseBlurKernel) compose the P renders of a pixel with the kernel's weights
+        (renderer.py:299,332-354).  PBE's kernel reads the coarse level's composited features of the pixel's own ray first (:286-302)."""
+        if self.kernel_type == "PBE":
+            raise NotImplementedError("kernel_type PBE in training needs the differentiable composite-feature coarse render, which is not built: "
+                                      "coarse_render returns the features, but no gradient reaches the coarse level through them "
+                                      "(blurmodel.SparseBlurKernel itself takes feats and returns their gradient)")
+        if self.kernel_type not in ("RBK", "DSK"):
+            raise NotImplementedError(f"kernel_type {self.kernel_type!r}: RBK and DSK are built")
 
     def _tv(self, other_loss, N_importance):
         """TV regulariser of the tri-planes, renderer.py:361-365 / :385-389."""

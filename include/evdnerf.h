@@ -119,6 +119,45 @@ int evd_rigid_blur_forward(const evd_rigid_blur_desc* d, const evd_rigid_blur_pa
 int evd_rigid_blur_backward(const evd_rigid_blur_desc* d, const evd_rigid_blur_params* p, const float* rays, const long* ids, const float* x, long R,
                             const float* d_new_rays, const float* d_weight, const float* d_img_embed, float* grads, float* d_rays, float* d_x,
                             void* workspace, size_t workspace_bytes, void* stream);
+/* BlurModel.forward, networks/pdrf/blurmodel.py:109-224 (kernel_type DSK and PBE: the sparse kernel of Deblur-NeRF / PDRF), with
+ * ViewEmbedding.forward in front: canonical positions -> embedded rows -> linears / linears1 -> offsets, translations, softmax weights ->
+ * the P rays of every pixel (the call site is networks/renderer.py:303-304, the module is built at run_nerf.py:184-203).  The parameters
+ * are the reference module's own tensors, float32 in torch layout, read in place.
+ *   kernel_type 0 = DSK, 1 = PBE (point 0 keeps the pixel's own ray, no align); num_pt = P (1..16); in_embed 1..4, spatial_embed 0..4 =
+ *   frequencies of the two positional embeddings; embed_cnl = C, width of an image's embedding row; feat_cnl = F, width of a row's feats
+ *   columns (PBE; 0 for DSK); row width 2 (1 + 2 in_embed) + C + F + (spatial_embed ? 2 (1 + 2 spatial_embed) : 0) <= 127; num_hidden
+ *   1..4 layers of num_wide 1..64 units; n_img = rows of the embedding table (0 without one); n_pattern = rows of pattern_pos /
+ *   pattern_trans (1 with isglobal); poses_per_image = n > 0: poses is [n, 3, 4] indexed by ids (the module's `poses` buffer), 0: [R, 3, 4];
+ *   H, W = image size (spatial embedding); fx, fy, cx, cy = K[0][0], K[1][1], K[0][2], K[1][2].  Anything else: EVD_E_INVALID. */
+typedef struct {
+    int kernel_type, num_pt, in_embed, spatial_embed, embed_cnl, feat_cnl, num_hidden, num_wide, short_cut, isglobal, optim_trans,
+        optim_spatialvariant_trans, n_img, n_pattern, poses_per_image, H, W;
+    float kernel_hwindow, random_hwindow, fx, fy, cx, cy;
+} evd_sparse_blur_desc;
+typedef struct {
+    const float *pattern_pos, *pattern_trans;                /* dev [n_pattern, P, 2]; pattern_trans NULL without optim_trans */
+    const float* table;                                      /* img_embed.img_embed dev [n_img, C], or NULL */
+    const float *linears_w[4], *linears_b[4];                /* linears.{0,2,..}: dev [num_wide, row width | num_wide], [num_wide] */
+    const float *linears1_w[2], *linears1_b[2];              /* linears1.{0,2}: dev [num_wide, (row width +) num_wide], [3 | 5, num_wide] */
+} evd_sparse_blur_params;
+/* bytes of the workspace both calls take for R rays (0 for an unsupported descriptor) */
+size_t evd_sparse_blur_workspace_bytes(const evd_sparse_blur_desc* d, long R);
+/* One launch for the network and the rays; DSK's align is a mean over the batch, which a second launch of one workgroup sums from per-ray
+ * terms.  ids dev [R] int64; a ray's embedding row is table[ids[r]] or, with x != NULL, x[r] (x dev [R, C]); rays_x, rays_y dev [R];
+ * poses dev [R, 3, 4] (or [n, 3, 4]); noise dev [R, P, 2] standard normal or NULL (no perturbation); feats dev [R P, F] or NULL (zeros).
+ * -> new_rays dev [R, P, 3, 2], weight dev [R, P], align dev [1] (DSK; NULL allowed for PBE), img_embed dev [R, C] (the rows, bit for bit). */
+int evd_sparse_blur_forward(const evd_sparse_blur_desc* d, const evd_sparse_blur_params* p, const long* ids, const float* x, const float* rays_x,
+                            const float* rays_y, const float* poses, const float* noise, const float* feats, long R, float* new_rays, float* weight,
+                            float* align, float* img_embed, void* workspace, size_t workspace_bytes, void* stream);
+/* torch.autograd of the above: two launches, no atomics, the same bits on every run.  d_new_rays dev [R, P, 3, 2], d_weight dev [R, P],
+ * d_align dev [1] or NULL, d_img_embed dev [R, C] or NULL (what arrives at the img_embed output).
+ * -> grads dev: one flat float32 buffer, overwritten: pattern_pos, pattern_trans (with optim_trans), table [n_img, C] (x == NULL form),
+ * linears.{0,2,..}.{weight,bias}, linears1.{0,2}.{weight,bias}; d_x dev [R, C] or NULL (x != NULL form); d_feats dev [R P, F] or NULL.
+ * R = 0 writes zeros.  No gradient goes to poses, pixel coordinates or the intrinsics. */
+int evd_sparse_blur_backward(const evd_sparse_blur_desc* d, const evd_sparse_blur_params* p, const long* ids, const float* x, const float* rays_x,
+                             const float* rays_y, const float* poses, const float* noise, const float* feats, long R, const float* d_new_rays,
+                             const float* d_weight, const float* d_align, const float* d_img_embed, float* grads, float* d_x, float* d_feats,
+                             void* workspace, size_t workspace_bytes, void* stream);
 /* The NaN / Inf guard of render_rays, networks/renderer.py:259-263 (there: isnan().any() + isinf().any() per result key = two
  * host synchronisations per key).  Here one launch: ptrs host[n_keys] (device arrays), counts host[n_keys] (floats per array),
  * n_keys <= 16 -> flags dev [n_keys] (unsigned): bit 0 = the key contains a NaN, bit 1 = an Inf.  Nothing synchronises; the caller

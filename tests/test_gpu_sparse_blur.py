@@ -1,0 +1,291 @@
+"""The sparse blur kernel network on the device (csrc/kernel_sparse_blur.hip through evdeblurnerf_amd.blurmodel.SparseBlurKernel) against the
+float64 restatement tests/sparse_blur_ref.py, on golden G39's four cases, and inside NeRFAll's training call with kernel_type DSK.
+
+Bounds, as in tests/test_gpu_rigid_blur.py.  The kernel gets the REFERENCE's own float32 error, as the fixture records it (ref_f32_err: the
+reference's float32 outputs / autograd gradients against the same module in float64; max abs for outputs, |delta| for align, relative L2
+per gradient tensor), times 4 for a different summation order; outputs get a floor of 2^-23 max|value|, so that a record that happens to be
+exact does not demand bit equality.  Where a test runs a subset or a multiple of a case's rays, per-tensor records do not carry over; it
+then uses the case's output records and the WORST tensor's gradient record, times 4 again.  In the whole call the kernel's parameter
+gradients get the `side` tolerance tests/test_gpu_train_call.py applies to g.new_rays / g.weight, whose linear images they are."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+import sparse_blur_ref as SR
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+FACTOR = 4.0
+KMAT = np.array([[350, 0, 200], [0, 350, 200], [0, 0, 1]], np.float32)
+EXTRA = {"dsk": {}, "dsk_full": dict(spatial_embed=2, random_hwindow=0.0), "dsk_sv": {}, "pbe": dict(spatial_embed=2)}      # what the tensors do not fix
+
+
+def T(a):
+    return torch.tensor(np.ascontiguousarray(a), device=DEV)
+
+
+def _module(c, tag):
+    from evdeblurnerf_amd.blurmodel import SparseBlurKernel
+    return SparseBlurKernel.from_state_dict(c["params"], c["cfg"]["kernel_type"], c["cfg"]["kernel_hwindow"], **EXTRA[tag]).to(DEV)
+
+
+def _run(mod, b, with_feats=True):
+    """b: dict(ids, rays_x, rays_y, poses, noise, feats, proj) -> outputs (numpy), {name: gradient} (feats' under 'feats')"""
+    mod.zero_grad(set_to_none=True)
+    info = {"images_idx": T(b["ids"]).reshape(-1, 1), "rays_x": T(b["rays_x"]), "rays_y": T(b["rays_y"])}
+    if b["poses"] is not None:
+        info["poses"] = T(b["poses"])
+    feats = T(b["feats"]).requires_grad_(True) if with_feats and b["feats"] is not None else None
+    new_rays, weight, align, extras = mod(400, 400, KMAT, None, info, feats=feats, return_img_embed=True, noise=None if b["noise"] is None else T(b["noise"]))
+    assert set(extras) == {"img_embed"} and (align is None) == (mod.kernel_type == "PBE")
+    proj = b["proj"]
+    loss = (new_rays * T(proj["new_rays"])).sum() + (weight * T(proj["weight"])).sum() + (extras["img_embed"] * T(proj["img_embed"])).sum()
+    if align is not None:
+        assert align.shape == ()
+        loss = loss + SR.ALIGN_C * align
+    loss.backward()
+    out = {k: v.detach().cpu().numpy() for k, v in dict(new_rays=new_rays, weight=weight, img_embed=extras["img_embed"]).items()}
+    if align is not None:
+        out["align"] = align.detach().cpu().numpy()
+    grads = {k: p.grad.detach().cpu().numpy().copy() for k, p in mod.named_parameters()}
+    if feats is not None:
+        grads["feats"] = feats.grad.cpu().numpy()
+    return out, grads
+
+
+def _bound(c, k, ref_value):
+    return max(FACTOR * c["err_out"][k], 2.0 ** -23 * float(np.abs(ref_value).max()))
+
+
+def _check(what, c, out, grads, ref, per_tensor):
+    """outputs against ref within the case's output records; gradients within their own records (per_tensor) or the worst tensor's"""
+    ref_g = dict(ref["grads"], **({"feats": ref["d_feats"]} if "d_feats" in ref else {}))
+    assert set(grads) == set(ref_g)
+    errs = {k: float(np.abs(out[k] - ref[k]).max()) for k in ("new_rays", "weight") + (("align",) if "align" in out else ())}
+    bounds = {k: _bound(c, k, ref[k]) for k in errs}
+    gerr = {k: SR.rel_l2(grads[k], ref_g[k]) for k in ref_g}
+    worst = max(c["err_g"].values())
+    gbound = {k: FACTOR * (c["err_g"][k] if per_tensor else worst) for k in gerr}
+    for k, e in errs.items():
+        print(f"{what} {k}: {e:.2e} (bound {bounds[k]:.2e})")
+    for k, e in gerr.items():
+        print(f"{what} d {k}: {e:.2e} of the norm (bound {gbound[k]:.2e})")
+    for k, e in errs.items():
+        assert e <= bounds[k], (k, e, bounds[k])
+    for k, e in gerr.items():
+        assert e <= gbound[k], (k, e, gbound[k])
+
+
+def _ref(c, b):
+    return SR.run(c["params"], c["cfg"], 400, 400, c["K4"], b["ids"], b["rays_x"], b["rays_y"], b["poses"], b["noise"], b["proj"], feats=b["feats"])
+
+
+@pytest.mark.parametrize("tag", SR.G39_CASES)
+def test_G39_outputs_and_gradients(tag):
+    g = load_golden("G39_sparse_blur")
+    c = SR.g39_case(g, tag)
+    ref = SR.g39_reference(g, tag)
+    mod = _module(c, tag)
+    assert {k for k, _ in mod.named_parameters()} == set(SR.param_keys(c["cfg"]))
+    out, grads = _run(mod, c)
+    R, P = len(c["ids"]), c["cfg"]["num_pt"]
+    assert out["new_rays"].shape == (R, P, 3, 2) and out["weight"].shape == (R, P)
+    assert np.array_equal(out["img_embed"], c["params"]["img_embed.img_embed"][c["ids"]])
+    _check(f"G39 {tag}", c, out, grads, ref, per_tensor=True)
+    assert not grads["img_embed.img_embed"][SR.ABSENT_IMAGE].any()
+    assert np.abs(grads["img_embed.img_embed"]).sum(1).astype(bool).sum() == len(set(c["ids"].tolist()))
+    if not c["cfg"]["isglobal"]:
+        assert not grads["pattern_pos"][SR.ABSENT_IMAGE].any()
+        assert "pattern_trans" not in grads or not grads["pattern_trans"][SR.ABSENT_IMAGE].any()
+    if tag == "pbe":                                                 # the feats=None forward
+        out0, _ = _run(mod, c, with_feats=False)
+        ref0 = SR.run(c["params"], c["cfg"], 400, 400, c["K4"], c["ids"], c["rays_x"], c["rays_y"], c["poses"], c["noise"], c["proj"])
+        for k in ("new_rays", "weight"):
+            e = float(np.abs(out0[k] - ref0[k]).max())
+            bound = max(FACTOR * float(g["pbe.ref_f32_err.out_nofeats." + k]), 2.0 ** -23 * float(np.abs(ref0[k]).max()))
+            print(f"G39 pbe feats=None {k}: {e:.2e} (bound {bound:.2e})")
+            assert e <= bound, (k, e)
+
+
+@pytest.mark.parametrize("tag,R", [(tag, R) for tag, T_ in (("dsk", 3), ("dsk_full", 1)) for R in sorted({1, max(T_ - 1, 1), T_, T_ + 1})])
+def test_tile_edges(tag, R):
+    """a tile holds T = 16 // P whole rays: T = 3 at P = 5, T = 1 at P = 10"""
+    from evdeblurnerf_amd.blurmodel import SparseBlurKernel
+    g = load_golden("G39_sparse_blur")
+    c = SR.g39_case(g, tag)
+    assert SparseBlurKernel.TILE_ROWS // c["cfg"]["num_pt"] == {"dsk": 3, "dsk_full": 1}[tag]
+    b = SR.subset(c, np.arange(R) + 40)
+    mod = _module(c, tag)
+    out, grads = _run(mod, b)
+    _check(f"{tag} R = {R}", c, out, grads, _ref(c, b), per_tensor=False)
+    absent = sorted(set(range(7)) - set(b["ids"].tolist()))
+    assert not grads["img_embed.img_embed"][absent].any() and not grads["pattern_pos"][absent].any()
+
+
+def test_empty_batch_is_a_no_op():
+    g = load_golden("G39_sparse_blur")
+    c = SR.g39_case(g, "dsk_full")
+    mod = _module(c, "dsk_full")
+    out, grads = _run(mod, SR.subset(c, np.arange(0)))
+    assert out["new_rays"].shape == (0, 10, 3, 2) and out["weight"].shape == (0, 10) and out["img_embed"].shape == (0, 32)
+    assert all(not v.any() for v in grads.values()) and set(grads) == set(SR.param_keys(c["cfg"]))
+
+
+def test_backward_twice_gives_the_same_bits_and_more_tiles_than_workgroups():
+    """T = 3 rays per tile at P = 5 and at most GRID_CAP = 128 workgroups: 404 rays = 135 tiles, so some workgroups take two tiles with their
+    weight-gradient accumulators resident"""
+    from evdeblurnerf_amd.blurmodel import SparseBlurKernel
+    g = load_golden("G39_sparse_blur")
+    c = SR.g39_case(g, "dsk")
+    R = SparseBlurKernel.GRID_CAP * (SparseBlurKernel.TILE_ROWS // 5) + 20
+    rs = np.random.RandomState(13)
+    idx = rs.randint(0, len(c["ids"]), R)
+    b = SR.subset(c, idx)
+    b["ids"] = rs.choice([0, 1, 2, 4, 5, 6], R).astype(np.int64)
+    b["noise"] = rs.standard_normal((R, 5, 2)).astype(np.float32)
+    b["proj"] = dict(new_rays=rs.standard_normal((R, 5, 3, 2)).astype(np.float32), weight=rs.standard_normal((R, 5)).astype(np.float32),
+                     img_embed=rs.standard_normal((R, 32)).astype(np.float32))
+    mod = _module(c, "dsk")
+    out1, g1 = _run(mod, b)
+    out2, g2 = _run(mod, b)
+    for k in g1:
+        assert np.array_equal(g1[k], g2[k]), k
+    assert all(np.array_equal(out1[k], out2[k]) for k in out1)
+    _check(f"R = {R}", c, out1, g1, _ref(c, b), per_tensor=False)
+    assert not g1["img_embed.img_embed"][SR.ABSENT_IMAGE].any() and not g1["pattern_pos"][SR.ABSENT_IMAGE].any()
+
+
+def test_per_ray_form_equals_the_table_form():
+    """x = table[ids] through the Function: the same outputs and network gradients bit for bit (the same arithmetic on the same rows), and
+    d x = the rows whose per-image sums are the table's gradient"""
+    from evdeblurnerf_amd.blurmodel import _SparseBlurFn
+    g = load_golden("G39_sparse_blur")
+    c = SR.g39_case(g, "dsk")
+    mod = _module(c, "dsk")
+    out, grads = _run(mod, c)
+    table = mod.img_embed.img_embed.detach()
+    ids = T(c["ids"])
+    x = table[ids].clone().requires_grad_(True)
+    mod.zero_grad(set_to_none=True)
+    new_rays, weight, align, img_embed = _SparseBlurFn.apply(mod._desc(400, 400, KMAT, 32, 0), ids, x, T(c["rays_x"]).reshape(-1), T(c["rays_y"]).reshape(-1),
+                                                             T(c["poses"]), T(c["noise"]), None, mod.pattern_pos, None, None, *mod._net())
+    proj = c["proj"]
+    ((new_rays * T(proj["new_rays"])).sum() + (weight * T(proj["weight"])).sum() + (img_embed * T(proj["img_embed"])).sum() + SR.ALIGN_C * align.sum()).backward()
+    assert np.array_equal(new_rays.detach().cpu().numpy(), out["new_rays"]) and np.array_equal(weight.detach().cpu().numpy(), out["weight"])
+    assert np.array_equal(align.detach().cpu().numpy().reshape(()), out["align"]) and torch.equal(img_embed.detach(), x.detach())
+    for k, p in mod.named_parameters():
+        if k != "img_embed.img_embed":
+            assert np.array_equal(p.grad.cpu().numpy(), grads[k]), k
+    ref = SR.run(c["params"], c["cfg"], 400, 400, c["K4"], c["ids"], c["rays_x"], c["rays_y"], c["poses"], c["noise"], proj,
+                 x=c["params"]["img_embed.img_embed"][c["ids"]])
+    e = SR.rel_l2(x.grad.cpu().numpy(), ref["d_x"])
+    print(f"per-ray form d x: {e:.2e} of the norm (bound {FACTOR:.0f} x {c['err_g']['img_embed.img_embed']:.2e})")
+    assert e <= FACTOR * c["err_g"]["img_embed.img_embed"]
+    summed = np.zeros_like(grads["img_embed.img_embed"], dtype=np.float64)
+    np.add.at(summed, c["ids"], x.grad.cpu().numpy().astype(np.float64))
+    assert SR.rel_l2(grads["img_embed.img_embed"], summed) < 1e-6                    # float32 sums of at most 100 rows
+
+
+@pytest.mark.parametrize("kw,what", [(dict(num_wide=65), "num_wide"), (dict(num_hidden=5), "num_hidden"), (dict(view_embed_cnl=120), "row width"),
+                                     (dict(num_pt=17), "num_pt"), (dict(in_embed=5), "in_embed"), (dict(spatial_embed=5), "spatial_embed")])
+def test_rejected_shapes(kw, what):
+    from evdeblurnerf_amd._lib import EvdError
+    from evdeblurnerf_amd.blurmodel import SparseBlurKernel
+    kw = dict(dict(num_pt=5), **kw)
+    mod = SparseBlurKernel(4, kw.pop("num_pt"), 10, "DSK", **kw).to(DEV)
+    info = {"images_idx": torch.zeros((5, 1), dtype=torch.int64, device=DEV), "rays_x": torch.zeros((5, 1), device=DEV),
+            "rays_y": torch.zeros((5, 1), device=DEV), "poses": torch.zeros((5, 3, 4), device=DEV)}
+    with pytest.raises(EvdError, match="evd_sparse_blur_forward") as ei:
+        mod(400, 400, KMAT, None, info)
+    assert what in str(ei.value)
+
+
+class _Replay(torch.nn.Module):
+    """stands where the kernel stood and replays its recorded outputs as autograd leaves"""
+
+    def __init__(self, seen):
+        super().__init__()
+        self.leaf = {k: v.detach().clone().requires_grad_(True) for k, v in seen.items()}
+
+    def forward(self, H, W, K, rays, rays_info, feats=None, return_img_embed=False, **kw):
+        return self.leaf["new_rays"], self.leaf["weight"], self.leaf["align"], ({"img_embed": self.leaf["img_embed"]} if return_img_embed else {})
+
+
+def test_whole_training_call_with_kernel_type_DSK():
+    """tests/test_gpu_train_call.py's small c2f NeRFAll (5 points per pixel, AWP on an embedding of width 32) with kernel_type DSK and the kernel of
+    G39's `dsk` case: the call runs, composes rgb = sum_p weight rgb_pts, hands align on as other_loss['align'] [1, 1], and the kernel's
+    parameter gradients are the float64 backward (tests/sparse_blur_ref.py) of the gradients that a replay of the kernel's outputs as
+    leaves receives in a second call"""
+    from test_gpu_train_call import CALL_KW, G32_CASES, _model, rel
+    from evdeblurnerf_amd import weights as W
+    prec, awp_kind = "f16x3", "torch"
+    tol = G32_CASES[(prec, awp_kind)]
+    g = load_golden("G32_train_forward")
+    c = SR.g39_case(load_golden("G39_sparse_blur"), "dsk")
+    kern = _module(c, "dsk")
+    seen = {}
+    kern.register_forward_hook(lambda m, i, o: seen.update(new_rays=o[0], weight=o[1], align=o[2], img_embed=o[3]["img_embed"]))
+    model, awp, _ = _model(32, g, prec, awp_kind, kern)
+    model.kernel_type = "DSK"
+    render = model.render_rays_train
+    model.render_rays_train = lambda *a, **k: (lambda out: (seen.update(rgb_map=out["rgb_map"]), out)[1])(render(*a, **k))
+    R, P = 32, 5
+    Kc = W.synthetic_camera()
+    rs = np.random.RandomState(7)
+    poses = np.concatenate([np.eye(3, dtype=np.float32)[None].repeat(R, 0) + 0.02 * rs.standard_normal((R, 3, 3)).astype(np.float32),
+                            0.1 * rs.standard_normal((R, 3, 1)).astype(np.float32)], -1)
+    info = {"images_idx": T(c["ids"][:R]).reshape(-1, 1), "rays_x": T(c["rays_x"][:R]), "rays_y": T(c["rays_y"][:R]), "poses": T(poses)}
+    rays = torch.zeros((R, 3, 2), device=DEV)                                         # (BlurModel does not read them)
+    proj = {k: T(rs.standard_normal((R, 3)).astype(np.float32)) for k in ("rgb", "rgb1", "rgb_awp")}
+
+    def call():
+        rgb, rgb1, other_loss, other_tensors = model(400, 400, Kc, 1 << 20, rays=rays, rays_info=info, force_naive=False, return_pts0_rgb=True,
+                                                     kernel_noise=T(c["noise"][:R]), **CALL_KW)
+        loss = (rgb * proj["rgb"]).sum() + (rgb1 * proj["rgb1"]).sum() + (other_tensors["rgb_awp"] * proj["rgb_awp"]).sum() + \
+            0.3 * other_loss["align"].sum() + 0.1 * other_loss["TV"].sum()
+        loss.backward()
+        return rgb, other_loss, other_tensors
+
+    rgb, other_loss, other_tensors = call()                                           # it no longer raises
+    assert set(other_loss) == {"TV", "align"} and {"rgb_awp", "stage1_img_embed", "stage1_rgb_pts0", "stage1_rgb1_pts0"} <= set(other_tensors)
+    assert other_loss["align"].shape == (1, 1) and torch.equal(other_loss["align"].reshape(()), seen["align"])
+    assert seen["new_rays"].shape == (R, P, 3, 2) and seen["rgb_map"].shape == (R * P, 3)
+    assert torch.equal(rgb, (seen["rgb_map"].reshape(R, P, 3) * seen["weight"][..., None]).sum(1))
+    assert torch.equal(other_tensors["stage1_rgb_pts0"], seen["rgb_map"].reshape(R, P, 3)[:, 0]) and other_tensors["rgb_awp"].shape == (R, 3)
+    grads = {k: p.grad.detach().cpu().numpy().copy() for k, p in kern.named_parameters()}
+    model.kernelsnet = rp = _Replay({k: seen[k] for k in ("new_rays", "weight", "align", "img_embed")})
+    rgb2, _, _ = call()
+    assert rel(rgb2.detach().cpu().numpy(), rgb.detach().cpu().numpy()) < 1e-6
+    K4 = (float(Kc[0, 0]), float(Kc[1, 1]), float(Kc[0, 2]), float(Kc[1, 2]))
+    ref = SR.run(c["params"], c["cfg"], 400, 400, K4, c["ids"][:R], c["rays_x"][:R], c["rays_y"][:R], poses, c["noise"][:R], None,
+                 d_out={k: v.grad.cpu().numpy() for k, v in rp.leaf.items()})
+    errs = {k: float(np.abs(rp.leaf[k].detach().cpu().numpy() - ref[k]).max()) for k in ("new_rays", "weight", "align")}
+    for k, e in errs.items():
+        print(f"whole call: {k} {e:.2e} (bound {_bound(c, k, ref[k]):.2e})")
+    side = {k: rel(grads[k], ref["grads"][k]) for k in grads}
+    print("whole call: kernel parameter gradients, error / norm:", {k: f"{v:.1e}" for k, v in side.items()}, f"(bound {tol['side']:.0e})")
+    for k, e in errs.items():
+        assert e <= _bound(c, k, ref[k]), (k, e)
+    assert set(side) == set(SR.param_keys(c["cfg"])) and max(side.values()) < tol["side"], side
+
+
+def test_training_with_kernel_type_PBE_still_raises():
+    """both training branches of NeRFAll.forward: the differentiable one (enable_training) and the plain one"""
+    from test_gpu_train_call import CALL_KW, _model
+    from evdeblurnerf_amd import weights as W
+    g = load_golden("G32_train_forward")
+    c = SR.g39_case(load_golden("G39_sparse_blur"), "pbe")
+    model, _, _ = _model(32, g, "f16x3", "torch", _module(c, "pbe"))
+    model.kernel_type = "PBE"
+    rays = torch.tensor(g["rays"], device=DEV)
+    info = {"images_idx": torch.tensor(g["images_idx"], device=DEV)}
+    for differentiable in (True, False):
+        levels = model._levels
+        if not differentiable:
+            model._levels = None
+        try:
+            with pytest.raises(NotImplementedError, match="composite-feature coarse render"):
+                model(400, 400, W.synthetic_camera(), 1 << 20, rays=rays, rays_info=info, force_naive=False, **CALL_KW)
+        finally:
+            model._levels = levels

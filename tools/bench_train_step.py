@@ -49,9 +49,11 @@ def main():
     ap.add_argument("--pixels", type=int, default=1024)
     ap.add_argument("--events", type=int, default=4096)
     ap.add_argument("--P", type=int, default=10)
-    ap.add_argument("--kernel", choices=["standin", "torch", "device"], default="standin",
+    ap.add_argument("--kernel", choices=["standin", "torch", "device", "dsk", "dsk-torch"], default="standin",
                     help="the blur kernel network: standin = RigidKernel above (what bench.py times), torch = RigidBlurringModel's function as PyTorch ops "
-                         "(tools/rigid_blur_torch.py), device = the library's kernels (evdeblurnerf_amd.blurmodel.RigidBlurKernel); 34 images, widths 32")
+                         "(tools/rigid_blur_torch.py), device = the library's kernels (evdeblurnerf_amd.blurmodel.RigidBlurKernel); 34 images, widths 32; "
+                         "dsk = kernel_type DSK at the options.py defaults on the library's kernels (blurmodel.SparseBlurKernel; pass --P 5), dsk-torch = the "
+                         "same function as float32 PyTorch ops (tools/sparse_blur_torch.py)")
     ap.add_argument("--awp", choices=["none", "fused", "torch"], default="none",
                     help="the shipped configs' adaptive weight proposal on the blur batch (kernel_use_awp): fused = evdeblurnerf_amd.awp.FusedAWP around a "
                          "module with the reference's surface (tools/awp_standin.py), torch = that module's plain PyTorch forward on depth_feature")
@@ -85,6 +87,22 @@ def run(a):
     blur_info = None
     if kernel_kind == "standin":
         kern = RigidKernel(a.P).to(dev)
+    elif kernel_kind in ("dsk", "dsk-torch"):
+        from evdeblurnerf_amd.blurmodel import SparseBlurKernel
+        args.kernel_type = "DSK"
+        torch.manual_seed(0)
+        kern = SparseBlurKernel(34, a.P, 10, "DSK", embed_init="normal").to(dev)
+        if kernel_kind == "dsk-torch":
+            sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+            from sparse_blur_torch import TorchSparseBlur
+            twin = TorchSparseBlur(34, a.P, 10, "DSK").to(dev)
+            twin.load_state_dict(kern.state_dict())
+            kern = twin
+        gen = torch.Generator().manual_seed(1)
+        blur_info = {"images_idx": torch.randint(0, 34, (a.pixels, 1), generator=gen).to(dev),
+                     "rays_x": (torch.randint(0, 400, (a.pixels, 1), generator=gen).float() + 0.5).to(dev),
+                     "rays_y": (torch.randint(0, 400, (a.pixels, 1), generator=gen).float() + 0.5).to(dev),
+                     "poses": torch.as_tensor(W.synthetic_pose(1)[None].repeat(a.pixels, 0)).to(dev)}
     else:
         from evdeblurnerf_amd.blurmodel import RigidBlurKernel
         torch.manual_seed(0)
@@ -158,6 +176,8 @@ def run(a):
         loss, _ = blur_loss_from_partials(pb, fine_loss_weight=0.5, w_pts0=0.1)
         if "rgb_awp" in tens:               # the AWP composition's image term (run_nerf.py:470-480)
             loss = loss + ((tens["rgb_awp"] - tgt) ** 2).mean()
+        if "align" in other:                # the DSK kernel's alignment term (run_nerf.py:502-504)
+            loss = loss + 0.1 * other["align"].sum()
         loss = loss + 0.1 * event_loss_from_partials(pe) + 0.01 * other["TV"].sum()
         opt.zero_grad(set_to_none=True)
         loss.backward()

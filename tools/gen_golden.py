@@ -1806,12 +1806,168 @@ def G38_lpips():
     print(f"  wrote {os.path.relpath(path, ROOT)}  ({os.path.getsize(path) / 1024:.1f} KiB)")
 
 
+# --------------------------------------------------------------------------- G39: the sparse blur kernel network (DSK / PBE)
+SPARSE_BLUR_CASES = {         # BlurModel constructor arguments (options.py defaults unless named); R rays of 7 images
+    "dsk": dict(kernel_type="DSK", R=100, seed=3901),
+    "dsk_full": dict(kernel_type="DSK", num_pt=10, short_cut=True, optim_trans=True, spatial_embed=2, random_hwindow=0.0, R=67, seed=3902),
+    "dsk_sv": dict(kernel_type="DSK", num_pt=3, optim_spatialvariant_trans=True, isglobal=True, num_wide=32, num_hidden=2, poses_buffer=True, R=50, seed=3903),
+    "pbe": dict(kernel_type="PBE", spatial_embed=2, R=50, seed=3904),
+}
+SPARSE_BLUR_DEFAULTS = dict(num_pt=5, kernel_hwindow=10, random_hwindow=0.25, in_embed=3, spatial_embed=0, num_hidden=3, num_wide=64, feat_cnl=15,
+                            short_cut=False, isglobal=False, optim_trans=False, optim_spatialvariant_trans=False)
+SPARSE_BLUR_N_IMG, SPARSE_BLUR_EMBED, SPARSE_BLUR_ALIGN_C = 7, 32, 0.7
+
+
+def _sparse_blur_module(cfg, sd, dtype):
+    from networks.pdrf.blurmodel import BlurModel
+    from networks.embedding import ViewEmbedding
+    ve = ViewEmbedding(num_embed=SPARSE_BLUR_N_IMG, embed_dim=SPARSE_BLUR_EMBED, init_params="normal")
+    kw = {k: v for k, v in cfg.items() if k not in ("kernel_type", "num_pt", "kernel_hwindow")}
+    kern = BlurModel(SPARSE_BLUR_N_IMG, cfg["num_pt"], cfg["kernel_hwindow"], cfg["kernel_type"], ve, view_embed_cnl=SPARSE_BLUR_EMBED,
+                     poses=t(sd["poses"]) if "poses" in sd else None, **kw)
+    kern.load_state_dict({k: t(v) for k, v in sd.items()}, strict=True)
+    return kern.to(dtype)
+
+
+def _sparse_blur_run(kern, c, feats, dtype):
+    """outputs, autograd gradients (every parameter, feats) of the recorded loss, and the smallest |hidden pre-activation| / |argument of
+    align's absolute values|, in `dtype` throughout; the module's randn_like draw is replaced by the recorded one"""
+    D = lambda a: None if a is None else t(a).to(dtype)
+    pre_min, last, hooks = [np.inf], [None], []
+    lin_relu = [m for m in kern.linears if isinstance(m, torch.nn.Linear)] + [kern.linears1[0]]
+    for m in lin_relu:
+        hooks.append(m.register_forward_hook(lambda mod, i, o: pre_min.__setitem__(0, min(pre_min[0], float(o.detach().abs().min())))))
+    hooks.append(kern.linears1.register_forward_hook(lambda mod, i, o: last.__setitem__(0, n(o).astype(np.float64))))
+    old = torch.randn_like
+    torch.randn_like = lambda x, *a, **k: D(c["noise"]).reshape(x.shape)
+    try:
+        with torch.enable_grad():
+            f = None if feats is None else D(feats).requires_grad_(True)
+            info = {"images_idx": t(c["ids"]), "rays_x": D(c["rays_x"]), "rays_y": D(c["rays_y"])}
+            if c["poses"] is not None:
+                info["poses"] = D(c["poses"])
+            new_rays, weight, align, extras = kern(400, 400, D(c["K"]), None, info, feats=f, return_img_embed=True)
+            loss = (new_rays * D(c["proj"]["new_rays"])).sum() + (weight * D(c["proj"]["weight"])).sum() + (extras["img_embed"] * D(c["proj"]["img_embed"])).sum()
+            if align is not None:
+                loss = loss + SPARSE_BLUR_ALIGN_C * align
+            named = list(kern.named_parameters())
+            g = torch.autograd.grad(loss, [p for _, p in named] + ([f] if f is not None else []), allow_unused=True)
+    finally:
+        torch.randn_like = old
+        for h in hooks:
+            h.remove()
+    out = dict(new_rays=n(new_rays), weight=n(weight), img_embed=n(extras["img_embed"]))
+    if align is not None:
+        out["align"] = n(align).reshape(1)
+    grads = {k: n(gi) for (k, _), gi in zip(named, g)}
+    if f is not None:
+        grads["feats"] = n(g[-1])
+    return out, grads, dict(pre_min=pre_min[0], x1=last[0])
+
+
+def _sparse_blur_point0(sd, cfg, c, x1):
+    """-> delta_pos [R, P, 2] and the arguments of align's absolute values (point 0 of new_rays_xy and of delta_trans), from the network's
+    last output x1 [R, P, 3 or 5]"""
+    ids = c["ids"][:, 0]
+    pick = (lambda a: np.broadcast_to(a, (len(ids),) + a.shape[1:])) if cfg["isglobal"] else (lambda a: a[ids])
+    pt = np.tanh(pick(sd["pattern_pos"]).astype(np.float64)) * cfg["kernel_hwindow"] + c["noise"].astype(np.float64) * cfg["random_hwindow"]
+    sv = cfg["optim_spatialvariant_trans"]
+    dpos = x1[..., 2:4] if sv else x1[..., 0:2]
+    trans = pick(sd["pattern_trans"]).astype(np.float64) if cfg["optim_trans"] else x1[..., 0:2] if sv else None
+    args = (dpos + pt)[:, 0].reshape(-1)
+    return dpos, args if trans is None else np.concatenate([args, trans[:, 0].reshape(-1) * 0.01])
+
+
+def G39_sparse_blur():
+    """BlurModel.forward (pdrf/blurmodel.py:109-224) with ViewEmbedding 'param' (embedding.py:6-32), the real modules on the CPU, kernel_type
+    DSK and PBE: four cases (SPARSE_BLUR_CASES), 7 images of which image 3 has no ray, H = W = 400, K = (350, 350, 200, 200), integer pixel
+    coordinates, random poses, DRAWN parameters (a fresh module weighs every point 0.19...0.21).  Recorded per case: configuration, state dict,
+    inputs (the randn_like draw included), projections, the float32 outputs and autograd gradients of
+    sum(new_rays proj) + sum(weight proj) + sum(img_embed proj) + 0.7 align, and ref_f32_err: those float32 results against the SAME module in
+    float64 on the same float32-valued inputs (max abs per output, |delta| for align, relative L2 per gradient tensor).  The seed is redrawn
+    until no hidden pre-activation and no argument of align's absolute values is within 1e-5 of its kink."""
+    out = {}
+    for tag, case in SPARSE_BLUR_CASES.items():
+        cfg = dict(SPARSE_BLUR_DEFAULTS, **{k: v for k, v in case.items() if k not in ("R", "seed", "poses_buffer")})
+        R, P = case["R"], cfg["num_pt"]
+        for attempt in range(20):
+            rs = np.random.RandomState(case["seed"] + 100 * attempt)
+            f32 = lambda *shape, s=1.0: (rs.standard_normal(shape) * s).astype(np.float32)
+            n_pat = 1 if cfg["isglobal"] else SPARSE_BLUR_N_IMG
+            e_in, e_sp = 2 * (1 + 2 * cfg["in_embed"]), (2 * (1 + 2 * cfg["spatial_embed"]) if cfg["spatial_embed"] else 0)
+            in_cnl = e_in + SPARSE_BLUR_EMBED + e_sp + (cfg["feat_cnl"] if cfg["kernel_type"] == "PBE" else 0)
+            wide, n_out = cfg["num_wide"], 5 if cfg["optim_spatialvariant_trans"] else 3
+            sd = {"pattern_pos": f32(n_pat, P, 2, s=0.5)}
+            if cfg["optim_trans"]:
+                sd["pattern_trans"] = f32(n_pat, P, 2, s=0.5)
+            sd["img_embed.img_embed"] = f32(SPARSE_BLUR_N_IMG, SPARSE_BLUR_EMBED)
+            for i in range(cfg["num_hidden"]):
+                fan = in_cnl if i == 0 else wide
+                sd[f"linears.{2 * i}.weight"], sd[f"linears.{2 * i}.bias"] = f32(wide, fan, s=(2.0 / (fan + wide)) ** 0.5), f32(wide, s=0.1)
+            fan = wide + in_cnl if cfg["short_cut"] else wide
+            sd["linears1.0.weight"], sd["linears1.0.bias"] = f32(wide, fan, s=(2.0 / (fan + wide)) ** 0.5), f32(wide, s=0.1)
+            sd["linears1.2.weight"], sd["linears1.2.bias"] = f32(n_out, wide, s=0.5), f32(n_out, s=0.5)
+            if case.get("poses_buffer"):
+                sd["poses"] = f32(SPARSE_BLUR_N_IMG, 3, 4)
+            present = [i for i in range(SPARSE_BLUR_N_IMG) if i != 3]                 # image 3 has no ray in the batch
+            c = dict(ids=rs.choice(present, size=(R, 1)).astype(np.int64), rays_x=rs.randint(0, 400, (R, 1)).astype(np.float32),
+                     rays_y=rs.randint(0, 400, (R, 1)).astype(np.float32), poses=None if case.get("poses_buffer") else f32(R, 3, 4),
+                     noise=f32(R, P, 2), K=np.array([[350, 0, 200], [0, 350, 200], [0, 0, 1]], np.float32),
+                     proj=dict(new_rays=f32(R, P, 3, 2), weight=f32(R, P), img_embed=f32(R, SPARSE_BLUR_EMBED)))
+            feats = f32(R * P, cfg["feat_cnl"]) if cfg["kernel_type"] == "PBE" else None
+            k32, k64 = _sparse_blur_module(cfg, sd, torch.float32), _sparse_blur_module(cfg, sd, torch.float64)
+            o32, g32, pre32 = _sparse_blur_run(k32, c, feats, torch.float32)
+            o64, g64, pre64 = _sparse_blur_run(k64, c, feats, torch.float64)
+            kink = min(pre32["pre_min"], pre64["pre_min"])
+            dpos, align_args = _sparse_blur_point0(sd, cfg, c, pre64["x1"])
+            if cfg["kernel_type"] == "DSK":
+                kink = min(kink, float(np.abs(align_args).min()))
+            if kink >= 1e-5:
+                break
+            print(f"   {tag}: a value {kink:.1e} from a kink, redrawing")
+        else:
+            raise AssertionError(f"{tag}: no seed keeps the float32 / float64 comparison free of kink flips")
+        assert all(v.dtype == np.float32 for v in o32.values()) and all(v.dtype == np.float64 for v in o64.values())
+        assert np.array_equal(o32["img_embed"], sd["img_embed.img_embed"][c["ids"][:, 0]])
+        span = o32["weight"].max(1) - o32["weight"].min(1)
+        assert (span >= 0.1).mean() > 0.5, f"{tag}: weights span {np.median(span):.2f} within a ray"
+        assert np.abs(dpos).max() >= 1.0, f"{tag}: |delta_pos| reaches {np.abs(dpos).max():.2f} pixels only"
+        pre = tag + "."
+        out.update({pre + "cfg." + k: np.asarray(v) for k, v in cfg.items()})
+        out.update({pre + "sd." + k: v for k, v in sd.items()})
+        out.update({pre + k: c[k] for k in ("ids", "rays_x", "rays_y", "noise") if not (k == "noise" and cfg["random_hwindow"] == 0)})
+        out[pre + "K4"] = np.array([350, 350, 200, 200], np.float64)
+        if c["poses"] is not None:
+            out[pre + "poses"] = c["poses"]
+        out.update({pre + "proj." + k: v for k, v in c["proj"].items()})
+        out.update({pre + "out." + k: v for k, v in o32.items()})
+        out.update({pre + "g." + k: v for k, v in g32.items()})
+        for k in o32:
+            if k != "img_embed":
+                out[pre + "ref_f32_err.out." + k] = np.float64(np.abs(o32[k].astype(np.float64) - o64[k]).max())
+        for k in g32:
+            out[pre + "ref_f32_err.g." + k] = np.float64(np.linalg.norm(g32[k].astype(np.float64) - g64[k]) / np.linalg.norm(g64[k]))
+        if feats is not None:                                               # PBE: the feats=None forward too
+            out[pre + "feats"] = feats
+            z32, _, _ = _sparse_blur_run(k32, c, None, torch.float32)
+            z64, _, _ = _sparse_blur_run(k64, c, None, torch.float64)
+            for k in ("new_rays", "weight"):
+                out[pre + "out_nofeats." + k] = z32[k]
+                out[pre + "ref_f32_err.out_nofeats." + k] = np.float64(np.abs(z32[k].astype(np.float64) - z64[k]).max())
+        errs = {k[len(pre + "ref_f32_err."):]: float(v) for k, v in out.items() if k.startswith(pre + "ref_f32_err.")}
+        print(f"   {tag}: weight span (median) {np.median(span):.2f}, |delta_pos| up to {np.abs(dpos).max():.1f} px, nearest kink {kink:.1e}; float32 error of "
+              f"the reference: " + ", ".join(f"{k} {v:.1e}" for k, v in errs.items()))
+    path = os.path.join(OUT, "G39_sparse_blur.npz")
+    np.savez_compressed(path, **out)                                        # (keeps the float64 error records)
+    print(f"  wrote {os.path.relpath(path, ROOT)}  ({os.path.getsize(path) / 1024:.1f} KiB)")
+
+
 ALL = [G1_embedder, G2_nerf_mlp, G3_nerf_raw2outputs, G4_voxel_raw2outputs, G5_sample_pdf, G6_rays,
        G7_render_nerf, G8_appfeature, G9_render_c2f, G10_rbk_weighted_sum, G11_crf, G12_egm_loss, G13_edi,
        G14_loss_assembly, G15_awp_feature_integration, G16_rbk_warp, G17_compute_successor, G18_nerf_grads, G19_c2f_grads, G20_loss_grads,
        G21_awp_sample_embed, G22_mam, G23_render_nerf_no_viewdirs, G24_render_other_multires, G25_pbe_composite_feature,
        G26_sample_events, G27_awp_per_ray, G28_image_batch, G29_pose_track, G30_c2f_grads_16k, G31_event_hops, G32_train_forward,
-       G33_train_trajectory, G34_event_tables, G35_llff_poses, G36_edi_prior, G37_rigid_blur, G38_lpips]
+       G33_train_trajectory, G34_event_tables, G35_llff_poses, G36_edi_prior, G37_rigid_blur, G38_lpips, G39_sparse_blur]
 
 if __name__ == "__main__":
     want = set(sys.argv[1:])
