@@ -103,6 +103,14 @@ class SparseBlurParams(C.Structure):
                 ("linears1_w", _vp * 2), ("linears1_b", _vp * 2)]
 
 
+class AdamSegment(C.Structure):
+    _fields_ = [("param", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("mirror_f32", _vp), ("mirror_f16", _vp), ("n", C.c_long), ("group", C.c_int), ("clip", C.c_int)]
+
+
+class AdamGroup(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("lr", "beta1", "beta2", "eps", "weight_decay")]
+
+
 class LpipsDesc(C.Structure):
     _fields_ = [("conv_w", _fp * 5), ("conv_b", _fp * 5), ("lin", _fp * 5), ("shift", C.c_float * 3), ("scale", C.c_float * 3)]
 
@@ -197,6 +205,7 @@ SIGNATURES = {
     "evd_voxel_grid_sizes": (_I, [_vp, C.POINTER(C.c_long)]),
     "evd_voxel_get_grids": (_I, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp]),
     "evd_voxel_load_grids": (_I, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp]),
+    "evd_voxel_grid_mirrors": (_I, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "evd_voxel_sample_bwd": (_I, [_vp, _vp, _L, _vp, _I, _I, C.POINTER(VoxelGridGrads), _vp, _vp]),
     "evd_voxel_sample_bwd_workspace_bytes": (_S, [_vp, _L]),
     "evd_voxel_sample_bwd_ws": (_I, [_vp, _vp, _L, _vp, _I, _I, C.POINTER(VoxelGridGrads), _vp, _vp, _S, _vp]),
@@ -252,6 +261,11 @@ SIGNATURES = {
     "evd_lpips_destroy": (None, [_vp]),
     "evd_lpips_workspace_bytes": (_S, [_I, _I, _I]),
     "evd_lpips": (_I, [_vp, _vp, _vp, _I, _I, _I, _vp, _vp, _S, _vp]),
+    "evd_adam_create": (_I, [C.POINTER(AdamSegment), _I, _I, C.POINTER(_vp)]),
+    "evd_adam_destroy": (None, [_vp]),
+    "evd_adam_workspace_bytes": (_S, [_vp]),
+    "evd_grad_norm": (_I, [_vp, C.POINTER(_vp), _vp, _vp, _S, _vp]),
+    "evd_adam_step": (_I, [_vp, C.POINTER(_vp), C.POINTER(C.c_long), C.POINTER(AdamGroup), _I, _F, _vp, _I, _vp, _S, _vp]),
 }
 
 _lib = None

@@ -84,6 +84,11 @@ __device__ __forceinline__ float act(int code, float x) {
     }
 }
 
+// The float16 copy of one grid value, as evd_voxel_create, k_load_grids and the optimizer step's mirror (kernels_optim.hip) make it: round
+// to nearest, SATURATED to +-65504 (NaN stays NaN).  The half-precision gathers skip no tap: an outside tap reads a clamped cell with
+// weight 0, and 0 x inf would be NaN where the reference's zero padding gives 0.
+__host__ __device__ static inline _Float16 f16_sat(float x) { return (_Float16)(x > 65504.f ? 65504.f : (x < -65504.f ? -65504.f : x)); }
+
 // torch.linspace(start, end, steps)[i] (ATen RangeFactories: symmetric fill)
 __host__ __device__ __forceinline__ float linspace_at(float start, float end, int steps, int i) {
     if (steps == 1) return start;

@@ -65,10 +65,7 @@ void evd_voxel_destroy(evd_voxel* v) {
     delete v;
 }
 
-// The float16 copy of one grid value, as evd_voxel_create and k_load_grids make it: round to nearest, SATURATED to +-65504 (NaN stays NaN).
-// The half-precision gathers skip no tap: an outside tap reads a clamped cell with weight 0, and 0 x inf would be NaN where the reference's
-// zero padding gives 0.
-__host__ __device__ static inline _Float16 f16_sat(float x) { return (_Float16)(x > 65504.f ? 65504.f : (x < -65504.f ? -65504.f : x)); }
+// (the float16 copy of one grid value, as evd_voxel_create and k_load_grids make it, is f16_sat of evd_common.h)
 
 int evd_voxel_create(const evd_voxel_desc* d, evd_voxel** out) {
     EVD_REQUIRE(d && out, "evd_voxel_create: null argument");
@@ -830,6 +827,16 @@ int evd_voxel_load_grids(evd_voxel* v, const float* const* plane, const float* c
     const long bx = cdiv(nmax / 4 + 1, 256L) < 2048 ? cdiv(nmax / 4 + 1, 256L) : 2048;
     hipLaunchKernelGGL(k_load_grids, dim3((unsigned)bx, 7), dim3(256), 0, st, segs);
     EVD_LAUNCH_CHECK();
+    return EVD_OK;
+}
+
+int evd_voxel_grid_mirrors(const evd_voxel* v, float** plane_f32, float** line_f32, float** basis_f32, void** plane_f16, void** line_f16) {
+    EVD_REQUIRE(v && plane_f32 && line_f32 && basis_f32 && plane_f16 && line_f16, "evd_voxel_grid_mirrors: null argument");
+    for (int i = 0; i < 3; ++i) {
+        plane_f32[i] = (float*)v->plane[i].p; line_f32[i] = (float*)v->line[i].p;
+        plane_f16[i] = v->plane_h[i].p; line_f16[i] = v->line_h[i].p;
+    }
+    *basis_f32 = (float*)v->basis.p;
     return EVD_OK;
 }
 

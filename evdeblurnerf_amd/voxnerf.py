@@ -404,7 +404,19 @@ class VoxelNeRFBase:
         ts = [t.detach().contiguous().float() for t in grids]
         pl, li = (C.c_void_p * 3)(*[t.data_ptr() for t in ts[:3]]), (C.c_void_p * 3)(*[t.data_ptr() for t in ts[3:6]])
         L.check(L.lib().evd_voxel_load_grids(self._h, pl, li, L.ptr(ts[6]), L.stream_ptr()), "evd_voxel_load_grids")
+        self.grids_loaded(grids)
+
+    def grids_loaded(self, grids):
+        """note that the level's own copies hold the current values of `grids`: after load_grids, or after a writer that stored them
+        there itself (optim.Adam(model=...) writes every new grid value through grid_mirrors() in its step)"""
         self._synced = tuple((t.data_ptr(), t._version) for t in grids) + (L.backward_generation(),)
+
+    def grid_mirrors(self):
+        """([7 float32 device addresses], [6 float16 device addresses + None]) of the level's grid copies, in grid_params() order
+        (evd_voxel_grid_mirrors); element counts are evd_voxel_grid_sizes"""
+        pf, lf, ph, lh, bf = (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_void_p * 3)(), C.c_void_p()
+        L.check(L.lib().evd_voxel_grid_mirrors(self._h, pf, lf, C.byref(bf), ph, lh), "evd_voxel_grid_mirrors")
+        return list(pf) + list(lf) + [bf.value], list(ph) + list(lh) + [None]
 
     def _sync(self, grids):
         if getattr(self, "_synced", None) != tuple((t.data_ptr(), t._version) for t in grids) + (L.backward_generation(),):

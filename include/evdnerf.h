@@ -428,6 +428,12 @@ typedef struct { float *plane[3], *line[3], *basis; } evd_voxel_grid_grads;
 int evd_voxel_grid_sizes(const evd_voxel* v, long* sizes);
 int evd_voxel_get_grids(const evd_voxel* v, float* const* plane, float* const* line, float* basis, void* stream);
 int evd_voxel_load_grids(evd_voxel* v, const float* const* plane, const float* const* line, const float* basis, void* stream);
+/* Where the level keeps its grids: the seven float32 device arrays (plane_f32[0..2], line_f32[0..2], *basis_f32) evd_voxel_load_grids
+ * writes, and the float16 copies of the planes and lines (plane_f16 / line_f16; the basis has none).  Order and element layout are
+ * those of evd_voxel_get_grids / evd_voxel_load_grids.  A writer that stores a new grid value to BOTH (the float16 one through the
+ * saturating conversion of evd_voxel_load_grids) has done what evd_voxel_load_grids does: the optimizer step's mirrors (evd_adam_step).
+ * Host call, touches no device state; the pointers stay valid until evd_voxel_destroy. */
+int evd_voxel_grid_mirrors(const evd_voxel* v, float** plane_f32, float** line_f32, float** basis_f32, void** plane_f16, void** line_f16);
 /* Backward of evd_voxel_sample (VoxelNeRFBase.sample / compute_appfeature, voxnerf.py:132-151,203-208; app_actfn none):
  * d_out dev rows of d_stride floats, the app_dim gradient columns start at d_col -> gradients ADDED into g (caller zeroes;
  * NULL = not wanted) with float32 hardware atomics; like the reference's grid_sample backward (voxnerf.py:144) the summation
@@ -853,6 +859,52 @@ void evd_lpips_destroy(evd_lpips_model* m);
 size_t evd_lpips_workspace_bytes(int B, int H, int W);
 int evd_lpips(const evd_lpips_model* m, const float* pred, const float* target, int B, int H, int W, double* out, void* workspace, size_t workspace_bytes,
               void* stream);
+
+/* ---------------------------------------------------------------- optimizer step (run_nerf.py:593-613)
+ * clip_grad_norm_ + torch.optim.Adam(amsgrad=False, maximize=False).step() over any number of float32 arrays in ONE launch, with the
+ * hand-over to the library folded in: the new value of a parameter can be stored to a float32 and a float16 mirror in the same pass
+ * (the grids of a PDRF level: evd_voxel_grid_mirrors), and the gradient just consumed can be cleared.
+ *
+ * A SEGMENT is one contiguous float32 array -- a parameter with its gradient and moments; `n` elements, 0 allowed; starts need only
+ * 4-byte alignment (leaves are views at arbitrary element offsets of a flat tensor).  The 16-byte-aligned body of a segment moves as
+ * 16-byte loads / stores where param, grad, exp_avg, exp_avg_sq and the mirrors share the parameter's phase within 16 bytes (the float16
+ * mirror: within 8), head and tail -- and a segment whose arrays do not -- element by element.  The table lives in device memory
+ * (uploaded by the first step), so there may be thousands of segments.
+ * A GROUP is Adam's hyper-parameter set, passed by value per call (the learning rate changes every step).
+ * Arithmetic per element, float32, IEEE division and square root, as torch/optim/adam.py _single_tensor_adam writes it:
+ *   g = grad * clip_coef (flagged segments, max_norm > 0);  g += weight_decay * p;  m += (1 - beta1) (g - m);
+ *   v = v beta2 + ((1 - beta2) g) g;  denom = sqrt(v) / sqrt(bc2) + eps;  p += (-(lr / bc1) m) / denom
+ * with bc1 = 1 - beta1^t, bc2 = 1 - beta2^t, t = steps[i] + 1 evaluated on the host in float64 PER SEGMENT.
+ * clip_coef = min(1, max_norm / (total_norm[0] + 1e-6)) is formed on the device from the scalar evd_grad_norm wrote
+ * (torch.nn.utils.clip_grad_norm_'s float32 arithmetic; a non-finite norm propagates as it does there); the stored gradients are not scaled. */
+typedef struct evd_adam evd_adam;
+typedef struct {
+    float* param;               /* dev [n] */
+    float* exp_avg;             /* dev [n] */
+    float* exp_avg_sq;          /* dev [n] */
+    float* mirror_f32;          /* dev [n] or NULL: receives the new parameter value */
+    void* mirror_f16;           /* dev [n] float16 or NULL: receives it rounded to nearest and saturated to +-65504 */
+    long n;
+    int group;                  /* index into the groups of evd_adam_step */
+    int clip;                   /* counts towards evd_grad_norm and is scaled by the clip coefficient */
+} evd_adam_segment;
+typedef struct { double lr, beta1, beta2, eps, weight_decay; } evd_adam_group;
+/* Host only: validates and copies the table (no device call; NULL param / exp_avg / exp_avg_sq with n > 0, n < 0, group outside
+ * 0..ngroups-1 are EVD_E_INVALID).  nseg = 0 is allowed. */
+int evd_adam_create(const evd_adam_segment* segments, int nseg, int ngroups, evd_adam** out);
+void evd_adam_destroy(evd_adam* a);
+/* Device scratch of evd_adam_step / evd_grad_norm: the per-call segment table (gradient pointers, step sizes) and the norm's partial sums */
+size_t evd_adam_workspace_bytes(const evd_adam* a);
+/* total_norm[0] (dev float32) = L2 norm over the flagged segments whose grads[i] is not NULL.  Float64 partial sums per workgroup and
+ * one fixed-order finishing launch, no floating-point atomics: the same bits from call to call.  grads: HOST array of nseg device pointers. */
+int evd_grad_norm(evd_adam* a, const float* const* grads, float* total_norm, void* workspace, size_t workspace_bytes, void* stream);
+/* One step.  grads: HOST array of nseg device pointers; a NULL entry skips the segment (parameter, moments and step count untouched: torch's
+ * `p.grad is None`).  steps: HOST array of nseg step counts BEFORE this step (the caller adds one to those it passed a gradient for).
+ * groups: ngroups entries, as at creation.  max_norm > 0: clip with the DEVICE scalar total_norm (required then).  zero_grads: every
+ * gradient consumed is overwritten with zeros in the same pass.  No host synchronisation and no pageable copy in the steady state: the
+ * per-call table travels through pinned staging buffers the handle rotates.  nseg = 0 / all n = 0: EVD_OK, nothing launched. */
+int evd_adam_step(evd_adam* a, const float* const* grads, const long* steps, const evd_adam_group* groups, int ngroups, float max_norm,
+                  const float* total_norm, int zero_grads, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- measurement aid (no reference counterpart)
  * Sustained rate of back-to-back v_mfma_f32_32x32x16_bf16 issue on every SIMD of the current device, in dense
