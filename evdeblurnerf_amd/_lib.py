@@ -257,6 +257,10 @@ SIGNATURES = {
     "evd_img_metrics_workspace_bytes": (_S, [_I, _I, _I]),
     "evd_img_metrics": (_I, [_vp, _vp, _vp, _I, _I, _I, _I, _I, _I, _vp, _vp, _S, _vp]),
     "evd_to8b": (_I, [_vp, _L, _vp, _vp]),
+    "evd_frame_workspace_bytes": (_S, [_I, _L, _I]),
+    "evd_frame_range": (_I, [_vp, _vp, _I, _I, _I, _L, _vp, _vp, _S, _vp]),
+    "evd_frame_map": (_I, [_vp, _vp, _I, _I, _I, _L, _vp, _I, _vp, _vp, _vp]),
+    "evd_frame_colormap": (_I, [_vp, _L, _vp, _vp, _vp]),
     "evd_lpips_create": (_I, [C.POINTER(LpipsDesc), C.POINTER(_vp)]),
     "evd_lpips_destroy": (None, [_vp]),
     "evd_lpips_workspace_bytes": (_S, [_I, _I, _I]),

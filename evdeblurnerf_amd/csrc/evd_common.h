@@ -84,6 +84,12 @@ __device__ __forceinline__ float act(int code, float x) {
     }
 }
 
+// to8b, utils/misc.py:6, (255 * np.clip(x, 0, 1)).astype(np.uint8): float32 product, truncation; NaN -> 0 (evd_to8b, the frame pictures)
+__device__ __forceinline__ unsigned char to8b_u8(float v) {
+    v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
+    return v == v ? (unsigned char)(int)(255.f * v) : (unsigned char)0;
+}
+
 // The float16 copy of one grid value, as evd_voxel_create, k_load_grids and the optimizer step's mirror (kernels_optim.hip) make it: round
 // to nearest, SATURATED to +-65504 (NaN stays NaN).  The half-precision gathers skip no tap: an outside tap reads a clamped cell with
 // weight 0, and 0 x inf would be NaN where the reference's zero padding gives 0.

@@ -242,12 +242,6 @@ __global__ __launch_bounds__(IM_FINISH_THREADS) void k_img_metrics_finish(const 
     }
 }
 
-// (255 * np.clip(x, 0, 1)).astype(np.uint8): float32 product, truncation; NaN -> 0
-__device__ __forceinline__ unsigned char im_to8b(float v) {
-    v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
-    return v == v ? (unsigned char)(int)(255.f * v) : (unsigned char)0;
-}
-
 // 4 values per thread; `vec`: x 16-byte and out 4-byte aligned (the last n % 4 values go one by one)
 __global__ __launch_bounds__(256) void k_to8b(const float* __restrict__ x, long n, unsigned char* __restrict__ out, int vec) {
     const long i = (blockIdx.x * 256L + threadIdx.x) * 4;
@@ -255,13 +249,13 @@ __global__ __launch_bounds__(256) void k_to8b(const float* __restrict__ x, long 
     if (vec && i + 4 <= n) {
         const float4 v = *reinterpret_cast<const float4*>(x + i);
         uchar4 o;
-        o.x = im_to8b(v.x);
-        o.y = im_to8b(v.y);
-        o.z = im_to8b(v.z);
-        o.w = im_to8b(v.w);
+        o.x = to8b_u8(v.x);
+        o.y = to8b_u8(v.y);
+        o.z = to8b_u8(v.z);
+        o.w = to8b_u8(v.w);
         *reinterpret_cast<uchar4*>(out + i) = o;
     } else {
-        for (long j = i; j < n && j < i + 4; ++j) out[j] = im_to8b(x[j]);
+        for (long j = i; j < n && j < i + 4; ++j) out[j] = to8b_u8(x[j]);
     }
 }
 

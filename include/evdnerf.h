@@ -820,6 +820,45 @@ int evd_img_metrics(const float* pred, const float* target, const float* mask, i
  * out dev uint8 [n]. */
 int evd_to8b(const float* x, long n, unsigned char* out, void* stream);
 
+/* ---------------------------------------------------------------- test-set, video and render-only passes: 8-bit pictures of frame stacks
+ * The arithmetic between render_path and the image / video / logger calls (run_nerf.py:374-389, 663-679, 726-732): depth pictures, error
+ * maps and the video's normalised RGB, as uint8 on the device.  Two calls per picture kind, no host synchronisation between them:
+ * evd_frame_range writes (lo, hi) pairs to device memory, evd_frame_map reads them there.
+ *
+ * A stack is n_frames contiguous frames of per_frame VALUES.  The value v of an element comes from a tagged source:
+ *   EVD_FRAME_SRC_PLAIN    v = x[i]                                             x dev float32 [n_frames * per_frame], y ignored
+ *   EVD_FRAME_SRC_INVERT   v = 1 - x[i]                                         (:374, :663)
+ *   EVD_FRAME_SRC_SQERR    v = (((x0 - y0)^2 + (x1 - y1)^2) + (x2 - y2)^2) / 3  x, y dev float32 [n_frames * per_frame, 3]: per_frame counts
+ *                                                                               PIXELS; np.mean(-1) of a float32 [..., 3] array (:670)
+ * Every step is one correctly rounded float32 operation in NumPy's order (IEEE division, no contraction), so the bytes are defined bit for
+ * bit.  The scope picks the slices a range belongs to: EVD_FRAME_SCOPE_ALL one (lo, hi) for the stack, EVD_FRAME_SCOPE_FRAME one per frame.
+ *
+ * evd_frame_range: range dev float32 [2] (ALL) or [2 n_frames] (FRAME), (min v, max v) per slice with fminf / fmaxf: a NaN value is
+ *   skipped (a slice of nothing but NaN gives (+inf, -inf)).  Workgroup partials go to the workspace
+ *   (evd_frame_workspace_bytes(n_frames, per_frame, scope); 0 for sizes the entries reject) and a finish launch folds them in a fixed
+ *   order; no floating-point atomics.  The error is not stored.
+ * evd_frame_map: y = subtract_lo ? (v - lo) / (hi - lo) : v / hi;  g = (uint8)(255 * clip(y, 0, 1)), truncated as evd_to8b does;
+ *   out dev uint8 [n_frames * per_frame] receives g, or with lut (dev uint8 [256, 3]) out [n_frames * per_frame, 3] receives the three
+ *   bytes lut[255 - g] (the table's rows in the order given; cv2.applyColorMap(255 - g, ...) with the caller's table).
+ *   Two stated deviations where the reference's result is undefined: hi == 0 (hi == lo with subtract_lo) gives grey level 0 for the
+ *   whole slice, and a NaN value gives grey level 0.
+ * Memory bound: both read the sources once (4 or 24 bytes per value), the map writes 1 or 3 bytes.  16-byte loads and packed byte stores
+ * where a slice's pointers allow it, element by element for its head and tail (and for the whole slice where they do not).
+ * Asynchronous on `stream`; the sizes must satisfy 3 n_frames per_frame < 2^40. */
+#define EVD_FRAME_SRC_PLAIN 0
+#define EVD_FRAME_SRC_INVERT 1
+#define EVD_FRAME_SRC_SQERR 2
+#define EVD_FRAME_SCOPE_ALL 0
+#define EVD_FRAME_SCOPE_FRAME 1
+size_t evd_frame_workspace_bytes(int n_frames, long per_frame, int scope);
+int evd_frame_range(const float* x, const float* y, int source, int scope, int n_frames, long per_frame, float* range, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int evd_frame_map(const float* x, const float* y, int source, int scope, int n_frames, long per_frame, const float* range, int subtract_lo,
+                  const unsigned char* lut, unsigned char* out, void* stream);
+/* The bare table lookup, cv2.applyColorMap(g, table) with the caller's table: out[i, :] = lut[g[i], :].  g dev uint8 [n], lut dev uint8
+ * [256, 3], out dev uint8 [n, 3]; n = 0: nothing launched. */
+int evd_frame_colormap(const unsigned char* g, long n, const unsigned char* lut, unsigned char* out, void* stream);
+
 /* LPIPS, the fourth metric of the test-set pass: compute_img_metric(im1t, im2t, 'lpips'), utils/metrics.py:92-95 (called at run_nerf.py:688),
  * i.e. networks/lpips/lpips.py LPIPS(net='alex', version='0.1', lpips=True, spatial=False) in eval mode, float32 throughout.
  * The WEIGHTS ARE THE CALLER'S: torchvision's pretrained AlexNet `features` (not part of the reference checkout; torchvision downloads
