@@ -880,6 +880,58 @@ static int sample_bwd_ws(const evd_voxel* v, bool half_grids, const float* pts, 
     return launch_voxel_sample_bwd(v->gp, pts, n, d_out, d_stride, d_col, gg, d_pts, as_stream(stream));
 }
 
+// ---- the deterministic scatter (kernel_voxel_scatter_det.hip; run_nerf.py:50)
+// the exponent k of the fixed-point scale 2^k (unit 2^-k): with frexpf(cmax) -> E (cmax < 2^E) and h = ceil(log2(4 n)), k = 62 - h - E; a cell
+// receives at most 4 n terms of magnitude < 2^E, so its sum stays below 2^62.  k is clamped to 126 (k_scatter_lines' clamp: 2^k stays a
+// finite float32; a batch whose maximum is that small is resolved to 2^-126).  0 where no scale exists (cmax not finite, not positive).
+int evd_scatter_det_unit_exp(float cmax, long n) {
+    if (!(cmax > 0.f) || !std::isfinite(cmax) || n < 1) return 0;
+    int E;
+    (void)frexpf(cmax, &E);
+    int h = 0;
+    while (h < 62 && (1L << h) < 4 * n) ++h;
+    const int k = 62 - h - E;
+    return k > 126 ? 126 : k;
+}
+
+// the region of the workspace behind its 256-byte alignment: the shadow, or (a batch without a scale) the hybrid form's scratch
+static size_t det_region_bytes(const evd_voxel* v, long n) {
+    const size_t a = voxel_scatter_det_region_bytes(v->gp), b = voxel_scatter_hybrid_ok(v->gp, n) ? voxel_scatter_hybrid_workspace_bytes(v->gp, n) : 0;
+    return a > b ? a : b;
+}
+
+size_t evd_voxel_sample_bwd_det_workspace_bytes(const evd_voxel* v, long n) {
+    if (!v || n <= 0) return 0;
+    return det_region_bytes(v, n) + 256;
+}
+
+int evd_voxel_sample_bwd_det(const evd_voxel* v, int precision, const float* pts, long n, const float* d_out, int d_stride, int d_col,
+                             const evd_voxel_grid_grads* g, float* d_pts, void* workspace, size_t workspace_bytes, void* stream) {
+    EVD_REQUIRE(v && pts && d_out && g && n >= 0 && d_stride >= d_col + v->app_dim, "evd_voxel_sample_bwd_det: bad arguments");
+    EVD_REQUIRE(precision >= 0 && precision <= EVD_PREC_F16M, "evd_voxel_sample_bwd_det: unknown precision %d", precision);
+    EVD_REQUIRE(v->app_act == EVD_ACT_NONE, "evd_voxel_sample_bwd_det: only app_actfn none is built (all shipped configs)");
+    if (n == 0) return EVD_OK;
+    const size_t need = evd_voxel_sample_bwd_det_workspace_bytes(v, n);
+    if (!workspace || workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_voxel_sample_bwd_det: workspace %zu < %zu bytes", workspace_bytes, need);
+    hipStream_t st = as_stream(stream);
+    const bool half = grids_half_for(v, precision);
+    GridGrads gg;
+    for (int i = 0; i < 3; ++i) { gg.plane[i] = g->plane[i]; gg.line[i] = g->line[i]; }
+    gg.basis = g->basis;
+    char* region = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    int rc = launch_voxel_scatter_det_scale(v->gp, half, pts, n, d_out, d_stride, d_col, gg, region, st);
+    if (rc) return rc;
+    // the one host read of this entry: the unit is a function of the batch's maximum, and a batch without one takes another path
+    unsigned bits = 0;
+    EVD_HIP(hipMemcpyAsync(&bits, region, sizeof(bits), hipMemcpyDeviceToHost, st));
+    EVD_HIP(hipStreamSynchronize(st));
+    float cmax;
+    memcpy(&cmax, &bits, sizeof(cmax));
+    if (!std::isfinite(cmax))          // a NaN / Inf contribution: no scale exists, the gradients show it as the default path does
+        return sample_bwd_ws(v, half, pts, n, d_out, d_stride, d_col, g, d_pts, region, det_region_bytes(v, n), stream);
+    return launch_voxel_scatter_det_add(v->gp, half, pts, n, d_out, d_stride, d_col, gg, d_pts, region, evd_scatter_det_unit_exp(cmax, n), st);
+}
+
 int evd_voxel_tv_loss_bwd(const evd_voxel* v, const float* d_loss, const evd_voxel_grid_grads* g, void* stream) {
     EVD_REQUIRE(v && g && d_loss, "evd_voxel_tv_loss_bwd: null argument");
     hipStream_t st = as_stream(stream);

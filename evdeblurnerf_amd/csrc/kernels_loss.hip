@@ -125,7 +125,45 @@ __global__ void k_crf_forward(const CrfParams crf, const float* __restrict__ x, 
     }
 }
 
-// spec: run_nerf.py:443-497 + networks/renderer.py:327-336
+// spec: run_nerf.py:443-497 + networks/renderer.py:327-336.  The terms of one (pixel, colour channel): the five squared errors into se
+// (entries that do not apply stay as they are) and the three weighted sums, which are also written out where wanted.
+__device__ __forceinline__ void blur_loss_lane(const CrfParams& crf, int skip_learn, const float* __restrict__ rgb_p,
+                                               const float* __restrict__ rgb0_p, const float* __restrict__ w1, const float* __restrict__ w2,
+                                               const float* __restrict__ tgt, const float* __restrict__ tgt0, long r, int ch, int P,
+                                               float* __restrict__ o_rgb, float* __restrict__ o_rgb1, float* __restrict__ o_awp, float (&se)[5]) {
+    float a = 0.f, b = 0.f, c = 0.f;
+    for (int p = 0; p < P; ++p) {
+        const float wa = w1[r * P + p], wb = w2 ? w2[r * P + p] : 0.f;
+        const float f = rgb_p[(r * P + p) * 3 + ch];
+        a += f * wa;
+        c += f * wb;
+        if (rgb0_p) b += rgb0_p[(r * P + p) * 3 + ch] * wa;
+    }
+    const float t = tgt[r * 3 + ch];
+    float d = crf_apply(crf, a, nullptr, skip_learn) - t;
+    se[0] = d * d;
+    if (o_rgb) o_rgb[r * 3 + ch] = a;
+    if (rgb0_p) {
+        d = crf_apply(crf, b, nullptr, skip_learn) - t;
+        se[1] = d * d;
+        if (o_rgb1) o_rgb1[r * 3 + ch] = b;
+    }
+    if (w2) {
+        d = crf_apply(crf, c, nullptr, skip_learn) - t;
+        se[2] = d * d;
+        if (o_awp) o_awp[r * 3 + ch] = c;
+    }
+    if (tgt0) {
+        const float t0 = tgt0[r * 3 + ch];
+        d = crf_apply(crf, rgb_p[(r * P) * 3 + ch], nullptr, skip_learn) - t0;     // rgb_pts[:, 0] renderer.py:374
+        se[3] = d * d;
+        if (rgb0_p) {
+            d = crf_apply(crf, rgb0_p[(r * P) * 3 + ch], nullptr, skip_learn) - t0;
+            se[4] = d * d;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_blur_loss(const CrfParams crf, int skip_learn, const float* __restrict__ rgb_p,
                                                    const float* __restrict__ rgb0_p, const float* __restrict__ w1,
                                                    const float* __restrict__ w2, const float* __restrict__ tgt,
@@ -140,37 +178,7 @@ __global__ __launch_bounds__(256) void k_blur_loss(const CrfParams crf, int skip
     float cnt = 0.f;
     if (r < R) {
         cnt = 1.f;
-        float a = 0.f, b = 0.f, c = 0.f;
-        for (int p = 0; p < P; ++p) {
-            const float wa = w1[r * P + p], wb = w2 ? w2[r * P + p] : 0.f;
-            const float f = rgb_p[(r * P + p) * 3 + ch];
-            a += f * wa;
-            c += f * wb;
-            if (rgb0_p) b += rgb0_p[(r * P + p) * 3 + ch] * wa;
-        }
-        const float t = tgt[r * 3 + ch];
-        float d = crf_apply(crf, a, nullptr, skip_learn) - t;
-        se[0] = d * d;
-        if (o_rgb) o_rgb[r * 3 + ch] = a;
-        if (rgb0_p) {
-            d = crf_apply(crf, b, nullptr, skip_learn) - t;
-            se[1] = d * d;
-            if (o_rgb1) o_rgb1[r * 3 + ch] = b;
-        }
-        if (w2) {
-            d = crf_apply(crf, c, nullptr, skip_learn) - t;
-            se[2] = d * d;
-            if (o_awp) o_awp[r * 3 + ch] = c;
-        }
-        if (tgt0) {
-            const float t0 = tgt0[r * 3 + ch];
-            d = crf_apply(crf, rgb_p[(r * P) * 3 + ch], nullptr, skip_learn) - t0;     // rgb_pts[:, 0] renderer.py:374
-            se[3] = d * d;
-            if (rgb0_p) {
-                d = crf_apply(crf, rgb0_p[(r * P) * 3 + ch], nullptr, skip_learn) - t0;
-                se[4] = d * d;
-            }
-        }
+        blur_loss_lane(crf, skip_learn, rgb_p, rgb0_p, w1, w2, tgt, tgt0, r, ch, P, o_rgb, o_rgb1, o_awp, se);
     }
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
@@ -181,11 +189,92 @@ __global__ __launch_bounds__(256) void k_blur_loss(const CrfParams crf, int skip
     if (threadIdx.x == 0) atomicAdd(partial + 5, n);
 }
 
+// ---- the deterministic forms (evd_crf_set_deterministic; run_nerf.py:50): a bounded grid walks the batch with a grid-stride loop, every lane
+// sums its elements in index order, the workgroup sum (block_sum: a fixed shuffle tree, then the wavefronts in order) goes to the handle's
+// buffer of per-workgroup partials, and k_det_fold -- ONE wavefront -- adds them in workgroup order and performs the call's single
+// out[k] += sum.  No floating-point atomic: the same bits for the same batch.
+constexpr int DET_BLOCKS = 256;         // workgroups of a deterministic loss launch at most = rows of the handle's buffer
+
+__global__ __launch_bounds__(64) void k_det_fold(const float* __restrict__ wg, int blocks, int K, float* __restrict__ out) {
+    for (int k = threadIdx.x; k < K; k += 64) {
+        float s = 0.f;
+        int b = 0;
+        for (; b + 8 <= blocks; b += 8) {             // eight loads in flight, added in workgroup order
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = wg[(long)(b + j) * K + k];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s += v[j];
+        }
+        for (; b < blocks; ++b) s += wg[(long)b * K + k];
+        out[k] += s;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_blur_loss_det(const CrfParams crf, int skip_learn, const float* __restrict__ rgb_p,
+                                                       const float* __restrict__ rgb0_p, const float* __restrict__ w1,
+                                                       const float* __restrict__ w2, const float* __restrict__ tgt,
+                                                       const float* __restrict__ tgt0, long R, int P, float* __restrict__ wg,
+                                                       float* __restrict__ o_rgb, float* __restrict__ o_rgb1, float* __restrict__ o_awp) {
+    __shared__ float red[8];
+    float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < 3 * R; idx += gridDim.x * 256L) {
+        float se[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        blur_loss_lane(crf, skip_learn, rgb_p, rgb0_p, w1, w2, tgt, tgt0, idx / 3, (int)(idx % 3), P, o_rgb, o_rgb1, o_awp, se);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) acc[k] += se[k];
+        acc[5] += 1.f;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const float s = block_sum(acc[k], red);
+        if (threadIdx.x == 0) wg[blockIdx.x * 6 + k] = s;
+    }
+}
+
 // Backward of k_blur_loss ("next" row f-1, slice): with g[k] = dL/d partial[k] (k = 0..4) and a = sum_p w1 rgb_p etc.
 //   d a = 2 g0 (crf(a) - t) crf'(a),  d b = 2 g1 (..rgb0..),  d c = 2 g2 (..w2..),  pts0 terms act on p = 0;
 //   d rgb_p[p] = d a w1[p] + d c w2[p],   d rgb0_p[p] = d b w1[p],   d w1[p] = d a . rgb_p[p] + d b . rgb0_p[p],   d w2[p] = d c . rgb_p[p].
 // One lane per (pixel, channel); d w1 / d w2 sum the three channels of a pixel with two DPP adds inside the lane triple... the
 // triples straddle wavefront rows, so the channel sum goes through atomicAdd on the zero-initialised outputs instead.
+struct BlurBwdCoef { float da, db, dc; };
+__device__ __forceinline__ BlurBwdCoef blur_bwd_coef(const CrfParams& crf, int skip_learn, const float* __restrict__ rgb_p,
+                                                     const float* __restrict__ rgb0_p, const float* __restrict__ w1, const float* __restrict__ w2,
+                                                     const float* __restrict__ tgt, long r, int ch, int P, float g0, float g1, float g2) {
+    float a = 0.f, b = 0.f, c = 0.f;
+    for (int p = 0; p < P; ++p) {
+        const float wa = w1[r * P + p], wb = w2 ? w2[r * P + p] : 0.f;
+        const float f = rgb_p[(r * P + p) * 3 + ch];
+        a += f * wa;
+        c += f * wb;
+        if (rgb0_p) b += rgb0_p[(r * P + p) * 3 + ch] * wa;
+    }
+    const float t = tgt[r * 3 + ch];
+    BlurBwdCoef k;
+    k.da = 2.f * g0 * (crf_apply(crf, a, nullptr, skip_learn) - t) * crf_grad_simple(crf, a);
+    k.db = rgb0_p ? 2.f * g1 * (crf_apply(crf, b, nullptr, skip_learn) - t) * crf_grad_simple(crf, b) : 0.f;
+    k.dc = w2 ? 2.f * g2 * (crf_apply(crf, c, nullptr, skip_learn) - t) * crf_grad_simple(crf, c) : 0.f;
+    return k;
+}
+// sub-exposure p of (pixel r, channel ch): writes d rgb_p / d rgb0_p, returns this channel's terms of d w1[q] and d w2[q]
+struct BlurBwdW { float w1, w2; };
+__device__ __forceinline__ BlurBwdW blur_bwd_sub(const CrfParams& crf, int skip_learn, const float* __restrict__ rgb_p,
+                                                 const float* __restrict__ rgb0_p, const float* __restrict__ w1, const float* __restrict__ w2,
+                                                 const float* __restrict__ tgt0, long r, int ch, int p, int P, const BlurBwdCoef& k, float g3, float g4,
+                                                 float* __restrict__ d_rgb_p, float* __restrict__ d_rgb0_p) {
+    const long q = r * P + p;
+    const float f = rgb_p[q * 3 + ch], f0 = rgb0_p ? rgb0_p[q * 3 + ch] : 0.f;
+    float dr = k.da * w1[q] + (w2 ? k.dc * w2[q] : 0.f), dr0 = k.db * w1[q];
+    if (p == 0 && tgt0) {                           // pts0 / EDI-prior terms on the p = 0 render (renderer.py:374)
+        const float t0 = tgt0[r * 3 + ch];
+        dr += 2.f * g3 * (crf_apply(crf, f, nullptr, skip_learn) - t0) * crf_grad_simple(crf, f);
+        if (rgb0_p) dr0 += 2.f * g4 * (crf_apply(crf, f0, nullptr, skip_learn) - t0) * crf_grad_simple(crf, f0);
+    }
+    d_rgb_p[q * 3 + ch] = dr;
+    if (d_rgb0_p) d_rgb0_p[q * 3 + ch] = dr0;
+    return BlurBwdW{k.da * f + k.db * f0, k.dc * f};
+}
+
 __global__ __launch_bounds__(64) void k_blur_loss_bwd(const CrfParams crf, int skip_learn, const float* __restrict__ rgb_p,
                                                       const float* __restrict__ rgb0_p, const float* __restrict__ w1,
                                                       const float* __restrict__ w2, const float* __restrict__ tgt,
@@ -197,31 +286,38 @@ __global__ __launch_bounds__(64) void k_blur_loss_bwd(const CrfParams crf, int s
     const long r = idx / 3;
     const int ch = (int)(idx % 3);
     if (r >= R) return;
-    float a = 0.f, b = 0.f, c = 0.f;
-    for (int p = 0; p < P; ++p) {
-        const float wa = w1[r * P + p], wb = w2 ? w2[r * P + p] : 0.f;
-        const float f = rgb_p[(r * P + p) * 3 + ch];
-        a += f * wa;
-        c += f * wb;
-        if (rgb0_p) b += rgb0_p[(r * P + p) * 3 + ch] * wa;
-    }
-    const float t = tgt[r * 3 + ch];
-    const float da = 2.f * g0 * (crf_apply(crf, a, nullptr, skip_learn) - t) * crf_grad_simple(crf, a);
-    const float db = rgb0_p ? 2.f * g1 * (crf_apply(crf, b, nullptr, skip_learn) - t) * crf_grad_simple(crf, b) : 0.f;
-    const float dc = w2 ? 2.f * g2 * (crf_apply(crf, c, nullptr, skip_learn) - t) * crf_grad_simple(crf, c) : 0.f;
+    const BlurBwdCoef k = blur_bwd_coef(crf, skip_learn, rgb_p, rgb0_p, w1, w2, tgt, r, ch, P, g0, g1, g2);
     for (int p = 0; p < P; ++p) {
         const long q = r * P + p;
-        const float f = rgb_p[q * 3 + ch], f0 = rgb0_p ? rgb0_p[q * 3 + ch] : 0.f;
-        float dr = da * w1[q] + (w2 ? dc * w2[q] : 0.f), dr0 = db * w1[q];
-        if (p == 0 && tgt0) {                           // pts0 / EDI-prior terms on the p = 0 render (renderer.py:374)
-            const float t0 = tgt0[r * 3 + ch];
-            dr += 2.f * g3 * (crf_apply(crf, f, nullptr, skip_learn) - t0) * crf_grad_simple(crf, f);
-            if (rgb0_p) dr0 += 2.f * g4 * (crf_apply(crf, f0, nullptr, skip_learn) - t0) * crf_grad_simple(crf, f0);
+        const BlurBwdW dw = blur_bwd_sub(crf, skip_learn, rgb_p, rgb0_p, w1, w2, tgt0, r, ch, p, P, k, g3, g4, d_rgb_p, d_rgb0_p);
+        if (d_w1) atomicAdd(d_w1 + q, dw.w1);
+        if (d_w2 && w2) atomicAdd(d_w2 + q, dw.w2);
+    }
+}
+
+// The deterministic form: one lane per PIXEL, which adds the three channel terms of d w1 / d w2 in channel order and writes the sum
+__global__ __launch_bounds__(64) void k_blur_loss_bwd_det(const CrfParams crf, int skip_learn, const float* __restrict__ rgb_p,
+                                                          const float* __restrict__ rgb0_p, const float* __restrict__ w1,
+                                                          const float* __restrict__ w2, const float* __restrict__ tgt,
+                                                          const float* __restrict__ tgt0, long R, int P, float g0, float g1, float g2,
+                                                          float g3, float g4, const float* __restrict__ gdev, float* __restrict__ d_rgb_p,
+                                                          float* __restrict__ d_rgb0_p, float* __restrict__ d_w1, float* __restrict__ d_w2) {
+    if (gdev) { g0 = gdev[0]; g1 = gdev[1]; g2 = gdev[2]; g3 = gdev[3]; g4 = gdev[4]; }
+    const long r = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    BlurBwdCoef k[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) k[ch] = blur_bwd_coef(crf, skip_learn, rgb_p, rgb0_p, w1, w2, tgt, r, ch, P, g0, g1, g2);
+    for (int p = 0; p < P; ++p) {
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const BlurBwdW dw = blur_bwd_sub(crf, skip_learn, rgb_p, rgb0_p, w1, w2, tgt0, r, ch, p, P, k[ch], g3, g4, d_rgb_p, d_rgb0_p);
+            s1 += dw.w1;
+            s2 += dw.w2;
         }
-        d_rgb_p[q * 3 + ch] = dr;
-        if (d_rgb0_p) d_rgb0_p[q * 3 + ch] = dr0;
-        if (d_w1) atomicAdd(d_w1 + q, da * f + db * f0);
-        if (d_w2 && w2) atomicAdd(d_w2 + q, dc * f);
+        if (d_w1) d_w1[r * P + p] = s1;
+        if (d_w2 && w2) d_w2[r * P + p] = s2;
     }
 }
 
@@ -236,11 +332,12 @@ struct EventLane {
     float cn, cp;
     const float* src;           // the colour input this lane reads
 };
+// blk: the 16-event block of the batch this workgroup is on (the default kernels: blockIdx.x; the deterministic ones walk several)
 __device__ __forceinline__ EventLane event_lane(const float* start, const float* end, const float* start0, const float* end0, const float* cum_neg,
-                                                const float* cum_pos, const unsigned char* cmask, long N) {
+                                                const float* cum_pos, const unsigned char* cmask, long N, long blk) {
     EventLane L;
     L.sub = threadIdx.x & 15; L.which = L.sub >> 2; L.c = L.sub & 3;
-    const long i = blockIdx.x * (long)(blockDim.x >> 4) + (threadIdx.x >> 4);
+    const long i = blk * (long)(blockDim.x >> 4) + (threadIdx.x >> 4);
     L.on = i < N;
     L.ii = L.on ? i : N - 1;
     L.have0 = start0 && end0;
@@ -270,14 +367,14 @@ __device__ __forceinline__ EventChain event_chain(const EventLane& L, float v, i
     return k;
 }
 
-__global__ __launch_bounds__(256) void k_event_loss(const CrfParams crf, int skip_learn, int add_bii_feat, int tonemap_only,
-                                                    const float* __restrict__ start, const float* __restrict__ end,
-                                                    const float* __restrict__ start0, const float* __restrict__ end0,
-                                                    const float* __restrict__ cum_neg, const float* __restrict__ cum_pos,
-                                                    float thr_neg, float thr_pos, const unsigned char* __restrict__ cmask,
-                                                    float cw0, float cw1, float cw2, int has_cw, long N, float* __restrict__ partial) {
-    __shared__ float red[8];
-    const EventLane L = event_lane(start, end, start0, end0, cum_neg, cum_pos, cmask, N);
+// this lane's terms of the 16-event block blk, ADDED to s_f (fine), s_c (coarse), s_w (weight); every lane of the workgroup calls it (DPP moves)
+__device__ __forceinline__ void event_loss_terms(const CrfParams& crf, int skip_learn, int add_bii_feat, int tonemap_only,
+                                                 const float* __restrict__ start, const float* __restrict__ end,
+                                                 const float* __restrict__ start0, const float* __restrict__ end0,
+                                                 const float* __restrict__ cum_neg, const float* __restrict__ cum_pos,
+                                                 float thr_neg, float thr_pos, const unsigned char* __restrict__ cmask,
+                                                 float cw0, float cw1, float cw2, int has_cw, long N, long blk, float& s_f, float& s_c, float& s_w) {
+    const EventLane L = event_lane(start, end, start0, end0, cum_neg, cum_pos, cmask, N, blk);
     float v = 0.f;
     if (L.eval) {
         const float f[2] = {L.cn, L.cp};
@@ -287,9 +384,20 @@ __global__ __launch_bounds__(256) void k_event_loss(const CrfParams crf, int ski
     // pred = log(luma(end)) - log(luma(start)): quads 0 - 1 (fine) and 2 - 3 (coarse) of the 16-lane group
     const float pred = ev.lg - dpp_f32<0x104>(0.f, ev.lg);                        // row_shl:4 -> lane l reads lane l + 4
     const float d = pred - ev.bii, w = ev.w;
+    if (L.on && L.sub == 0) { s_f += d * d * w; s_w += w; }
+    if (L.on && L.sub == 8 && L.have0) s_c += d * d * w;
+}
+
+__global__ __launch_bounds__(256) void k_event_loss(const CrfParams crf, int skip_learn, int add_bii_feat, int tonemap_only,
+                                                    const float* __restrict__ start, const float* __restrict__ end,
+                                                    const float* __restrict__ start0, const float* __restrict__ end0,
+                                                    const float* __restrict__ cum_neg, const float* __restrict__ cum_pos,
+                                                    float thr_neg, float thr_pos, const unsigned char* __restrict__ cmask,
+                                                    float cw0, float cw1, float cw2, int has_cw, long N, float* __restrict__ partial) {
+    __shared__ float red[8];
     float s_f = 0.f, s_c = 0.f, s_w = 0.f;
-    if (L.on && L.sub == 0) { s_f = d * d * w; s_w = w; }
-    if (L.on && L.sub == 8 && L.have0) s_c = d * d * w;
+    event_loss_terms(crf, skip_learn, add_bii_feat, tonemap_only, start, end, start0, end0, cum_neg, cum_pos, thr_neg, thr_pos, cmask, cw0, cw1, cw2,
+                     has_cw, N, blockIdx.x, s_f, s_c, s_w);
     const float a = block_sum(s_f, red), b = block_sum(s_c, red), cc = block_sum(s_w, red);
     if (threadIdx.x == 0) {
         atomicAdd(partial + 0, a);
@@ -298,26 +406,44 @@ __global__ __launch_bounds__(256) void k_event_loss(const CrfParams crf, int ski
     }
 }
 
+// the deterministic form (see k_blur_loss_det): workgroup b walks the 16-event blocks b, b + gridDim.x, ...
+__global__ __launch_bounds__(256) void k_event_loss_det(const CrfParams crf, int skip_learn, int add_bii_feat, int tonemap_only,
+                                                        const float* __restrict__ start, const float* __restrict__ end,
+                                                        const float* __restrict__ start0, const float* __restrict__ end0,
+                                                        const float* __restrict__ cum_neg, const float* __restrict__ cum_pos,
+                                                        float thr_neg, float thr_pos, const unsigned char* __restrict__ cmask,
+                                                        float cw0, float cw1, float cw2, int has_cw, long N, float* __restrict__ wg) {
+    __shared__ float red[8];
+    float s_f = 0.f, s_c = 0.f, s_w = 0.f;
+    for (long blk = blockIdx.x; blk * 16 < N; blk += gridDim.x)
+        event_loss_terms(crf, skip_learn, add_bii_feat, tonemap_only, start, end, start0, end0, cum_neg, cum_pos, thr_neg, thr_pos, cmask, cw0, cw1, cw2,
+                         has_cw, N, blk, s_f, s_c, s_w);
+    const float a = block_sum(s_f, red), b = block_sum(s_c, red), cc = block_sum(s_w, red);
+    if (threadIdx.x == 0) {
+        wg[blockIdx.x * 3 + 0] = a;
+        wg[blockIdx.x * 3 + 1] = b;
+        wg[blockIdx.x * 3 + 2] = cc;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Backward of k_event_loss ("next" row f-1, slice): gradients of  g_f * partial[0] + g_c * partial[1]  w.r.t. the four colour
 // inputs and w.r.t. the parameters of the learnable event-CRF (d_params in the CrfLayout order).  Same lane set-up as the forward kernel;
 // every lane re-runs its CRF evaluation keeping the three hidden layers, back-propagates  d out -> d (input, parameters),  the parameter
 // contributions are summed over the wavefront with DPP adds, over the block in LDS and added to the global gradient once per block.
-__global__ __launch_bounds__(256) void k_event_loss_bwd(const CrfParams crf, int skip_learn, int add_bii_feat, int tonemap_only,
-                                                        const float* __restrict__ start, const float* __restrict__ end,
-                                                        const float* __restrict__ start0, const float* __restrict__ end0,
-                                                        const float* __restrict__ cum_neg, const float* __restrict__ cum_pos,
-                                                        float thr_neg, float thr_pos, const unsigned char* __restrict__ cmask,
-                                                        float cw0, float cw1, float cw2, int has_cw, long N, float g_f, float g_c,
-                                                        const float* __restrict__ gdev, float* __restrict__ d_start, float* __restrict__ d_end,
-                                                        float* __restrict__ d_start0, float* __restrict__ d_end0,
-                                                        float* __restrict__ d_params) {
-    __shared__ float pacc[CRF_NPARAM];
-    if (gdev) { g_f = gdev[0]; g_c = gdev[1]; }
-    for (int i = threadIdx.x; i < CRF_NPARAM; i += blockDim.x) pacc[i] = 0.f;
-    __syncthreads();
+// The 16-event block blk on this workgroup (every lane calls it).  pacc: the LDS accumulator of the parameter sums -- the workgroup's,
+// added to with LDS float atomics (OWN = false), or this WAVEFRONT's own slot, added to by its lane 0 alone (OWN = true: the deterministic form)
+template <bool OWN>
+__device__ __forceinline__ void event_loss_bwd_block(const CrfParams& crf, int skip_learn, int add_bii_feat, int tonemap_only,
+                                                     const float* __restrict__ start, const float* __restrict__ end,
+                                                     const float* __restrict__ start0, const float* __restrict__ end0,
+                                                     const float* __restrict__ cum_neg, const float* __restrict__ cum_pos,
+                                                     float thr_neg, float thr_pos, const unsigned char* __restrict__ cmask,
+                                                     float cw0, float cw1, float cw2, int has_cw, long N, long blk, float g_f, float g_c,
+                                                     float* __restrict__ d_start, float* __restrict__ d_end,
+                                                     float* __restrict__ d_start0, float* __restrict__ d_end0, float* pacc) {
     const int lane = threadIdx.x & 63;
-    const EventLane L = event_lane(start, end, start0, end0, cum_neg, cum_pos, cmask, N);
+    const EventLane L = event_lane(start, end, start0, end0, cum_neg, cum_pos, cmask, N, blk);
     const int which = L.which, c = L.c, ch = L.ch;
     const bool active = L.on && L.eval;
     const bool learn = crf.map_type == 2 && !skip_learn;
@@ -404,7 +530,10 @@ __global__ __launch_bounds__(256) void k_event_loss_bwd(const CrfParams crf, int
         // parameter contributions, summed over the wavefront, then into the block's LDS accumulator
         auto add = [&](int idx, float val) {
             const float t = wave_sum_dpp(val);
-            if (lane == 0) atomicAdd(&pacc[idx], t);
+            if (lane == 0) {
+                if (OWN) pacc[idx] += t;
+                else atomicAdd(&pacc[idx], t);
+            }
         };
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -427,10 +556,49 @@ __global__ __launch_bounds__(256) void k_event_loss_bwd(const CrfParams crf, int
         float* dst = which == 0 ? d_end : which == 1 ? d_start : which == 2 ? d_end0 : d_start0;
         if (dst) dst[L.ii * 3 + c] = d_x;
     }
-    if (learn && d_params) {
+}
+
+__global__ __launch_bounds__(256) void k_event_loss_bwd(const CrfParams crf, int skip_learn, int add_bii_feat, int tonemap_only,
+                                                        const float* __restrict__ start, const float* __restrict__ end,
+                                                        const float* __restrict__ start0, const float* __restrict__ end0,
+                                                        const float* __restrict__ cum_neg, const float* __restrict__ cum_pos,
+                                                        float thr_neg, float thr_pos, const unsigned char* __restrict__ cmask,
+                                                        float cw0, float cw1, float cw2, int has_cw, long N, float g_f, float g_c,
+                                                        const float* __restrict__ gdev, float* __restrict__ d_start, float* __restrict__ d_end,
+                                                        float* __restrict__ d_start0, float* __restrict__ d_end0,
+                                                        float* __restrict__ d_params) {
+    __shared__ float pacc[CRF_NPARAM];
+    if (gdev) { g_f = gdev[0]; g_c = gdev[1]; }
+    for (int i = threadIdx.x; i < CRF_NPARAM; i += blockDim.x) pacc[i] = 0.f;
+    __syncthreads();
+    event_loss_bwd_block<false>(crf, skip_learn, add_bii_feat, tonemap_only, start, end, start0, end0, cum_neg, cum_pos, thr_neg, thr_pos, cmask,
+                                cw0, cw1, cw2, has_cw, N, blockIdx.x, g_f, g_c, d_start, d_end, d_start0, d_end0, pacc);
+    if (crf.map_type == 2 && !skip_learn && d_params) {
         __syncthreads();
         for (int k = threadIdx.x; k < CRF_NPARAM; k += blockDim.x) if (pacc[k] != 0.f) atomicAdd(d_params + k, pacc[k]);
     }
+}
+
+// The deterministic form: workgroup b walks the 16-event blocks b, b + gridDim.x, ...; a wavefront's parameter sums (a fixed DPP tree over
+// its lanes) are added to the wavefront's OWN LDS slot in block order, the four slots are folded in wavefront order and the workgroup's
+// row of partials goes to the handle's buffer (k_det_fold adds the rows in workgroup order).  No LDS and no global float atomic.
+__global__ __launch_bounds__(256) void k_event_loss_bwd_det(const CrfParams crf, int skip_learn, int add_bii_feat, int tonemap_only,
+                                                            const float* __restrict__ start, const float* __restrict__ end,
+                                                            const float* __restrict__ start0, const float* __restrict__ end0,
+                                                            const float* __restrict__ cum_neg, const float* __restrict__ cum_pos,
+                                                            float thr_neg, float thr_pos, const unsigned char* __restrict__ cmask,
+                                                            float cw0, float cw1, float cw2, int has_cw, long N, float g_f, float g_c,
+                                                            const float* __restrict__ gdev, float* __restrict__ d_start, float* __restrict__ d_end,
+                                                            float* __restrict__ d_start0, float* __restrict__ d_end0, float* __restrict__ wg) {
+    __shared__ float pacc[4][CRF_NPARAM];
+    if (gdev) { g_f = gdev[0]; g_c = gdev[1]; }
+    for (int i = threadIdx.x; i < 4 * CRF_NPARAM; i += blockDim.x) (&pacc[0][0])[i] = 0.f;
+    __syncthreads();
+    for (long blk = blockIdx.x; blk * 16 < N; blk += gridDim.x)
+        event_loss_bwd_block<true>(crf, skip_learn, add_bii_feat, tonemap_only, start, end, start0, end0, cum_neg, cum_pos, thr_neg, thr_pos, cmask,
+                                   cw0, cw1, cw2, has_cw, N, blk, g_f, g_c, d_start, d_end, d_start0, d_end0, pacc[threadIdx.x >> 6]);
+    __syncthreads();
+    for (int k = threadIdx.x; k < CRF_NPARAM; k += blockDim.x) wg[(long)blockIdx.x * CRF_NPARAM + k] = ((pacc[0][k] + pacc[1][k]) + pacc[2][k]) + pacc[3][k];
 }
 
 }  // namespace evd
@@ -439,7 +607,12 @@ using namespace evd;
 
 struct evd_crf {
     CrfParams p;
+    // evd_crf_set_deterministic: the loss entries on this handle launch their deterministic forms; wg [DET_BLOCKS][CRF_NPARAM] holds the
+    // per-workgroup partials of the launch in flight (allocated on first enable)
+    bool deterministic = false;
+    DevBuf wg;
 };
+static unsigned det_grid(long work_blocks) { return (unsigned)(work_blocks < DET_BLOCKS ? work_blocks : DET_BLOCKS); }
 
 // argument rules common to the event-loss entries
 static int event_check(const char* who, const evd_crf* crf_ev, int add_bii_feat, int tonemap_only, const void* start, const void* end,
@@ -494,7 +667,21 @@ int evd_crf_create(const evd_crf_desc* d, evd_crf** out) {
     return EVD_OK;
 }
 
-void evd_crf_destroy(evd_crf* c) { delete c; }
+void evd_crf_destroy(evd_crf* c) {
+    if (!c) return;
+    c->wg.release();
+    delete c;
+}
+
+int evd_crf_set_deterministic(evd_crf* c, int on) {
+    EVD_REQUIRE(c, "evd_crf_set_deterministic: null handle");
+    if (on && !c->wg.p) {
+        int rc = c->wg.alloc(sizeof(float) * (size_t)DET_BLOCKS * CRF_NPARAM);
+        if (rc) return rc;
+    }
+    c->deterministic = on != 0;
+    return EVD_OK;
+}
 
 int evd_crf_forward(const evd_crf* crf, const float* x, const float* feat, int feat_per_channel, int skip_learn,
                     int luma, long n, float* out, void* stream) {
@@ -510,6 +697,15 @@ int evd_blur_loss_reduce(const evd_crf* crf_rgb, int skip_learn, const float* rg
                          float* partial, float* out_rgb, float* out_rgb1, float* out_awp, void* stream) {
     EVD_REQUIRE(crf_rgb && rgb_p && w1 && tgt && partial && R >= 0 && P >= 1, "evd_blur_loss_reduce: bad arguments");
     if (R == 0) return EVD_OK;
+    if (crf_rgb->deterministic) {
+        float* wg = (float*)crf_rgb->wg.p;
+        const unsigned blocks = det_grid(cdiv(3 * R, 256));
+        k_blur_loss_det<<<blocks, 256, 0, as_stream(stream)>>>(crf_rgb->p, skip_learn, rgb_p, rgb0_p, w1, w2, tgt, tgt0, R, P, wg, out_rgb, out_rgb1, out_awp);
+        EVD_LAUNCH_CHECK();
+        k_det_fold<<<1, 64, 0, as_stream(stream)>>>(wg, (int)blocks, 6, partial);
+        EVD_LAUNCH_CHECK();
+        return EVD_OK;
+    }
     k_blur_loss<<<cdiv(3 * R, 64), 64, 0, as_stream(stream)>>>(crf_rgb->p, skip_learn, rgb_p, rgb0_p, w1, w2, tgt, tgt0, R, P, partial,
                                                              out_rgb, out_rgb1, out_awp);
     EVD_LAUNCH_CHECK();
@@ -527,6 +723,12 @@ static int blur_loss_bwd(const evd_crf* crf_rgb, int skip_learn, const float* rg
     if (d_w2) EVD_HIP(hipMemsetAsync(d_w2, 0, sizeof(float) * (size_t)R * P, st));
     const float zero5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     const float* g = g_partial ? g_partial : zero5;
+    if (crf_rgb->deterministic) {
+        k_blur_loss_bwd_det<<<cdiv(R, 64), 64, 0, st>>>(crf_rgb->p, skip_learn, rgb_p, rgb0_p, w1, w2, tgt, tgt0, R, P, g[0], g[1], g[2], g[3], g[4], g_dev,
+                                                        d_rgb_p, rgb0_p ? d_rgb0_p : nullptr, d_w1, d_w2);
+        EVD_LAUNCH_CHECK();
+        return EVD_OK;
+    }
     k_blur_loss_bwd<<<cdiv(3 * R, 64), 64, 0, st>>>(crf_rgb->p, skip_learn, rgb_p, rgb0_p, w1, w2, tgt, tgt0, R, P, g[0], g[1], g[2], g[3], g[4], g_dev,
                                                     d_rgb_p, rgb0_p ? d_rgb0_p : nullptr, d_w1, d_w2);
     EVD_LAUNCH_CHECK();
@@ -555,6 +757,16 @@ int evd_event_loss_reduce(const evd_crf* crf_ev, int skip_learn, int add_bii_fea
     if (int e = event_check("evd_event_loss_reduce", crf_ev, add_bii_feat, tonemap_only, start, end, cum_neg, cum_pos, color_mask, partial != nullptr, N)) return e;
     if (N == 0) return EVD_OK;
     const ColorWeights cw(color_weight);
+    if (crf_ev->deterministic) {
+        float* wg = (float*)crf_ev->wg.p;
+        const unsigned blocks = det_grid(cdiv(N, 16));
+        k_event_loss_det<<<blocks, 256, 0, as_stream(stream)>>>(crf_ev->p, skip_learn, add_bii_feat, tonemap_only, start, end, start0, end0,
+                                                                cum_neg, cum_pos, thr_neg, thr_pos, color_mask, cw.c[0], cw.c[1], cw.c[2], cw.given, N, wg);
+        EVD_LAUNCH_CHECK();
+        k_det_fold<<<1, 64, 0, as_stream(stream)>>>(wg, (int)blocks, 3, partial);
+        EVD_LAUNCH_CHECK();
+        return EVD_OK;
+    }
     k_event_loss<<<cdiv(N, 16), 256, 0, as_stream(stream)>>>(crf_ev->p, skip_learn, add_bii_feat, tonemap_only, start, end, start0, end0,
                                                               cum_neg, cum_pos, thr_neg, thr_pos, color_mask, cw.c[0], cw.c[1], cw.c[2],
                                                               cw.given, N, partial);
@@ -590,6 +802,19 @@ static int event_loss_bwd(const evd_crf* crf_ev, int skip_learn, int add_bii_fea
     if (d_params) EVD_HIP(hipMemsetAsync(d_params, 0, sizeof(float) * CRF_NPARAM, st));
     if (N == 0) return EVD_OK;
     const ColorWeights cw(color_weight);
+    if (crf_ev->deterministic) {
+        float* wg = (float*)crf_ev->wg.p;
+        const unsigned blocks = det_grid(cdiv(N, 16));
+        k_event_loss_bwd_det<<<blocks, 256, 0, st>>>(crf_ev->p, skip_learn, add_bii_feat, tonemap_only, start, end, start0, end0, cum_neg, cum_pos,
+                                                     thr_neg, thr_pos, color_mask, cw.c[0], cw.c[1], cw.c[2], cw.given, N, g_fine, g_coarse, g_dev,
+                                                     d_start, d_end, (start0 && end0) ? d_start0 : nullptr, (start0 && end0) ? d_end0 : nullptr, wg);
+        EVD_LAUNCH_CHECK();
+        if (d_params && crf_ev->p.map_type == 2 && !skip_learn) {
+            k_det_fold<<<1, 64, 0, st>>>(wg, (int)blocks, CRF_NPARAM, d_params);
+            EVD_LAUNCH_CHECK();
+        }
+        return EVD_OK;
+    }
     k_event_loss_bwd<<<cdiv(N, 16), 256, 0, st>>>(crf_ev->p, skip_learn, add_bii_feat, tonemap_only, start, end, start0, end0, cum_neg, cum_pos,
                                                   thr_neg, thr_pos, color_mask, cw.c[0], cw.c[1], cw.c[2], cw.given, N, g_fine, g_coarse, g_dev,
                                                   d_start, d_end, (start0 && end0) ? d_start0 : nullptr, (start0 && end0) ? d_end0 : nullptr, d_params);

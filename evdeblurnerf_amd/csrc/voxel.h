@@ -47,6 +47,15 @@ bool voxel_sample_bwd_w_ok(const GridParams& g);
 int launch_voxel_sample_bwd_w(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
                               float* d_pts, float* rows_l, LTap* ltap, unsigned* lmax, bool half_grids, hipStream_t st);
 
+// ---- the deterministic scatter (kernel_voxel_scatter_det.hip): 64-bit fixed-point shadow accumulators in the caller's region, one unit 2^-k
+// per call.  _scale zeroes the shadow and leaves the float bits of the batch's largest |contribution| in the region's first word; the host
+// reads it, takes k from evd_scatter_det_unit_exp and runs _add (adds, finish kernels, d pts, basis_mat partials).
+size_t voxel_scatter_det_region_bytes(const GridParams& g);
+int launch_voxel_scatter_det_scale(const GridParams& g, bool half_grids, const float* pts, long n, const float* d_out, int d_stride, int d_col,
+                                   const GridGrads& gg, void* region, hipStream_t st);
+int launch_voxel_scatter_det_add(const GridParams& g, bool half_grids, const float* pts, long n, const float* d_out, int d_stride, int d_col,
+                                 const GridGrads& gg, float* d_pts, void* region, int k, hipStream_t st);
+
 constexpr int TV_MAX_BLOCKS = 4096;     // partial (dh^2, dw^2) pairs per tensor
 struct TvShape { int C[6], H[6], W[6], blocks[6]; };
 // one launch for the six tensors of a level (round 6: twelve launches per iteration -- half of them on 586 x 64 line grids, whose kernels are

@@ -737,7 +737,7 @@ class NeRFAll:
     # ------------------------------------------------------------------ forward, renderer.py:266-397
     # ---- the reference's nn.Module surface for a training loop (optimizer groups run_nerf.py:245-263, iteration :423-613,
     # ---- checkpoint :617-638) ---------------------------------------------------------------------------------------------
-    def enable_training(self, state_dict, grads_in_place=False):
+    def enable_training(self, state_dict, grads_in_place=False, deterministic=False):
         """Create the trainable tensors from a state dict and keep them in the model: ONE LEAF PER REFERENCE PARAMETER
         (`named_parameters()` yields the reference's names), so that `parameters()`, `get_parameters(type, match_re, not_match_re)`,
         `grad_vars` and `grad_vars_vol` feed optimizer groups exactly like renderer.py:58-79,112-127 / run_nerf.py:245-263, and
@@ -750,9 +750,15 @@ class NeRFAll:
         grads_in_place=True: the backward kernels ADD the parameter and grid gradients straight into persistent buffers whose slices
         are the leaves' .grad, and return None to autograd.  Valid for the reference's loop only -- optimizer.zero_grad();
         loss.backward(); optimizer.step() (run_nerf.py:593-601) -- and what it saves per blurfactory iteration is ~90 gradient
-        additions, ~50 copies and the zero-fill + re-add of 165 MB of grid gradients per scatter."""
+        additions, ~50 copies and the zero-fill + re-add of 165 MB of grid gradients per scatter.
+
+        deterministic=True (either setting of grads_in_place): the tri-plane levels scatter through evd_voxel_sample_bwd_det
+        (VoxelNeRFBase.set_deterministic), so two runs from the same state give the same bits.  It covers this library's kernels; the loss
+        reductions are switched on their CRFs (TonemappingTransform.set_deterministic); torch modules the caller puts in the loop and the
+        all-reduce of dist.GradReducer are the caller's (torch.use_deterministic_algorithms)."""
         from collections import OrderedDict
         self._grads_in_place = bool(grads_in_place)
+        self._deterministic = bool(deterministic)
         levels = []
         for prefix, net, p in (("mlp_coarse.", self.mlp_coarse, None), ("mlp_fine.", self.mlp_fine, None)):
             if net is None:
@@ -773,6 +779,7 @@ class NeRFAll:
                 grids = OrderedDict([(f"{prefix}app_plane.{i}", g[i]) for i in range(3)] + [(f"{prefix}app_line.{i}", g[3 + i]) for i in range(3)]
                                     + [(f"{prefix}basis_mat.weight", g[6])])
                 net._grads_in_place = self._grads_in_place
+                net.set_deterministic(self._deterministic)
                 net._grid_grad_flat = (torch.empty((sum(t.numel() for t in g),), dtype=torch.float32, device=self.device)
                                        if self._grads_in_place else None)
             net._synced = net._synced_net = None

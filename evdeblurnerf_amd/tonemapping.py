@@ -53,6 +53,12 @@ class CRF:
         self._take_pending()
         return self._h
 
+    def set_deterministic(self, on=True):
+        """evd_crf_set_deterministic: the blur / event loss entries called with this CRF (losses._BlurLoss / _EventLoss) reduce in a
+        fixed order, without floating-point atomics (run_nerf.py:50).  One stream at a time while on."""
+        L.check(L.lib().evd_crf_set_deterministic(self._h, int(bool(on))), "evd_crf_set_deterministic")
+        return self
+
     @staticmethod
     def identity_state_dict(extra_features=0, seed=42, steps=3000, device="cuda"):
         """CRF.init_identity (tonemapping.py:29-57; `tone_mapping_learn_init_identity = True` in the shipped configs, wired at
@@ -148,6 +154,12 @@ class TonemappingTransform:
         return self
 
     def eval(self):
+        return self
+
+    def set_deterministic(self, on=True):
+        """both CRFs: the loss reductions that run on them become bit-reproducible (CRF.set_deterministic)"""
+        self.tonemapping_rgb.set_deterministic(on)
+        self.tonemapping_event.set_deterministic(on)
         return self
 
     def encode_rgb(self, x, skip_learn_crf=False, rgb_extra_feat=None, **kwargs):      # tonemapping.py:111-118

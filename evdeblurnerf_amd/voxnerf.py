@@ -105,12 +105,23 @@ class _VoxelSample(torch.autograd.Function):
             g, g_stride = d_out.reshape(-1, net.app_dim).contiguous().float(), net.app_dim
         grads, gs = _grid_grads(net, ctx.saved_tensors, in_place=getattr(net, "_grads_in_place", _GRADS_IN_PLACE) and not torch.is_grad_enabled())
         d_pts = torch.empty_like(pts) if ctx.needs_input_grad[0] else None
+        prec = L.PREC[ctx.precision] if ctx.precision is not None else L.PREC["f32"]
+        if getattr(net, "_deterministic", False):
+            # the deterministic scatter (csrc/kernel_voxel_scatter_det.hip): 64-bit fixed-point shadow accumulators in a workspace the
+            # level keeps across calls (8 B per plane / line gradient element: ~240 MB for the shipped fine level, nine scatters per iteration)
+            nb = int(L.lib().evd_voxel_sample_bwd_det_workspace_bytes(net._h, pts.shape[0]))
+            ws = getattr(net, "_det_ws", None)
+            if ws is None or ws.numel() < nb or ws.device != pts.device:
+                ws = net._det_ws = torch.empty((nb,), dtype=torch.uint8, device=pts.device)
+            L.check(L.lib().evd_voxel_sample_bwd_det(net._h, prec, L.ptr(pts), pts.shape[0], C.c_void_p(g.data_ptr()), g_stride, 0, C.byref(gs), L.ptr(d_pts),
+                                                     L.ptr(ws), ws.numel(), L.stream_ptr()), "evd_voxel_sample_bwd_det")
+            _bwd_done(net)
+            return (d_pts.reshape(ctx.pts.shape) if d_pts is not None else None, None, None, *grads)
         # scratch for the hybrid form of the scatter (csrc/kernel_voxel_scatter.hip: plane taps by direct float atomics, line taps through
         # fixed-point LDS slices -- a third fewer atomic requests, 24-27 % faster)
         nb = int(L.lib().evd_voxel_sample_bwd_workspace_bytes(net._h, pts.shape[0]))
         ws = torch.empty((nb,), dtype=torch.uint8, device=pts.device) if nb else None
         # in the forward's arithmetic mode: where it interpolated the float16 grid copies, the re-gather of the backward reads them too
-        prec = L.PREC[ctx.precision] if ctx.precision is not None else L.PREC["f32"]
         L.check(L.lib().evd_voxel_sample_bwd_prec(net._h, prec, L.ptr(pts), pts.shape[0], C.c_void_p(g.data_ptr()), g_stride, 0, C.byref(gs), L.ptr(d_pts), L.ptr(ws), nb,
                                                   L.stream_ptr()), "evd_voxel_sample_bwd_prec")
         _bwd_done(net)
@@ -250,6 +261,14 @@ class VoxelNeRFBase:
 
     def train(self, mode=True):
         self.training = mode
+        return self
+
+    def set_deterministic(self, on=True):
+        """The backward of sample_train through evd_voxel_sample_bwd_det: bit-reproducible plane / line / basis gradients and d pts (the
+        reference's seed_everything(..., deterministic=True), run_nerf.py:50).  Off (default): the float-atomic scatter, unchanged."""
+        self._deterministic = bool(on)
+        if not on:
+            self._det_ws = None
         return self
 
     # voxnerf.py:153-201; returns the reference 5-tuple (rgb_map, density, acc_map, weights, depth_map).  Sigma is channel 0, the

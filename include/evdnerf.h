@@ -457,6 +457,32 @@ int evd_voxel_sample_bwd_ws(const evd_voxel* v, const float* pts, long n, const 
  * computed, at half the gather's loads and bytes; the other modes are evd_voxel_sample_bwd_ws. */
 int evd_voxel_sample_bwd_prec(const evd_voxel* v, int precision, const float* pts, long n, const float* d_out, int d_stride, int d_col,
                               const evd_voxel_grid_grads* g, float* d_pts, void* workspace, size_t workspace_bytes, void* stream);
+/* The DETERMINISTIC scatter (the reference asks for repeatable runs, seed_everything(args.seed, deterministic=True), run_nerf.py:50, and
+ * names grid_sample's backward, voxnerf.py:144, as the operation that cannot repeat).  Arguments as evd_voxel_sample_bwd_prec: ADDS into
+ * the gradients of g (NULL = not wanted), overwrites d_pts, reads the float16 grid copies where the forward of `precision` did; n == 0 is a
+ * no-op; every n_comp evd_voxel_sample_bwd takes.  Every tap contribution w_tap x (d coef x other) is computed in float32 (d coef: one
+ * float32 fmaf chain over app_dim per element, a function of the sample alone), converted with round-to-nearest to signed 64-bit fixed
+ * point and added with an integer atomic to a shadow accumulator in the workspace; a finish kernel adds (float)(acc x unit) to each
+ * gradient element once and leaves the accumulator zero (the entry zeroes the shadow itself: the workspace may hold anything).
+ *   unit:  ONE per call.  cmax = the largest |contribution| of the batch (a first pass over the same arithmetic, atomicMax on the float's
+ *          bits); frexpf(cmax) -> E (cmax < 2^E), h = ceil(log2(4 n)), unit = 2^(E - (62 - h)) = 2^-k with k = evd_scatter_det_unit_exp(cmax, n).
+ *          A cell receives at most 4 n terms below 2^(62 - h) units: no overflow for any input; contributions more than 62 - h bits (>= 40
+ *          for n <= 2^20) below the batch maximum are flushed.  k is clamped to 126, so that 2^k is a finite float32.
+ *   guarantee:  the plane and line gradients are bit-identical from run to run AND under any permutation of the samples; d_pts is a fixed-order
+ *          sum per sample (bit-identical per sample under permutation); the basis gradient is summed per workgroup (tile t on workgroup t mod
+ *          min(tiles, 512)) and the workgroups' partials are folded in workgroup order: bit-identical from run to run for a given n, NOT
+ *          permutation invariant.
+ *   non-finite d_out or grids (cmax not finite):  no unit exists; the batch is scattered by evd_voxel_sample_bwd_prec into the same workspace,
+ *          so a NaN / Inf reaches the gradients exactly as it does there.
+ * The entry READS cmax ON THE HOST between its two passes: it synchronises the stream once per call (the exception to the conventions above;
+ * it cannot be captured into a graph).  Workspace: 8 B per plane and line gradient element + 512 x app_dim x sum(n_comp) x 4 B of
+ * workgroup partials (or the size of evd_voxel_sample_bwd_workspace_bytes where that is larger) + 512 B; NULL level -> 0. */
+size_t evd_voxel_sample_bwd_det_workspace_bytes(const evd_voxel* v, long n);
+int evd_voxel_sample_bwd_det(const evd_voxel* v, int precision, const float* pts, long n, const float* d_out, int d_stride, int d_col,
+                             const evd_voxel_grid_grads* g, float* d_pts, void* workspace, size_t workspace_bytes, void* stream);
+/* pure host function: the exponent k of the fixed-point scale 2^k above (k = 62 - ceil(log2(4 n)) - E, at most 126); 0 where cmax is
+ * not finite or not positive or n < 1 */
+int evd_scatter_det_unit_exp(float cmax, long n);
 /* d_loss[0] * d TV_loss_app / d grid added into g (voxnerf.py:126-130, 306-324); d_loss is a DEVICE scalar (no host sync) */
 int evd_voxel_tv_loss_bwd(const evd_voxel* v, const float* d_loss, const evd_voxel_grid_grads* g, void* stream);
 
@@ -474,6 +500,13 @@ typedef struct {
 } evd_crf_desc;
 int evd_crf_create(const evd_crf_desc* desc, evd_crf** out);
 void evd_crf_destroy(evd_crf* crf);
+/* Deterministic loss reductions (run_nerf.py:50).  With on != 0, evd_blur_loss_reduce, evd_blur_loss_bwd(_dev), evd_event_loss_reduce and
+ * evd_event_loss_bwd(_dev) called with THIS handle launch forms without floating-point atomics: a bounded grid (<= 256 workgroups) walks the
+ * batch, per-workgroup sums go to a buffer of the handle (allocated on the first enable, outside the iteration loop) and one wavefront adds them
+ * in workgroup order and performs the call's single partial[k] += sum (d_params: overwritten, as before); d_w1 / d_w2 are the three channel
+ * terms added in channel order.  Same bits for the same batch.  While on, the handle is NOT re-entrant for these entries (one launch's partials
+ * live in the handle's buffer): one stream at a time.  With on == 0 (the default) every kernel, launch and bit is as before. */
+int evd_crf_set_deterministic(evd_crf* crf, int on);
 /* CRF.forward (+ rec601/rec709/avg luma of TonemappingTransform.encode_luma, tonemapping.py:120-139).
  * x dev [n,3]; feat dev NULL | [n,E] (feat_per_channel 0) | [n,3,E] (1).  luma < 0: out [n,3];
  * luma 0/1/2 = rec601/rec709/avg: out [n,1]. */

@@ -62,12 +62,15 @@ def main():
     ap.add_argument("--plain-autograd", action="store_true",
                     help="parameter / grid gradients returned to autograd (the library's default) instead of accumulated in place by the backward kernels "
                          "(NeRFAll.enable_training(grads_in_place=True): what a run_nerf.py-style loop opts into)")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="the bit-reproducible training mode: NeRFAll.enable_training(deterministic=True) (fixed-point tri-plane scatter) and "
+                         "CRF.set_deterministic (fixed-order loss reductions); covers the library's kernels, not --awp torch / --kernel torch")
     ap.add_argument("--merge-events", action="store_true", help="render the event batch's start and end rays in one call (integration option; the reference calls nerf() twice)")
     ap.add_argument("--mam", choices=["mean", "corr"], default="corr",
                     help="the AWP module's motion aggregation: corr = the reference's MotionAggregationModule structure (MAMLike), mean = a small stand-in")
     a = ap.parse_args()
     ms, nr, loss = run(a)
-    print(f"blurfactory TRAINING iteration [{a.precision}, {a.kernel} blur kernel]: {nr} rays x (64 + 64) samples, losses, TV, backward, Adam, re-pack: {ms:.2f} ms "
+    print(f"blurfactory TRAINING iteration [{a.precision}, {a.kernel} blur kernel{', deterministic' if a.deterministic else ''}]: {nr} rays x (64 + 64) samples, losses, TV, backward, Adam, re-pack: {ms:.2f} ms "
           f"({nr / ms / 1e3:.2f} M rays/s); loss = {loss:.5f}")
 
 
@@ -122,10 +125,14 @@ def run(a):
         awpnet = RefLikeAWP(P=a.P, view_ch=4 if kernel_kind == "standin" else 32, mam=getattr(a, "mam", "corr")).to(dev)
         if awp_mode == "fused":
             awpnet = FusedAWP(awpnet, precision=a.precision if a.precision in ("f16", "bf16") else "f16", graph_per_ray=bool(getattr(a, "graph", False)))
-    model = NeRFAll(args, sd, kernelsnet=kern, awpnet=awpnet, precision=a.precision).enable_training(sd, grads_in_place=not getattr(a, "plain_autograd", False)).train()
+    model = NeRFAll(args, sd, kernelsnet=kern, awpnet=awpnet, precision=a.precision).enable_training(sd, grads_in_place=not getattr(a, "plain_autograd", False),
+                                                                                                     deterministic=bool(getattr(a, "deterministic", False))).train()
     model.use_awp = awpnet is not None
     crf_rgb = CRF("gamma")
     crf_ev = CRF("learn", state_dict=W.make_crf_state_dict(5, extra_features=2), extra_features=2)
+    if getattr(a, "deterministic", False):
+        crf_rgb.set_deterministic(True)
+        crf_ev.set_deterministic(True)
     crf_flat = crf_ev.flat_params(dev)
     # run_nerf.py:245-263 builds torch.optim.Adam over the same parameter groups; fused=True is that optimizer's single-kernel implementation
     opt = torch.optim.Adam([{"params": model.parameters(), "lr": 5e-4}, {"params": [crf_flat], "lr": 1e-4}], fused=not bool(os.environ.get("EVD_ADAM_FOREACH")))

@@ -50,7 +50,7 @@ def train_one(a, precision, teacher, K, kw, held, held_t, log_every):
     import time
     torch.manual_seed(1234)                                  # the same stratification draws for every mode
     student, sd = make(202, a.coarse_voxels, a.fine_voxels, precision)
-    student.enable_training(sd, grads_in_place=True).train()
+    student.enable_training(sd, grads_in_place=True, deterministic=a.deterministic).train()
     nets = student.get_parameters("net", not_match_re=r"basis_mat")
     grids = student.grad_vars_vol + student.get_parameters("net", match_re=r"basis_mat")
     opt = torch.optim.Adam([{"params": nets, "lr": 1e-3}, {"params": grids, "lr": 2e-2}])
@@ -97,6 +97,8 @@ def main():
     ap.add_argument("--coarse-voxels", type=int, default=64 ** 3)
     ap.add_argument("--fine-voxels", type=int, default=128 ** 3)
     ap.add_argument("--log-every", type=int, default=0, help="rows of the loss curve (default: 10 rows)")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="train with NeRFAll.enable_training(deterministic=True): the bit-reproducible fixed-point tri-plane scatter")
     a = ap.parse_args()
     modes = a.precision.split(",")
     K = W.synthetic_camera()
