@@ -5,6 +5,7 @@
 #include "nerf_mlp_kernel.h"
 #include "nerf_net.h"
 #include "nerf_train.h"
+#include "nerf_train_generic.h"
 #include "pack.h"
 
 #include <cmath>
@@ -102,7 +103,7 @@ extern "C" {
 
 const char* evd_last_error(void) { return evd::err_buf(); }
 long evd_debug_side_spin_count(void) { return evd::g_side_spins.load(std::memory_order_relaxed); }
-int evd_version(void) { return 120; }      // 110: training entries (evd_*_train, evd_*_backward, evd_*_load_params, ...); 120: evd_awp_embed_*, the f16x3 training mode (evd_*_train_store_bytes_prec), evd_voxel_mlp_backward(awp_store), evd_voxel_sample_bwd_ws, evd_merge_features
+int evd_version(void) { return 130; }      // 130: evd_nerf_train_store_bytes_net, evd_nerf_backward_workspace_bytes_net (generic NeRF training path, netwidth 128); 110: training entries (evd_*_train, evd_*_backward, evd_*_load_params, ...); 120: evd_awp_embed_*, the f16x3 training mode (evd_*_train_store_bytes_prec), evd_voxel_mlp_backward(awp_store), evd_voxel_sample_bwd_ws, evd_merge_features
 
 int evd_device_count(void) {
     int n = 0;
@@ -136,7 +137,7 @@ int evd_nerf_create(const evd_nerf_desc* d, evd_nerf** out) {
                 "evd_nerf_create: multires %d / multires_views %d out of range (0..%d / 0..10)", d->multires, d->multires_views, PE_L_MAX);
     const int L = d->multires, Lv = d->multires_views, VKS = pe_ksteps(Lv) <= 2 ? 2 : 4;
     const bool standard = L == PE_L && Lv == PE_LV;
-    EVD_REQUIRE(d->W == 256 || d->W == 64, "evd_nerf_create: netwidth %d not built (64, 256)", d->W);
+    EVD_REQUIRE(d->W == 256 || d->W == 128 || d->W == 64, "evd_nerf_create: netwidth %d not built (64, 128, 256)", d->W);
     EVD_REQUIRE(d->D >= 1 && d->D <= EVD_MAX_LAYERS, "evd_nerf_create: netdepth %d out of range", d->D);
     const bool no_views = !d->views_w && !d->feature_w && !d->alpha_w && !d->rgb_w && d->output_w;
     EVD_REQUIRE(no_views || (d->views_w && d->feature_w && d->alpha_w && d->rgb_w),
@@ -351,6 +352,8 @@ int evd_nerf_create(const evd_nerf_desc* d, evd_nerf** out) {
         if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(EVD_E_HIP, "evd_nerf_create: the folded f16c stream could not be packed");
         dev_params.release();
     }
+    // generic training path (nerf_train_generic.h): its backward reads the float32 parameters in place
+    if (!rc && nerf_generic_trains(n, EVD_PREC_F16X3)) rc = n->params_f32.upload(arena.data(), arena.size() * sizeof(float));
     if (rc) { evd_nerf_destroy(n); return rc; }
     *out = n;
     return EVD_OK;
@@ -372,6 +375,7 @@ void evd_nerf_destroy(evd_nerf* n) {
     n->bias_f.release();
     n->bias_f_src.release();
     n->fold_arena.release();
+    n->params_f32.release();
     n->side.release();
     delete n;
 }
@@ -400,6 +404,7 @@ int evd_nerf_load_params(evd_nerf* net, const float* params, void* stream) {
     const long nb = (long)(net->bias.bytes / sizeof(float));
     hipLaunchKernelGGL(k_gather_f32, dim3((unsigned)cdiv(nb, 256L)), dim3(256), 0, st, params, (const int*)net->bias_src.p, nb, (float*)net->bias.p);
     EVD_LAUNCH_CHECK();
+    if (net->params_f32.p) EVD_HIP(hipMemcpyAsync(net->params_f32.p, params, net->params_f32.bytes, hipMemcpyDeviceToDevice, st));
     return nerf_fold_pack(net, params, st);
 }
 

@@ -4,6 +4,7 @@
 #include "nerf_mlp.h"
 #include "nerf_net.h"
 #include "nerf_train.h"
+#include "nerf_train_generic.h"
 
 #include <cstdint>
 #include <cstdlib>
@@ -21,6 +22,10 @@ static bool train_built(const evd_nerf* n, int prec) {
     return prec >= 0 && prec < EVD_NUM_PREC && is_train_prec(prec) && n->pipe_chunks[prec] > 0;
 }
 static int store_prec(int prec) { return (prec == EVD_PREC_F16C || prec == EVD_PREC_F16M) ? EVD_PREC_F16 : prec; }
+// what both entries say to a network / precision pair that neither path trains
+#define EVD_TRAIN_REFUSAL(entry)                                                                                                              \
+    entry ": the training path is built for precision f16 / bf16 / f16x3 / f16c / f16m on the netdepth 8, netwidth 256, skips [4] network; "  \
+          "every other view-branch network trains in f16x3 only (use_viewdirs=False networks: not built)"
 }  // namespace evd
 
 
@@ -32,14 +37,31 @@ size_t evd_nerf_train_store_bytes_prec(int precision, long nsamp) {
     return (nsamp < 0 || sp < 0 || sp >= EVD_NUM_PREC || !is_train_prec(sp)) ? 0 : (size_t)train_tiles(nsamp) * astore::tile_bytes(sp);
 }
 
+size_t evd_nerf_train_store_bytes_net(const evd_nerf* net, int precision, long nsamp) {
+    if (!net || nsamp < 0) return 0;
+    if (train_built(net, precision)) return evd_nerf_train_store_bytes_prec(precision, nsamp);
+    return nerf_generic_trains(net, precision) ? nerf_generic_store_bytes(net, nsamp) : 0;
+}
+
 int evd_nerf_mlp_train(const evd_nerf* net, int precision, const float* ray_batch, const float* z, long R, int S, float* raw,
                        void* store, size_t store_bytes, void* stream) {
     EVD_REQUIRE(net && ray_batch && z && raw && store, "evd_nerf_mlp_train: null argument");
-    EVD_REQUIRE(train_built(net, precision),
-                "evd_nerf_mlp_train: the training path is built for precision f16 / bf16 / f16x3 / f16c / f16m on the netdepth 8, netwidth 256, skips [4] network");
+    const bool generic = !train_built(net, precision) && nerf_generic_trains(net, precision);
+    EVD_REQUIRE(generic || train_built(net, precision), EVD_TRAIN_REFUSAL("evd_nerf_mlp_train"));
     EVD_REQUIRE(R >= 0 && S >= 1, "evd_nerf_mlp_train: bad shape R=%ld S=%d", R, S);
     if (R == 0) return EVD_OK;
     const long nsamp = R * (long)S;
+    if (generic) {          // the generic inference kernel with stores: its stream, its encodings at run-time frequency counts
+        const size_t need = nerf_generic_store_bytes(net, nsamp);
+        if (store_bytes < need) return fail(EVD_E_WORKSPACE, "evd_nerf_mlp_train: store %zu < %zu bytes", store_bytes, need);
+        MlpParams g{};
+        g.wstream = (const char*)net->stream[EVD_PREC_F16X3].data.p;
+        g.bias = (const float*)net->bias.p;
+        g.ray_batch = ray_batch; g.z = z; g.nsamp = nsamp; g.S = S; g.ncol = 11;
+        g.D = net->D; g.skip = net->skip; g.nchunks = net->nchunks[EVD_PREC_F16X3]; g.nbias = (int)(net->bias.bytes / sizeof(float));
+        g.raw = raw; g.act = (char*)store; g.pe_l = net->multires; g.pe_lv = net->multires_views;
+        return launch_nerf_train_fwd_generic(net->W, g, as_stream(stream));
+    }
     if (store_bytes < evd_nerf_train_store_bytes_prec(precision, nsamp))
         return fail(EVD_E_WORKSPACE, "evd_nerf_mlp_train: store %zu < %zu bytes", store_bytes, evd_nerf_train_store_bytes_prec(precision, nsamp));
     MlpParams p{};
@@ -62,17 +84,36 @@ int evd_nerf_mlp_train(const evd_nerf* net, int precision, const float* ray_batc
 // scratch of the backward: the wgrad partial sums of the largest block (8 x 9 accumulator tiles per wavefront group) + the loss-scale word
 static const int WGRAD_BLOCKS = 256;
 size_t evd_nerf_backward_workspace_bytes(void) { return (size_t)WGRAD_BLOCKS * 8 * 9 * 4096 + 512; }
+size_t evd_nerf_backward_workspace_bytes_net(const evd_nerf* net, int precision) {
+    if (!net) return 0;
+    if (train_built(net, precision)) return evd_nerf_backward_workspace_bytes();
+    return nerf_generic_trains(net, precision) ? nerf_generic_workspace_bytes() : 0;
+}
 
 int evd_nerf_mlp_backward(const evd_nerf* net, int precision, const float* d_raw, long R, int S, void* store, size_t store_bytes,
                           const evd_nerf_grads* grads, const float* pts, const float* viewdirs, int vd_stride, float* d_pts, float* d_dirs,
                           void* workspace, size_t workspace_bytes, void* stream) {
     EVD_REQUIRE((!d_pts || pts) && (!d_dirs || viewdirs), "evd_nerf_mlp_backward: d_pts / d_dirs need the forward's pts / viewdirs");
     EVD_REQUIRE(net && d_raw && store && grads && workspace, "evd_nerf_mlp_backward: null argument");
-    EVD_REQUIRE(train_built(net, precision),
-                "evd_nerf_mlp_backward: the training path is built for precision f16 / bf16 / f16x3 / f16c / f16m on the netdepth 8, netwidth 256, skips [4] network");
+    const bool generic = !train_built(net, precision) && nerf_generic_trains(net, precision);
+    EVD_REQUIRE(generic || train_built(net, precision), EVD_TRAIN_REFUSAL("evd_nerf_mlp_backward"));
     EVD_REQUIRE(R >= 0 && S >= 1, "evd_nerf_mlp_backward: bad shape R=%ld S=%d", R, S);
     if (R == 0) return EVD_OK;
     const long nsamp = R * (long)S;
+    if (generic) {
+        if (store_bytes < nerf_generic_store_bytes(net, nsamp))
+            return fail(EVD_E_WORKSPACE, "evd_nerf_mlp_backward: store %zu < %zu bytes", store_bytes, nerf_generic_store_bytes(net, nsamp));
+        if (workspace_bytes < nerf_generic_workspace_bytes())
+            return fail(EVD_E_WORKSPACE, "evd_nerf_mlp_backward: workspace %zu < %zu bytes", workspace_bytes, nerf_generic_workspace_bytes());
+        GenBwdPlan g;
+        g.net = net; g.d_raw = d_raw; g.nsamp = nsamp; g.store = (float*)store;
+        g.partial = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+        for (int l = 0; l < EVD_MAX_LAYERS; ++l) { g.grads.pts_w[l] = l < net->D ? grads->pts_w[l] : nullptr; g.grads.pts_b[l] = l < net->D ? grads->pts_b[l] : nullptr; }
+        g.grads.views_w = grads->views_w; g.grads.views_b = grads->views_b; g.grads.feature_w = grads->feature_w; g.grads.feature_b = grads->feature_b;
+        g.grads.alpha_w = grads->alpha_w; g.grads.alpha_b = grads->alpha_b; g.grads.rgb_w = grads->rgb_w; g.grads.rgb_b = grads->rgb_b;
+        g.accumulate = grads->accumulate ? 1 : 0; g.d_pts = d_pts; g.d_dirs = d_dirs;
+        return run_nerf_backward_generic(g, as_stream(stream));
+    }
     if (store_bytes < evd_nerf_train_store_bytes_prec(precision, nsamp))
         return fail(EVD_E_WORKSPACE, "evd_nerf_mlp_backward: store %zu < %zu bytes", store_bytes, evd_nerf_train_store_bytes_prec(precision, nsamp));
     if (workspace_bytes < evd_nerf_backward_workspace_bytes())

@@ -146,12 +146,16 @@ int nerf_mlp_generic_dispatch(int prec, int W, const MlpParams& p, hipStream_t s
     EVD_CASE(EVD_PREC_F16, 256);
     EVD_CASE(EVD_PREC_F16X3, 256);
     EVD_CASE(EVD_PREC_F32, 256);
+    EVD_CASE(EVD_PREC_BF16, 128);
+    EVD_CASE(EVD_PREC_F16, 128);
+    EVD_CASE(EVD_PREC_F16X3, 128);
+    EVD_CASE(EVD_PREC_F32, 128);
     EVD_CASE(EVD_PREC_BF16, 64);
     EVD_CASE(EVD_PREC_F16, 64);
     EVD_CASE(EVD_PREC_F16X3, 64);
     EVD_CASE(EVD_PREC_F32, 64);
 #undef EVD_CASE
-    return fail(EVD_E_INVALID, "evd_nerf_mlp: no kernel for precision %d, width %d (built: W in {64,256})", prec, W);
+    return fail(EVD_E_INVALID, "evd_nerf_mlp: no kernel for precision %d, width %d (built: W in {64,128,256})", prec, W);
 }
 
 int nerf_mlp_pipe_dispatch(int prec, const MlpParams& p, hipStream_t st) {

@@ -174,7 +174,8 @@ class NeRF:
         return raw, feat
 
     # Training forward: the same raw plus the activation store evd_nerf_mlp_backward consumes (f16 / bf16, or f16x3 = the float32-grade
-    # mode with (hi, lo) fragments; 8 x 256 network)
+    # mode with (hi, lo) fragments; 8 x 256 network).  Every other view-branch network trains in f16x3 on the generic kernels; the
+    # per-network size queries are all this class knows about which path runs.
     def mlpforward_train(self, ray_batch, z_vals, precision=None):
         if not self.use_viewdirs:
             raise L.EvdError("the training path is not built for use_viewdirs=False networks")
@@ -182,9 +183,10 @@ class NeRF:
         z = z_vals.contiguous().float()
         R, S = z.shape
         raw = torch.empty((R, S, 4), dtype=torch.float32, device=z.device)
-        nb = int(L.lib().evd_nerf_train_store_bytes_prec(L.PREC[precision or self.precision], R * S))
+        nb = int(L.lib().evd_nerf_train_store_bytes_net(self._h, L.PREC[precision or self.precision], R * S))
         if nb == 0 and R * S > 0:
-            raise L.EvdError(f"the training path is built for precision f16 / bf16 / f16x3 / f16c / f16m, not {precision or self.precision}")
+            raise L.EvdError(f"no training path for this network in precision {precision or self.precision}: the netdepth 8, netwidth 256, "
+                             "skips [4], multires 10 / 4 network trains in f16 / bf16 / f16x3 / f16c / f16m, every other one in f16x3")
         store = torch.empty((nb,), dtype=torch.uint8, device=z.device)
         L.check(L.lib().evd_nerf_mlp_train(self._h, L.PREC[precision or self.precision], L.ptr(rb), L.ptr(z), R, S, L.ptr(raw),
                                             L.ptr(store), nb, L.stream_ptr()), "evd_nerf_mlp_train")
@@ -257,7 +259,7 @@ class NeRF:
             else:
                 head = {"views_linears.0": "views", "feature_linear": "feature", "alpha_linear": "alpha", "rgb_linear": "rgb"}[name]
                 setattr(gs, head + field, base + 4 * off)
-        nb = int(L.lib().evd_nerf_backward_workspace_bytes())
+        nb = int(L.lib().evd_nerf_backward_workspace_bytes_net(self._h, L.PREC[precision or self.precision]))
         ws = torch.empty((nb,), dtype=torch.uint8, device=g.device)
         want = pts is not None
         d_pts = torch.empty((R * S, 3), dtype=torch.float32, device=g.device) if want else None

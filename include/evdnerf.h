@@ -250,9 +250,18 @@ int evd_nerf_mlp(const evd_nerf* net, int precision, const float* ray_batch, con
  * EVD_E_INVALID otherwise.  EVD_PREC_F16X3 is the float32-grade training mode (the reference trains in float32, run_nerf.py:593-601):
  * every stored fragment is a (hi, lo) float16 pair, every product of the forward, the dgrad and the wgrad kernels is the 3-MFMA
  * split product -- twice the store (evd_nerf_train_store_bytes_prec), gradients equal to float32 autograd to ~1e-5.
- * evd_nerf_train_store_bytes = the half-precision size (kept for existing callers). */
+ * evd_nerf_train_store_bytes = the half-precision size (kept for existing callers).
+ * Every other view-branch network (netdepth 1..EVD_MAX_LAYERS, netwidth 64 / 128 / 256, one skip index or none, multires 0..10,
+ * multires_views 0..10) trains in EVD_PREC_F16X3 only, on the generic kernels (csrc/kernel_nerf_train_generic.hip): the forward is
+ * evd_nerf_mlp's generic kernel with stores (raw bit-equal to evd_nerf_mlp), the store holds float32 rows (sample position and
+ * direction, every layer's output) and the backward's per-sample gradient rows, and the backward multiplies in exact float32 on the
+ * matrix cores with no floating-point atomics (bit-reproducible).  The sizes depend on the network:
+ * evd_nerf_train_store_bytes_net / evd_nerf_backward_workspace_bytes_net return, for the 8 x 256 / (10, 4) / skips [4] network, what
+ * evd_nerf_train_store_bytes_prec / evd_nerf_backward_workspace_bytes return; for a network on the generic path its sizes in
+ * EVD_PREC_F16X3 and 0 in every other precision (EVD_PREC_F32 included: no training path).  use_viewdirs=False networks: 0. */
 size_t evd_nerf_train_store_bytes(long nsamp);
 size_t evd_nerf_train_store_bytes_prec(int precision, long nsamp);
+size_t evd_nerf_train_store_bytes_net(const evd_nerf* net, int precision, long nsamp);
 int evd_nerf_mlp_train(const evd_nerf* net, int precision, const float* ray_batch, const float* z, long R, int S,
                        float* raw, void* store, size_t store_bytes, void* stream);
 
@@ -272,8 +281,11 @@ typedef struct {
  * precision under a power-of-two loss scale chosen from max |d_raw|, float32 accumulation; the scale is removed before the
  * gradients are written.  d_pts / d_dirs dev [R*S,3] (NULL = not wanted): d loss / d sample position through PE(pts) (both
  * pts_linears[0] and the skip layer) and / d view direction through PE(dirs), per sample -- they need the forward's positions
- * pts dev [R*S,3] (= o + d z) and viewdirs (rows of vd_stride floats per ray).  workspace: evd_nerf_backward_workspace_bytes(). */
+ * pts dev [R*S,3] (= o + d z) and viewdirs (rows of vd_stride floats per ray).  workspace: evd_nerf_backward_workspace_bytes().
+ * A network on the generic path (see evd_nerf_mlp_train): store and workspace sized by the *_net queries, float32 arithmetic without a
+ * loss scale, pts / viewdirs read from the store. */
 size_t evd_nerf_backward_workspace_bytes(void);
+size_t evd_nerf_backward_workspace_bytes_net(const evd_nerf* net, int precision);
 int evd_nerf_mlp_backward(const evd_nerf* net, int precision, const float* d_raw, long R, int S, void* store, size_t store_bytes,
                           const evd_nerf_grads* grads, const float* pts, const float* viewdirs, int vd_stride, float* d_pts,
                           float* d_dirs, void* workspace, size_t workspace_bytes, void* stream);
