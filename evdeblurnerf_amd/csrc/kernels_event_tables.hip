@@ -101,6 +101,12 @@ __global__ __launch_bounds__(256) void k_ef_flags(const double* __restrict__ t, 
     }
 }
 
+// the running (min, max) of the kept polarities start at (INT_MAX, INT_MIN): set on the device, so that no copy from host memory is in flight
+// when evd_event_filter returns
+__global__ void k_ef_init(int* __restrict__ pminmax) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) { pminmax[0] = 0x7fffffff; pminmax[1] = (int)0x80000000; }
+}
+
 __global__ __launch_bounds__(256) void k_ef_write(const long long* __restrict__ ids, const double* __restrict__ t, const double* __restrict__ p, long N,
                                                   const int* __restrict__ keep, const int* __restrict__ pos_incl, const int* __restrict__ pminmax,
                                                   double* __restrict__ out, long long* __restrict__ count, int* __restrict__ bad) {
@@ -135,19 +141,35 @@ __global__ __launch_bounds__(256) void k_cm_int(const double* __restrict__ id_to
     cmap[id * 3] = c[0]; cmap[id * 3 + 1] = c[1]; cmap[id * 3 + 2] = c[2];
 }
 
-// the dict lookup `(inv_mapx[j, i], inv_mapy[j, i]) in coords_to_id` (:229): id_to_coords is sorted by (key x, key y) -> binary search
-__global__ __launch_bounds__(256) void k_cm_lookup(const double* __restrict__ id_to_coords, long Nc, int h, int w, const float* __restrict__ mx, const float* __restrict__ my,
-                                                   int* __restrict__ last_pixel) {
-    const long pix = blockIdx.x * 256L + threadIdx.x;
-    if (pix >= (long)h * w) return;
-    const u64 qx = et_key((double)mx[pix]), qy = et_key((double)my[pix]);
+// index of the row of id_to_coords (sorted by (key x, key y)) whose 16 bytes are (kx, ky), or -1
+__device__ __forceinline__ long cm_find(const double* __restrict__ id_to_coords, long Nc, u64 kx, u64 ky) {
     long lo = 0, hi = Nc;
     while (lo < hi) {
         const long mid = (lo + hi) >> 1;
         const u64 cx = et_key(id_to_coords[2 * mid]), cy = et_key(id_to_coords[2 * mid + 1]);
-        if (cx < qx || (cx == qx && cy < qy)) lo = mid + 1; else hi = mid;
+        if (cx < kx || (cx == kx && cy < ky)) lo = mid + 1; else hi = mid;
     }
-    if (lo < Nc && et_key(id_to_coords[2 * lo]) == qx && et_key(id_to_coords[2 * lo + 1]) == qy) atomicMax(last_pixel + lo, (int)pix);   // the later pixel overwrites (:228-230)
+    return (lo < Nc && et_key(id_to_coords[2 * lo]) == kx && et_key(id_to_coords[2 * lo + 1]) == ky) ? lo : -1;
+}
+
+// the dict lookup `(inv_mapx[j, i], inv_mapy[j, i]) in coords_to_id` (:229-232).  The dict matches by VALUE: -0.0 and 0.0 are one key, while
+// id_to_coords keeps the sign of a zero and is sorted by its raw bytes, where the two lie far apart.  So a zero component of the query is
+// probed with both signs (up to four binary searches); should both signs be in the table, the dict holds the later id (:201) and that one
+// gets the colour.  A NaN map entry equals nothing and matches nothing.
+__global__ __launch_bounds__(256) void k_cm_lookup(const double* __restrict__ id_to_coords, long Nc, int h, int w, const float* __restrict__ mx, const float* __restrict__ my,
+                                                   int* __restrict__ last_pixel) {
+    const long pix = blockIdx.x * 256L + threadIdx.x;
+    if (pix >= (long)h * w) return;
+    const double qx = (double)mx[pix], qy = (double)my[pix];
+    if (qx != qx || qy != qy) return;
+    const int nx = qx == 0.0 ? 2 : 1, ny = qy == 0.0 ? 2 : 1;
+    long id = -1;
+    for (int a = 0; a < nx; ++a)
+        for (int b = 0; b < ny; ++b) {
+            const long f = cm_find(id_to_coords, Nc, et_key(a ? -qx : qx), et_key(b ? -qy : qy));
+            id = f > id ? f : id;
+        }
+    if (id >= 0) atomicMax(last_pixel + id, (int)pix);                      // the later pixel overwrites (:229-232)
 }
 
 __global__ __launch_bounds__(256) void k_cm_from_pixels(const int* __restrict__ last_pixel, long Nc, int w, unsigned char* __restrict__ cmap) {
@@ -265,8 +287,7 @@ int evd_event_filter(const long long* coord_ids, const double* t, const double* 
     int* keep = (int*)w; w += al256((size_t)N * 4);
     int* pos = (int*)w; w += al256((size_t)N * 4);
     int* pminmax = (int*)w;
-    const int init[2] = {0x7fffffff, (int)0x80000000};
-    EVD_HIP(hipMemcpyAsync(pminmax, init, sizeof(init), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_ef_init, dim3(1), dim3(1), 0, st, pminmax);
     hipLaunchKernelGGL(k_ef_flags, dim3((unsigned)cdiv(N, 256L)), dim3(256), 0, st, t, p, N, tmin, tmax, keep, pminmax);
     size_t sb = scan_bytes;
     EVD_HIP(hipcub::DeviceScan::InclusiveSum(tmp, sb, (const int*)keep, pos, (int)N, st));

@@ -35,7 +35,9 @@ __global__ void k_succ_jump(const int* __restrict__ in, long n, int* __restrict_
     out[k] = in[in[k]];
 }
 
-__global__ void k_succ_write(const int* __restrict__ keys, const int* __restrict__ idx, const int* __restrict__ seg_end, long n,
+// An id outside [0, HW) (events.compute_successor refuses such a stream; the sort looks at the low bits of HW - 1 only) is never used as an
+// index into the two per-pixel tables; what the four outputs hold for such a stream is unspecified.
+__global__ void k_succ_write(const int* __restrict__ keys, const int* __restrict__ idx, const int* __restrict__ seg_end, long n, long HW,
                              long long* __restrict__ successor, int* __restrict__ num_successors,
                              long long* __restrict__ latest_seen, long long* __restrict__ first_seen) {
     const long k = blockIdx.x * (long)blockDim.x + threadIdx.x;
@@ -44,8 +46,9 @@ __global__ void k_succ_write(const int* __restrict__ keys, const int* __restrict
     const bool last = end == k;
     successor[e] = last ? (long long)e : (long long)idx[k + 1];
     num_successors[e] = end - (int)k;
-    if (k == 0 || keys[k - 1] != keys[k]) latest_seen[keys[k]] = e;      // first event of the pixel (events.py:112)
-    if (last) first_seen[keys[k]] = e;                                     // last event of the pixel (:114-115)
+    const bool inside = keys[k] >= 0 && (long)keys[k] < HW;
+    if (inside && (k == 0 || keys[k - 1] != keys[k])) latest_seen[keys[k]] = e;      // first event of the pixel (events.py:112)
+    if (inside && last) first_seen[keys[k]] = e;                                     // last event of the pixel (:114-115)
 }
 
 // EventsDataset.sample_events (data/loader_events.py:259-304) for one event id per thread: the reference's gathers, gather_successor
@@ -194,7 +197,7 @@ int evd_compute_successor(const int* pixel_ids, long N, long HW, long long* succ
         k_succ_jump<<<cdiv(N, 256), 256, 0, st>>>(ja, N, jb);
         int* t = ja; ja = jb; jb = t;
     }
-    k_succ_write<<<cdiv(N, 256), 256, 0, st>>>(keys, idx, ja, N, successor, num_successors, latest_seen, first_seen);
+    k_succ_write<<<cdiv(N, 256), 256, 0, st>>>(keys, idx, ja, N, HW, successor, num_successors, latest_seen, first_seen);
     EVD_LAUNCH_CHECK();
     return EVD_OK;
 }

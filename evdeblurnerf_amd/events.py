@@ -14,10 +14,16 @@ from . import _lib as L
 def compute_successor(pixel_ids, num_pixels):
     """utils/events.py:72-120 with flat pixel ids (y * w + x, int), events in stream order.
     Returns (successor_idx int64 [N], num_successors int32 [N], latest_seen_idx int64 [num_pixels], first_seen_idx int64 [num_pixels])
-    exactly as the reference's loop: latest_seen holds each pixel's FIRST event, first_seen its LAST one."""
+    exactly as the reference's loop: latest_seen holds each pixel's FIRST event, first_seen its LAST one.  An id outside [0, num_pixels)
+    raises (the reference's loop would index outside its tables): one min / max read-back, the function runs once per dataset."""
+    num_pixels = int(num_pixels)
+    n = pixel_ids.shape[0]
+    if n:
+        lo, hi = (int(v) for v in torch.stack(list(torch.aminmax(pixel_ids))).tolist())
+        if lo < 0 or hi >= num_pixels:
+            raise L.EvdError(f"compute_successor: pixel ids in [{lo}, {hi}], outside [0, {num_pixels})")
     ids = pixel_ids.to(torch.int32).contiguous()
     dev = ids.device
-    n = ids.shape[0]
     succ = torch.empty((n,), dtype=torch.int64, device=dev)
     nsucc = torch.empty((n,), dtype=torch.int32, device=dev)
     latest = torch.empty((num_pixels,), dtype=torch.int64, device=dev)
@@ -212,9 +218,16 @@ class EventTables:
                                      L.ptr(ws), nb, L.stream_ptr()), "evd_event_filter")
         n_ev = int(cnt.item())
         ev3 = ev3[:n_ev]
-        self.intcoords = bool(torch.all(self.id_to_coords == torch.trunc(self.id_to_coords)).item()) if n_coords else True       # :194
+        self.intcoords = True
+        if n_coords:                                                           # :196, and the extent of the coordinates, in one read-back
+            c = self.id_to_coords
+            whole, xmin, ymin, xmax, ymax = torch.cat([torch.all(c == torch.trunc(c)).to(torch.float64)[None], c.min(0).values, c.max(0).values]).tolist()
+            self.intcoords = bool(whole)
+            if self.intcoords and (xmin < 0 or ymin < 0 or xmax >= w or ymax >= h):
+                raise L.EvdError(f"integer event coordinates x in [{xmin:g}, {xmax:g}], y in [{ymin:g}, {ymax:g}] outside the {h} x {w} sensor: "
+                                 "the reference's coords_to_id store fails (loader_events.py:199)")
         self.coords_to_id = None
-        if self.intcoords:                                                     # :195-197
+        if self.intcoords:                                                     # :198-199
             c2i = torch.full((h, w), -1, dtype=torch.int32, device=dev)
             c2i[self.id_to_coords[:, 1].long(), self.id_to_coords[:, 0].long()] = torch.arange(n_coords, dtype=torch.int32, device=dev)
             self.coords_to_id = c2i

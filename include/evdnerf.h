@@ -727,7 +727,8 @@ int evd_edi_prior(const double* events, long N, const double* id_to_coords, long
  * compute_successor, utils/events.py:72-120 (flat_xy = True): pixel_ids dev int32 [N] (y * w + x of every event, in stream
  * order), HW = number of pixels -> successor dev int64 [N] (index of the next event at the same pixel, or the event itself),
  * num_successors dev int32 [N], latest_seen dev int64 [HW] (the pixel's first event, -1 if none), first_seen dev int64 [HW]
- * (its last event).  Bit-identical to the reference loop. */
+ * (its last event).  Bit-identical to the reference loop.  Every id must lie in [0, HW) (events.compute_successor checks it): an id outside
+ * is never used as an index into latest_seen / first_seen, but the outputs are then unspecified. */
 size_t evd_compute_successor_workspace_bytes(long N);
 int evd_compute_successor(const int* pixel_ids, long N, long HW, long long* successor, int* num_successors,
                           long long* latest_seen, long long* first_seen, void* workspace, size_t workspace_bytes, void* stream);
@@ -806,8 +807,9 @@ int evd_sample_events_track(const double* events, long N, int ncol, const float*
  *   count dev int64 [1], bad_polarity dev int32 [1] or NULL: set when the kept polarities are not {-1, 1} afterwards (the reference asserts).
  * evd_event_color_map -- loader_events.py:208-236: id_to_color_map dev uint8 [Ncoords, 3], one-hot r / g / b of the Bayer pattern
  *   (r g / g b).  inv_mapx == NULL: integer coordinates, the colour of the pixel itself (:215-218).  Else inv_mapx / inv_mapy dev
- *   float32 [h, w] (ev_map.npz): the colour of the LAST pixel in raster order whose map entry equals the coordinate (:226-230; id_to_coords
- *   must be the table evd_event_coord_ids wrote -- it is searched in its byte order); unmapped dev int32 [1] or NULL: set when a coordinate
+ *   float32 [h, w] (ev_map.npz): the colour of the LAST pixel in raster order whose map entry equals the coordinate BY VALUE, as the
+ *   reference's dict lookup does (:229-232): -0.0 finds 0.0 and the other way round, a NaN entry finds nothing (id_to_coords must be the
+ *   table evd_event_coord_ids wrote -- it is searched in its byte order); unmapped dev int32 [1] or NULL: set when a coordinate
  *   that is not a silent pixel's (noev_coord_ids [n_noev]) got no colour (the reference asserts, :231-234). */
 size_t evd_event_coord_ids_workspace_bytes(long N, int h, int w);
 int evd_event_coord_ids(const float* x, const float* y, long N, int h, int w, long long* ev_coord_ids, long long* noev_coord_ids, double* id_to_coords,

@@ -332,6 +332,8 @@ def weighted_sum(x, ccw):
 
 def compute_successor(ids, hw):
     """utils/events.py:72-120 on flat pixel ids -> (successor int64 [N], num_successors int32 [N], latest_seen, first_seen int64 [hw])"""
+    if np.size(ids) and (np.min(ids) < 0 or np.max(ids) >= hw):
+        raise IndexError(f"compute_successor: ids outside [0, {hw})")           # the C loop indexes its tables unchecked
     ids = np.ascontiguousarray(ids, dtype=np.int32)
     n = ids.shape[0]
     succ, nsucc = np.empty(n, np.int64), np.empty(n, np.int32)
@@ -414,9 +416,12 @@ def image_batch(ray_ids, images, poses, K, pts0_images=None):
     return out
 
 
-def event_tables(x, y, t, p, h, w, tmin, tmax, ev_map=None, color_events=True, min_step=0):
+def event_tables(x, y, t, p, h, w, tmin, tmax, ev_map=None, color_events=True, min_step=0, check=True):
     """The array-level part of LLFFEventsDataset.load_event_data (data/loader_events.py:186-255 with utils/events.py:39-66, 72-120): ->
-    dict(events [N', 4], id_to_coords, noev_coord_ids, id_to_color_map, events_num_successors, events_with_successor_idx, intcoords)"""
+    dict(events [N', 4], id_to_coords, noev_coord_ids, id_to_color_map, events_num_successors, events_with_successor_idx, intcoords,
+    coords_to_id ([h, w] int32 for integer coordinates, else None), latest_seen, first_seen).  Raises where the reference does: ValueError
+    for its asserts (:206, :216-217, :221-222, :236), IndexError for an integer coordinate past the sensor (:199).  check=False returns the
+    tables where :206 or :236 would fire."""
     x, y = _f(x), _f(y)
     t, p = np.ascontiguousarray(t, dtype=np.float64), np.ascontiguousarray(p, dtype=np.float64)
     N, HW = x.shape[0], int(h) * int(w)
@@ -433,23 +438,35 @@ def event_tables(x, y, t, p, h, w, tmin, tmax, ev_map=None, color_events=True, m
     fn.restype = C.c_long
     n = int(fn(ev_ids.ctypes.data_as(ll), t.ctypes.data_as(dp), p.ctypes.data_as(dp), C.c_long(N), C.c_double(tmin), C.c_double(tmax), ev3.ctypes.data_as(dp)))
     if n < 0:
-        raise ValueError("polarities are not {-1, 1} after the normalisation (loader_events.py:206)")
+        if check:
+            raise ValueError("polarities are not {-1, 1} after the normalisation (loader_events.py:206)")
+        n = -n - 1
     ev3 = ev3[:n]
+    intcoords = bool(np.all(i2c.astype(np.int32) == i2c))
+    c2i = None
+    if intcoords:                                              # :198-199; numpy's indexed store is what raises there
+        c2i = np.full((int(h), int(w)), -1, np.int32)
+        c2i[np.int64(i2c[:, 1]), np.int64(i2c[:, 0])] = np.arange(nc)
     cmap = None
     if color_events:
+        if intcoords and ev_map is not None:
+            raise ValueError("integer coordinates but an ev_map was given (loader_events.py:216-217)")
+        if not intcoords and ev_map is None:
+            raise ValueError("float coordinates but no ev_map was given (loader_events.py:221-222)")
         cmap = np.zeros((max(nc, 1), 3), np.uint8)
         fn = lib().evo_event_color_map
         fn.restype = C.c_long
         mx, my = (None, None) if ev_map is None else (_f(ev_map[0]), _f(ev_map[1]))
         bad = int(fn(i2c.ctypes.data_as(dp), C.c_long(nc), int(h), int(w), _p(mx) if mx is not None else None, _p(my) if my is not None else None,
                      noev.ctypes.data_as(ll), C.c_long(noev.shape[0]), cmap.ctypes.data_as(C.POINTER(C.c_ubyte))))
-        if bad:
+        if bad and check:
             raise ValueError(f"{bad} event coordinates without exactly one colour (loader_events.py:231-234)")
         cmap = cmap[:nc]
-    succ, nsucc, _, _ = compute_successor(ev3[:, 0].astype(np.int64), max(nc, 1))
+    succ, nsucc, latest, first = compute_successor(ev3[:, 0].astype(np.int64), max(nc, 1))
     events = np.concatenate([ev3, np.asarray(succ, dtype=np.float64).reshape(-1, 1)], -1)
     return {"events": events, "id_to_coords": i2c, "noev_coord_ids": noev, "id_to_color_map": cmap, "events_num_successors": np.asarray(nsucc),
-            "events_with_successor_idx": np.where(np.asarray(nsucc) > min_step)[0], "intcoords": bool(np.all(i2c.astype(np.int32) == i2c))}
+            "events_with_successor_idx": np.where(np.asarray(nsucc) > min_step)[0], "intcoords": intcoords, "coords_to_id": c2i,
+            "latest_seen": latest, "first_seen": first}
 
 
 def rbk_warp(rays, r, v, num_motion, use_origin=True, want_transform=False):
