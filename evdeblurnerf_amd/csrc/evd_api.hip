@@ -446,31 +446,26 @@ int evd_nerf_mlp(const evd_nerf* net, int precision, const float* ray_batch, con
 }
 
 // ------------------------------------------------------------------------------------------------
-// NeRFAll.render + render_rays, mode='nerf' (networks/renderer.py:399-466, 129-264 else-branch)
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-size_t evd_nerf_render_workspace_bytes(const evd_render_cfg* cfg, long R) {
-    if (!cfg || R < 0) return 0;
+// NeRFAll.render + render_rays, mode='nerf' (networks/renderer.py:399-466, 129-264 else-branch).  The workspace of both entries: rb is the
+// ray batch evd_nerf_render packs, z0 the first pass's z
+struct NerfRenderWs { float *rb, *z2, *z0, *raw, *wts, *wts0, *zs; };
+static const size_t NERF_RENDER_WS_SLACK = 256;     // alignment slack for an unaligned caller pointer
+static size_t nerf_render_layout(const evd_render_cfg* cfg, long R, void* workspace, NerfRenderWs* L) {
     const size_t S = cfg->N_samples, Ni = cfg->N_importance > 0 ? cfg->N_importance : 0, St = S + Ni, r = (size_t)R;
-    size_t b = 0;
-    b += align256(r * 11 * 4);          // ray_batch
-    b += align256(r * St * 4);          // z (merged)
-    b += align256(r * S * 4);           // z0
-    b += align256(r * St * 16);         // raw
-    b += align256(r * St * 4);          // weights
-    b += align256(r * S * 4);           // weights0
-    b += align256(r * (Ni ? Ni : 1) * 4);  // z_samples
-    return b + 256;
+    Workspace ws(workspace);
+    L->rb = ws.take<float>(r * 11);
+    L->z2 = ws.take<float>(r * St);             // z (merged)
+    L->z0 = ws.take<float>(r * S); L->raw = ws.take<float>(r * St * 4);
+    L->wts = ws.take<float>(r * St); L->wts0 = ws.take<float>(r * S);
+    L->zs = ws.take<float>(r * (Ni ? Ni : 1));  // z_samples
+    return ws.used() + NERF_RENDER_WS_SLACK;
 }
+size_t evd_nerf_render_workspace_bytes(const evd_render_cfg* cfg, long R) { NerfRenderWs L; return (!cfg || R < 0) ? 0 : nerf_render_layout(cfg, R, nullptr, &L); }
 
 }  // extern "C"
-// where the first pass's z lives (an output the caller asked for, else the workspace slot): shared by the two entries below
-static float* render_z_slot(const evd_render_cfg* cfg, long R, const evd_render_out* out, void* workspace) {
-    const int S = cfg->N_samples, Ni = cfg->N_importance > 0 ? cfg->N_importance : 0, St = S + Ni;
-    char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    w += align256((size_t)R * 11 * 4) + align256((size_t)R * St * 4);
-    float* z0 = (float*)w;
-    return Ni ? (out->z_vals0 ? out->z_vals0 : z0) : (out->z_vals ? out->z_vals : z0);
+// where the first pass's z lives: an output the caller asked for, else the workspace slot
+static float* render_zc(const evd_render_cfg* cfg, const evd_render_out* out, const NerfRenderWs& L) {
+    return cfg->N_importance > 0 ? (out->z_vals0 ? out->z_vals0 : L.z0) : (out->z_vals ? out->z_vals : L.z0);
 }
 static int render_rays_impl(const evd_nerf* coarse, const evd_nerf* fine, const evd_render_cfg* cfg, const float* rb,
                             long R, const float* t_rand, const float* u, const float* noise0, const float* noise1,
@@ -485,22 +480,14 @@ static int render_rays_impl(const evd_nerf* coarse, const evd_nerf* fine, const 
     EVD_REQUIRE(!(cfg->perturb > 0.f) || (t_rand && (cfg->N_importance <= 0 || u)),
                 "evd_nerf_render_rays: perturb > 0 needs explicit t_rand (and u) draws");
     if (R == 0) return EVD_OK;
-    const size_t need = evd_nerf_render_workspace_bytes(cfg, R);
+    NerfRenderWs L;
+    const size_t need = nerf_render_layout(cfg, R, workspace, &L);
     if (!workspace || workspace_bytes < need)
         return fail(EVD_E_WORKSPACE, "evd_nerf_render_rays: workspace %zu < %zu bytes", workspace_bytes, need);
     const int S = cfg->N_samples, Ni = cfg->N_importance > 0 ? cfg->N_importance : 0, St = S + Ni;
-    char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    auto take = [&](size_t bytes) { char* p = w; w += align256(bytes); return (float*)p; };
-    const size_t r = (size_t)R;
-    (void)take(r * 11 * 4);             // ray_batch slot (used by evd_nerf_render)
-    float* z2 = take(r * St * 4);
-    float* z0 = take(r * S * 4);
-    float* raw = take(r * St * 16);
-    float* wts = take(r * St * 4);
-    float* wts0 = take(r * S * 4);
-    float* zs = take(r * (Ni ? Ni : 1) * 4);
+    float *z2 = L.z2, *raw = L.raw, *wts = L.wts, *wts0 = L.wts0, *zs = L.zs;
     int rc;
-    float* zc = (Ni ? (out->z_vals0 ? out->z_vals0 : z0) : (out->z_vals ? out->z_vals : z0));
+    float* zc = render_zc(cfg, out, L);
     if (!z_done && (rc = evd_sample_z(cfg, rb, nc, R, t_rand, zc, stream))) return rc;
     auto pass = [&](const evd_nerf* net, const float* z, int Sp, const float* noise, float* rgb, float* depth, float* acc,
                     float* weights, float* raw_out, float* feat) -> int {
@@ -536,15 +523,15 @@ int evd_nerf_render(const evd_nerf* coarse, const evd_nerf* fine, const evd_rend
                     evd_render_out* out, void* workspace, size_t workspace_bytes, void* stream) {
     EVD_REQUIRE(cfg && out && (rays || R == 0), "evd_nerf_render: null argument");
     if (R == 0) return EVD_OK;
-    const size_t need = evd_nerf_render_workspace_bytes(cfg, R);
+    NerfRenderWs L;
+    const size_t need = nerf_render_layout(cfg, R, workspace, &L);
     if (!workspace || workspace_bytes < need)
         return fail(EVD_E_WORKSPACE, "evd_nerf_render: workspace %zu < %zu bytes", workspace_bytes, need);
-    float* rb = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     // ray packing and z stratification in ONE launch (they are 44 B per ray and 4 B per sample)
     const bool fused_z = cfg->use_viewdirs && cfg->N_samples >= 1;
-    int rc = fused_z ? evd_ray_batch_z(cfg, rays, R, t_rand, rb, render_z_slot(cfg, R, out, workspace), stream) : evd_ray_batch(cfg, rays, R, rb, stream);
+    int rc = fused_z ? evd_ray_batch_z(cfg, rays, R, t_rand, L.rb, render_zc(cfg, out, L), stream) : evd_ray_batch(cfg, rays, R, L.rb, stream);
     if (rc) return rc;
-    return render_rays_impl(coarse, fine, cfg, rb, R, t_rand, u, noise0, noise1, out, workspace, workspace_bytes, stream, fused_z);
+    return render_rays_impl(coarse, fine, cfg, L.rb, R, t_rand, u, noise0, noise1, out, workspace, workspace_bytes, stream, fused_z);
 }
 
 }  // extern "C"

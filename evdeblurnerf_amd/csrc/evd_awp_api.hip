@@ -121,7 +121,8 @@ size_t evd_awp_embed_store_bytes(const evd_awp_embed* a, long nsamp) {
 }
 
 static const int AWP_WGRAD_BLOCKS = 256;
-size_t evd_awp_embed_backward_workspace_bytes(void) { return (size_t)AWP_WGRAD_BLOCKS * 13 * 4096 + 512; }     // the fused backward's 13 blocks per workgroup (awp_bwd_fused.h); a per-layer wgrad needs 2 x 5
+static const size_t AWP_WGRAD_PARTIAL_BYTES = (size_t)AWP_WGRAD_BLOCKS * 13 * 4096;      // the fused backward's 13 blocks per workgroup (awp_bwd_fused.h); a per-layer wgrad needs 2 x 5
+size_t evd_awp_embed_backward_workspace_bytes(void) { WgradWs L; return wgrad_layout(AWP_WGRAD_PARTIAL_BYTES, nullptr, &L); }
 
 int evd_awp_embed_forward(const evd_awp_embed* a, int precision, const float* geo_rows, const evd_voxel* fine, const void* fine_store,
                           size_t fine_store_bytes, long nsamp, float* h_local, void* store, size_t store_bytes, void* stream) {
@@ -154,8 +155,9 @@ int evd_awp_embed_backward(const evd_awp_embed* a, int precision, const float* d
     EVD_REQUIRE(pi >= 0, "evd_awp_embed_backward: built for precision f16 / bf16");
     if (nsamp == 0) return EVD_OK;
     if (store_bytes < evd_awp_embed_store_bytes(a, nsamp)) return fail(EVD_E_WORKSPACE, "evd_awp_embed_backward: store %zu < %zu bytes", store_bytes, evd_awp_embed_store_bytes(a, nsamp));
-    if (workspace_bytes < evd_awp_embed_backward_workspace_bytes())
-        return fail(EVD_E_WORKSPACE, "evd_awp_embed_backward: workspace %zu < %zu bytes", workspace_bytes, evd_awp_embed_backward_workspace_bytes());
+    WgradWs ws;
+    const size_t need = wgrad_layout(AWP_WGRAD_PARTIAL_BYTES, workspace, &ws);
+    if (workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_awp_embed_backward: workspace %zu < %zu bytes", workspace_bytes, need);
     AwpBwdPlan b;
     b.d_h_local = d_h_local; b.d_h_absmax = d_h_absmax; b.nsamp = nsamp; b.tiles = awp_tiles(nsamp); b.store = (char*)store;
     for (int l = 0; l < AWP_D; ++l) {
@@ -163,7 +165,7 @@ int evd_awp_embed_backward(const evd_awp_embed* a, int precision, const float* d
         b.grads.w[l] = grads->w[l]; b.grads.b[l] = grads->b[l];
     }
     b.maps = (const int*)a->maps.p;
-    b.partial = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    b.partial = ws.partial;
     b.wgrad_blocks = AWP_WGRAD_BLOCKS;
     b.d_geo_rows = d_geo_rows;
     return precision == EVD_PREC_F16 ? run_awp_backward_f16(b, as_stream(stream)) : run_awp_backward_bf16(b, as_stream(stream));

@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -61,6 +62,22 @@ inline bool env_flag_on(const char* name) {         // a switch that is on unles
 }
 
 inline long cdiv(long a, long b) { return (a + b - 1) / b; }
+
+// Caller-provided scratch memory (DESIGN.md, C ABI): every entry has ONE layout function that carves its workspace with this, and its
+// *_workspace_bytes query is that function with a null base.  Slots start 256-byte aligned; the caller's pointer need not be.
+inline size_t ws_round_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+inline void* ws_align_ptr(void* p) { return (void*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
+struct Workspace {
+    explicit Workspace(void* base) : base_((char*)ws_align_ptr(base)) {}       // null: size only, every take() returns null
+    template <typename T> T* take(size_t count) {
+        const size_t at = used_;
+        used_ += ws_round_up(count * sizeof(T));
+        return base_ ? (T*)(base_ + at) : nullptr;
+    }
+    size_t used() const { return used_; }       // bytes behind the aligned base; a layout adds its slack for the alignment itself
+private:
+    char* base_; size_t used_ = 0;
+};
 
 // compute units of the current device (`fallback` when the query fails)
 inline int device_cus(int fallback = 256) {
@@ -193,6 +210,16 @@ struct BwdPlanBase {
     hipEvent_t ev = nullptr;
     int accumulate = 0;                 // 1: the parameter gradients are ADDED into the caller's buffers
 };
+
+// The workspace of the four training backwards (NeRF pipelined and generic, voxel level, AWP embedding): [loss-scale word, 256 B]
+// [wgrad partials, a multiple of 256 B].  The backwards without a loss scale leave the word unused.
+struct WgradWs { unsigned* maxbits; float* partial; };
+constexpr size_t WGRAD_WS_SLACK = 256;      // alignment slack for an unaligned caller pointer
+inline size_t wgrad_layout(size_t partial_bytes, void* workspace, WgradWs* L) {
+    Workspace ws(workspace);
+    L->maxbits = ws.take<unsigned>(1); L->partial = ws.take<float>(partial_bytes / sizeof(float));
+    return ws.used() + WGRAD_WS_SLACK;
+}
 
 // TEST HOOK (tests/test_gpu_dist.py), defined once in evd_api.hip: EVD_TEST_SIDE_SPIN_US=N makes every wgrad launch on a handle's side
 // stream start N microseconds late (a spin kernel in front of it), so that a missing join of the side stream into the caller's stream --

@@ -81,13 +81,23 @@ int evd_nerf_mlp_train(const evd_nerf* net, int precision, const float* ray_batc
            : precision == EVD_PREC_BF16 ? launch_nerf_train_fwd_bf16(p, as_stream(stream)) : launch_nerf_train_fwd_f16x3(p, as_stream(stream));
 }
 
-// scratch of the backward: the wgrad partial sums of the largest block (8 x 9 accumulator tiles per wavefront group) + the loss-scale word
+// scratch of the backward (evd_common.h wgrad_layout): the wgrad partial sums of the largest block (8 x 9 accumulator tiles per wavefront group; generic: GEN_WS_FLOATS)
 static const int WGRAD_BLOCKS = 256;
-size_t evd_nerf_backward_workspace_bytes(void) { return (size_t)WGRAD_BLOCKS * 8 * 9 * 4096 + 512; }
+static size_t wgrad_partial_bytes(bool generic) { return generic ? GEN_WS_FLOATS * sizeof(float) : (size_t)WGRAD_BLOCKS * 8 * 9 * 4096; }
+size_t evd_nerf_backward_workspace_bytes(void) { WgradWs L; return wgrad_layout(wgrad_partial_bytes(false), nullptr, &L); }
 size_t evd_nerf_backward_workspace_bytes_net(const evd_nerf* net, int precision) {
-    if (!net) return 0;
-    if (train_built(net, precision)) return evd_nerf_backward_workspace_bytes();
-    return nerf_generic_trains(net, precision) ? nerf_generic_workspace_bytes() : 0;
+    WgradWs L;
+    if (!net || !(train_built(net, precision) || nerf_generic_trains(net, precision))) return 0;
+    return wgrad_layout(wgrad_partial_bytes(!train_built(net, precision)), nullptr, &L);
+}
+
+// the caller's gradient pointers as the plans carry them
+static BwdGrads plan_grads(const evd_nerf* net, const evd_nerf_grads* grads) {
+    BwdGrads g;
+    for (int l = 0; l < EVD_MAX_LAYERS; ++l) { g.pts_w[l] = l < net->D ? grads->pts_w[l] : nullptr; g.pts_b[l] = l < net->D ? grads->pts_b[l] : nullptr; }
+    g.views_w = grads->views_w; g.views_b = grads->views_b; g.feature_w = grads->feature_w; g.feature_b = grads->feature_b;
+    g.alpha_w = grads->alpha_w; g.alpha_b = grads->alpha_b; g.rgb_w = grads->rgb_w; g.rgb_b = grads->rgb_b;
+    return g;
 }
 
 int evd_nerf_mlp_backward(const evd_nerf* net, int precision, const float* d_raw, long R, int S, void* store, size_t store_bytes,
@@ -100,33 +110,25 @@ int evd_nerf_mlp_backward(const evd_nerf* net, int precision, const float* d_raw
     EVD_REQUIRE(R >= 0 && S >= 1, "evd_nerf_mlp_backward: bad shape R=%ld S=%d", R, S);
     if (R == 0) return EVD_OK;
     const long nsamp = R * (long)S;
+    const size_t need_store = generic ? nerf_generic_store_bytes(net, nsamp) : evd_nerf_train_store_bytes_prec(precision, nsamp);
+    if (store_bytes < need_store) return fail(EVD_E_WORKSPACE, "evd_nerf_mlp_backward: store %zu < %zu bytes", store_bytes, need_store);
+    WgradWs ws;
+    const size_t need = wgrad_layout(wgrad_partial_bytes(generic), workspace, &ws);
+    if (workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_nerf_mlp_backward: workspace %zu < %zu bytes", workspace_bytes, need);
     if (generic) {
-        if (store_bytes < nerf_generic_store_bytes(net, nsamp))
-            return fail(EVD_E_WORKSPACE, "evd_nerf_mlp_backward: store %zu < %zu bytes", store_bytes, nerf_generic_store_bytes(net, nsamp));
-        if (workspace_bytes < nerf_generic_workspace_bytes())
-            return fail(EVD_E_WORKSPACE, "evd_nerf_mlp_backward: workspace %zu < %zu bytes", workspace_bytes, nerf_generic_workspace_bytes());
         GenBwdPlan g;
         g.net = net; g.d_raw = d_raw; g.nsamp = nsamp; g.store = (float*)store;
-        g.partial = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-        for (int l = 0; l < EVD_MAX_LAYERS; ++l) { g.grads.pts_w[l] = l < net->D ? grads->pts_w[l] : nullptr; g.grads.pts_b[l] = l < net->D ? grads->pts_b[l] : nullptr; }
-        g.grads.views_w = grads->views_w; g.grads.views_b = grads->views_b; g.grads.feature_w = grads->feature_w; g.grads.feature_b = grads->feature_b;
-        g.grads.alpha_w = grads->alpha_w; g.grads.alpha_b = grads->alpha_b; g.grads.rgb_w = grads->rgb_w; g.grads.rgb_b = grads->rgb_b;
+        g.partial = ws.partial; g.grads = plan_grads(net, grads);
         g.accumulate = grads->accumulate ? 1 : 0; g.d_pts = d_pts; g.d_dirs = d_dirs;
         return run_nerf_backward_generic(g, as_stream(stream));
     }
-    if (store_bytes < evd_nerf_train_store_bytes_prec(precision, nsamp))
-        return fail(EVD_E_WORKSPACE, "evd_nerf_mlp_backward: store %zu < %zu bytes", store_bytes, evd_nerf_train_store_bytes_prec(precision, nsamp));
-    if (workspace_bytes < evd_nerf_backward_workspace_bytes())
-        return fail(EVD_E_WORKSPACE, "evd_nerf_mlp_backward: workspace %zu < %zu bytes", workspace_bytes, evd_nerf_backward_workspace_bytes());
     precision = store_prec(precision);          // the mixed modes: the float16 mode's store, W^T streams and kernels
     BwdPlan b;
     int rc0;
     b.d_raw = d_raw; b.nsamp = nsamp; b.tiles = train_tiles(nsamp); b.store = (char*)store;
     for (int k = 0; k < EVD_BWD_NSTREAMS; ++k) b.wt[k] = (const char*)net->bwd[precision][k].data.p;
     b.maps = (const int*)net->wmaps.p;
-    char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    b.maxbits = (unsigned*)w;
-    b.partial = (float*)(w + 256);
+    b.maxbits = ws.maxbits; b.partial = ws.partial;
     b.wgrad_blocks = WGRAD_BLOCKS; b.skip = net->skip;
     // the wgrad launches run on the handle's side stream, forked from / joined to the caller's stream with events (stream order
     // as seen by the caller is unchanged): measured 3.41 -> 3.05 ms at 2^19 samples with 192 persistent wgrad workgroups
@@ -138,9 +140,7 @@ int evd_nerf_mlp_backward(const evd_nerf* net, int precision, const float* d_raw
         b.wgrad_blocks = nb;
     }
     b.pts = pts; b.viewdirs = viewdirs; b.vd_stride = vd_stride; b.S = S; b.d_pts = d_pts; b.d_dirs = d_dirs;
-    for (int l = 0; l < EVD_MAX_LAYERS; ++l) { b.grads.pts_w[l] = l < net->D ? grads->pts_w[l] : nullptr; b.grads.pts_b[l] = l < net->D ? grads->pts_b[l] : nullptr; }
-    b.grads.views_w = grads->views_w; b.grads.views_b = grads->views_b; b.grads.feature_w = grads->feature_w; b.grads.feature_b = grads->feature_b;
-    b.grads.alpha_w = grads->alpha_w; b.grads.alpha_b = grads->alpha_b; b.grads.rgb_w = grads->rgb_w; b.grads.rgb_b = grads->rgb_b;
+    b.grads = plan_grads(net, grads);
     b.accumulate = grads->accumulate ? 1 : 0;
     return precision == EVD_PREC_F16 ? run_nerf_backward_f16(b, as_stream(stream))
            : precision == EVD_PREC_BF16 ? run_nerf_backward_bf16(b, as_stream(stream)) : run_nerf_backward_f16x3(b, as_stream(stream));

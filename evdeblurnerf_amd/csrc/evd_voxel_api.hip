@@ -341,17 +341,22 @@ int evd_voxel_sample_prec(const evd_voxel* v, int precision, const float* pts, l
     return sample_for(v, precision, pts, n, out, out_stride, out_col, stream);
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// composite_feature levels: the per-sample geo rows [R S, G] and the composited map [R, G]
-static size_t composite_scratch_bytes(const evd_voxel* v, long R, int S) {
-    return v->composite_feature ? align256((size_t)R * S * v->geo * 4) + align256((size_t)R * v->geo * 4) : 0;
+// composite_feature levels: the per-sample geo rows [R S, G] and the composited map [R, G] in the running entry's workspace (else nothing, null)
+struct CompositeWs { float *rows = nullptr, *map = nullptr; };
+static CompositeWs composite_layout(Workspace& ws, const evd_voxel* v, long R, int S) {
+    if (!v->composite_feature) return {};
+    float* rows = ws.take<float>((size_t)R * S * v->geo);
+    return {rows, ws.take<float>((size_t)R * v->geo)};
 }
 
-size_t evd_voxel_forward_workspace_bytes(const evd_voxel* v, long R, int S) {
-    if (!v || R < 0 || S < 1) return 0;
-    return align256((size_t)R * S * 16) + composite_scratch_bytes(v, R, S) + 512;
+struct VoxelForwardWs { float* raw; CompositeWs cs; };
+static const size_t VOXEL_FORWARD_WS_SLACK = 512;       // alignment slack for an unaligned caller pointer plus the historical margin
+static size_t voxel_forward_layout(const evd_voxel* v, long R, int S, void* workspace, VoxelForwardWs* L) {
+    Workspace ws(workspace);
+    L->raw = ws.take<float>((size_t)R * S * 4); L->cs = composite_layout(ws, v, R, S);
+    return ws.used() + VOXEL_FORWARD_WS_SLACK;
 }
+size_t evd_voxel_forward_workspace_bytes(const evd_voxel* v, long R, int S) { VoxelForwardWs L; return (!v || R < 0 || S < 1) ? 0 : voxel_forward_layout(v, R, S, nullptr, &L); }
 
 // activation of the geo rows before they are composited (voxnerf.py:172: rgb_activate(raw[..., 1:]))
 static __global__ __launch_bounds__(256) void k_act_inplace(float* __restrict__ x, long n, int code) {
@@ -403,6 +408,15 @@ static __global__ __launch_bounds__(256) void k_color_rows(const float* __restri
     }
 }
 
+// what the inference pass and the training forward of a level fill alike (the stream is chosen later, with the kernel)
+static VoxMlpParams vox_mlp_params(const evd_voxel* v, const float* pts, const float* viewdirs, int vd_stride, const float* fts, int ft_stride,
+                                   long R, int S, float* raw, float* feature, char* act) {
+    VoxMlpParams p{};
+    p.pts = pts; p.viewdirs = viewdirs; p.fts = fts; p.nsamp = R * (long)S; p.S = S; p.vd_stride = vd_stride; p.ft_stride = ft_stride;
+    p.bias = (const float*)v->bias.p; p.nbias = (int)(v->bias.bytes / sizeof(float)); p.raw = raw; p.feature = feature; p.act = act;
+    return p;
+}
+
 // the compensated mode's stream into p, re-packed first if evd_voxel_load_params has run since its last use
 static int use_pipe_c(const evd_voxel* v, VoxMlpParams& p, hipStream_t st) {
     if (v->pipe_c_stale) {
@@ -452,21 +466,17 @@ static int voxel_level_forward(const evd_voxel* v, int precision, VoxMlpParams& 
 static int voxel_pass(const evd_voxel* v, int precision, const float* pts, const float* viewdirs, int vd_stride, const float* fts,
                       int ft_stride, const float* z, const float* rays_d, int rd_stride, long R, int S, int is_train,
                       const float* noise, float* color, float* depth, float* acc, float* weights, float* feature, float* raw,
-                      void* stream, float* cscratch = nullptr) {
+                      void* stream, const CompositeWs& cs = {}) {
     // composite_feature (PBE, voxnerf.py:223-239): the per-sample geo rows are composited, the colour network runs per ray; `feature`
-    // is then the composited map [R, G] (NULL: not wanted) and cscratch holds the rows + the map
-    float* crows = nullptr;
-    float* cmap = nullptr;
+    // is then the composited map [R, G] (NULL: not wanted) and cs holds the rows + the map
+    float *crows = nullptr, *cmap = nullptr;
     if (v->composite_feature) {
-        if (!cscratch) return fail(EVD_E_WORKSPACE, "evd_voxel: a composite_feature level needs its scratch (workspace sized by the *_workspace_bytes query of this handle)");
-        crows = cscratch;
-        cmap = feature ? feature : (float*)((char*)cscratch + align256((size_t)R * S * v->geo * 4));
+        if (!cs.rows) return fail(EVD_E_WORKSPACE, "evd_voxel: a composite_feature level needs its scratch (workspace sized by the *_workspace_bytes query of this handle)");
+        crows = cs.rows;
+        cmap = feature ? feature : cs.map;
         feature = crows;
     }
-    VoxMlpParams p;
-    p.bias = (const float*)v->bias.p;
-    p.pts = pts; p.viewdirs = viewdirs; p.fts = fts; p.nsamp = R * (long)S; p.S = S; p.vd_stride = vd_stride; p.ft_stride = ft_stride;
-    p.nbias = (int)(v->bias.bytes / sizeof(float)); p.raw = raw; p.feature = feature; p.act = nullptr;
+    VoxMlpParams p = vox_mlp_params(v, pts, viewdirs, vd_stride, fts, ft_stride, R, S, raw, feature, nullptr);
     p.pe_l = v->multires; p.pe_lv = v->multires_views;
     int rc = voxel_level_forward(v, precision, p, as_stream(stream));
     if (rc) return rc;
@@ -500,34 +510,37 @@ int evd_voxel_forward(const evd_voxel* v, int precision, const float* pts, const
     EVD_REQUIRE(F == v->ft_dim, "evd_voxel_forward: fts has %d channels, this level takes %d", F, v->ft_dim);
     EVD_REQUIRE(weights, "evd_voxel_forward: the weights output is required");
     if (R == 0) return EVD_OK;
-    const size_t need = evd_voxel_forward_workspace_bytes(v, R, S);
+    VoxelForwardWs L;
+    const size_t need = voxel_forward_layout(v, R, S, workspace, &L);
     if (!workspace || workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_voxel_forward: workspace %zu < %zu bytes", workspace_bytes, need);
-    float* raw = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    float* cs = v->composite_feature ? (float*)((char*)raw + align256((size_t)R * S * 16)) : nullptr;
     return voxel_pass(v, precision, pts, viewdirs, vd_stride, fts, F, z, rays_d, rays_d_stride, R, S, is_train, nullptr,
-                      color, depth, acc, weights, feature, raw, stream, cs);
+                      color, depth, acc, weights, feature, L.raw, stream, L.cs);
+}
+
+// The workspace of evd_c2f_render and evd_c2f_render_rays: slot 0 is the ray batch evd_c2f_render packs
+struct C2fRenderWs { float *rb, *z0, *z2, *pts, *ft, *ft0, *ftn, *ptn; int* order; float *raw, *wts0, *wts, *zs; CompositeWs cs0, cs1; };
+static const size_t C2F_RENDER_WS_SLACK = 512;          // alignment slack for an unaligned caller pointer plus the historical margin
+static size_t c2f_render_layout(const evd_voxel* coarse, const evd_voxel* fine, const evd_render_cfg* cfg, long R, void* workspace, C2fRenderWs* L) {
+    const size_t S = cfg->N_samples, Ni = cfg->N_importance > 0 ? cfg->N_importance : 0, St = S + Ni, Nn = Ni ? Ni : 1, r = (size_t)R;
+    Workspace ws(workspace);
+    L->rb = ws.take<float>(r * 11); L->z0 = ws.take<float>(r * S);
+    L->z2 = ws.take<float>(r * St);             // z merged
+    L->pts = ws.take<float>(r * St * 3);
+    L->ft = ws.take<float>(r * St * 64);        // features [n,64]
+    L->ft0 = ws.take<float>(r * S * 32);        // coarse features at the coarse samples [R*S,32]
+    L->ftn = ws.take<float>(r * Nn * 32);       // coarse features at the new samples
+    L->ptn = ws.take<float>(r * Nn * 3);        // new points
+    L->order = ws.take<int>(r * St);            // sort order
+    L->raw = ws.take<float>(r * St * 4); L->wts0 = ws.take<float>(r * S); L->wts = ws.take<float>(r * St);
+    L->zs = ws.take<float>(r * Nn);             // z_samples
+    L->cs0 = composite_layout(ws, coarse, R, (int)S);      // a composite_feature level (kernel_type PBE): geo rows + composited map
+    L->cs1 = (fine && Ni) ? composite_layout(ws, fine, R, (int)St) : CompositeWs{};
+    return ws.used() + C2F_RENDER_WS_SLACK;
 }
 
 size_t evd_c2f_render_workspace_bytes(const evd_voxel* coarse, const evd_voxel* fine, const evd_render_cfg* cfg, long R) {
-    if (!coarse || !cfg || R < 0) return 0;
-    const size_t S = cfg->N_samples, Ni = cfg->N_importance > 0 ? cfg->N_importance : 0, St = S + Ni, r = (size_t)R;
-    size_t b = 0;
-    b += align256(r * 11 * 4);              // ray_batch
-    b += align256(r * S * 4);               // z0
-    b += align256(r * St * 4);              // z merged
-    b += align256(r * St * 12);             // pts
-    b += align256(r * St * 64 * 4);         // features [n,64]
-    b += align256(r * S * 32 * 4);          // coarse features at the coarse samples [R*S,32]
-    b += align256(r * (Ni ? Ni : 1) * 32 * 4);   // coarse features at the new samples
-    b += align256(r * (Ni ? Ni : 1) * 12);  // new points
-    b += align256(r * St * 4);              // sort order
-    b += align256(r * St * 16);             // raw
-    b += align256(r * S * 4);               // weights0
-    b += align256(r * St * 4);              // weights
-    b += align256(r * (Ni ? Ni : 1) * 4);   // z_samples
-    b += composite_scratch_bytes(coarse, R, (int)S);       // a composite_feature coarse level (kernel_type PBE): geo rows + composited map
-    if (fine && Ni) b += composite_scratch_bytes(fine, R, (int)St);
-    return b + 512;
+    C2fRenderWs L;
+    return (!coarse || !cfg || R < 0) ? 0 : c2f_render_layout(coarse, fine, cfg, R, nullptr, &L);
 }
 
 int evd_c2f_render_rays(const evd_voxel* coarse, const evd_voxel* fine, const evd_render_cfg* cfg, const float* rb, long R,
@@ -541,28 +554,12 @@ int evd_c2f_render_rays(const evd_voxel* coarse, const evd_voxel* fine, const ev
     EVD_REQUIRE(coarse->ft_dim == coarse->app_dim && (!fine || fine->ft_dim == coarse->app_dim + fine->app_dim),
                 "evd_c2f_render_rays: feature widths do not chain (coarse app_dim %d, fine input %d)", coarse->app_dim, fine ? fine->ft_dim : -1);
     if (R == 0) return EVD_OK;
-    const size_t need = evd_c2f_render_workspace_bytes(coarse, fine, cfg, R);
+    C2fRenderWs L;
+    const size_t need = c2f_render_layout(coarse, fine, cfg, R, workspace, &L);
     if (!workspace || workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_c2f_render_rays: workspace %zu < %zu bytes", workspace_bytes, need);
     const int S = cfg->N_samples, Ni = cfg->N_importance > 0 ? cfg->N_importance : 0, St = S + Ni;
     hipStream_t st = as_stream(stream);
-    char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    auto take = [&](size_t bytes) { char* p = w; w += align256(bytes); return (float*)p; };
-    const size_t r = (size_t)R;
-    (void)take(r * 11 * 4);
-    float* z0 = take(r * S * 4);
-    float* z2 = take(r * St * 4);
-    float* pts = take(r * St * 12);
-    float* ft = take(r * St * 64 * 4);
-    float* ft0 = take(r * S * 32 * 4);
-    float* ftn = take(r * (Ni ? Ni : 1) * 32 * 4);
-    float* ptn = take(r * (Ni ? Ni : 1) * 12);
-    int* order = (int*)take(r * St * 4);
-    float* raw = take(r * St * 16);
-    float* wts0 = take(r * S * 4);
-    float* wts = take(r * St * 4);
-    float* zs = take(r * (Ni ? Ni : 1) * 4);
-    float* cs0 = coarse->composite_feature ? (float*)take(composite_scratch_bytes(coarse, R, S)) : nullptr;
-    float* cs1 = (fine && Ni && fine->composite_feature) ? (float*)take(composite_scratch_bytes(fine, R, St)) : nullptr;
+    float *z0 = L.z0, *z2 = L.z2, *pts = L.pts, *ft = L.ft, *ft0 = L.ft0, *ftn = L.ftn, *ptn = L.ptn, *raw = L.raw, *wts0 = L.wts0, *wts = L.wts, *zs = L.zs;
     const int FS = 64;      // feature row stride: coarse features at column 0, fine at column coarse->app_dim (renderer.py:195)
     int rc;
     float* zc = (Ni ? (out->z_vals0 ? out->z_vals0 : z0) : (out->z_vals ? out->z_vals : z0));
@@ -575,25 +572,25 @@ int evd_c2f_render_rays(const evd_voxel* coarse, const evd_voxel* fine, const ev
         if ((rc = sample_for(coarse, cfg->precision, pts, R * (long)S, ft, FS, 0, stream))) return rc;      // renderer.py:183
         float* wo = out->weights ? out->weights : wts;
         return voxel_pass(coarse, cfg->precision, pts, rb + 8, 11, ft, FS, zc, rb + 3, 11, R, S, cfg->is_train, noise0,
-                          out->rgb, out->depth, out->acc, wo, out->feature, out->raw ? out->raw : raw, stream, cs0);
+                          out->rgb, out->depth, out->acc, wo, out->feature, out->raw ? out->raw : raw, stream, L.cs0);
     }
     if ((rc = sample_for(coarse, cfg->precision, pts, R * (long)S, ft0, FC, 0, stream))) return rc;          // renderer.py:183
     float* w0 = out->weights0 ? out->weights0 : wts0;
     if ((rc = voxel_pass(coarse, cfg->precision, pts, rb + 8, 11, ft0, FC, zc, rb + 3, 11, R, S, cfg->is_train, noise0,
-                         out->rgb0, out->depth0, out->acc0, w0, nullptr, raw, stream, cs0))) return rc;
+                         out->rgb0, out->depth0, out->acc0, w0, nullptr, raw, stream, L.cs0))) return rc;
     float* zm = out->z_vals ? out->z_vals : z2;
     // (+ the positions of the new and of the merged samples: the coarse pass is done with `pts`)
-    if ((rc = launch_sample_pdf_merge_pts(zc, w0, R, S, Ni, cfg->perturb == 0.f, u, zs, zm, order, out->z_std, rb, 11, ptn, pts, st))) return rc;
+    if ((rc = launch_sample_pdf_merge_pts(zc, w0, R, S, Ni, cfg->perturb == 0.f, u, zs, zm, L.order, out->z_std, rb, 11, ptn, pts, st))) return rc;
     // merged sample set (renderer.py:205-213), as the reference does it: coarse features are sampled at the NEW points only
     // (:209) and the rows of the old and new points are gathered by the sort order (:212-213); the fine level is sampled at
     // all merged points (:211 samples the new ones and :194 the old ones -- a pure function of the point either way).
     const long n2 = R * (long)St;
     if ((rc = sample_for(coarse, cfg->precision, ptn, R * (long)Ni, ftn, FC, 0, stream))) return rc;
-    if ((rc = launch_merge_features(ft0, ftn, order, R, S, Ni, FC, ft, FS, st))) return rc;
+    if ((rc = launch_merge_features(ft0, ftn, L.order, R, S, Ni, FC, ft, FS, st))) return rc;
     if ((rc = sample_for(fine, cfg->precision, pts, n2, ft, FS, coarse->app_dim, stream))) return rc;
     float* wo = out->weights ? out->weights : wts;
     return voxel_pass(fine, cfg->precision, pts, rb + 8, 11, ft, FS, zm, rb + 3, 11, R, St, cfg->is_train, noise1,
-                      out->rgb, out->depth, out->acc, wo, out->feature, out->raw ? out->raw : raw, stream, cs1);
+                      out->rgb, out->depth, out->acc, wo, out->feature, out->raw ? out->raw : raw, stream, L.cs1);
 }
 
 int evd_c2f_render(const evd_voxel* coarse, const evd_voxel* fine, const evd_render_cfg* cfg, const float* rays, long R,
@@ -601,12 +598,12 @@ int evd_c2f_render(const evd_voxel* coarse, const evd_voxel* fine, const evd_ren
                    evd_render_out* out, void* workspace, size_t workspace_bytes, void* stream) {
     EVD_REQUIRE(cfg && coarse && (rays || R == 0), "evd_c2f_render: null argument");
     if (R == 0) return EVD_OK;
-    const size_t need = evd_c2f_render_workspace_bytes(coarse, fine, cfg, R);
+    C2fRenderWs L;
+    const size_t need = c2f_render_layout(coarse, fine, cfg, R, workspace, &L);
     if (!workspace || workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_c2f_render: workspace %zu < %zu bytes", workspace_bytes, need);
-    float* rb = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    int rc = evd_ray_batch(cfg, rays, R, rb, stream);
+    int rc = evd_ray_batch(cfg, rays, R, L.rb, stream);
     if (rc) return rc;
-    return evd_c2f_render_rays(coarse, fine, cfg, rb, R, t_rand, u, noise0, noise1, out, workspace, workspace_bytes, stream);
+    return evd_c2f_render_rays(coarse, fine, cfg, L.rb, R, t_rand, u, noise0, noise1, out, workspace, workspace_bytes, stream);
 }
 
 int evd_points(const float* ray_batch, int ncol, const float* z, long R, int S, float* pts, void* stream) {
@@ -684,7 +681,8 @@ size_t evd_voxel_train_store_bytes_prec(const evd_voxel* v, int precision, long 
            : (size_t)vox_tiles(nsamp) * voxel_store_tile_bytes_prec(v->hidden_dim, vox_store_prec(precision));
 }
 
-size_t evd_voxel_backward_workspace_bytes(void) { return (size_t)VOX_WGRAD_BLOCKS * 8 * 9 * 4096 + 512; }
+static const size_t VOX_WGRAD_PARTIAL_BYTES = (size_t)VOX_WGRAD_BLOCKS * 8 * 9 * 4096;
+size_t evd_voxel_backward_workspace_bytes(void) { WgradWs L; return wgrad_layout(VOX_WGRAD_PARTIAL_BYTES, nullptr, &L); }
 
 int evd_voxel_mlp_train(const evd_voxel* v, int precision, const float* pts, const float* viewdirs, int vd_stride, const float* fts, int ft_stride,
                         long R, int S, float* raw, float* feature, void* store, size_t store_bytes, void* stream) {
@@ -696,10 +694,7 @@ int evd_voxel_mlp_train(const evd_voxel* v, int precision, const float* pts, con
     const long nsamp = R * (long)S;
     if (store_bytes < evd_voxel_train_store_bytes_prec(v, precision, nsamp))
         return fail(EVD_E_WORKSPACE, "evd_voxel_mlp_train: store %zu < %zu bytes", store_bytes, evd_voxel_train_store_bytes_prec(v, precision, nsamp));
-    VoxMlpParams p;
-    p.bias = (const float*)v->bias.p;
-    p.pts = pts; p.viewdirs = viewdirs; p.fts = fts; p.nsamp = nsamp; p.S = S; p.vd_stride = vd_stride; p.ft_stride = ft_stride;
-    p.nbias = (int)(v->bias.bytes / sizeof(float)); p.raw = raw; p.feature = feature; p.act = (char*)store;
+    VoxMlpParams p = vox_mlp_params(v, pts, viewdirs, vd_stride, fts, ft_stride, R, S, raw, feature, (char*)store);
     const bool mixed = precision == EVD_PREC_F16C || precision == EVD_PREC_F16M;      // a float32-grade forward writing the float16 mode's store
     if (mixed && feature) return fail(EVD_E_INVALID, "evd_voxel_mlp_train: float32 feature rows are not built in EVD_PREC_F16C / EVD_PREC_F16M (the geo features stay fragments in the store)");
     if (precision == EVD_PREC_F16C && v->pipe_c_chunks > 0) {        // the level's compensated kernel (fine level)
@@ -727,7 +722,9 @@ int evd_voxel_mlp_backward(const evd_voxel* v, int precision, const float* d_raw
     const long nsamp = R * (long)S;
     if (store_bytes < evd_voxel_train_store_bytes_prec(v, precision, nsamp))
         return fail(EVD_E_WORKSPACE, "evd_voxel_mlp_backward: store %zu < %zu bytes", store_bytes, evd_voxel_train_store_bytes_prec(v, precision, nsamp));
-    if (workspace_bytes < evd_voxel_backward_workspace_bytes()) return fail(EVD_E_WORKSPACE, "evd_voxel_mlp_backward: workspace %zu < %zu bytes", workspace_bytes, evd_voxel_backward_workspace_bytes());
+    WgradWs ws;
+    const size_t need_ws = wgrad_layout(VOX_WGRAD_PARTIAL_BYTES, workspace, &ws);
+    if (workspace_bytes < need_ws) return fail(EVD_E_WORKSPACE, "evd_voxel_mlp_backward: workspace %zu < %zu bytes", workspace_bytes, need_ws);
     precision = vox_store_prec(precision);      // EVD_PREC_F16C: the float16 mode's store, W^T streams and kernels
     VoxBwdPlan b;
     b.d_raw = d_raw; b.raw = raw; b.d_feature = d_feature; b.nsamp = nsamp; b.tiles = vox_tiles(nsamp); b.store = (char*)store;
@@ -742,10 +739,7 @@ int evd_voxel_mlp_backward(const evd_voxel* v, int precision, const float* d_raw
     }
     for (int k = 0; k < VBWD_NSTREAMS; ++k) b.wt[k] = (const char*)v->bwd[precision][k].data.p;
     b.maps = (const int*)v->wmaps.p;
-    char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    b.maxbits = (unsigned*)w;
-    b.partial = (float*)(w + 256);
-    b.wgrad_blocks = VOX_WGRAD_BLOCKS;
+    b.maxbits = ws.maxbits; b.partial = ws.partial; b.wgrad_blocks = VOX_WGRAD_BLOCKS;
     b.side = nullptr; b.ev = nullptr;
     static const bool overlap = env_flag("EVD_BWD_OVERLAP_VOXEL");     // measured: no gain for the level networks (7.70 vs 7.86 ms per c2f iteration), off
     if (overlap) {
@@ -840,14 +834,19 @@ int evd_voxel_grid_mirrors(const evd_voxel* v, float** plane_f32, float** line_f
     return EVD_OK;
 }
 
+static GridGrads grid_grads(const evd_voxel_grid_grads* g) {
+    GridGrads gg;
+    for (int i = 0; i < 3; ++i) { gg.plane[i] = g->plane[i]; gg.line[i] = g->line[i]; }
+    gg.basis = g->basis;
+    return gg;
+}
+
 int evd_voxel_sample_bwd(const evd_voxel* v, const float* pts, long n, const float* d_out, int d_stride, int d_col,
                          const evd_voxel_grid_grads* g, float* d_pts, void* stream) {
     EVD_REQUIRE(v && pts && d_out && g && n >= 0 && d_stride >= d_col + v->app_dim, "evd_voxel_sample_bwd: bad arguments");
     EVD_REQUIRE(v->app_act == EVD_ACT_NONE, "evd_voxel_sample_bwd: only app_actfn none is built (all shipped configs)");
     if (n == 0) return EVD_OK;
-    GridGrads gg;
-    for (int i = 0; i < 3; ++i) { gg.plane[i] = g->plane[i]; gg.line[i] = g->line[i]; }
-    gg.basis = g->basis;
+    const GridGrads gg = grid_grads(g);
     return launch_voxel_sample_bwd(v->gp, pts, n, d_out, d_stride, d_col, gg, d_pts, as_stream(stream));
 }
 
@@ -872,9 +871,7 @@ static int sample_bwd_ws(const evd_voxel* v, bool half_grids, const float* pts, 
     EVD_REQUIRE(v && pts && d_out && g && n >= 0 && d_stride >= d_col + v->app_dim, "evd_voxel_sample_bwd_ws: bad arguments");
     EVD_REQUIRE(v->app_act == EVD_ACT_NONE, "evd_voxel_sample_bwd_ws: only app_actfn none is built (all shipped configs)");
     if (n == 0) return EVD_OK;
-    GridGrads gg;
-    for (int i = 0; i < 3; ++i) { gg.plane[i] = g->plane[i]; gg.line[i] = g->line[i]; }
-    gg.basis = g->basis;
+    const GridGrads gg = grid_grads(g);
     if (workspace && workspace_bytes > 0 && voxel_scatter_hybrid_ok(v->gp, n))
         return launch_voxel_sample_bwd_hybrid(v->gp, pts, n, d_out, d_stride, d_col, gg, d_pts, workspace, workspace_bytes, as_stream(stream), half_grids);
     return launch_voxel_sample_bwd(v->gp, pts, n, d_out, d_stride, d_col, gg, d_pts, as_stream(stream));
@@ -900,9 +897,10 @@ static size_t det_region_bytes(const evd_voxel* v, long n) {
     return a > b ? a : b;
 }
 
+static const size_t DET_WS_SLACK = 256;        // alignment slack for an unaligned caller pointer: the region starts at ws_align_ptr(workspace)
 size_t evd_voxel_sample_bwd_det_workspace_bytes(const evd_voxel* v, long n) {
     if (!v || n <= 0) return 0;
-    return det_region_bytes(v, n) + 256;
+    return det_region_bytes(v, n) + DET_WS_SLACK;
 }
 
 int evd_voxel_sample_bwd_det(const evd_voxel* v, int precision, const float* pts, long n, const float* d_out, int d_stride, int d_col,
@@ -915,10 +913,8 @@ int evd_voxel_sample_bwd_det(const evd_voxel* v, int precision, const float* pts
     if (!workspace || workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_voxel_sample_bwd_det: workspace %zu < %zu bytes", workspace_bytes, need);
     hipStream_t st = as_stream(stream);
     const bool half = grids_half_for(v, precision);
-    GridGrads gg;
-    for (int i = 0; i < 3; ++i) { gg.plane[i] = g->plane[i]; gg.line[i] = g->line[i]; }
-    gg.basis = g->basis;
-    char* region = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    const GridGrads gg = grid_grads(g);
+    char* region = (char*)ws_align_ptr(workspace);
     int rc = launch_voxel_scatter_det_scale(v->gp, half, pts, n, d_out, d_stride, d_col, gg, region, st);
     if (rc) return rc;
     // the one host read of this entry: the unit is a function of the batch's maximum, and a batch without one takes another path
@@ -932,17 +928,22 @@ int evd_voxel_sample_bwd_det(const evd_voxel* v, int precision, const float* pts
     return launch_voxel_scatter_det_add(v->gp, half, pts, n, d_out, d_stride, d_col, gg, d_pts, region, evd_scatter_det_unit_exp(cmax, n), st);
 }
 
-int evd_voxel_tv_loss_bwd(const evd_voxel* v, const float* d_loss, const evd_voxel_grid_grads* g, void* stream) {
-    EVD_REQUIRE(v && g && d_loss, "evd_voxel_tv_loss_bwd: null argument");
-    hipStream_t st = as_stream(stream);
+// the six TV terms of a level: planes at weight 1e-2, lines at 1e-3; g = the gradients they are added to (null: the loss only)
+static TvJobs tv_jobs(const evd_voxel* v, const evd_voxel_grid_grads* g) {
     TvJobs jobs;
     jobs.n = 6;
     for (int i = 0; i < 3; ++i) {
         const int C = v->n_comp[i], Wp = v->grid[kMat0[i]], Hp = v->grid[kMat1[i]], Lp = v->grid[kVec[i]];
-        jobs.j[i] = TvJob{(const float*)v->plane[i].p, g->plane[i], Hp, Wp, C, 1e-2f, 0, 0};
-        jobs.j[3 + i] = TvJob{(const float*)v->line[i].p, g->line[i], Lp, 1, C, 1e-3f, 0, 0};
+        jobs.j[i] = TvJob{(const float*)v->plane[i].p, g ? g->plane[i] : nullptr, Hp, Wp, C, 1e-2f, 0, 0};
+        jobs.j[3 + i] = TvJob{(const float*)v->line[i].p, g ? g->line[i] : nullptr, Lp, 1, C, 1e-3f, 0, 0};
     }
-    return launch_tv_bwd_level(jobs, d_loss, st);
+    return jobs;
+}
+
+int evd_voxel_tv_loss_bwd(const evd_voxel* v, const float* d_loss, const evd_voxel_grid_grads* g, void* stream) {
+    EVD_REQUIRE(v && g && d_loss, "evd_voxel_tv_loss_bwd: null argument");
+    TvJobs jobs = tv_jobs(v, g);
+    return launch_tv_bwd_level(jobs, d_loss, as_stream(stream));
 }
 
 int evd_voxel_tv_loss(const evd_voxel* v, float* out, void* stream) {
@@ -950,13 +951,7 @@ int evd_voxel_tv_loss(const evd_voxel* v, float* out, void* stream) {
     hipStream_t st = as_stream(stream);
     double* acc = (double*)v->tv_acc.p;
     TvShape s;
-    TvJobs jobs;
-    jobs.n = 6;
-    for (int i = 0; i < 3; ++i) {
-        const int C = v->n_comp[i], Wp = v->grid[kMat0[i]], Hp = v->grid[kMat1[i]], Lp = v->grid[kVec[i]];
-        jobs.j[i] = TvJob{(const float*)v->plane[i].p, nullptr, Hp, Wp, C, 1e-2f, 0, 0};
-        jobs.j[3 + i] = TvJob{(const float*)v->line[i].p, nullptr, Lp, 1, C, 1e-3f, 0, 0};
-    }
+    TvJobs jobs = tv_jobs(v, nullptr);
     int rc = launch_tv_level(jobs, acc, &s, st);
     if (rc) return rc;
     return launch_tv_finish(acc, s, out, st);

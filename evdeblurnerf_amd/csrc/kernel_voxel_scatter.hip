@@ -121,7 +121,6 @@ __global__ __launch_bounds__(SC_NT) void k_scatter_lines(const LineJobs jobs, co
 }
 
 static const int kM0[3] = {0, 0, 1}, kM1[3] = {1, 2, 2}, kV[3] = {2, 1, 0};
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static int launch_lines(const GridParams& g, const GridGrads& gg, const float* rows_l, const LTap* ltap, long n, hipStream_t st, const unsigned* gmax = nullptr) {
     const int ctot = g.n_comp[0] + g.n_comp[1] + g.n_comp[2];
@@ -163,32 +162,33 @@ bool voxel_scatter_hybrid_ok(const GridParams& g, long n) {
     return n > 0 && n < (1L << 31);
 }
 
-// rows_l [n, ctot] | ltap [n, 3] | the max |line row| word (k_scatter_lines' fixed-point scale), with 256 bytes for the alignment of the start
-size_t voxel_scatter_hybrid_workspace_bytes(const GridParams& g, long n) {
-    if (n <= 0) return 0;
+// rows_l [n, ctot] | ltap [n, 3] | the max |line row| word (k_scatter_lines' fixed-point scale)
+struct HybridWs { float* rows_l; LTap* ltap; unsigned* lmax; };
+static const size_t HYBRID_WS_SLACK = 256;      // alignment slack for an unaligned caller pointer
+static size_t hybrid_layout(const GridParams& g, long n, void* workspace, HybridWs* L) {
     const size_t ctot = (size_t)(g.n_comp[0] + g.n_comp[1] + g.n_comp[2]);
-    return al256((size_t)n * ctot * 4) + al256((size_t)n * 3 * sizeof(LTap)) + 512;
+    Workspace ws(workspace);
+    L->rows_l = ws.take<float>((size_t)n * ctot); L->ltap = ws.take<LTap>((size_t)n * 3); L->lmax = ws.take<unsigned>(1);
+    return ws.used() + HYBRID_WS_SLACK;
 }
+size_t voxel_scatter_hybrid_workspace_bytes(const GridParams& g, long n) { HybridWs L; return n <= 0 ? 0 : hybrid_layout(g, n, nullptr, &L); }
 
 int launch_voxel_sample_bwd_hybrid(const GridParams& g, const float* pts, long n, const float* d_out, int d_stride, int d_col, const GridGrads& gg,
                                    float* d_pts, void* workspace, size_t workspace_bytes, hipStream_t st, bool half_grids) {
-    if (workspace_bytes < voxel_scatter_hybrid_workspace_bytes(g, n))
-        return fail(EVD_E_WORKSPACE, "evd_voxel_sample_bwd: workspace %zu < %zu bytes", workspace_bytes, voxel_scatter_hybrid_workspace_bytes(g, n));
-    const size_t ctot = (size_t)(g.n_comp[0] + g.n_comp[1] + g.n_comp[2]);
-    char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    float* rows_l = (float*)w;
-    LTap* ltap = (LTap*)(w + al256((size_t)n * ctot * 4));
+    HybridWs L;
+    const size_t need = hybrid_layout(g, n, workspace, &L);
+    if (workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_voxel_sample_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
+    float* rows_l = L.rows_l; LTap* ltap = L.ltap;
     if (!voxel_sample_bwd_w_ok(g)) {
         int rc = launch_voxel_sample_bwd_planes(g, pts, n, d_out, d_stride, d_col, gg, d_pts, rows_l, ltap, st);
         if (rc) return rc;
         return launch_lines(g, gg, rows_l, ltap, n, st);
     }
     // max |line row| of the whole batch, taken by the main kernel: k_scatter_lines' scale without a pass of its own over the rows
-    unsigned* lmax = (unsigned*)(w + voxel_scatter_hybrid_workspace_bytes(g, n) - 512);
-    EVD_HIP(hipMemsetAsync(lmax, 0, sizeof(unsigned), st));
-    int rc = launch_voxel_sample_bwd_w(g, pts, n, d_out, d_stride, d_col, gg, d_pts, rows_l, ltap, lmax, half_grids, st);
+    EVD_HIP(hipMemsetAsync(L.lmax, 0, sizeof(unsigned), st));
+    int rc = launch_voxel_sample_bwd_w(g, pts, n, d_out, d_stride, d_col, gg, d_pts, rows_l, ltap, L.lmax, half_grids, st);
     if (rc) return rc;
-    return launch_lines(g, gg, rows_l, ltap, n, st, lmax);
+    return launch_lines(g, gg, rows_l, ltap, n, st, L.lmax);
 }
 
 }  // namespace evd

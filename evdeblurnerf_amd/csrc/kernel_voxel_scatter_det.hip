@@ -257,32 +257,24 @@ static __global__ __launch_bounds__(256) void k_scatter_det_basis(const float* _
 }
 
 static const int kDM0[3] = {0, 0, 1}, kDM1[3] = {1, 2, 2}, kDV[3] = {2, 1, 0};
-static size_t det_al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static void det_sizes(const GridParams& g, long* elems) {
-    for (int i = 0; i < 3; ++i) {
-        elems[i] = (long)g.grid[kDM0[i]] * g.grid[kDM1[i]] * g.n_comp[i];
-        elems[3 + i] = (long)g.grid[kDV[i]] * g.n_comp[i];
-    }
-}
-
 // [max word, 256 B] [shadow: the six accumulator arrays, each 256-byte aligned] [basis partials: SD_BLOCKS x app_dim x ctot floats]
-size_t voxel_scatter_det_region_bytes(const GridParams& g) {
-    long e[6];
-    det_sizes(g, e);
-    size_t b = 256;
-    for (int k = 0; k < 6; ++k) b += det_al256((size_t)e[k] * 8);
-    const size_t ctot = (size_t)(g.n_comp[0] + g.n_comp[1] + g.n_comp[2]);
-    return b + det_al256((size_t)SD_BLOCKS * g.app_dim * ctot * 4);
+struct DetRegion { unsigned* cmax; unsigned long long* acc[6]; long elems[6]; float* bpart; };     // (aligned by the caller, who adds the slack for that)
+static size_t det_region_layout(const GridParams& g, void* region, DetRegion* L) {
+    Workspace ws(region);
+    L->cmax = ws.take<unsigned>(1);
+    for (int i = 0; i < 3; ++i) { L->elems[i] = (long)g.grid[kDM0[i]] * g.grid[kDM1[i]] * g.n_comp[i]; L->elems[3 + i] = (long)g.grid[kDV[i]] * g.n_comp[i]; }
+    for (int k = 0; k < 6; ++k) L->acc[k] = ws.take<unsigned long long>((size_t)L->elems[k]);
+    L->bpart = ws.take<float>((size_t)SD_BLOCKS * g.app_dim * (g.n_comp[0] + g.n_comp[1] + g.n_comp[2]));
+    return ws.used();
 }
+size_t voxel_scatter_det_region_bytes(const GridParams& g) { DetRegion L; return det_region_layout(g, nullptr, &L); }
 
 struct DetPlan {
     DetShadow sh;
     DetSegs segs;
     unsigned* cmax;
     float* bpart;
-    char* shadow0;
-    size_t shadow_bytes;
+    size_t zero_bytes;          // the max word + the shadow: what pass 0 clears, from cmax on
     unsigned blocks;
     size_t lds;
 };
@@ -291,21 +283,15 @@ static int det_plan(const GridParams& g, long n, const GridGrads& gg, void* regi
     if (g.app_dim > SD_MAXF) return fail(EVD_E_INVALID, "evd_voxel_sample_bwd_det: app_dim %d > %d", g.app_dim, SD_MAXF);
     const int ctot = g.n_comp[0] + g.n_comp[1] + g.n_comp[2];
     if (ctot > VS_MAXC) return fail(EVD_E_INVALID, "evd_voxel_sample_bwd_det: sum(n_comp) %d > %d", ctot, VS_MAXC);
-    long e[6];
-    det_sizes(g, e);
-    char* w = (char*)region;
-    p.cmax = (unsigned*)w;
-    w += 256;
-    p.shadow0 = w;
+    DetRegion L;
+    det_region_layout(g, region, &L);
+    p.cmax = L.cmax; p.bpart = gg.basis ? L.bpart : nullptr; p.zero_bytes = (size_t)((char*)L.bpart - (char*)L.cmax);
     for (int k = 0; k < 6; ++k) {
         float* grad = k < 3 ? gg.plane[k] : gg.line[k - 3];
-        unsigned long long* acc = grad ? (unsigned long long*)w : nullptr;
+        unsigned long long* acc = grad ? L.acc[k] : nullptr;
         (k < 3 ? p.sh.plane[k] : p.sh.line[k - 3]) = acc;
-        p.segs.s[k] = DetSeg{acc, grad, e[k]};
-        w += det_al256((size_t)e[k] * 8);
+        p.segs.s[k] = DetSeg{acc, grad, L.elems[k]};
     }
-    p.shadow_bytes = (size_t)(w - p.shadow0);
-    p.bpart = gg.basis ? (float*)w : nullptr;
     const long tiles = cdiv(n, (long)VS_SAMPLES);
     p.blocks = (unsigned)(tiles < SD_BLOCKS ? tiles : SD_BLOCKS);
     p.lds = ((size_t)g.app_dim * ctot + (size_t)VS_SAMPLES * (g.app_dim | 1) + (size_t)3 * VS_SAMPLES * (ctot | 1)) * sizeof(float);
@@ -322,7 +308,7 @@ int launch_voxel_scatter_det_scale(const GridParams& g, bool half_grids, const f
     DetPlan p;
     int rc = det_plan(g, n, gg, region, p);
     if (rc) return rc;
-    EVD_HIP(hipMemsetAsync(region, 0, 256 + p.shadow_bytes, st));
+    EVD_HIP(hipMemsetAsync(p.cmax, 0, p.zero_bytes, st));
     if (half_grids) EVD_SD(0, true, g, pts, n, d_out, d_stride, d_col, p.sh, nullptr, nullptr, p.cmax, 0.f)
     else EVD_SD(0, false, g, pts, n, d_out, d_stride, d_col, p.sh, nullptr, nullptr, p.cmax, 0.f)
     EVD_LAUNCH_CHECK();

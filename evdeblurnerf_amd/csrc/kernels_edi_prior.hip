@@ -182,10 +182,15 @@ __global__ void k_edi_splat(const float* __restrict__ x, const float* __restrict
         }
 }
 
-static inline size_t edi_al256(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline size_t edi_win_bytes(int c, int steps) { return 2 * edi_al256((size_t)c * steps * 8); }
 static inline size_t edi_plane_bytes(int steps, int h, int w) { return (size_t)(steps - 1) * h * w * 16; }
-static inline size_t edi_ws_bytes(int c, int steps, int h, int w) { return edi_win_bytes(c, steps) + (size_t)c * edi_plane_bytes(steps, h, w) + 256; }
+// workspace of evd_edi_prior at a chunk of c images: the window bounds [c, steps] x 2 | the accumulator planes, which end the workspace unpadded
+struct EdiWs { long long *left, *right; u64* acc; };
+static const size_t EDI_WS_SLACK = 256;     // alignment slack for an unaligned caller pointer
+static size_t edi_layout(int c, int steps, int h, int w, void* workspace, EdiWs* L) {
+    Workspace ws(workspace);
+    L->left = ws.take<long long>((size_t)c * steps); L->right = ws.take<long long>((size_t)c * steps); L->acc = ws.take<u64>(0);
+    return ws.used() + (size_t)c * edi_plane_bytes(steps, h, w) + EDI_WS_SLACK;
+}
 
 }  // namespace evd
 
@@ -195,7 +200,8 @@ extern "C" {
 
 size_t evd_edi_prior_workspace_bytes(int n_img, int steps, int h, int w) {
     if (n_img < 1 || steps < 3 || !(steps & 1) || steps > EDI_MAX_STEPS || h < 1 || w < 1 || (long)h * w >= (1L << 31)) return 0;
-    return edi_ws_bytes(n_img < EDI_MAX_CHUNK ? n_img : EDI_MAX_CHUNK, steps, h, w);
+    EdiWs L;
+    return edi_layout(n_img < EDI_MAX_CHUNK ? n_img : EDI_MAX_CHUNK, steps, h, w, nullptr, &L);
 }
 
 int evd_edi_prior(const double* events, long N, const double* id_to_coords, long n_coords, const double* boundaries, const float* images,
@@ -205,16 +211,14 @@ int evd_edi_prior(const double* events, long N, const double* id_to_coords, long
     EVD_REQUIRE(N >= 0 && n_coords >= 0 && n_img >= 1 && h >= 1 && w >= 1 && (long)h * w < (1L << 31) && n_img < 65536,
                 "evd_edi_prior: bad sizes N=%ld n_coords=%ld n_img=%d h=%d w=%d", N, n_coords, n_img, h, w);
     EVD_REQUIRE(boundaries && images && prior_out && (N == 0 || (events && id_to_coords)), "evd_edi_prior: null argument");
-    const size_t need = edi_ws_bytes(1, steps, h, w);
+    EdiWs L;
+    const size_t need = edi_layout(1, steps, h, w, workspace, &L);
     EVD_REQUIRE(workspace && workspace_bytes >= need, "evd_edi_prior: workspace %zu < %zu bytes (one image)", workspace_bytes, need);
     int chunk = n_img < EDI_MAX_CHUNK ? n_img : EDI_MAX_CHUNK;
-    while (edi_ws_bytes(chunk, steps, h, w) > workspace_bytes) --chunk;       // >= 1: checked above
+    while (edi_layout(chunk, steps, h, w, workspace, &L) > workspace_bytes) --chunk;       // >= 1: checked above; L is the layout at the chunk that fits
     hipStream_t st = as_stream(stream);
     const long hw = (long)h * w;
-    char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    long long* left = (long long*)p; p += edi_al256((size_t)chunk * steps * 8);
-    long long* right = (long long*)p; p += edi_al256((size_t)chunk * steps * 8);
-    u64* acc = (u64*)p;
+    long long *left = L.left, *right = L.right; u64* acc = L.acc;
     if (bad_id) EVD_HIP(hipMemsetAsync(bad_id, 0, sizeof(int), st));
     for (int c0 = 0; c0 < n_img; c0 += chunk) {
         const int cn = n_img - c0 < chunk ? n_img - c0 : chunk;

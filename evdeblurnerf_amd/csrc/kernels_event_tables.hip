@@ -193,7 +193,46 @@ __global__ __launch_bounds__(256) void k_cm_mark_noev(const long long* __restric
     if (i < n && noev_ids[i] >= 0 && noev_ids[i] < Nc) is_noev[noev_ids[i]] = 1;
 }
 
-static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+// The workspaces of the three entries.  Each slack: alignment slack for an unaligned caller pointer plus the historical margin.
+// hipcub scratch (the larger of sort and scan) | kx, ky, key scratch x 2 | iota, perm a, perm b, head, uid | silent + its int image and inclusive rank
+struct CoordIdsWs { void* tmp; size_t tmp_bytes; u64 *kx, *ky, *ka, *kb; int *iota, *pa, *pb, *head, *uid; unsigned char* silent; int *silent_i, *silent_rank; };
+static const size_t COORD_IDS_WS_SLACK = 512;
+static size_t coord_ids_layout(long N, int h, int w, void* workspace, CoordIdsWs* L) {
+    const size_t HW = (size_t)h * w, M = (size_t)N + HW;
+    const u64* k = nullptr; u64* ko = nullptr; const int* v = nullptr; int* vo = nullptr; size_t sort_bytes = 0, scan_bytes = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, k, ko, v, vo, (int)M);
+    (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, v, vo, (int)M);
+    L->tmp_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
+    Workspace ws(workspace);
+    L->tmp = ws.take<char>(L->tmp_bytes);
+    L->kx = ws.take<u64>(M); L->ky = ws.take<u64>(M); L->ka = ws.take<u64>(M); L->kb = ws.take<u64>(M);
+    L->iota = ws.take<int>(M); L->pa = ws.take<int>(M); L->pb = ws.take<int>(M); L->head = ws.take<int>(M); L->uid = ws.take<int>(M);
+    L->silent = ws.take<unsigned char>(HW); L->silent_i = ws.take<int>(HW); L->silent_rank = ws.take<int>(HW);
+    return ws.used() + COORD_IDS_WS_SLACK;
+}
+
+// scan scratch | keep flags, their inclusive positions | min / max polarity (two words)
+struct EventFilterWs { void* tmp; size_t tmp_bytes; int *keep, *pos, *pminmax; };
+static const size_t EVENT_FILTER_WS_SLACK = 512;
+static size_t event_filter_layout(long N, void* workspace, EventFilterWs* L) {
+    const size_t n = (size_t)(N > 0 ? N : 1);
+    const int* v = nullptr; int* vo = nullptr; L->tmp_bytes = 0;
+    (void)hipcub::DeviceScan::InclusiveSum(nullptr, L->tmp_bytes, v, vo, (int)n);
+    Workspace ws(workspace);
+    L->tmp = ws.take<char>(L->tmp_bytes);
+    L->keep = ws.take<int>(n); L->pos = ws.take<int>(n); L->pminmax = ws.take<int>(2);
+    return ws.used() + EVENT_FILTER_WS_SLACK;
+}
+
+// the last pixel that maps to each coordinate | the coordinates without events
+struct ColorMapWs { int* last_pixel; unsigned char* is_noev; };
+static const size_t COLOR_MAP_WS_SLACK = 512;
+static size_t color_map_layout(long n_coords, void* workspace, ColorMapWs* L) {
+    const size_t n = (size_t)(n_coords > 0 ? n_coords : 1);
+    Workspace ws(workspace);
+    L->last_pixel = ws.take<int>(n); L->is_noev = ws.take<unsigned char>(n);
+    return ws.used() + COLOR_MAP_WS_SLACK;
+}
 
 }  // namespace evd
 
@@ -201,47 +240,20 @@ using namespace evd;
 
 extern "C" {
 
-size_t evd_event_coord_ids_workspace_bytes(long N, int h, int w) {
-    if (N < 0 || h < 1 || w < 1) return 0;
-    const size_t M = (size_t)N + (size_t)h * w;
-    size_t sort_bytes = 0, scan_bytes = 0;
-    const u64* k = nullptr; u64* ko = nullptr; const int* v = nullptr; int* vo = nullptr;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, k, ko, v, vo, (int)M);
-    (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, v, vo, (int)M);
-    const size_t tmp = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-    // kx, ky, key scratch x 2 (u64) | iota, perm a, perm b, head, uid (int) | silent (u8) + its int image and inclusive rank
-    return al256(tmp) + 4 * al256(M * 8) + 5 * al256(M * 4) + al256((size_t)h * w) + 2 * al256((size_t)h * w * 4) + 512;
-}
+size_t evd_event_coord_ids_workspace_bytes(long N, int h, int w) { CoordIdsWs L; return (N < 0 || h < 1 || w < 1) ? 0 : coord_ids_layout(N, h, w, nullptr, &L); }
 
 int evd_event_coord_ids(const float* x, const float* y, long N, int h, int w, long long* ev_coord_ids, long long* noev_coord_ids, double* id_to_coords,
                         long long* counts, void* workspace, size_t workspace_bytes, void* stream) {
     EVD_REQUIRE(N >= 0 && h >= 1 && w >= 1 && (long)N + (long)h * w < (1L << 31), "evd_event_coord_ids: bad sizes (N + h w < 2^31)");
     EVD_REQUIRE(noev_coord_ids && id_to_coords && counts && (N == 0 || (x && y && ev_coord_ids)), "evd_event_coord_ids: null argument");
-    const size_t need = evd_event_coord_ids_workspace_bytes(N, h, w);
+    CoordIdsWs L;
+    const size_t need = coord_ids_layout(N, h, w, workspace, &L);
     if (!workspace || workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_event_coord_ids: workspace %zu < %zu bytes", workspace_bytes, need);
     hipStream_t st = as_stream(stream);
     const long HW = (long)h * w, M = N + HW;
-    size_t sort_bytes = 0, scan_bytes = 0;
-    {
-        const u64* k = nullptr; u64* ko = nullptr; const int* v = nullptr; int* vo = nullptr;
-        (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, k, ko, v, vo, (int)M);
-        (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, v, vo, (int)M);
-    }
-    const size_t tmp_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-    char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    void* tmp = p; p += al256(tmp_bytes);
-    u64* kx = (u64*)p; p += al256(M * 8);
-    u64* ky = (u64*)p; p += al256(M * 8);
-    u64* ka = (u64*)p; p += al256(M * 8);
-    u64* kb = (u64*)p; p += al256(M * 8);
-    int* iota = (int*)p; p += al256(M * 4);
-    int* pa = (int*)p; p += al256(M * 4);
-    int* pb = (int*)p; p += al256(M * 4);
-    int* head = (int*)p; p += al256(M * 4);
-    int* uid = (int*)p; p += al256(M * 4);
-    unsigned char* silent = (unsigned char*)p; p += al256(HW);
-    int* silent_i = (int*)p; p += al256(HW * 4);
-    int* silent_rank = (int*)p; p += al256(HW * 4);
+    const size_t tmp_bytes = L.tmp_bytes; void* tmp = L.tmp; unsigned char* silent = L.silent;
+    u64 *kx = L.kx, *ky = L.ky, *ka = L.ka, *kb = L.kb;
+    int *iota = L.iota, *pa = L.pa, *pb = L.pb, *head = L.head, *uid = L.uid, *silent_i = L.silent_i, *silent_rank = L.silent_rank;
     EVD_HIP(hipMemsetAsync(silent, 1, HW, st));
     if (N > 0) hipLaunchKernelGGL(k_et_mark, dim3((unsigned)cdiv(N, 256L)), dim3(256), 0, st, x, y, N, h, w, silent);
     hipLaunchKernelGGL(k_et_keys, dim3((unsigned)cdiv(M, 256L)), dim3(256), 0, st, x, y, N, h, w, silent, kx, ky, iota);
@@ -263,14 +275,7 @@ int evd_event_coord_ids(const float* x, const float* y, long N, int h, int w, lo
     EVD_LAUNCH_CHECK();
     return EVD_OK;
 }
-
-size_t evd_event_filter_workspace_bytes(long N) {
-    if (N < 0) return 0;
-    size_t scan_bytes = 0;
-    const int* v = nullptr; int* vo = nullptr;
-    (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, v, vo, (int)(N > 0 ? N : 1));
-    return al256(scan_bytes) + 2 * al256((size_t)(N > 0 ? N : 1) * 4) + 256 + 512;
-}
+size_t evd_event_filter_workspace_bytes(long N) { EventFilterWs L; return N < 0 ? 0 : event_filter_layout(N, nullptr, &L); }
 
 int evd_event_filter(const long long* coord_ids, const double* t, const double* p, long N, double tmin, double tmax, double* events_out, long long* count,
                      int* bad_polarity, void* workspace, size_t workspace_bytes, void* stream) {
@@ -278,26 +283,20 @@ int evd_event_filter(const long long* coord_ids, const double* t, const double* 
     hipStream_t st = as_stream(stream);
     if (bad_polarity) EVD_HIP(hipMemsetAsync(bad_polarity, 0, sizeof(int), st));
     if (N == 0) { EVD_HIP(hipMemsetAsync(count, 0, sizeof(long long), st)); return EVD_OK; }
-    const size_t need = evd_event_filter_workspace_bytes(N);
+    EventFilterWs L;
+    const size_t need = event_filter_layout(N, workspace, &L);
     if (!workspace || workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_event_filter: workspace %zu < %zu bytes", workspace_bytes, need);
-    size_t scan_bytes = 0;
-    { const int* v = nullptr; int* vo = nullptr; (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, v, vo, (int)N); }
-    char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    void* tmp = w; w += al256(scan_bytes);
-    int* keep = (int*)w; w += al256((size_t)N * 4);
-    int* pos = (int*)w; w += al256((size_t)N * 4);
-    int* pminmax = (int*)w;
+    int *keep = L.keep, *pos = L.pos, *pminmax = L.pminmax;
     hipLaunchKernelGGL(k_ef_init, dim3(1), dim3(1), 0, st, pminmax);
     hipLaunchKernelGGL(k_ef_flags, dim3((unsigned)cdiv(N, 256L)), dim3(256), 0, st, t, p, N, tmin, tmax, keep, pminmax);
-    size_t sb = scan_bytes;
-    EVD_HIP(hipcub::DeviceScan::InclusiveSum(tmp, sb, (const int*)keep, pos, (int)N, st));
+    size_t sb = L.tmp_bytes;
+    EVD_HIP(hipcub::DeviceScan::InclusiveSum(L.tmp, sb, (const int*)keep, pos, (int)N, st));
     hipLaunchKernelGGL(k_ef_write, dim3((unsigned)cdiv(N, 256L)), dim3(256), 0, st, coord_ids, t, p, N, (const int*)keep, (const int*)pos, (const int*)pminmax, events_out,
                        count, bad_polarity);
     EVD_LAUNCH_CHECK();
     return EVD_OK;
 }
-
-size_t evd_event_color_map_workspace_bytes(long n_coords) { return n_coords < 0 ? 0 : al256((size_t)(n_coords > 0 ? n_coords : 1) * 4) + al256((size_t)(n_coords > 0 ? n_coords : 1)) + 512; }
+size_t evd_event_color_map_workspace_bytes(long n_coords) { ColorMapWs L; return n_coords < 0 ? 0 : color_map_layout(n_coords, nullptr, &L); }
 
 int evd_event_color_map(const double* id_to_coords, long n_coords, int h, int w, const float* inv_mapx, const float* inv_mapy, const long long* noev_coord_ids,
                         long n_noev, unsigned char* id_to_color_map, int* unmapped, void* workspace, size_t workspace_bytes, void* stream) {
@@ -311,11 +310,10 @@ int evd_event_color_map(const double* id_to_coords, long n_coords, int h, int w,
         EVD_LAUNCH_CHECK();
         return EVD_OK;
     }
-    const size_t need = evd_event_color_map_workspace_bytes(n_coords);
+    ColorMapWs L;
+    const size_t need = color_map_layout(n_coords, workspace, &L);
     if (!workspace || workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_event_color_map: workspace %zu < %zu bytes", workspace_bytes, need);
-    char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    int* last_pixel = (int*)p; p += al256((size_t)n_coords * 4);
-    unsigned char* is_noev = (unsigned char*)p;
+    int* last_pixel = L.last_pixel; unsigned char* is_noev = L.is_noev;
     EVD_HIP(hipMemsetAsync(last_pixel, 0xff, (size_t)n_coords * 4, st));            // -1
     EVD_HIP(hipMemsetAsync(is_noev, 0, (size_t)n_coords, st));
     hipLaunchKernelGGL(k_cm_lookup, dim3((unsigned)cdiv((long)h * w, 256L)), dim3(256), 0, st, id_to_coords, n_coords, h, w, inv_mapx, inv_mapy, last_pixel);

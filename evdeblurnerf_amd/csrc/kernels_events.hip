@@ -154,19 +154,26 @@ __global__ __launch_bounds__(256) void k_interpolate_poses(const PoseTrackDev tr
     for (int k = 0; k < 12; ++k) out[i * 12 + k] = c2w[k];
 }
 
+// workspace of evd_compute_successor: iota, sorted keys, sorted indices, two pointer-jumping arrays | the sort's scratch
+struct SuccessorWs { int *iota, *keys, *idx, *ja, *jb; void* sort_tmp; size_t sort_bytes; };
+static const size_t SUCCESSOR_WS_SLACK = 512;       // alignment slack for an unaligned caller pointer plus the historical margin
+static size_t successor_layout(long N, void* workspace, SuccessorWs* L) {
+    const size_t n = (size_t)(N > 0 ? N : 1);
+    const int* ki = nullptr; int* ko = nullptr; L->sort_bytes = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, L->sort_bytes, ki, ko, ki, ko, (int)n);
+    Workspace ws(workspace);
+    L->iota = ws.take<int>(n); L->keys = ws.take<int>(n); L->idx = ws.take<int>(n); L->ja = ws.take<int>(n); L->jb = ws.take<int>(n);
+    L->sort_tmp = ws.take<char>(L->sort_bytes);
+    return ws.used() + SUCCESSOR_WS_SLACK;
+}
+
 }  // namespace evd
 
 using namespace evd;
 
 extern "C" {
 
-size_t evd_compute_successor_workspace_bytes(long N) {
-    if (N < 0) return 0;
-    size_t sort_bytes = 0;
-    const int* ki = nullptr; int* ko = nullptr;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, ki, ko, ki, ko, (int)(N > 0 ? N : 1));
-    return ((sort_bytes + 255) & ~(size_t)255) + 5 * (((size_t)(N > 0 ? N : 1) * 4 + 255) & ~(size_t)255) + 512;
-}
+size_t evd_compute_successor_workspace_bytes(long N) { SuccessorWs L; return N < 0 ? 0 : successor_layout(N, nullptr, &L); }
 
 int evd_compute_successor(const int* pixel_ids, long N, long HW, long long* successor, int* num_successors,
                           long long* latest_seen, long long* first_seen, void* workspace, size_t workspace_bytes, void* stream) {
@@ -177,21 +184,14 @@ int evd_compute_successor(const int* pixel_ids, long N, long HW, long long* succ
     k_fill_i64<<<cdiv(HW, 256), 256, 0, st>>>(first_seen, HW, -1);
     EVD_LAUNCH_CHECK();
     if (N == 0) return EVD_OK;
-    const size_t need = evd_compute_successor_workspace_bytes(N);
+    SuccessorWs L;
+    const size_t need = successor_layout(N, workspace, &L);
     if (!workspace || workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_compute_successor: workspace %zu < %zu bytes", workspace_bytes, need);
-    const size_t arr = ((size_t)N * 4 + 255) & ~(size_t)255;
-    char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    int* iota = (int*)w; w += arr;
-    int* keys = (int*)w; w += arr;
-    int* idx = (int*)w; w += arr;
-    int* ja = (int*)w; w += arr;
-    int* jb = (int*)w; w += arr;
-    size_t sort_bytes = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, pixel_ids, keys, iota, idx, (int)N);
+    int *iota = L.iota, *keys = L.keys, *idx = L.idx, *ja = L.ja, *jb = L.jb;
     k_iota_i32<<<cdiv(N, 256), 256, 0, st>>>(iota, N);
     int bits = 1;
     while (bits < 31 && (1L << bits) < HW) ++bits;
-    EVD_HIP(hipcub::DeviceRadixSort::SortPairs(w, sort_bytes, pixel_ids, keys, iota, idx, (int)N, 0, bits, st));   // stable: stream order inside a pixel
+    EVD_HIP(hipcub::DeviceRadixSort::SortPairs(L.sort_tmp, L.sort_bytes, pixel_ids, keys, iota, idx, (int)N, 0, bits, st));   // stable: stream order inside a pixel
     k_succ_init<<<cdiv(N, 256), 256, 0, st>>>(keys, N, ja);
     for (long span = 1; span < N; span <<= 1) {          // pointer jumping to the segment end
         k_succ_jump<<<cdiv(N, 256), 256, 0, st>>>(ja, N, jb);

@@ -274,7 +274,7 @@ int evd_frame_range(const float* x, const float* y, int source, int scope, int n
     const size_t need = (size_t)(slices * bps) * 2 * sizeof(float) + 256;
     EVD_REQUIRE(workspace && workspace_bytes >= need, "evd_frame_range: workspace %zu < %zu bytes", workspace_bytes, need);
     hipStream_t st = as_stream(stream);
-    float* partials = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    float* partials = (float*)ws_align_ptr(workspace);
     const FrameWalk w = {x, y, n, bps};
     const unsigned grid = (unsigned)(slices * bps);
     if (source == EVD_FRAME_SRC_PLAIN) k_frame_range<EVD_FRAME_SRC_PLAIN><<<grid, FR_THREADS, 0, st>>>(w, partials);

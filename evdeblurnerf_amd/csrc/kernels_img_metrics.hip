@@ -287,7 +287,7 @@ int evd_img_metrics(const float* pred, const float* target, const float* mask, i
     const size_t need = im_ws_bytes(B, Hr, Wr);
     EVD_REQUIRE(workspace && workspace_bytes >= need, "evd_img_metrics: workspace %zu < %zu bytes", workspace_bytes, need);
     hipStream_t st = as_stream(stream);
-    double* partials = (double*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    double* partials = (double*)ws_align_ptr(workspace);
     k_img_metrics<<<(unsigned)(B * tiles), IM_THREADS, 0, st>>>(pred, target, mask, mask_ch, H, W, margin_h, margin_w, Hr, Wr, (int)cdiv(Wr, IM_TW), (int)tiles,
                                                                 partials);
     k_img_metrics_finish<<<1, IM_FINISH_THREADS, 0, st>>>(partials, B, (int)tiles, Hr, Wr, mask ? 1 : 0, out);

@@ -387,7 +387,7 @@ int evd_lpips(const evd_lpips_model* m, const float* pred, const float* target, 
     EVD_REQUIRE(workspace && workspace_bytes >= need, "evd_lpips: workspace %zu < %zu bytes", workspace_bytes, need);
     hipStream_t st = as_stream(stream);
     float* buf[2];
-    buf[0] = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    buf[0] = (float*)ws_align_ptr(workspace);
     buf[1] = buf[0] + pl.buf_floats;
     double* partials = (double*)(buf[1] + pl.buf_floats);
 

@@ -37,7 +37,6 @@ inline bool nerf_generic_trains(const evd_nerf* n, int prec) {
     return prec == EVD_PREC_F16X3 && !n->no_views && n->pipe_chunks[EVD_PREC_F16X3] == 0 && n->nchunks[EVD_PREC_F16X3] > 0;
 }
 inline size_t nerf_generic_store_bytes(const evd_nerf* n, long nsamp) { return (size_t)GenStore(nsamp, n->D, n->W).total() * sizeof(float); }
-inline size_t nerf_generic_workspace_bytes() { return GEN_WS_FLOATS * sizeof(float) + 512; }
 
 int launch_nerf_train_fwd_generic(int W, const MlpParams& p, hipStream_t st);
 
