@@ -10,6 +10,7 @@
 // A ray's channels lie along the lanes of a lane group, CPL consecutive channels per lane; the group supplies the cross-lane steps.
 #pragma once
 
+#include "ray_math.h"       // ray_norm: |d| of dist
 #include "wave_ops.h"
 
 namespace evd {
@@ -32,9 +33,6 @@ struct AwpRowGroup {
     static __device__ __forceinline__ float sum(float v) { return row_sum_dpp(v); }
 };
 
-__device__ __forceinline__ float awp_ray_norm(const float* d) {
-    return sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d[0], d[0]), __fmul_rn(d[1], d[1])), __fmul_rn(d[2], d[2])));
-}
 // z[s+1] - z[s], 0 on the last sample, and dist[s] = (z[s+1] - z[s]) |d| (awp.py:61-63); s <= S - 1
 __device__ __forceinline__ float awp_dz(const float* zz, int s, bool last) { return last ? 0.f : __fsub_rn(zz[s + 1], zz[s]); }
 __device__ __forceinline__ float awp_dist(const float* zz, int s, int S, float norm) { return s < S - 1 ? __fmul_rn(__fsub_rn(zz[s + 1], zz[s]), norm) : 0.f; }

@@ -606,12 +606,6 @@ int evd_c2f_render(const evd_voxel* coarse, const evd_voxel* fine, const evd_ren
     return evd_c2f_render_rays(coarse, fine, cfg, L.rb, R, t_rand, u, noise0, noise1, out, workspace, workspace_bytes, stream);
 }
 
-int evd_points(const float* ray_batch, int ncol, const float* z, long R, int S, float* pts, void* stream) {
-    EVD_REQUIRE(ray_batch && z && pts && ncol >= 6 && R >= 0 && S >= 1, "evd_points: bad arguments");
-    if (R == 0) return EVD_OK;
-    return launch_points(ray_batch, ncol, z, R * (long)S, S, pts, as_stream(stream));
-}
-
 // ---- the coarse feature rows of the merged sample set (renderer.py:209-213), as an operation of its own for the training path
 int evd_merge_features(const float* old, const float* fresh, const int* order, long R, int S, int N, int F, float* out, int out_stride, void* stream) {
     EVD_REQUIRE(old && fresh && order && out && R >= 0 && S >= 1 && N >= 1 && F >= 4 && F % 4 == 0 && out_stride >= F && out_stride % 4 == 0,

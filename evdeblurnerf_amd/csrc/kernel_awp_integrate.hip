@@ -13,7 +13,7 @@ __global__ __launch_bounds__(256) void k_awp_integrate(const float* __restrict__
     const int lane = threadIdx.x & 63;
     const long n = blockIdx.x * (long)(blockDim.x >> 6) + (threadIdx.x >> 6);
     if (n >= N) return;
-    const float norm = awp_ray_norm(rays_d + n * 3);
+    const float norm = ray_norm(rays_d + n * 3);
     const float* fr = feat + n * (long)S * C;
     const float* zz = z + n * (long)S;
     float acc[CPL], Q[CPL];
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void k_awp_integrate_bwd(const float* __restri
     const long n = blockIdx.x * (long)(blockDim.x >> 6) + (threadIdx.x >> 6);
     if (n >= N) return;
     const float* d = rays_d + n * 3;
-    const float norm = awp_ray_norm(d);
+    const float norm = ray_norm(d);
     const float* fr = feat + n * (long)S * C;
     const float* zz = z + n * (long)S;
     constexpr int PF = CPL == 1 ? 4 : 2;                 // rows per block; the NEXT block's rows are loaded while this one is processed
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void k_awp_integrate_c64(const float* __restri
     const int l16 = threadIdx.x & 15;
     const long n0 = blockIdx.x * 16L + (threadIdx.x >> 4);
     const long n = n0 < N ? n0 : N - 1;                   // (rays past the end compute on the last ray and write nothing: the DPP rows stay whole)
-    const float norm = awp_ray_norm(rays_d + n * 3);
+    const float norm = ray_norm(rays_d + n * 3);
     const float4* fr = reinterpret_cast<const float4*>(feat + n * (long)S * 64) + l16;
     const float* zz = z + n * (long)S;
     float acc[4] = {0.f, 0.f, 0.f, 0.f}, Q[4] = {1.f, 1.f, 1.f, 1.f};
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void k_awp_integrate_bwd_c64(const float* __re
     const bool live = n0 < N;
     const long n = live ? n0 : N - 1;
     const float* d = rays_d + n * 3;
-    const float norm = awp_ray_norm(d);
+    const float norm = ray_norm(d);
     const float4* fr = reinterpret_cast<const float4*>(feat + n * (long)S * 64) + l16;
     float4* dfr = reinterpret_cast<float4*>(d_feat + n * (long)S * 64) + l16;
     const float* zz = z + n * (long)S;

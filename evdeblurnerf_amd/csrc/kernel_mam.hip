@@ -340,7 +340,7 @@ __global__ __launch_bounds__(256) void k_local_consumers_bwd(const LocalBwdParam
     const float4 u4 = reinterpret_cast<const float4*>(q.u)[l];
     mam_bwd_stage_dP(m, q.d_inter, b, P);
     for (int i = tid; i < P * S; i += 256) zl[i] = q.z[b * P * S + i];
-    if (tid < P) nrm[tid] = awp_ray_norm(q.rays_d + (b * P + tid) * 3);
+    if (tid < P) nrm[tid] = ray_norm(q.rays_d + (b * P + tid) * 3);
     __syncthreads();
     mam_bwd_cP(m, q.h_inter, b, P);
     float4 du = make_float4(0.f, 0.f, 0.f, 0.f);

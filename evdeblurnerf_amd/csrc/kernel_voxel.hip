@@ -1,8 +1,7 @@
 // PDRF backbone (reference networks/pdrf/voxnerf.py): the small row kernels around the tri-plane levels and the generic level network.
 // The feature gather is in kernel_voxel_sample.hip, its backward in kernel_voxel_sample_bwd.hip / kernel_voxel_scatter.hip, the TV
-// regulariser in kernel_voxel_tv.hip.
+// regulariser in kernel_voxel_tv.hip, the sample positions pts = o + d z (k_points) with the ray front end in kernels_rays.hip.
 //
-//   k_points           pts = o + d z                                      (renderer.py:180,206)
 //   k_merge_features   the merged-sample feature rows of the c2f pass      (renderer.py:205-213), and its backward
 //   k_f32_to_f16       the float16 copies of the grids
 //   k_voxel_mlp        VoxelNeRFBase.forward, per-sample part             (voxnerf.py:210-221,240-254)
@@ -10,15 +9,6 @@
 #include "voxel_taps.h"          // f16x4
 
 namespace evd {
-
-__global__ void k_points(const float* __restrict__ rb, int nc, const float* __restrict__ z, long n, int S, float* __restrict__ pts) {
-    const long s = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (s >= n) return;
-    const float* r = rb + (s / S) * nc;
-    const float zv = z[s];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) pts[s * 3 + c] = __fadd_rn(r[c], __fmul_rn(r[3 + c], zv));
-}
 
 // merged-sample feature rows of the c2f pass (renderer.py:205-213): out[r, k, 0:F] = order[r, k] < S ? old[r, order] : fresh[r, order - S]
 // -- the reference's gather of cat([ft_comb0, ft_comb1]) by the sort order, 16 bytes per lane
@@ -173,12 +163,6 @@ int voxel_mlp_dispatch(int prec, int HD, int G, int FT, const VoxMlpParams& p, h
 #undef EVD_CASE
     return fail(EVD_E_INVALID, "evd_voxel: no kernel for precision %d hidden %d geo %d features %d "
                 "(built: coarse 64/15/32, fine 256/128/64)", prec, HD, G, FT);
-}
-
-int launch_points(const float* rb, int nc, const float* z, long n, int S, float* pts, hipStream_t st) {
-    k_points<<<cdiv(n, 256), 256, 0, st>>>(rb, nc, z, n, S, pts);
-    EVD_LAUNCH_CHECK();
-    return EVD_OK;
 }
 
 int launch_merge_features(const float* old, const float* fresh, const int* order, long R, int S, int N, int F, float* out, int out_stride,

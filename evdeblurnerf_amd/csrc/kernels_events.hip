@@ -5,8 +5,8 @@
 // distance to the segment end.  Results are bit-identical to the reference loop.
 #include <hipcub/hipcub.hpp>
 
-#include "evd_common.h"
 #include "pose_track.h"
+#include "ray_math.h"
 
 namespace evd {
 
@@ -52,7 +52,7 @@ __global__ void k_succ_write(const int* __restrict__ keys, const int* __restrict
 }
 
 // EventsDataset.sample_events (data/loader_events.py:259-304) for one event id per thread: the reference's gathers, gather_successor
-// (utils/events.py:221-257), and get_rays_pix (utils/rays.py:25-36, the arithmetic of k_get_rays_pix) on the start and the end pose.
+// (utils/events.py:221-257), and get_rays_pix (utils/rays.py:25-36, camera_ray_dir as in k_get_rays_pix) on the start and the end pose.
 // TRACK: the two poses are interpolate_poses(timestamp) evaluated here (pose_track.h; the reference's scipy round trip :280-283);
 // else rows of a per-event pose table.  An id outside [0, N), or a successor outside it in the single-hop branch (an event without
 // successor carries -1: the reference would wrap to events[-1]), gives zero polarity sums, successor -1, the start pose twice, and sets
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void k_sample_events(const double* __restrict_
         for (int c = 0; c < 3; ++c) cmap_out[i * 3 + c] = cmap[pix * 3 + c];
     }
     const float cx = id_to_coords[pix * 2], cy = id_to_coords[pix * 2 + 1];
-    const float d0 = (cx + (halfpix - k02)) / k00, d1 = -(cy + (halfpix - k12)) / k11, d2 = -1.f;
+    const float d0 = (cx + (halfpix - k02)) / k00, d1 = -(cy + (halfpix - k12)) / k11;
     const long long e2 = end < 0 ? id : end;       // an invalid chain: the start pose twice (the reference would index events[-1])
     if (mismatch && end >= 0 && (long long)ev[end * ncol] != pix) atomicExch(mismatch, 1);
 #pragma unroll
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void k_sample_events(const double* __restrict_
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             out[r * 2] = c2w[r * 4 + 3];
-            out[r * 2 + 1] = __fadd_rn(__fadd_rn(__fmul_rn(d0, c2w[r * 4]), __fmul_rn(d1, c2w[r * 4 + 1])), __fmul_rn(d2, c2w[r * 4 + 2]));
+            out[r * 2 + 1] = camera_ray_dir(d0, d1, c2w, r);
         }
     }
 }

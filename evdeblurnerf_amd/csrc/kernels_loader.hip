@@ -2,7 +2,7 @@
 // The reference keeps images [n_img, H, W, 3] and poses [n_img, 3, 4] on the device and builds a batch with six indexing / stacking
 // launches + get_rays_pix; here one thread per ray id does the unravel (:118-123, C order), the three gathers and the pixel-centre ray.
 // Integer / gather work, a few hundred KB per batch: latency-bound, one launch is the whole optimisation.
-#include "evd_common.h"
+#include "ray_math.h"
 
 namespace evd {
 
@@ -33,11 +33,11 @@ __global__ __launch_bounds__(256) void k_image_batch(const long long* __restrict
 #pragma unroll
     for (int k = 0; k < 12; ++k) p[k] = c2w[k];
     // get_rays_pix on the integer pixel (utils/rays.py:25-36): the int64 coordinate meets a float scalar -> float32 arithmetic
-    const float d0 = ((float)x + hx) / k00, d1 = -((float)y + hy) / k11, d2 = -1.f;
+    const float d0 = ((float)x + hx) / k00, d1 = -((float)y + hy) / k11;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         rays[i * 6 + r * 2] = p[r * 4 + 3];
-        rays[i * 6 + r * 2 + 1] = __fadd_rn(__fadd_rn(__fmul_rn(d0, p[r * 4]), __fmul_rn(d1, p[r * 4 + 1])), __fmul_rn(d2, p[r * 4 + 2]));
+        rays[i * 6 + r * 2 + 1] = camera_ray_dir(d0, d1, p, r);
     }
     rays_x[i] = (float)x + 0.5f;                            // ray_x + HALF_PIX (:343-344)
     rays_y[i] = (float)y + 0.5f;

@@ -1,4 +1,5 @@
-// Shared between the tri-plane level's kernel units (kernel_voxel*.hip: kernels + launchers) and evd_voxel_api.hip (C ABI).
+// Shared between the tri-plane level's kernel units (kernel_voxel*.hip: kernels + launchers) and evd_voxel_api.hip (C ABI); also the one
+// place where the internal launchers of kernels_rays.hip / kernels_sample_pdf.hip that the c2f render calls are declared.
 #pragma once
 
 #include "evd_common.h"
@@ -65,10 +66,9 @@ struct TvJobs { TvJob j[6]; int n; };
 int launch_tv_level(TvJobs& jobs, double* partials /* job i at i * 2 * TV_MAX_BLOCKS */, TvShape* shape, hipStream_t st);
 int launch_tv_bwd_level(TvJobs& jobs, const float* d_loss, hipStream_t st);
 
-int launch_points(const float* rb, int nc, const float* z, long n, int S, float* pts, hipStream_t st);
-// evd_sample_z + the sample positions (kernels_render.hip)
+// evd_sample_z + the sample positions (kernels_rays.hip)
 int launch_sample_z_pts(const evd_render_cfg* cfg, const float* ray_batch, int ncol, long R, const float* t_rand, float* z, float* pts, hipStream_t stream);
-// evd_sample_pdf_merge + the positions o + d z of the new / of the merged samples (kernels_render.hip)
+// evd_sample_pdf_merge + the positions o + d z of the new / of the merged samples (kernels_sample_pdf.hip)
 int launch_sample_pdf_merge_pts(const float* z, const float* weights, long R, int S, int N, int det, const float* u,
                                 float* z_samples, float* z_merged, int* order, float* z_std,
                                 const float* rb, int rb_cols, float* pts_new, float* pts_merged, hipStream_t stream);

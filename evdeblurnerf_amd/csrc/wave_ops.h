@@ -1,10 +1,49 @@
-// Wave-level and row-level DPP primitives and the fast activations of the compositing scan (kernels_render.hip); the loss, AWP-scan,
-// MAM, AWP-tail and voxel kernels share the DPP scans and sums.
+// Wave-level and row-level primitives (64-wide wavefronts) and the fast activations of the compositing scan (kernels_composite.hip); the
+// loss, AWP-scan, MAM, AWP-tail and voxel kernels share the DPP scans and sums.
+//
+// Two families.  They associate the 64 terms differently, so a kernel that moves from one to the other changes the last bits of its sums:
+//   shuffle (__shfl_*, an LDS crossbar round trip per step): float64 values, which DPP does not move in one instruction, integer flag
+//            words, and the kernels that are not bound by the reduction (k_composite, k_points_bwd, k_sample_pdf_merge, k_numerics_flags)
+//   DPP     (lane exchange inside the VALU): the float32 scans and sums of the bandwidth-bound kernels
 #pragma once
 
 #include "evd_common.h"
 
 namespace evd {
+
+constexpr int WAVE = 64;
+
+// ------------------------------------------------------------------------------------------------
+// shuffle family: butterfly sums (the result in every lane) and Hillis-Steele inclusive scans
+template <class T>                       // float or double
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
+    return v;
+}
+// bitwise OR over the 64 lanes
+__device__ __forceinline__ unsigned wave_or(unsigned v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v |= __shfl_xor(v, off, WAVE);
+    return v;
+}
+// inclusive product scan over the 64 lanes
+__device__ __forceinline__ float wave_scan_mul(float v, int lane) {
+#pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) {
+        float o = __shfl_up(v, off, WAVE);
+        if (lane >= off) v *= o;
+    }
+    return v;
+}
+__device__ __forceinline__ double wave_scan_add_d(double v, int lane) {
+#pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) {
+        double o = __shfl_up(v, off, WAVE);
+        if (lane >= off) v += o;
+    }
+    return v;
+}
 
 // ------------------------------------------------------------------------------------------------
 // DPP (data-parallel primitive) wave operations: register-to-register lane exchange inside the VALU, no LDS
@@ -67,6 +106,13 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
            __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32)) +
            __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
 }
+// sum over the 64 lanes, valid in LANE 63 only (row sums, then the two row broadcasts of the scan): 6 DPP adds, no readlane
+__device__ __forceinline__ float wave_sum_to63(float v) {
+    v = row_sum_dpp(v);
+    v += dpp_f32<0x142, 0xa>(0.f, v);
+    v += dpp_f32<0x143, 0xc>(0.f, v);
+    return v;
+}
 
 // e^x on the hardware exp2 (v_exp_f32, 1 ulp) behind one multiply: relative error <= 1e-6 for |x| <= 16 against ~20 instructions of the
 // IEEE expf -- the AWP scans evaluate one exponential per (sample, channel) and were bound by the instruction count, not by HBM
@@ -80,6 +126,5 @@ __device__ __forceinline__ float act_fast(int code, float x) {
     if (code == EVD_ACT_NONE) return x;
     return act(code, x);
 }
-
 
 }  // namespace evd

@@ -6,7 +6,7 @@ Every function below is plain arithmetic on "numbers" that may be
   * float64 torch tensors               -> autograd.
 The formulas are those of the reference (utils/rays.py:8-36 camera model, :104-145 NDC warp; networks/renderer.py:423-446 ray packing;
 networks/embedding.py:88-98 positional encoding; networks/dpnerf/blurmodel.py:51-82 with utils/rigid_warping.py:18-49,72-132 the SE(3)
-exponential of the sub-exposure poses), in the operation order that the comments of csrc/kernels_render.hip state.  Vectors are lists of
+exponential of the sub-exposure poses), in the operation order that the comments of csrc/kernels_rays.hip and csrc/ray_math.h state.  Vectors are lists of
 components, so that nothing here depends on an array library's stacking; `cols` / fe_bound.stack go between the two forms.  Scalars that
 the reference holds as Python doubles and rounds to float32 when they meet a tensor (cw, ch, 2 near, 1e-10) are Python floats that are
 float32 numbers.
