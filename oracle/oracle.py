@@ -182,7 +182,7 @@ def embed(x, L):
 def nerf_mlp(net: Nerf, emb, want_after=False, want_before=False):
     emb = _f(emb)
     n = emb.shape[0]
-    raw = np.empty((n, 4 if net.s.use_viewdirs else net.s.output_ch), np.float32)
+    raw = np.empty((n, 4), np.float32)          # evo_nerf_mlp keeps channels 0..3 of an output_ch 4 or 5 head (evd_oracle.c)
     fa = np.empty((n, net.s.W), np.float32) if want_after else None
     fb = np.empty((n, net.s.W), np.float32) if want_before else None
     lib().evo_nerf_mlp(C.byref(net.s), _p(emb), C.c_long(n), _p(raw), _p(fa), _p(fb))

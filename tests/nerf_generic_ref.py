@@ -1,7 +1,9 @@
 """float64 torch restatement of NeRF.mlpforward + eval (networks/nerf.py:46-72,131-162, embedding.py:88-98) for any depth, width,
 frequency counts and skip index, and the cases of the generic training path's tests (tests/test_gpu_nerf_generic_train.py).  The
 restatement returns the pre-activation of every ReLU; it is pinned to the reference's real NeRF class by golden G40
-(tools/gen_golden_nerf_generic.py, tests/test_nerf_generic_ref.py).  Test infrastructure only."""
+(tools/gen_golden_nerf_generic.py, tests/test_nerf_generic_ref.py).  The same class, through optional arguments that leave the plain
+call untouched, is the reference of the inference pass's arm tests (tests/nerf_level_ref.py): the half-precision mode model, structural
+faults, the two feature outputs and the use_viewdirs=False head.  Test infrastructure only."""
 import functools
 
 import numpy as np
@@ -47,37 +49,122 @@ def positions(rb, z):
     return pts, dirs
 
 
-class GenericNerf(torch.nn.Module):
-    """NeRF.eval on embedded inputs, networks/nerf.py:131-162 with use_viewdirs: D layers of width W, `skip` = the one index of
-    `skips` (None: no skip; the reference concatenates AFTER layer `skip`, so the next layer is the wide one)"""
+QUANT = {"f16": torch.float16, "bf16": torch.bfloat16}
 
-    def __init__(self, sd, D, Wd, L, Lv, skip, prefix=""):
+
+def live_units(h):
+    """indices of the units of a post-ReLU activation [n, W] that are positive on at least a quarter of the samples, ascending"""
+    return torch.nonzero((h > 0).double().mean(0) >= 0.25).reshape(-1).tolist()
+
+
+def swap_pair(h):
+    """two live units of one 16-block whose activations differ, highest-indexed first; None if there are none"""
+    live = live_units(h)
+    for u in reversed(live):
+        for v in reversed(live):
+            if v < u and v // 16 == u // 16 and not torch.equal(h[:, u], h[:, v]):
+                return u, v
+    return None
+
+
+class GenericNerf(torch.nn.Module):
+    """NeRF.eval on embedded inputs, networks/nerf.py:131-162: D layers of width W, `skip` = the one index of `skips` (None: no skip; the
+    reference concatenates AFTER layer `skip`, so the next layer is the wide one).  use_viewdirs=False: `output_linear` replaces the view
+    branch (nerf.py:158-160), raw = its rows 0..3, dirs is not read.
+
+    forward() alone is the exact float64 network.  Its optional arguments serve tests/nerf_level_ref.py:
+      quant   "f16" / "bf16", the MODEL of the single-product half-precision modes: weights rounded to nearest in the type, the input of
+              every linear layer (both encodings, hidden activations after ReLU, the feature_linear output entering views_linears.0, the
+              views activation entering rgb_linear) rounded to nearest in the type, products and sums exact, biases float32 values added
+              in float64; raw and the feature rows that are OUTPUT are left unrounded.
+      fault   one structural fault, what a packing or column-map mistake produces (nerf_level_ref.faults_of lists those of a network).
+              A fault on a unit picks the highest-indexed live unit (live_units) of that activation, on this call's own samples.
+      out     a dict that receives "feature1" (the feature_linear output, extract_feature="after_linear"; None without the view branch),
+              "feature2" (h after the last pts_linears ReLU, "before_linear"; always [n, W]: a skip index of D-1 never concatenates),
+              "A" (the largest absolute output of any linear layer) and "unit" (what a unit fault picked, None where nothing was live)."""
+
+    def __init__(self, sd, D, Wd, L, Lv, skip, prefix="", use_viewdirs=True):
         super().__init__()
-        self.D, self.W, self.L, self.Lv, self.skip = D, Wd, L, Lv, skip
+        self.D, self.W, self.L, self.Lv, self.skip, self.use_viewdirs = D, Wd, L, Lv, skip, use_viewdirs
         self.p = torch.nn.ParameterDict({k[len(prefix):].replace(".", "_"): torch.nn.Parameter(torch.tensor(np.asarray(v), dtype=torch.float64))
                                          for k, v in sd.items() if k.startswith(prefix)})
 
-    def lin(self, name, x):
-        y = x @ self.p[name + "_weight"].T
-        return y + self.p[name + "_bias"] if name + "_bias" in self.p else y
+    def lin(self, name, x, quant=None, fault=None, rec=None):
+        w = self.p[name + "_weight"]
+        if quant is not None:
+            x, w = x.to(QUANT[quant]).double(), w.to(QUANT[quant]).double()
+        y = x @ w.T
+        if name + "_bias" in self.p and fault != "nobias_" + name:
+            y = y + self.p[name + "_bias"]
+        if rec is not None:
+            rec.append(float(y.detach().abs().max()))
+        return y
 
-    def forward(self, pts, dirs, pre=None):
+    @staticmethod
+    def _without(x, cols):
+        x = x.clone()
+        x[:, cols] = 0
+        return x
+
+    def _unit_fault(self, h, kind, out):
+        """hid: zero the highest-indexed live unit; swap: exchange two live units of one 16-block"""
+        if kind == "hid":
+            live = live_units(h)
+            pick = live[-1] if live else None
+            if pick is not None:
+                h = self._without(h, [pick])
+        else:
+            pick = swap_pair(h)
+            if pick is not None:
+                h = h.clone()
+                h[:, list(pick)] = h[:, list(pick[::-1])]
+        if out is not None:
+            out["unit"] = pick
+        return h
+
+    def forward(self, pts, dirs, pre=None, quant=None, fault=None, out=None):
         """raw [n, 4] = (rgb, alpha); pre: dict that receives the pre-activation of every ReLU ("h0" .. "h{D-1}", "hv")"""
-        pe, ped = embed(pts, self.L), embed(dirs, self.Lv)
-        h = pe
+        rec = [] if out is not None else None
+        lin = lambda name, x: self.lin(name, x, quant, fault.replace(".", "_") if fault else None, rec)     # "nobias_views_linears.0"
+        pe = embed(pts, self.L)
+        pe0 = self._without(pe, [-3, -2, -1]) if fault == "top_pts_cos" else pe
+        pe_skip = self._without(pe, [-3, -2, -1]) if fault == "skip_top_cos" else pe
+        h = pe0
         for l in range(self.D):
-            x = self.lin(f"pts_linears_{l}", h)
+            x = lin(f"pts_linears_{l}", h)
             if pre is not None:
                 pre[f"h{l}"] = x
             h = torch.relu(x)
+            if fault in (f"hid{l}", f"swap{l}"):
+                h = self._unit_fault(h, fault[:-len(str(l))], out)
             if self.skip is not None and l == self.skip and l < self.D - 1:
-                h = torch.cat([pe, h], -1)
-        alpha = self.lin("alpha_linear", h)
-        f = self.lin("feature_linear", h)
-        x = self.lin("views_linears_0", torch.cat([f, ped], -1))
+                h = torch.cat([pe_skip, h], -1)
+        if out is not None:
+            out["feature2"] = torch.roll(h, 1, 1) if fault == "feat_roll" else h
+        if not self.use_viewdirs:
+            raw = lin("output_linear", h)[:, :4]
+            if fault == "out_swap":
+                raw = raw[:, [0, 1, 3, 2]]
+            if out is not None:
+                out["feature1"], out["A"] = None, max(rec)
+            return raw
+        ped = embed(dirs, self.Lv)
+        if fault == "top_dir_cos":
+            ped = self._without(ped, [-3, -2, -1])
+        alpha = lin("alpha_linear", h)
+        f = lin("feature_linear", h)
+        if out is not None:
+            out["feature1"] = torch.roll(f, 1, 1) if fault == "feat_roll" else f
+        x = lin("views_linears_0", torch.cat([self._without(f, [-1]) if fault == "last_feat" else f, ped], -1))
         if pre is not None:
             pre["hv"] = x
-        return torch.cat([self.lin("rgb_linear", torch.relu(x)), alpha], -1)
+        hv = torch.relu(x)
+        if fault == "last_hv":
+            hv = self._unit_fault(hv, "hid", out)
+        raw = torch.cat([lin("rgb_linear", hv), alpha], -1)
+        if out is not None:
+            out["A"] = max(rec)
+        return raw
 
 
 def case_net(name, sd=None):
