@@ -47,7 +47,7 @@ class NerfGrads(C.Structure):
 
 
 class VoxelGrads(C.Structure):
-    _fields_ = [("sigma_w", _vp * 2), ("color_w", _vp * 3), ("color_b", _vp * 3), ("accumulate", C.c_int)]
+    _fields_ = [("sigma_w", _vp * 4), ("color_w", _vp * 4), ("color_b", _vp * 4), ("accumulate", C.c_int)]
 
 
 class AwpEmbedGrads(C.Structure):
@@ -201,6 +201,7 @@ SIGNATURES = {
     "evd_voxel_train_store_bytes": (_S, [_vp, _L]),
     "evd_voxel_train_store_bytes_prec": (_S, [_vp, _I, _L]),
     "evd_voxel_backward_workspace_bytes": (_S, []),
+    "evd_voxel_backward_workspace_bytes_net": (_S, [_vp, _I]),
     "evd_voxel_mlp_train": (_I, [_vp, _I, _vp, _vp, _I, _vp, _I, _L, _I, _vp, _vp, _vp, _S, _vp]),
     "evd_voxel_geo_feat_dim": (_I, [_vp]),
     "evd_voxel_mlp_backward": (_I, [_vp, _I, _vp, _vp, _vp, _vp, _S, _L, _I, _vp, _S, C.POINTER(VoxelGrads), _vp, _I, _vp, _vp, _I, _vp, _vp, _vp, _S, _vp]),
@@ -234,6 +235,7 @@ SIGNATURES = {
     "evd_voxel_forward": (_I, [_vp, _I, _vp, _vp, _I, _vp, _I, _vp, _vp, _I, _L, _I, _I,
                                _vp, _vp, _vp, _vp, _vp, _vp, _S, _vp]),
     "evd_voxel_forward_workspace_bytes": (_S, [_vp, _L, _I]),
+    "evd_voxel_mlp": (_I, [_vp, _I, _vp, _vp, _I, _vp, _I, _L, _I, _vp, _vp, _vp]),
     "evd_c2f_render_workspace_bytes": (_S, [_vp, _vp, C.POINTER(RenderCfg), _L]),
     "evd_c2f_render_rays": (_I, [_vp, _vp, C.POINTER(RenderCfg), _vp, _L, _vp, _vp, _vp, _vp,
                                  C.POINTER(RenderOut), _vp, _S, _vp]),

@@ -86,6 +86,9 @@ class _SampleEmbed(torch.autograd.Function):
         if geo is not None:
             n, rows, dev = geo.R * geo.S, None, geo.store.device
         else:
+            if src.shape[-1] != embed.input_ch:
+                raise L.EvdError(f"the AWP sample embedding reads {embed.input_ch} geo channels per sample (fine_geo_feat_dim of the shipped "
+                                 f"configurations), the rows given have {src.shape[-1]}: a fine level of another geo width cannot feed it")
             rows = src.reshape(-1, embed.input_ch).contiguous().float()
             n, dev = rows.shape[0], rows.device
         nb = int(lib.evd_awp_embed_store_bytes(embed._h, n))

@@ -4,6 +4,8 @@
 #include "nerf_mlp.h"
 #include "pack.h"
 #include "voxel.h"
+#include "voxel_generic.h"
+#include "nerf_train_generic.h"
 #include "voxel_mlp_kernel.h"
 #include "voxel_train.h"
 #include "awp_embed.h"
@@ -13,7 +15,7 @@
 #include <cstdlib>
 
 // the PDRF level networks keep packed streams for the first four arithmetic modes; EVD_PREC_F16C (compensated float16) has its own
-// stream (pipe_c) on the fine level; the 64-wide coarse level runs EVD_PREC_F16X3 next to it
+// stream (pipe_c) on the standard fine level; every other level runs EVD_PREC_F16X3 next to it
 #define EVD_VOX_NUM_PREC EVD_PREC_F16C
 
 using namespace evd;
@@ -36,7 +38,16 @@ struct evd_voxel {
     mutable DevBuf arena_dev;
     mutable bool pipe_c_stale = false;
     DevBuf cnet;                  // composite_feature levels: color_net.{0,1,2}.{weight,bias} as float32 in the reference layouts (k_color_rows)
-    long param_off[9];            // sigma_net.0, sigma_net.1, color_net.{0,1,2}.{weight,bias} in the parameter arena, [8] = total
+    // sigma_net.0 .. num_layers-1, then color_net.l.{weight,bias} in the parameter arena, [nblk] = total (a standard level: 8 blocks)
+    long param_off[VG_MAX_LAYERS + 2 * VG_MAX_LAYERS + 1];
+    int nblk;
+    // a level of any other shape than the two standard ones (voxel_generic.h): `stream` holds the layout of kernel_voxel_generic.hip in every
+    // mode, fwd / bwd / pipe_c stay empty; params_f32 is the float32 copy of the parameters its training backward reads in place
+    bool generic = false;
+    DevBuf params_f32;
+    int sigma_blk(int l) const { return l; }
+    int color_w_blk(int l) const { return num_layers + 2 * l; }
+    int color_b_blk(int l) const { return num_layers + 2 * l + 1; }
     GridParams gp;
     RepackBatch batch;            // table of every fragment stream, for the one-launch re-pack of evd_voxel_load_params
     mutable SideStream side;      // backward entry: wgrad side stream of THIS handle (created on first use)
@@ -44,10 +55,12 @@ struct evd_voxel {
 
 static const int kMat0[3] = {0, 0, 1}, kMat1[3] = {1, 2, 2}, kVec[3] = {2, 1, 0};
 
-// Where voxel_level_forward can take the generic kernel, i.e. which levels and modes need `stream`: a mode or an encoding without a pipelined
-// stream (EVD_PREC_F32, non-standard multires / multires_views), and the 64-wide level in every mode: for per-sample feature rows (also
-// the geo rows of a composite_feature level) it has no other kernel.  The fine level's pipelined kernels write those rows themselves.
-static bool has_generic_stream(bool piped, int hidden_dim) { return !piped || hidden_dim == 64; }
+// Where voxel_level_forward can take k_voxel_mlp on a STANDARD level, i.e. which levels and modes need its `stream`: a mode or an encoding
+// without a pipelined stream (EVD_PREC_F32, non-standard multires / multires_views), and the standard coarse level (64/15/32) in every mode:
+// for per-sample feature rows (also the geo rows of a composite_feature level) it has no other kernel.  The standard fine level's pipelined
+// kernels write those rows themselves.
+static bool std_coarse(const evd_voxel* v) { return !v->generic && v->hidden_dim == 64; }
+static bool has_generic_stream(bool piped, bool coarse) { return !piped || coarse; }
 
 extern "C" {
 
@@ -59,7 +72,7 @@ void evd_voxel_destroy(evd_voxel* v) {
         for (int k = 0; k < VBWD_NSTREAMS; ++k) v->bwd[i][k].release();
     }
     v->basis.release(); v->bias.release(); v->bias_src.release(); v->tv_acc.release(); v->wmaps.release();
-    v->pipe_c.release(); v->arena_dev.release(); v->cnet.release();
+    v->pipe_c.release(); v->arena_dev.release(); v->cnet.release(); v->params_f32.release();
     v->side.release();
     v->batch.release();
     delete v;
@@ -74,19 +87,29 @@ int evd_voxel_create(const evd_voxel_desc* d, evd_voxel** out) {
                 "evd_voxel_create: multires %d / multires_views %d out of range (0..%d / 0..%d)", d->multires, d->multires_views, PE_L_MAX, PE_LV);
     const int L = d->multires, Lv = d->multires_views;
     const bool standard = L == PE_L && Lv == PE_LV;
-    EVD_REQUIRE(d->num_layers == 2 && d->num_layers_color == 3, "evd_voxel_create: only 2 sigma + 3 colour layers are built (all shipped configs)");
+    const int NS = d->num_layers, NC = d->num_layers_color;
+    EVD_REQUIRE(NS >= 1 && NS <= VG_MAX_LAYERS && NC >= 1 && NC <= VG_MAX_LAYERS,
+                "evd_voxel_create: num_layers %d / num_layers_color %d out of range (1..%d each)", NS, NC, VG_MAX_LAYERS);
     const int IC = 3 * (1 + 2 * L), ICV = 3 * (1 + 2 * Lv);
     const int FT = d->input_ch - IC, HD = d->hidden_dim, G = d->geo_feat_dim;
-    EVD_REQUIRE((HD == 64 && G == 15 && FT == 32) || (HD == 256 && G == 128 && FT == 64),
-                "evd_voxel_create: (hidden %d, geo %d, features %d) not built: coarse 64/15/32 or fine 256/128/64", HD, G, FT);
+    EVD_REQUIRE((HD == 64 || HD == 128 || HD == 256) && G >= 1 && G <= 32 * VG_GT && FT >= 16 && FT <= 16 * VG_KF && FT % 16 == 0,
+                "evd_voxel_create: (hidden %d, geo %d, features %d) not built: hidden_dim 64, 128 or 256, geo_feat_dim 1..%d, "
+                "input_ch - 3 (1 + 2 multires) a multiple of 16 in 16..%d", HD, G, FT, 32 * VG_GT, 16 * VG_KF);
+    const bool generic = !voxel_standard_shape(NS, NC, HD, G, FT);
+    EVD_REQUIRE(!generic || !d->composite_feature,
+                "evd_voxel_create: composite_feature (kernel_type PBE) is built for the standard levels only (64/15/32 and 256/128/64 with 2 + 3 "
+                "layers): its per-ray colour network is three layers");
     const int ctot = d->n_comp[0] + d->n_comp[1] + d->n_comp[2];
     EVD_REQUIRE(ctot <= 128 && d->n_comp[0] % 4 == 0 && d->n_comp[1] % 4 == 0 && d->n_comp[2] % 4 == 0 && d->app_dim <= 64,
                 "evd_voxel_create: n_comp must be multiples of 4 with sum <= 128, app_dim <= 64");
     for (int i = 0; i < 3; ++i) EVD_REQUIRE(d->plane[i] && d->line[i] && d->grid[i] >= 1, "evd_voxel_create: missing grid %d", i);
-    EVD_REQUIRE(d->basis && d->sigma_w[0] && d->sigma_w[1] && d->color_w[0] && d->color_w[1] && d->color_w[2], "evd_voxel_create: missing weights");
+    EVD_REQUIRE(d->basis, "evd_voxel_create: missing weights");
+    for (int l = 0; l < NS; ++l) EVD_REQUIRE(d->sigma_w[l], "evd_voxel_create: missing weights (sigma_net.%d)", l);
+    for (int l = 0; l < NC; ++l) EVD_REQUIRE(d->color_w[l], "evd_voxel_create: missing weights (color_net.%d)", l);
 
     evd_voxel* v = new evd_voxel();
-    v->num_layers = 2; v->hidden_dim = HD; v->geo = G; v->num_layers_color = 3; v->input_ch = d->input_ch; v->ft_dim = FT;
+    v->num_layers = NS; v->hidden_dim = HD; v->geo = G; v->num_layers_color = NC; v->input_ch = d->input_ch; v->ft_dim = FT;
+    v->generic = generic; v->nblk = NS + 2 * NC;
     v->app_dim = d->app_dim; v->app_act = d->app_act; v->rgb_act = d->rgb_act; v->sigma_act = d->sigma_act;
     v->composite_feature = d->composite_feature ? 1 : 0; v->rmnear = d->rmnear;
     v->multires = L; v->multires_views = Lv;
@@ -130,169 +153,234 @@ int evd_voxel_create(const evd_voxel_desc* d, evd_voxel** out) {
     g.basis = (const float*)v->basis.p; g.app_dim = d->app_dim; g.app_act = d->app_act;
 
     // weight streams (order = kernel_voxel.hip k_voxel_mlp).  The parameters are first copied into one host arena in the
-    // canonical order sigma_net.0, sigma_net.1, color_net.{0,1,2}.{weight,bias}; every packed element records its arena index so that
-    // evd_voxel_load_params can re-pack on the device (pack.h).
+    // canonical order sigma_net.0 .., then color_net.l.{weight,bias} (a standard level: sigma_net.0, sigma_net.1,
+    // color_net.{0,1,2}.{weight,bias}); every packed element records its arena index so that evd_voxel_load_params can re-pack on the
+    // device (pack.h).  Layer shapes: voxnerf.py:48-82 (the colour network's hidden width is hidden_dim, :73,78).
     const int T = HD / 32, KS = HD / 16, KF = FT / 16;
-    const long psz[8] = {(long)HD * d->input_ch, (long)(1 + G) * HD, (long)HD * (G + ICV), HD, (long)HD * HD, HD, 3L * HD, 3};
-    long total = 0;
-    for (int i = 0; i < 8; ++i) { v->param_off[i] = total; total += psz[i]; }
-    v->param_off[8] = total;
-    std::vector<float> arena((size_t)total, 0.f);
-    {
-        const float* srcs[8] = {d->sigma_w[0], d->sigma_w[1], d->color_w[0], d->color_b[0], d->color_w[1], d->color_b[1], d->color_w[2], d->color_b[2]};
-        for (int i = 0; i < 8; ++i)
-            if (srcs[i]) memcpy(arena.data() + v->param_off[i], srcs[i], psz[i] * sizeof(float));
+    const int nblk = v->nblk;
+    long psz[VG_MAX_LAYERS + 2 * VG_MAX_LAYERS];
+    const float* srcs[VG_MAX_LAYERS + 2 * VG_MAX_LAYERS];
+    for (int l = 0; l < NS; ++l) {
+        psz[v->sigma_blk(l)] = (long)(l == NS - 1 ? 1 + G : HD) * (l == 0 ? d->input_ch : HD);
+        srcs[v->sigma_blk(l)] = d->sigma_w[l];
     }
+    for (int l = 0; l < NC; ++l) {
+        const long out = l == NC - 1 ? 3 : HD;
+        psz[v->color_w_blk(l)] = out * (l == 0 ? G + ICV : HD);
+        psz[v->color_b_blk(l)] = out;
+        srcs[v->color_w_blk(l)] = d->color_w[l];
+        srcs[v->color_b_blk(l)] = d->color_b[l];
+    }
+    long total = 0;
+    for (int i = 0; i < nblk; ++i) { v->param_off[i] = total; total += psz[i]; }
+    v->param_off[nblk] = total;
+    std::vector<float> arena((size_t)total, 0.f);
+    for (int i = 0; i < nblk; ++i)
+        if (srcs[i]) memcpy(arena.data() + v->param_off[i], srcs[i], psz[i] * sizeof(float));
     if (v->composite_feature) {       // the colour network runs per RAY on the composited features (voxnerf.py:231-239): plain float32 rows
-        rc = v->cnet.upload(arena.data() + v->param_off[2], (size_t)(v->param_off[8] - v->param_off[2]) * sizeof(float));
+        rc = v->cnet.upload(arena.data() + v->param_off[NS], (size_t)(v->param_off[nblk] - v->param_off[NS]) * sizeof(float));
         if (rc) { evd_voxel_destroy(v); return rc; }
     }
     const float* A = arena.data();
-    const float *sigma_w0 = A + v->param_off[0], *sigma_w1 = A + v->param_off[1], *color_w0 = A + v->param_off[2], *color_w1 = A + v->param_off[4],
-                *color_w2 = A + v->param_off[6];
-    const bool small = (1 + G) <= 32;
-    const int GT = (G + 31) / 32, GK = 2 * GT;
-    auto hid_col = [](int j, int kk) { return 16 * j + phi(kk); };
-    auto in0_col = [&](int j, int kk) {            // cat([fts, PE(pts)]): natural feature k-steps then the PE arrangement
-        if (j < KF) return 16 * j + kk;
-        const int c = pe_src_col(L, 8 * (j - KF) + (kk & 7), kk >> 3);
-        return c < 0 ? -1 : FT + c;
+    // A generic level (voxel_generic.h): the layer table of kernel_voxel_generic.hip in every mode; no pipelined, f16c or training streams
+    auto generic_streams = [&]() -> int {
+            const int GTg = (G + 31) / 32;
+            auto hid_col = [](int j, int kk) { return 16 * j + phi(kk); };
+            auto in0_col = [&](int j, int kk) {            // cat([fts, PE(pts)]): VG_KF natural feature k-steps (absent channels: zero), then the PE arrangement
+                if (j < VG_KF) return 16 * j + kk < FT ? 16 * j + kk : -1;
+                const int c = pe_src_col(L, 8 * (j - VG_KF) + (kk & 7), kk >> 3);
+                return c < 0 ? -1 : FT + c;
+            };
+            auto c0_col = [&](int j, int kk) {             // cat([h[..., 1:], PE(dirs)]) voxnerf.py:248: VG_GK geo k-steps, then the PE arrangement
+                if (j < VG_GK) { const int c = 16 * j + phi(kk); return c < G ? c : -1; }
+                const int c = pe_src_col(Lv, 8 * (j - VG_GK) + (kk & 7), kk >> 3);
+                return c < 0 ? -1 : G + c;
+            };
+            auto W_sig = [&](int l) { return A + v->param_off[v->sigma_blk(l)]; };
+            auto W_col = [&](int l) { return A + v->param_off[v->color_w_blk(l)]; };
+            auto build_generic = [&](StreamBuilder& sb) {
+                for (int l = 0; l + 1 < NS; ++l) {
+                    if (l == 0) sb.layer(W_sig(0), HD, d->input_ch, T, VG_KF + PE_KS, true, in0_col);
+                    else sb.layer(W_sig(l), HD, HD, T, KS, true, hid_col);
+                }
+                {   // the last sigma layer: the density row, then the geo rows in 32-channel tiles
+                    const float* Wl = W_sig(NS - 1);
+                    const int in_dim = NS == 1 ? d->input_ch : HD, ks = NS == 1 ? VG_KF + PE_KS : KS;
+                    auto sig_row = [](int, int r) { return r == 0 ? 0 : -1; };
+                    if (NS == 1) sb.layer_rc(Wl, in_dim, 1, ks, true, sig_row, in0_col);
+                    else sb.layer_rc(Wl, in_dim, 1, ks, true, sig_row, hid_col);
+                    for (int t = 0; t < GTg; ++t) {
+                        auto geo_row = [G, t](int, int r) { return 32 * t + r < G ? 1 + 32 * t + r : -1; };
+                        if (NS == 1) sb.layer_rc(Wl, in_dim, 1, ks, true, geo_row, in0_col);
+                        else sb.layer_rc(Wl, in_dim, 1, ks, true, geo_row, hid_col);
+                    }
+                }
+                for (int l = 0; l < NC; ++l) {
+                    const int out = l == NC - 1 ? 3 : HD, tiles = l == NC - 1 ? 1 : T;
+                    if (l == 0) sb.layer(W_col(0), out, G + ICV, tiles, VG_GK + PEV_KS, true, c0_col);
+                    else sb.layer(W_col(l), out, HD, tiles, KS, true, hid_col);
+                }
+            };
+            for (int prec = 0; prec < EVD_VOX_NUM_PREC; ++prec) {
+                v->nchunks[prec] = v->fwd_chunks[prec] = 0;
+                StreamBuilder sb(prec);
+                sb.arena = A;
+                build_generic(sb);
+                v->nchunks[prec] = (int)(sb.bytes.size() / chunk_bytes(prec));
+                if ((rc = v->stream[prec].upload(sb))) return rc;
+            }
+        return v->params_f32.upload(A, (size_t)total * sizeof(float));
     };
-    auto c0_col = [&](int j, int kk) {             // cat([h[...,1:], PE(dirs)]) voxnerf.py:248
-        const int gk = small ? 1 : G / 16;
-        if (j < gk) {
-            const int row = 16 * j + phi(kk);      // index into the sigma-layer output tile(s)
-            return small ? (row >= 1 && row <= G ? row - 1 : -1) : row;
-        }
-        const int c = pe_src_col(Lv, 8 * (j - gk) + (kk & 7), kk >> 3);
-        return c < 0 ? -1 : G + c;
-    };
-    auto build = [&](StreamBuilder& sb) {
-        sb.layer(sigma_w0, HD, d->input_ch, T, KF + PE_KS, false, in0_col);
-        if (small) {
-            sb.layer(sigma_w1, 1 + G, HD, 1, KS, false, hid_col);
-        } else {
-            sb.layer_rc(sigma_w1, HD, 1, KS, false, [](int, int r) { return r == 0 ? 0 : -1; }, hid_col);       // sigma row
-            sb.layer_rc(sigma_w1, HD, G / 32, KS, false, [](int t, int r) { return 1 + 32 * t + r; }, hid_col); // geo rows
-        }
-        sb.layer(color_w0, HD, G + ICV, T, (small ? 1 : G / 16) + PEV_KS, false, c0_col);
-        sb.layer(color_w1, HD, HD, T, KS, false, hid_col);
-        sb.layer(color_w2, 3, HD, 1, KS, true, hid_col);
-    };
-    // the same network in the layer table of voxel_mlp_kernel.h VoxNet (any level): sigma and geo always separate layers, the
-    // geo channels in GT zero-padded tiles
-    auto build_pipe = [&](StreamBuilder& sb) {
-        auto c0p = [&](int j, int kk) {
-            if (j < GK) { const int c = 16 * j + phi(kk); return c < G ? c : -1; }
-            const int c = pe_src_col(Lv, 8 * (j - GK) + (kk & 7), kk >> 3);
+    // A standard level: the streams of k_voxel_mlp, of the pipelined / resident / f16c kernels and of the training backward, and the wgrad index maps
+    auto standard_streams = [&]() -> int {
+        const float *sigma_w0 = A + v->param_off[0], *sigma_w1 = A + v->param_off[1], *color_w0 = A + v->param_off[2], *color_w1 = A + v->param_off[4],
+                    *color_w2 = A + v->param_off[6];
+        const bool small = (1 + G) <= 32;
+        const int GT = (G + 31) / 32, GK = 2 * GT;
+        auto hid_col = [](int j, int kk) { return 16 * j + phi(kk); };
+        auto in0_col = [&](int j, int kk) {            // cat([fts, PE(pts)]): natural feature k-steps then the PE arrangement
+            if (j < KF) return 16 * j + kk;
+            const int c = pe_src_col(L, 8 * (j - KF) + (kk & 7), kk >> 3);
+            return c < 0 ? -1 : FT + c;
+        };
+        auto c0_col = [&](int j, int kk) {             // cat([h[...,1:], PE(dirs)]) voxnerf.py:248
+            const int gk = small ? 1 : G / 16;
+            if (j < gk) {
+                const int row = 16 * j + phi(kk);      // index into the sigma-layer output tile(s)
+                return small ? (row >= 1 && row <= G ? row - 1 : -1) : row;
+            }
+            const int c = pe_src_col(Lv, 8 * (j - gk) + (kk & 7), kk >> 3);
             return c < 0 ? -1 : G + c;
         };
-        sb.layer(sigma_w0, HD, d->input_ch, T, KF + PE_KS, false, in0_col);
-        sb.layer_rc(sigma_w1, HD, 1, KS, false, [](int, int r) { return r == 0 ? 0 : -1; }, hid_col);
-        sb.layer_rc(sigma_w1, HD, GT, KS, false, [G](int t, int r) { return 32 * t + r < G ? 1 + 32 * t + r : -1; }, hid_col);
-        sb.layer(color_w0, HD, G + ICV, T, GK + PEV_KS, false, c0p);
-        sb.layer(color_w1, HD, HD, T, KS, false, hid_col);
-        sb.layer(color_w2, 3, HD, 1, KS, true, hid_col);
-    };
-    for (int prec = 0; prec < EVD_VOX_NUM_PREC; ++prec) {
-        const bool piped = standard && is_train_prec(prec);
-        v->nchunks[prec] = v->fwd_chunks[prec] = 0;
-        if (has_generic_stream(piped, HD)) {
-            StreamBuilder sb(prec);
-            sb.arena = A;
-            build(sb);
-            v->nchunks[prec] = (int)(sb.bytes.size() / chunk_bytes(prec));
-            if ((rc = v->stream[prec].upload(sb))) { evd_voxel_destroy(v); return rc; }
-        }
-        if (!piped) continue;
-        {   // same layers, single-tile groups, 16 KiB chunks (voxel_mlp_kernel.h): render and training forward
-            StreamBuilder sp(prec, PIPE_CB);
-            sp.arena = A;
-            sp.group = 1;
-            build_pipe(sp);
-            v->fwd_chunks[prec] = (int)(sp.bytes.size() / PIPE_CB);
-            if ((rc = v->fwd[prec].upload(sp))) { evd_voxel_destroy(v); return rc; }
-        }
-        // the W^T streams of the dgrad chain (voxel_train_kernel.h)
-        auto put = [&](int which, auto fill) {
-            StreamBuilder sb2(prec, PIPE_CB);
-            sb2.arena = A;
-            sb2.group = 1;
-            fill(sb2);
-            return v->bwd[prec][which].upload(sb2);
+        auto build = [&](StreamBuilder& sb) {
+            sb.layer(sigma_w0, HD, d->input_ch, T, KF + PE_KS, false, in0_col);
+            if (small) {
+                sb.layer(sigma_w1, 1 + G, HD, 1, KS, false, hid_col);
+            } else {
+                sb.layer_rc(sigma_w1, HD, 1, KS, false, [](int, int r) { return r == 0 ? 0 : -1; }, hid_col);       // sigma row
+                sb.layer_rc(sigma_w1, HD, G / 32, KS, false, [](int t, int r) { return 1 + 32 * t + r; }, hid_col); // geo rows
+            }
+            sb.layer(color_w0, HD, G + ICV, T, (small ? 1 : G / 16) + PEV_KS, false, c0_col);
+            sb.layer(color_w1, HD, HD, T, KS, false, hid_col);
+            sb.layer(color_w2, 3, HD, 1, KS, true, hid_col);
         };
-        rc = put(VBWD_C2, [&](StreamBuilder& b) { b.layer_transposed(color_w2, 3, HD, 0, HD, nullptr, 0, T, 1, true, [](int, int kk) { return kk < 3 ? kk : -1; }); });
-        if (!rc) rc = put(VBWD_C1, [&](StreamBuilder& b) { b.layer_transposed(color_w1, HD, HD, 0, HD, nullptr, 0, T, KS, true, hid_col); });
-        // rows of an encoding appended to a W^T layer: output row idx of the extra tiles <-> encoding column, so that the output
-        // fragments come out in the encoding's own arrangement (fragment j, position kk <-> pe_src_col(L, 8 j + (kk & 7), kk >> 3))
-        auto enc_row = [](int L_, int idx) { const int j = idx / 16, kk = phi_inv(idx % 16); return pe_src_col(L_, 8 * j + (kk & 7), kk >> 3); };
-        if (!rc) rc = put(VBWD_C0, [&](StreamBuilder& b) {       // [geo rows | direction-encoding rows] of color_net.0
-            b.layer_at(GT + 1, KS, true,
-                       [&](int t, int r) { if (t < GT) return 32 * t + r < G ? 32 * t + r : -1; const int c = enc_row(Lv, r); return c < 0 ? -1 : G + c; },
-                       hid_col, [&](int r, int c) { return color_w0 + (size_t)c * (G + ICV) + r; });
-        });
-        if (!rc) rc = put(VBWD_SIGGEO, [&](StreamBuilder& b) {
-            b.layer_transposed(sigma_w1, 1 + G, HD, 0, HD, nullptr, 0, T, GK + 1, true, [&](int j, int kk) {
-                if (j < GK) { const int c = 16 * j + phi(kk); return c < G ? 1 + c : -1; }
-                return kk == 0 ? 0 : -1;
+        // the same network in the layer table of voxel_mlp_kernel.h VoxNet (any level): sigma and geo always separate layers, the
+        // geo channels in GT zero-padded tiles
+        auto build_pipe = [&](StreamBuilder& sb) {
+            auto c0p = [&](int j, int kk) {
+                if (j < GK) { const int c = 16 * j + phi(kk); return c < G ? c : -1; }
+                const int c = pe_src_col(Lv, 8 * (j - GK) + (kk & 7), kk >> 3);
+                return c < 0 ? -1 : G + c;
+            };
+            sb.layer(sigma_w0, HD, d->input_ch, T, KF + PE_KS, false, in0_col);
+            sb.layer_rc(sigma_w1, HD, 1, KS, false, [](int, int r) { return r == 0 ? 0 : -1; }, hid_col);
+            sb.layer_rc(sigma_w1, HD, GT, KS, false, [G](int t, int r) { return 32 * t + r < G ? 1 + 32 * t + r : -1; }, hid_col);
+            sb.layer(color_w0, HD, G + ICV, T, GK + PEV_KS, false, c0p);
+            sb.layer(color_w1, HD, HD, T, KS, false, hid_col);
+            sb.layer(color_w2, 3, HD, 1, KS, true, hid_col);
+        };
+        for (int prec = 0; prec < EVD_VOX_NUM_PREC; ++prec) {
+            const bool piped = standard && is_train_prec(prec);
+            v->nchunks[prec] = v->fwd_chunks[prec] = 0;
+            if (has_generic_stream(piped, std_coarse(v))) {
+                StreamBuilder sb(prec);
+                sb.arena = A;
+                build(sb);
+                v->nchunks[prec] = (int)(sb.bytes.size() / chunk_bytes(prec));
+                if ((rc = v->stream[prec].upload(sb))) return rc;
+            }
+            if (!piped) continue;
+            {   // same layers, single-tile groups, 16 KiB chunks (voxel_mlp_kernel.h): render and training forward
+                StreamBuilder sp(prec, PIPE_CB);
+                sp.arena = A;
+                sp.group = 1;
+                build_pipe(sp);
+                v->fwd_chunks[prec] = (int)(sp.bytes.size() / PIPE_CB);
+                if ((rc = v->fwd[prec].upload(sp))) return rc;
+            }
+            // the W^T streams of the dgrad chain (voxel_train_kernel.h)
+            auto put = [&](int which, auto fill) {
+                StreamBuilder sb2(prec, PIPE_CB);
+                sb2.arena = A;
+                sb2.group = 1;
+                fill(sb2);
+                return v->bwd[prec][which].upload(sb2);
+            };
+            rc = put(VBWD_C2, [&](StreamBuilder& b) { b.layer_transposed(color_w2, 3, HD, 0, HD, nullptr, 0, T, 1, true, [](int, int kk) { return kk < 3 ? kk : -1; }); });
+            if (!rc) rc = put(VBWD_C1, [&](StreamBuilder& b) { b.layer_transposed(color_w1, HD, HD, 0, HD, nullptr, 0, T, KS, true, hid_col); });
+            // rows of an encoding appended to a W^T layer: output row idx of the extra tiles <-> encoding column, so that the output
+            // fragments come out in the encoding's own arrangement (fragment j, position kk <-> pe_src_col(L, 8 j + (kk & 7), kk >> 3))
+            auto enc_row = [](int L_, int idx) { const int j = idx / 16, kk = phi_inv(idx % 16); return pe_src_col(L_, 8 * j + (kk & 7), kk >> 3); };
+            if (!rc) rc = put(VBWD_C0, [&](StreamBuilder& b) {       // [geo rows | direction-encoding rows] of color_net.0
+                b.layer_at(GT + 1, KS, true,
+                           [&](int t, int r) { if (t < GT) return 32 * t + r < G ? 32 * t + r : -1; const int c = enc_row(Lv, r); return c < 0 ? -1 : G + c; },
+                           hid_col, [&](int r, int c) { return color_w0 + (size_t)c * (G + ICV) + r; });
             });
-        });
-        if (!rc) rc = put(VBWD_L0, [&](StreamBuilder& b) {       // [feature rows | point-encoding rows] of sigma_net.0
-            const int FTT = (FT + 31) / 32, in_dim = d->input_ch;
-            b.layer_at(FTT + 2, KS, true,
-                       [&](int t, int r) { if (t < FTT) return 32 * t + r < FT ? 32 * t + r : -1; const int c = enc_row(L, 32 * (t - FTT) + r); return c < 0 ? -1 : FT + c; },
-                       hid_col, [&](int r, int c) { return sigma_w0 + (size_t)c * in_dim + r; });
-        });
-        if (rc) { evd_voxel_destroy(v); return rc; }
-    }
-    if (standard && voxel_mlp_c_chunks(HD, G, FT) > 0) {     // compensated float16 mode: the layer table of voxel_mlp_c_kernel.h VoxNetC (groups of two tiles, 64-input blocks)
-        auto c0p = [&](int j, int kk) {
-            if (j < GK) { const int c = c_hid_col(j, kk); return c < G ? c : -1; }
-            const int c = pe_src_col(Lv, 8 * (j - GK) + (kk & 7), kk >> 3);
-            return c < 0 ? -1 : G + c;
-        };
-        auto sig_at = [=](int r, int c) -> const float* { return c < HD ? sigma_w1 + (size_t)r * HD + c : nullptr; };
-        StreamBuilderC sc(PIPE_CB);
-        sc.arena = A;
-        sc.layer(sigma_w0, HD, d->input_ch, T, KF + PE_KS, 2, in0_col);
-        sc.layer_at(1, KS, 1, [](int, int r) { return r == 0 ? 0 : -1; }, c_hid_col, sig_at);
-        sc.layer_at(GT, KS, 2, [G](int t, int r) { return 32 * t + r < G ? 1 + 32 * t + r : -1; }, c_hid_col, sig_at);
-        sc.layer(color_w0, HD, G + ICV, T, GK + PEV_KS, 2, c0p);
-        sc.layer(color_w1, HD, HD, T, KS, 2, c_hid_col);
-        sc.layer(color_w2, 3, HD, 1, KS, 1, c_hid_col);
-        v->pipe_c_chunks = (int)(sc.bytes.size() / PIPE_CB);
-        if (v->pipe_c_chunks != voxel_mlp_c_chunks(HD, G, FT))
-            rc = fail(EVD_E_INVALID, "evd_voxel_create: f16c stream has %d chunks, kernel expects %d", v->pipe_c_chunks, voxel_mlp_c_chunks(HD, G, FT));
-        if (!rc) rc = v->pipe_c.upload(sc);
-        if (rc) { evd_voxel_destroy(v); return rc; }
-    }
-    {   // wgrad index maps (voxel_train.h)
-        std::vector<int> m(VMAP_TOTAL, -1);
-        for (int i = 0; i < 256; ++i) { const int c = hid_col(i / 16, i % 16); m[VMAP_HID + i] = c < HD ? c : -1; }
-        for (int i = 0; i < 64; ++i) {
-            m[VMAP_FTS + i] = i < FT ? i : -1;
-            const int c = pe_src_col(L, 8 * (i / 16) + (i % 16 & 7), (i % 16) >> 3);
-            m[VMAP_PE + i] = c < 0 ? -1 : FT + c;
+            if (!rc) rc = put(VBWD_SIGGEO, [&](StreamBuilder& b) {
+                b.layer_transposed(sigma_w1, 1 + G, HD, 0, HD, nullptr, 0, T, GK + 1, true, [&](int j, int kk) {
+                    if (j < GK) { const int c = 16 * j + phi(kk); return c < G ? 1 + c : -1; }
+                    return kk == 0 ? 0 : -1;
+                });
+            });
+            if (!rc) rc = put(VBWD_L0, [&](StreamBuilder& b) {       // [feature rows | point-encoding rows] of sigma_net.0
+                const int FTT = (FT + 31) / 32, in_dim = d->input_ch;
+                b.layer_at(FTT + 2, KS, true,
+                           [&](int t, int r) { if (t < FTT) return 32 * t + r < FT ? 32 * t + r : -1; const int c = enc_row(L, 32 * (t - FTT) + r); return c < 0 ? -1 : FT + c; },
+                           hid_col, [&](int r, int c) { return sigma_w0 + (size_t)c * in_dim + r; });
+            });
+            if (rc) return rc;
         }
-        for (int i = 0; i < 32; ++i) {
-            const int c = pe_src_col(Lv, 8 * (i / 16) + (i % 16 & 7), (i % 16) >> 3);
-            m[VMAP_DIR + i] = c < 0 ? -1 : G + c;
+        if (standard && voxel_mlp_c_chunks(HD, G, FT) > 0) {     // compensated float16 mode: the layer table of voxel_mlp_c_kernel.h VoxNetC (groups of two tiles, 64-input blocks)
+            auto c0p = [&](int j, int kk) {
+                if (j < GK) { const int c = c_hid_col(j, kk); return c < G ? c : -1; }
+                const int c = pe_src_col(Lv, 8 * (j - GK) + (kk & 7), kk >> 3);
+                return c < 0 ? -1 : G + c;
+            };
+            auto sig_at = [=](int r, int c) -> const float* { return c < HD ? sigma_w1 + (size_t)r * HD + c : nullptr; };
+            StreamBuilderC sc(PIPE_CB);
+            sc.arena = A;
+            sc.layer(sigma_w0, HD, d->input_ch, T, KF + PE_KS, 2, in0_col);
+            sc.layer_at(1, KS, 1, [](int, int r) { return r == 0 ? 0 : -1; }, c_hid_col, sig_at);
+            sc.layer_at(GT, KS, 2, [G](int t, int r) { return 32 * t + r < G ? 1 + 32 * t + r : -1; }, c_hid_col, sig_at);
+            sc.layer(color_w0, HD, G + ICV, T, GK + PEV_KS, 2, c0p);
+            sc.layer(color_w1, HD, HD, T, KS, 2, c_hid_col);
+            sc.layer(color_w2, 3, HD, 1, KS, 1, c_hid_col);
+            v->pipe_c_chunks = (int)(sc.bytes.size() / PIPE_CB);
+            if (v->pipe_c_chunks != voxel_mlp_c_chunks(HD, G, FT))
+                rc = fail(EVD_E_INVALID, "evd_voxel_create: f16c stream has %d chunks, kernel expects %d", v->pipe_c_chunks, voxel_mlp_c_chunks(HD, G, FT));
+            if (!rc) rc = v->pipe_c.upload(sc);
+            if (rc) return rc;
         }
-        for (int i = 0; i < 128; ++i) {
-            const int c = hid_col(i / 16, i % 16);
-            m[VMAP_GEO_X + i] = c < G ? c : -1;
-            m[VMAP_GEO_Y + i] = c < G ? 1 + c : -1;
+        {   // wgrad index maps (voxel_train.h)
+            std::vector<int> m(VMAP_TOTAL, -1);
+            for (int i = 0; i < 256; ++i) { const int c = hid_col(i / 16, i % 16); m[VMAP_HID + i] = c < HD ? c : -1; }
+            for (int i = 0; i < 64; ++i) {
+                m[VMAP_FTS + i] = i < FT ? i : -1;
+                const int c = pe_src_col(L, 8 * (i / 16) + (i % 16 & 7), (i % 16) >> 3);
+                m[VMAP_PE + i] = c < 0 ? -1 : FT + c;
+            }
+            for (int i = 0; i < 32; ++i) {
+                const int c = pe_src_col(Lv, 8 * (i / 16) + (i % 16 & 7), (i % 16) >> 3);
+                m[VMAP_DIR + i] = c < 0 ? -1 : G + c;
+            }
+            for (int i = 0; i < 128; ++i) {
+                const int c = hid_col(i / 16, i % 16);
+                m[VMAP_GEO_X + i] = c < G ? c : -1;
+                m[VMAP_GEO_Y + i] = c < G ? 1 + c : -1;
+            }
+            for (int i = 0; i < 3; ++i) m[VMAP_COL + i] = i;
+            m[VMAP_SIG] = 0;
+            for (int i = 0; i < 16; ++i) { m[VMAP_F64_SG + i] = m[VMAP_GEO_Y + i]; m[VMAP_F64_SG + 16 + i] = m[VMAP_SIG + i]; }
+            for (int i = 0; i < 32; ++i) { m[VMAP_F64_C0 + i] = m[VMAP_GEO_X + i]; m[VMAP_F64_C0 + 32 + i] = m[VMAP_DIR + i]; }
+            for (int i = 0; i < 32; ++i) m[VMAP_F64_L0 + i] = m[VMAP_FTS + i];
+            for (int i = 0; i < 64; ++i) m[VMAP_F64_L0 + 32 + i] = m[VMAP_PE + i];
+            for (int i = 0; i < 128; ++i) m[VMAP_SG5 + i] = m[VMAP_GEO_Y + i];
+            for (int i = 0; i < 32; ++i) m[VMAP_SG5 + 128 + i] = m[VMAP_SIG + i];
+            if ((rc = v->wmaps.upload(m.data(), m.size() * sizeof(int)))) return rc;
         }
-        for (int i = 0; i < 3; ++i) m[VMAP_COL + i] = i;
-        m[VMAP_SIG] = 0;
-        for (int i = 0; i < 16; ++i) { m[VMAP_F64_SG + i] = m[VMAP_GEO_Y + i]; m[VMAP_F64_SG + 16 + i] = m[VMAP_SIG + i]; }
-        for (int i = 0; i < 32; ++i) { m[VMAP_F64_C0 + i] = m[VMAP_GEO_X + i]; m[VMAP_F64_C0 + 32 + i] = m[VMAP_DIR + i]; }
-        for (int i = 0; i < 32; ++i) m[VMAP_F64_L0 + i] = m[VMAP_FTS + i];
-        for (int i = 0; i < 64; ++i) m[VMAP_F64_L0 + 32 + i] = m[VMAP_PE + i];
-        for (int i = 0; i < 128; ++i) m[VMAP_SG5 + i] = m[VMAP_GEO_Y + i];
-        for (int i = 0; i < 32; ++i) m[VMAP_SG5 + 128 + i] = m[VMAP_SIG + i];
-        if ((rc = v->wmaps.upload(m.data(), m.size() * sizeof(int)))) { evd_voxel_destroy(v); return rc; }
-    }
+        return EVD_OK;
+    };
+    if ((rc = generic ? generic_streams() : standard_streams())) { evd_voxel_destroy(v); return rc; }
     std::vector<float> b(32 * 16, 0.f);            // zero block shared by the bias-free sigma layers
     std::vector<int32_t> bsrc(32 * 16, -1);
     auto push = [&](int block, int out_dim, int tiles) {
@@ -301,9 +389,7 @@ int evd_voxel_create(const evd_voxel_desc* d, evd_voxel** out) {
             bsrc.push_back(i < out_dim ? (int32_t)(v->param_off[block] + i) : -1);
         }
     };
-    push(3, HD, T);
-    push(5, HD, T);
-    push(7, 3, 1);
+    for (int l = 0; l < NC; ++l) push(v->color_b_blk(l), l == NC - 1 ? 3 : HD, l == NC - 1 ? 1 : T);
     rc = v->bias.upload(b.data(), b.size() * sizeof(float));
     if (!rc) rc = v->bias_src.upload(bsrc.data(), bsrc.size() * sizeof(int32_t));
     if (rc) { evd_voxel_destroy(v); return rc; }
@@ -327,7 +413,8 @@ static bool grids_half_for(const evd_voxel* v, int precision) {
     // float32 grids: its weights place the importance samples, and with float16 grids there the FINE image is at 1.0e-4.
     // The coarse features AT THE IMPORTANCE SAMPLES (renderer.py:209) also feed the fine networks only -- but there the float16 grids
     // cost 3.4e-5 of the fine image for ~1 % of the render: left on the float32 grids.
-    if (precision == EVD_PREC_F16C) return v->ft_dim > v->app_dim;
+    // A generic level has no compensated kernel: EVD_PREC_F16C is EVD_PREC_F16X3 there, grids included (as on the standard coarse level)
+    if (precision == EVD_PREC_F16C) return !v->generic && v->ft_dim > v->app_dim;
     return false;
 }
 static int sample_for(const evd_voxel* v, int precision, const float* pts, long n, float* out, int out_stride, int out_col, void* stream) {
@@ -432,18 +519,25 @@ static int use_pipe_c(const evd_voxel* v, VoxMlpParams& p, hipStream_t st) {
 
 // The network of a level's inference pass: picks the kernel and, with it, the stream of the handle it reads (p.wstream / p.nchunks).
 static int voxel_level_forward(const evd_voxel* v, int precision, VoxMlpParams& p, hipStream_t st) {
-    const bool coarse = v->hidden_dim == 64;
+    if (v->generic) {       // any other shape: its own kernel and stream in every mode; EVD_PREC_F16C runs float32-grade as on the standard coarse level
+        const int prec = precision == EVD_PREC_F16C ? EVD_PREC_F16X3 : precision;
+        p.wstream = (const char*)v->stream[prec].data.p;
+        p.nchunks = v->nchunks[prec];
+        const VoxGenShape g{v->num_layers, v->num_layers_color, v->geo, (v->geo + 31) / 32, v->ft_dim / 16};
+        return voxel_mlp_generic_dispatch(prec, v->hidden_dim, p, g, st);
+    }
+    const bool coarse = std_coarse(v);
     bool coarse_of_f16c = false;
     if (precision == EVD_PREC_F16C) {
-        if (v->pipe_c_chunks > 0) {     // the level's compensated kernel (fine level)
+        if (v->pipe_c_chunks > 0) {     // the level's compensated kernel (standard fine level)
             if (p.feature) return fail(EVD_E_INVALID, "evd_voxel: per-sample feature rows are not built in EVD_PREC_F16C (use EVD_PREC_F16X3)");
             int rc = use_pipe_c(v, p, st);
             return rc ? rc : launch_voxel_pipe_f16c(p, st);
         }
-        precision = EVD_PREC_F16X3;     // the 64-wide coarse level: float32-grade arithmetic (a few % of the render)
+        precision = EVD_PREC_F16X3;     // the standard coarse level: float32-grade arithmetic (a few % of the render)
         coarse_of_f16c = coarse;
     }
-    // the pipelined stream of a standard level; the 64-wide level's kernels on it write no per-sample feature rows
+    // the pipelined stream of a standard level; the coarse level's kernels on it write no per-sample feature rows
     if (v->fwd_chunks[precision] > 0 && !(coarse && p.feature)) {
         p.wstream = (const char*)v->fwd[precision].data.p;
         p.nchunks = v->fwd_chunks[precision];
@@ -515,6 +609,17 @@ int evd_voxel_forward(const evd_voxel* v, int precision, const float* pts, const
     if (!workspace || workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_voxel_forward: workspace %zu < %zu bytes", workspace_bytes, need);
     return voxel_pass(v, precision, pts, viewdirs, vd_stride, fts, F, z, rays_d, rays_d_stride, R, S, is_train, nullptr,
                       color, depth, acc, weights, feature, L.raw, stream, L.cs);
+}
+
+int evd_voxel_mlp(const evd_voxel* v, int precision, const float* pts, const float* viewdirs, int vd_stride, const float* fts, int ft_stride,
+                  long R, int S, float* raw, float* feature, void* stream) {
+    EVD_REQUIRE(v && pts && viewdirs && fts && raw, "evd_voxel_mlp: null argument");
+    EVD_REQUIRE(precision >= 0 && precision <= EVD_PREC_F16C, "evd_voxel_mlp: unknown precision %d", precision);
+    EVD_REQUIRE(R >= 0 && S >= 1 && vd_stride >= 3 && ft_stride >= v->ft_dim && ft_stride % 4 == 0, "evd_voxel_mlp: bad shape (fts rows of at least %d floats, a multiple of 4)", v->ft_dim);
+    if (R == 0) return EVD_OK;
+    VoxMlpParams p = vox_mlp_params(v, pts, viewdirs, vd_stride, fts, ft_stride, R, S, raw, feature, nullptr);
+    p.pe_l = v->multires; p.pe_lv = v->multires_views;
+    return voxel_level_forward(v, precision, p, as_stream(stream));
 }
 
 // The workspace of evd_c2f_render and evd_c2f_render_rays: slot 0 is the ray batch evd_c2f_render packs
@@ -628,19 +733,20 @@ static long vox_tiles(long nsamp) { return cdiv(nsamp, 256L) * 8; }
 // that is built (fine level), else the split-float16 forward writing the float16 store (coarse level)
 // EVD_PREC_F16M: the split-float16 forward on every level, same store and backward
 static bool vox_train_built(const evd_voxel* v, int prec) {
+    if (v->generic) return prec == EVD_PREC_F16X3;      // kernel_voxel_train_generic.hip; the other modes' training kernels are the standard levels'
     if (prec == EVD_PREC_F16C) return v->fwd_chunks[EVD_PREC_F16] > 0 && (v->pipe_c_chunks > 0 || v->fwd_chunks[EVD_PREC_F16X3] > 0);
     if (prec == EVD_PREC_F16M) return v->fwd_chunks[EVD_PREC_F16] > 0 && v->fwd_chunks[EVD_PREC_F16X3] > 0;
     return prec >= 0 && prec < EVD_VOX_NUM_PREC && v->fwd_chunks[prec] > 0;
 }
 static int vox_store_prec(int prec) { return (prec == EVD_PREC_F16C || prec == EVD_PREC_F16M) ? EVD_PREC_F16 : prec; }
 
-long evd_voxel_param_count(const evd_voxel* v) { return v ? v->param_off[8] : 0; }
+long evd_voxel_param_count(const evd_voxel* v) { return v ? v->param_off[v->nblk] : 0; }
 
 int evd_voxel_param_blocks(const evd_voxel* v, long* offsets, int capacity) {
     EVD_REQUIRE(v, "evd_voxel_param_blocks: null level");
     if (offsets)
-        for (int i = 0; i <= 8 && i < capacity; ++i) offsets[i] = v->param_off[i];
-    return 8;
+        for (int i = 0; i <= v->nblk && i < capacity; ++i) offsets[i] = v->param_off[i];
+    return v->nblk;
 }
 
 int evd_voxel_load_params(evd_voxel* v, const float* params, void* stream) {
@@ -655,12 +761,13 @@ int evd_voxel_load_params(evd_voxel* v, const float* params, void* stream) {
     }
     if ((rc = repack_batch(v->batch, all, params, st))) return rc;
     if (v->pipe_c_chunks > 0) {
-        const size_t bytes = (size_t)v->param_off[8] * sizeof(float);
+        const size_t bytes = (size_t)v->param_off[v->nblk] * sizeof(float);
         if (!v->arena_dev.p && (rc = v->arena_dev.alloc(bytes))) return rc;
         EVD_HIP(hipMemcpyAsync(v->arena_dev.p, params, bytes, hipMemcpyDeviceToDevice, st));
         v->pipe_c_stale = true;
     }
-    if (v->cnet.p) EVD_HIP(hipMemcpyAsync(v->cnet.p, params + v->param_off[2], v->cnet.bytes, hipMemcpyDeviceToDevice, st));
+    if (v->params_f32.p) EVD_HIP(hipMemcpyAsync(v->params_f32.p, params, v->params_f32.bytes, hipMemcpyDeviceToDevice, st));
+    if (v->cnet.p) EVD_HIP(hipMemcpyAsync(v->cnet.p, params + v->param_off[v->num_layers], v->cnet.bytes, hipMemcpyDeviceToDevice, st));
     const long nb = (long)(v->bias.bytes / sizeof(float));
     hipLaunchKernelGGL(k_gather_f32, dim3((unsigned)cdiv(nb, 256L)), dim3(256), 0, st, params, (const int*)v->bias_src.p, nb, (float*)v->bias.p);
     EVD_LAUNCH_CHECK();
@@ -668,20 +775,31 @@ int evd_voxel_load_params(evd_voxel* v, const float* params, void* stream) {
 }
 
 size_t evd_voxel_train_store_bytes(const evd_voxel* v, long nsamp) {
-    return (!v || nsamp < 0) ? 0 : (size_t)vox_tiles(nsamp) * voxel_store_tile_bytes(v->hidden_dim);
+    return (!v || nsamp < 0 || v->generic) ? 0 : (size_t)vox_tiles(nsamp) * voxel_store_tile_bytes(v->hidden_dim);
 }
 size_t evd_voxel_train_store_bytes_prec(const evd_voxel* v, int precision, long nsamp) {
-    return (!v || nsamp < 0 || !vox_train_built(v, precision)) ? 0
-           : (size_t)vox_tiles(nsamp) * voxel_store_tile_bytes_prec(v->hidden_dim, vox_store_prec(precision));
+    if (!v || nsamp < 0 || !vox_train_built(v, precision)) return 0;
+    if (v->generic) return (size_t)VoxGenStore(nsamp, v->hidden_dim, v->num_layers, v->num_layers_color).total() * sizeof(float);
+    return (size_t)vox_tiles(nsamp) * voxel_store_tile_bytes_prec(v->hidden_dim, vox_store_prec(precision));
 }
 
 static const size_t VOX_WGRAD_PARTIAL_BYTES = (size_t)VOX_WGRAD_BLOCKS * 8 * 9 * 4096;
 size_t evd_voxel_backward_workspace_bytes(void) { WgradWs L; return wgrad_layout(VOX_WGRAD_PARTIAL_BYTES, nullptr, &L); }
+// a generic level: the wgrad partial sums of the generic path behind a 256-byte alignment
+static const size_t VOX_GEN_WS_SLACK = 256;
+size_t evd_voxel_backward_workspace_bytes_net(const evd_voxel* v, int precision) {
+    if (!v) return 0;
+    if (!v->generic) return evd_voxel_backward_workspace_bytes();
+    return vox_train_built(v, precision) ? GEN_WS_FLOATS * sizeof(float) + VOX_GEN_WS_SLACK : 0;
+}
 
 int evd_voxel_mlp_train(const evd_voxel* v, int precision, const float* pts, const float* viewdirs, int vd_stride, const float* fts, int ft_stride,
                         long R, int S, float* raw, float* feature, void* store, size_t store_bytes, void* stream) {
     EVD_REQUIRE(v && pts && viewdirs && fts && raw && store, "evd_voxel_mlp_train: null argument");
     EVD_REQUIRE(!v->composite_feature, "evd_voxel_mlp_train: composite_feature levels (kernel_type PBE) are built for inference only");
+    EVD_REQUIRE(!v->generic || precision == EVD_PREC_F16X3, "evd_voxel_mlp_train: a level of this shape (hidden %d, geo %d, features %d, %d + %d layers) "
+                "trains in precision f16x3 only; the other training modes are built for the standard levels (64/15/32 and 256/128/64 with 2 + 3 layers)",
+                v->hidden_dim, v->geo, v->ft_dim, v->num_layers, v->num_layers_color);
     EVD_REQUIRE(vox_train_built(v, precision), "evd_voxel_mlp_train: the training path is built for precision f16 / bf16 / f16x3 / f16c / f16m");
     EVD_REQUIRE(R >= 0 && S >= 1 && ft_stride >= v->ft_dim && ft_stride % 4 == 0, "evd_voxel_mlp_train: bad shape");
     if (R == 0) return EVD_OK;
@@ -689,6 +807,14 @@ int evd_voxel_mlp_train(const evd_voxel* v, int precision, const float* pts, con
     if (store_bytes < evd_voxel_train_store_bytes_prec(v, precision, nsamp))
         return fail(EVD_E_WORKSPACE, "evd_voxel_mlp_train: store %zu < %zu bytes", store_bytes, evd_voxel_train_store_bytes_prec(v, precision, nsamp));
     VoxMlpParams p = vox_mlp_params(v, pts, viewdirs, vd_stride, fts, ft_stride, R, S, raw, feature, (char*)store);
+    if (v->generic) {       // the generic inference kernel's body in the split-float16 mode, writing float32 rows: raw is the inference call's, bit for bit
+        EVD_REQUIRE(vd_stride >= 3 && ((uintptr_t)store % 16) == 0, "evd_voxel_mlp_train: bad shape (the store 16-byte aligned)");
+        p.pe_l = v->multires; p.pe_lv = v->multires_views;
+        p.wstream = (const char*)v->stream[EVD_PREC_F16X3].data.p;
+        p.nchunks = v->nchunks[EVD_PREC_F16X3];
+        const VoxGenShape g{v->num_layers, v->num_layers_color, v->geo, (v->geo + 31) / 32, v->ft_dim / 16};
+        return voxel_train_fwd_generic_dispatch(v->hidden_dim, p, g, as_stream(stream));
+    }
     const bool mixed = precision == EVD_PREC_F16C || precision == EVD_PREC_F16M;      // a float32-grade forward writing the float16 mode's store
     if (mixed && feature) return fail(EVD_E_INVALID, "evd_voxel_mlp_train: float32 feature rows are not built in EVD_PREC_F16C / EVD_PREC_F16M (the geo features stay fragments in the store)");
     if (precision == EVD_PREC_F16C && v->pipe_c_chunks > 0) {        // the level's compensated kernel (fine level)
@@ -710,12 +836,30 @@ int evd_voxel_mlp_backward(const evd_voxel* v, int precision, const float* d_raw
                            float* d_pts, float* d_dirs, void* workspace, size_t workspace_bytes, void* stream) {
     EVD_REQUIRE((!d_pts || pts) && (!d_dirs || viewdirs), "evd_voxel_mlp_backward: d_pts / d_dirs need the forward's pts / viewdirs");
     EVD_REQUIRE(v && d_raw && raw && store && grads && workspace, "evd_voxel_mlp_backward: null argument");
+    EVD_REQUIRE(!v->generic || precision == EVD_PREC_F16X3, "evd_voxel_mlp_backward: a level of this shape (hidden %d, geo %d, features %d, %d + %d layers) "
+                "trains in precision f16x3 only; the other training modes are built for the standard levels (64/15/32 and 256/128/64 with 2 + 3 layers)",
+                v->hidden_dim, v->geo, v->ft_dim, v->num_layers, v->num_layers_color);
     EVD_REQUIRE(vox_train_built(v, precision), "evd_voxel_mlp_backward: the training path is built for precision f16 / bf16 / f16x3 / f16c / f16m");
     EVD_REQUIRE(R >= 0 && S >= 1 && (!d_fts || d_fts_stride >= v->ft_dim), "evd_voxel_mlp_backward: bad shape");
     if (R == 0) return EVD_OK;
     const long nsamp = R * (long)S;
     if (store_bytes < evd_voxel_train_store_bytes_prec(v, precision, nsamp))
         return fail(EVD_E_WORKSPACE, "evd_voxel_mlp_backward: store %zu < %zu bytes", store_bytes, evd_voxel_train_store_bytes_prec(v, precision, nsamp));
+    if (v->generic) {
+        EVD_REQUIRE(!awp_store, "evd_voxel_mlp_backward: awp_store goes with the f16 / bf16 modes of the standard fine level (pass the geo gradient as d_feature rows)");
+        EVD_REQUIRE(((uintptr_t)store % 16) == 0, "evd_voxel_mlp_backward: the store must be 16-byte aligned");
+        const size_t need = evd_voxel_backward_workspace_bytes_net(v, precision);
+        if (workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_voxel_mlp_backward: workspace %zu < %zu bytes", workspace_bytes, need);
+        VoxGenBwdPlan b{};
+        b.HD = v->hidden_dim; b.G = v->geo; b.FT = v->ft_dim; b.NS = v->num_layers; b.NC = v->num_layers_color; b.L = v->multires; b.Lv = v->multires_views;
+        b.params = (const float*)v->params_f32.p; b.off = v->param_off;
+        b.d_raw = d_raw; b.raw = raw; b.d_feature = d_feature; b.nsamp = nsamp; b.store = (float*)store; b.partial = (float*)ws_align_ptr(workspace);
+        for (int l = 0; l < b.NS; ++l) b.sigma_w[l] = grads->sigma_w[l];
+        for (int l = 0; l < b.NC; ++l) { b.color_w[l] = grads->color_w[l]; b.color_b[l] = grads->color_b[l]; }
+        b.accumulate = grads->accumulate ? 1 : 0;
+        b.d_fts = d_fts; b.d_fts_stride = d_fts_stride; b.d_pts = d_pts; b.d_dirs = d_dirs;
+        return run_voxel_backward_generic(b, as_stream(stream));
+    }
     WgradWs ws;
     const size_t need_ws = wgrad_layout(VOX_WGRAD_PARTIAL_BYTES, workspace, &ws);
     if (workspace_bytes < need_ws) return fail(EVD_E_WORKSPACE, "evd_voxel_mlp_backward: workspace %zu < %zu bytes", workspace_bytes, need_ws);

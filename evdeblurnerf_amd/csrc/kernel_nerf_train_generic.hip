@@ -205,6 +205,7 @@ struct GenDgrad {
     const float *eg, *ew;               // a second, one-row layer on the same input (alpha_linear): eg[4 s] * ew[k] is added, or null
     int add;                            // 1: out += (the point encoding collects layer 0 and the skip layer, in that fixed order)
     long nsamp;
+    int Mv;                             // rows m >= Mv of the weight are not read (zero): a gradient block narrower than the kernel's M
 };
 
 // out[s, k] = sum_m G[s, m] W[m, c0 + k].  One wavefront owns 32 samples: its G rows stay in registers (slot (i, e) of lane half hh is
@@ -232,8 +233,9 @@ __global__ __launch_bounds__(256, 2) void k_gen_dgrad(const GenDgrad a) {
 #pragma unroll 8
             for (int j = 0; j < M / 8; ++j) {      // 8 reads in flight per thread: two workgroups stay resident per CU at M = 256
                 const int m = (tid >> 5) + 8 * j;
-                const float w = wcol[(size_t)m * a.ldw];
-                wt[m * 32 + k] = kin ? w : 0.f;
+                const bool in = kin && m < a.Mv;
+                const float w = wcol[in ? (size_t)m * a.ldw : 0];
+                wt[m * 32 + k] = in ? w : 0.f;
             }
         }
         __syncthreads();
@@ -392,56 +394,57 @@ __global__ __launch_bounds__(256) void k_gen_wreduce(const float* __restrict__ p
     }
 }
 
-namespace {
+void GenChain::wgrad(const float* G, int ldg, int M, const float* X, int ldx, int K, float* dw, int ldw, int c0, float* db) {
+    if (rc || (!dw && !db) || K <= 0) return;
+    GenWgrad a;
+    a.G = G; a.ldg = ldg; a.M = M; a.X = X; a.ldx = ldx; a.K = K; a.partial = partial; a.nsamp = nsamp;
+    a.mt = (M + 31) / 32; a.kt = (K + 31) / 32; a.kg = (a.kt + GEN_KB - 1) / GEN_KB; a.bias = db ? 1 : 0;
+    const int Mp = a.mt * 32, Kp = a.kt * 32, tasks = a.mt * a.kg;
+    // sample ranges: about 2048 wavefronts in flight, as many as the workspace holds, at least 64 samples each; a function of the
+    // shapes alone, so that a repeated call sums in the same order
+    long nsplit = cdiv(2048, tasks);
+    const long cap = (long)(GEN_WS_FLOATS / ((size_t)Mp * Kp + Mp));
+    if (nsplit > cap) nsplit = cap;
+    if (nsplit > cdiv(nsamp, 64)) nsplit = cdiv(nsamp, 64);
+    if (nsplit < 1) nsplit = 1;
+    a.chunk = (int)(cdiv(cdiv(nsamp, nsplit), 8) * 8);
+    a.nsplit = (int)cdiv(nsamp, a.chunk);
+    hipLaunchKernelGGL(k_gen_wgrad, dim3((unsigned)cdiv((long)a.nsplit * tasks, 4)), dim3(256), 0, st, a);
+    if (hipGetLastError() != hipSuccess) { rc = fail(EVD_E_HIP, "%s: wgrad launch failed", who); return; }
+    const long ne = (dw ? (long)M * K : 0) + (db ? M : 0);
+    hipLaunchKernelGGL(k_gen_wreduce, dim3((unsigned)cdiv(ne, 32)), dim3(256), 0, st, (const float*)partial, a.nsplit, M, K, Mp, Kp, dw, ldw, c0, db,
+                       accumulate);
+    if (hipGetLastError() != hipSuccess) rc = fail(EVD_E_HIP, "%s: wgrad reduction launch failed", who);
+}
 
-struct GenChain {
-    const GenBwdPlan& b;
-    hipStream_t st;
-    int rc = EVD_OK;
-
-    // dW[:, c0 : c0 + K] (and db) of one layer from its gradient rows G [nsamp, M] and its input rows X [nsamp, K]
-    void wgrad(const float* G, int ldg, int M, const float* X, int ldx, int K, float* dw, int ldw, int c0, float* db) {
-        if (rc || (!dw && !db) || K <= 0) return;
-        GenWgrad a;
-        a.G = G; a.ldg = ldg; a.M = M; a.X = X; a.ldx = ldx; a.K = K; a.partial = b.partial; a.nsamp = b.nsamp;
-        a.mt = (M + 31) / 32; a.kt = (K + 31) / 32; a.kg = (a.kt + GEN_KB - 1) / GEN_KB; a.bias = db ? 1 : 0;
-        const int Mp = a.mt * 32, Kp = a.kt * 32, tasks = a.mt * a.kg;
-        // sample ranges: about 2048 wavefronts in flight, as many as the workspace holds, at least 64 samples each; a function of the
-        // shapes alone, so that a repeated call sums in the same order
-        long nsplit = cdiv(2048, tasks);
-        const long cap = (long)(GEN_WS_FLOATS / ((size_t)Mp * Kp + Mp));
-        if (nsplit > cap) nsplit = cap;
-        if (nsplit > cdiv(b.nsamp, 64)) nsplit = cdiv(b.nsamp, 64);
-        if (nsplit < 1) nsplit = 1;
-        a.chunk = (int)(cdiv(cdiv(b.nsamp, nsplit), 8) * 8);
-        a.nsplit = (int)cdiv(b.nsamp, a.chunk);
-        hipLaunchKernelGGL(k_gen_wgrad, dim3((unsigned)cdiv((long)a.nsplit * tasks, 4)), dim3(256), 0, st, a);
-        if (hipGetLastError() != hipSuccess) { rc = fail(EVD_E_HIP, "evd_nerf_mlp_backward: wgrad launch failed"); return; }
-        const long ne = (dw ? (long)M * K : 0) + (db ? M : 0);
-        hipLaunchKernelGGL(k_gen_wreduce, dim3((unsigned)cdiv(ne, 32)), dim3(256), 0, st, (const float*)b.partial, a.nsplit, M, K, Mp, Kp, dw, ldw, c0, db,
-                           b.accumulate);
-        if (hipGetLastError() != hipSuccess) rc = fail(EVD_E_HIP, "evd_nerf_mlp_backward: wgrad reduction launch failed");
+void GenChain::dgrad(int M, const float* G, int ldg, const float* Wm, int ldw, int c0, int K, float* out, int ldo, const float* mask, int ldm,
+                     const float* eg, const float* ew, int add, int Mv) {
+    if (rc || K <= 0) return;
+    GenDgrad a;
+    a.G = G; a.ldg = ldg; a.Wm = Wm; a.ldw = ldw; a.c0 = c0; a.K = K; a.out = out; a.ldo = ldo; a.mask = mask; a.ldm = ldm;
+    a.eg = eg; a.ew = ew; a.add = add; a.nsamp = nsamp; a.Mv = Mv > 0 ? Mv : M;
+    const dim3 grid((unsigned)cdiv(nsamp, 128)), block(256);
+    switch (M) {
+    case 32: hipLaunchKernelGGL(k_gen_dgrad<32>, grid, block, 0, st, a); break;
+    case 64: hipLaunchKernelGGL(k_gen_dgrad<64>, grid, block, 0, st, a); break;
+    case 128: hipLaunchKernelGGL(k_gen_dgrad<128>, grid, block, 0, st, a); break;
+    case 256: hipLaunchKernelGGL(k_gen_dgrad<256>, grid, block, 0, st, a); break;
+    default: rc = fail(EVD_E_INVALID, "%s: no dgrad kernel for %d gradient columns", who, M); return;
     }
+    if (hipGetLastError() != hipSuccess) rc = fail(EVD_E_HIP, "%s: dgrad launch failed", who);
+}
 
-    void dgrad(int M, const float* G, int ldg, const float* Wm, int ldw, int c0, int K, float* out, int ldo, const float* mask, int ldm,
-               const float* eg, const float* ew, int add) {
-        if (rc || K <= 0) return;
-        GenDgrad a;
-        a.G = G; a.ldg = ldg; a.Wm = Wm; a.ldw = ldw; a.c0 = c0; a.K = K; a.out = out; a.ldo = ldo; a.mask = mask; a.ldm = ldm;
-        a.eg = eg; a.ew = ew; a.add = add; a.nsamp = b.nsamp;
-        const dim3 grid((unsigned)cdiv(b.nsamp, 128)), block(256);
-        switch (M) {
-        case 32: hipLaunchKernelGGL(k_gen_dgrad<32>, grid, block, 0, st, a); break;
-        case 64: hipLaunchKernelGGL(k_gen_dgrad<64>, grid, block, 0, st, a); break;
-        case 128: hipLaunchKernelGGL(k_gen_dgrad<128>, grid, block, 0, st, a); break;
-        case 256: hipLaunchKernelGGL(k_gen_dgrad<256>, grid, block, 0, st, a); break;
-        default: rc = fail(EVD_E_INVALID, "evd_nerf_mlp_backward: no dgrad kernel for %d gradient columns", M); return;
-        }
-        if (hipGetLastError() != hipSuccess) rc = fail(EVD_E_HIP, "evd_nerf_mlp_backward: dgrad launch failed");
-    }
-};
+int launch_gen_encode(const float* in, long nsamp, int L, int Lv, float* ep, float* ed, hipStream_t st) {
+    hipLaunchKernelGGL(k_gen_encode, dim3((unsigned)cdiv(nsamp * 128, 256)), dim3(256), 0, st, in, nsamp, L, Lv, ep, ed);
+    EVD_LAUNCH_CHECK();
+    return EVD_OK;
+}
 
-}  // namespace
+int launch_gen_encode_bwd(const float* enc, const float* denc, long nsamp, int L, float* dx, hipStream_t st) {
+    hipLaunchKernelGGL(k_gen_encode_bwd, dim3((unsigned)cdiv(nsamp, 256)), dim3(256), 0, st, enc, denc, nsamp, L, dx);
+    EVD_LAUNCH_CHECK();
+    return EVD_OK;
+}
 
 int run_nerf_backward_generic(const GenBwdPlan& b, hipStream_t st) {
     const evd_nerf* net = b.net;
@@ -459,9 +462,8 @@ int run_nerf_backward_generic(const GenBwdPlan& b, hipStream_t st) {
     auto hrow = [&](int l) { return (const float*)(S + gs.h(l)); };
     const float *frow = S + gs.f(), *hv = S + gs.hv();
 
-    hipLaunchKernelGGL(k_gen_encode, dim3((unsigned)cdiv(n * 128, 256)), dim3(256), 0, st, (const float*)(S + gs.in()), n, L, Lv, ep, ed);
-    EVD_LAUNCH_CHECK();
-    GenChain c{b, st};
+    if (int rc = launch_gen_encode(S + gs.in(), n, L, Lv, ep, ed, st)) return rc;
+    GenChain c{n, b.partial, b.accumulate, st, "evd_nerf_mlp_backward"};
 
     // rgb_linear on hv (nerf.py:155-156)
     c.wgrad(b.d_raw, 4, 3, hv, H, H, b.grads.rgb_w, H, 0, b.grads.rgb_b);
@@ -497,14 +499,10 @@ int run_nerf_backward_generic(const GenBwdPlan& b, hipStream_t st) {
         float* t = cur; cur = oth; oth = t;
     }
     if (c.rc) return c.rc;
-    if (b.d_pts) {
-        hipLaunchKernelGGL(k_gen_encode_bwd, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, (const float*)ep, (const float*)dep, n, L, b.d_pts);
-        EVD_LAUNCH_CHECK();
-    }
-    if (b.d_dirs) {
-        hipLaunchKernelGGL(k_gen_encode_bwd, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, (const float*)ed, (const float*)ded, n, Lv, b.d_dirs);
-        EVD_LAUNCH_CHECK();
-    }
+    if (b.d_pts)
+        if (int rc = launch_gen_encode_bwd(ep, dep, n, L, b.d_pts, st)) return rc;
+    if (b.d_dirs)
+        if (int rc = launch_gen_encode_bwd(ed, ded, n, Lv, b.d_dirs, st)) return rc;
     return EVD_OK;
 }
 

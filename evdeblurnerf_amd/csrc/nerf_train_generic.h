@@ -52,4 +52,24 @@ struct GenBwdPlan {
 };
 int run_nerf_backward_generic(const GenBwdPlan& b, hipStream_t st);
 
+// The per-layer launches of that backward, shared with the generic PDRF level (kernel_voxel_train_generic.hip).  A failed launch sets rc
+// and turns the later calls into no-ops; `who` names the entry in the messages.
+struct GenChain {
+    long nsamp;
+    float* partial;             // GEN_WS_FLOATS floats
+    int accumulate;
+    hipStream_t st;
+    const char* who;
+    int rc = EVD_OK;
+    // dW[:, c0 : c0 + K] (and db) of one layer from its gradient rows G [nsamp, M] and its input rows X [nsamp, K]
+    void wgrad(const float* G, int ldg, int M, const float* X, int ldx, int K, float* dw, int ldw, int c0, float* db);
+    // out[s, k] = sum_{m < Mv} G[s, m] Wm[m, c0 + k], k < K (written up to the next multiple of 32: zeros); M = 32, 64, 128 or 256 columns of G
+    // are read, rows m >= Mv of Wm are not (Mv = 0: all M)
+    void dgrad(int M, const float* G, int ldg, const float* Wm, int ldw, int c0, int K, float* out, int ldo, const float* mask, int ldm,
+               const float* eg, const float* ew, int add, int Mv = 0);
+};
+// PE(pts), PE(dirs) as float32 rows of GEN_ENC columns from rows [nsamp, 8] = (pts xyz, 0, dirs xyz, 0); and d x [nsamp, 3] from d PE(x)
+int launch_gen_encode(const float* in, long nsamp, int L, int Lv, float* ep, float* ed, hipStream_t st);
+int launch_gen_encode_bwd(const float* enc, const float* denc, long nsamp, int L, float* dx, hipStream_t st);
+
 }  // namespace evd

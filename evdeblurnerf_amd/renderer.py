@@ -238,6 +238,10 @@ class NeRFAll:
                     input_ch=args.coarse_app_dim + args.fine_app_dim + ic, multires=args.multires, multires_views=args.multires_views,
                     render_rmnearplane=rm, app_dim=args.fine_app_dim, app_n_comp=args.fine_app_n_comp, n_voxels=args.fine_n_voxels,
                     app_actfn=_args_get(args, "fine_app_actfn", "none"), precision=precision)
+                awp_in = getattr(getattr(awpnet, "embed", None), "input_ch", None)       # the library's consumer (awp.FusedAWP): 128 channels
+                if self.use_awp and awp_in is not None and awp_in != self.mlp_fine.geo_feat_dim:
+                    raise L.EvdError(f"kernel_use_awp: the AWP sample embedding reads {awp_in} geo channels per sample, the fine level has "
+                                     f"fine_geo_feat_dim = {self.mlp_fine.geo_feat_dim}")
         self._ws = None
 
     # nn.Module-like switches used by run_nerf.py
@@ -764,6 +768,10 @@ class NeRFAll:
             if net is None:
                 levels.append(None)
                 continue
+            if self.mode == "c2f" and not net.is_standard_shape() and self.train_precision != "f16x3":
+                raise L.EvdError(f"{prefix[:-1]}: a level with hidden {net.hidden_dim}, geo {net.geo_feat_dim}, {net.ft_dim} feature channels and "
+                                 f"{net.num_layers} + {net.num_layers_color} layers trains in precision f16x3 only (the model's is "
+                                 f"{self.train_precision}); the other training modes are built for the standard PDRF levels")
             flat = net.flat_params(state_dict, prefix, self.device).detach()
             blocks = sorted(net.param_blocks(), key=lambda b: b[2])
             off = 0

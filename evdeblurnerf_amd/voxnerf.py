@@ -208,6 +208,7 @@ class VoxelNeRFBase:
         lo, hi = [float(v) for v in aabb[0]], [float(v) for v in aabb[1]]
         self.gridSize = pdrf_grid_size(lo, hi, n_voxels)
         self.hidden_dim, self.geo_feat_dim, self.app_dim = hidden_dim, geo_feat_dim, app_dim
+        self.num_layers, self.num_layers_color = num_layers, num_layers_color
         self.input_ch, self.precision = input_ch, precision
         self.ft_dim = input_ch - 3 * (1 + 2 * multires)
         self.rgb_activate, self.sigma_activate = rgb_activate, sigma_activate
@@ -319,18 +320,35 @@ class VoxelNeRFBase:
     PARAM_KEYS = ["sigma_net.0.weight", "sigma_net.1.weight", "color_net.0.weight", "color_net.0.bias", "color_net.1.weight",
                   "color_net.1.bias", "color_net.2.weight", "color_net.2.bias"]
 
+    def is_standard_shape(self):
+        """one of the two shapes with pipelined / f16c kernels and a training path in every training mode (csrc/voxel_generic.h
+        voxel_standard_shape); every other shape evd_voxel_create accepts is a generic level: inference in every mode, training in f16x3"""
+        return (self.num_layers, self.num_layers_color) == (2, 3) and (self.hidden_dim, self.geo_feat_dim, self.ft_dim) in ((64, 15, 32), (256, 128, 64))
+
+    def param_keys(self):
+        """the level's parameter names in the library's order: sigma_net.l.weight, then color_net.l.{weight,bias} (PARAM_KEYS on a
+        standard level)"""
+        keys = [f"sigma_net.{l}.weight" for l in range(self.num_layers)]
+        for l in range(self.num_layers_color):
+            keys += [f"color_net.{l}.weight", f"color_net.{l}.bias"]
+        return keys
+
     def param_blocks(self):
         if getattr(self, "_blocks", None) is None:
-            off = (C.c_long * 9)()
-            if L.lib().evd_voxel_param_blocks(self._h, off, 9) != 8:
+            keys = self.param_keys()
+            nb = len(keys)
+            off = (C.c_long * (nb + 1))()
+            if L.lib().evd_voxel_param_blocks(self._h, off, nb + 1) != nb:
                 raise L.EvdError("evd_voxel_param_blocks: unexpected parameter block count")
-            HD, G = self.hidden_dim, self.geo_feat_dim
-            outs = [HD, 1 + G, HD, HD, HD, HD, 3, 3]
+            HD, G, NS, NC = self.hidden_dim, self.geo_feat_dim, self.num_layers, self.num_layers_color
+            outs = [1 + G if l == NS - 1 else HD for l in range(NS)]
+            for l in range(NC):
+                outs += [3 if l == NC - 1 else HD] * 2
             blocks = []
-            for i, key in enumerate(self.PARAM_KEYS):
+            for i, key in enumerate(keys):
                 n = off[i + 1] - off[i]
                 blocks.append((key, (outs[i], n // outs[i]) if key.endswith("weight") else (n,), off[i]))
-            self._blocks, self._nparam = blocks, off[8]
+            self._blocks, self._nparam = blocks, off[nb]
         return self._blocks
 
     def flat_params(self, state_dict, prefix="", device="cuda"):
@@ -352,6 +370,17 @@ class VoxelNeRFBase:
         L.check(L.lib().evd_voxel_load_params(self._h, L.ptr(f), L.stream_ptr()), "evd_voxel_load_params")
         self._synced_net = (flat.data_ptr(), flat._version, L.backward_generation())
 
+    def mlpforward(self, pts, viewdirs, fts, precision=None, want_feature=False):
+        """the per-sample networks alone, inference (evd_voxel_mlp): pts [R, S, 3], viewdirs [R, 3], fts [R, S, ft_dim] ->
+        raw [R, S, 4] = (sigma, sigmoid(colour)) and, with want_feature, the geo rows [R, S, geo_feat_dim] (else None)"""
+        p, vd, ft = pts.contiguous().float(), viewdirs.contiguous().float(), fts.contiguous().float()
+        R, S = p.shape[:2]
+        raw = torch.empty((R, S, 4), dtype=torch.float32, device=p.device)
+        feature = torch.empty((R, S, self.geo_feat_dim), dtype=torch.float32, device=p.device) if want_feature else None
+        L.check(L.lib().evd_voxel_mlp(self._h, L.PREC[precision or self.precision], L.ptr(p), L.ptr(vd), vd.shape[-1], L.ptr(ft), ft.shape[-1],
+                                       R, S, L.ptr(raw), L.ptr(feature), L.stream_ptr()), "evd_voxel_mlp")
+        return raw, feature
+
     def mlpforward_train(self, pts, viewdirs, fts, precision=None, want_feature=False):
         p, vd, ft = pts.contiguous().float(), viewdirs.contiguous().float(), fts.contiguous().float()
         R, S = p.shape[:2]
@@ -359,7 +388,10 @@ class VoxelNeRFBase:
         feature = torch.empty((R, S, self.geo_feat_dim), dtype=torch.float32, device=p.device) if want_feature else None
         nb = int(L.lib().evd_voxel_train_store_bytes_prec(self._h, L.PREC[precision or self.precision], R * S))
         if nb == 0 and R * S > 0:
-            raise L.EvdError(f"the training path is built for precision f16 / bf16 / f16x3 / f16c / f16m, not {precision or self.precision}")
+            raise L.EvdError(f"the training path is built for the standard levels (64/15/32 and 256/128/64 with 2 + 3 layers) in precision "
+                             f"f16 / bf16 / f16x3 / f16c / f16m and for every other shape in f16x3 alone, not for hidden {self.hidden_dim} / geo "
+                             f"{self.geo_feat_dim} / features {self.ft_dim} with {self.num_layers} + {self.num_layers_color} layers in "
+                             f"{precision or self.precision}")
         store = torch.empty((nb,), dtype=torch.uint8, device=p.device)
         L.check(L.lib().evd_voxel_mlp_train(self._h, L.PREC[precision or self.precision], L.ptr(p), L.ptr(vd), vd.shape[-1], L.ptr(ft), ft.shape[-1],
                                              R, S, L.ptr(raw), L.ptr(feature), L.ptr(store), nb, L.stream_ptr()), "evd_voxel_mlp_train")
@@ -383,7 +415,10 @@ class VoxelNeRFBase:
             arr = getattr(gs, ("sigma_" if name == "sigma_net" else "color_") + ("w" if kind == "weight" else "b"))
             arr[int(idx)] = base + 4 * off
         d_fts = torch.empty((R * S, self.ft_dim), dtype=torch.float32, device=g.device) if want_fts else None      # every column is written (k_frags_to_rows)
-        nb = int(L.lib().evd_voxel_backward_workspace_bytes())
+        nb = int(L.lib().evd_voxel_backward_workspace_bytes_net(self._h, L.PREC[precision or self.precision]))
+        if nb == 0:
+            raise L.EvdError(f"a level with hidden {self.hidden_dim} / geo {self.geo_feat_dim} / features {self.ft_dim} and {self.num_layers} + "
+                             f"{self.num_layers_color} layers trains in precision f16x3 only, not in {precision or self.precision}")
         ws = torch.empty((nb,), dtype=torch.uint8, device=g.device)
         p = pts.contiguous().float() if pts is not None else None
         vd = viewdirs.contiguous().float() if viewdirs is not None else None

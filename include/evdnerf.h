@@ -360,6 +360,13 @@ typedef struct {                    /* host float32 pointers */
     const float *plane[3], *line[3], *basis;
 } evd_voxel_desc;
 
+/* Level shapes (reference options --coarse_hidden_dim, --fine_hidden_dim, --fine_geo_feat_dim, --kernel_feat_cnl,
+ * --{coarse,fine}_num_layers[_color], --fine_app_dim; options.py:134-163): hidden_dim 64, 128 or 256 (also the colour network's hidden
+ * width, voxnerf.py:73,78), geo_feat_dim 1..128, num_layers and num_layers_color 1..4, input_ch - 3 (1 + 2 multires) feature channels a
+ * multiple of 16 in 16..64; anything else is EVD_E_INVALID.  The STANDARD levels -- 64/15/32 and 256/128/64 (hidden / geo / features)
+ * with 2 + 3 layers -- have the pipelined, resident and compensated kernels and the training path.  Every other shape is a GENERIC
+ * level: inference in every arithmetic mode (EVD_PREC_F16C is EVD_PREC_F16X3 there, float32 grids included, as on the standard coarse level) through
+ * evd_voxel_mlp, evd_voxel_forward and the c2f render; no composite_feature, no training entries (EVD_E_INVALID). */
 int evd_voxel_create(const evd_voxel_desc* desc, evd_voxel** out);
 void evd_voxel_destroy(evd_voxel* v);
 /* VoxelNeRFBase.sample / compute_appfeature, voxnerf.py:203-208,132-151.  pts dev [n,3] -> out dev [n,out_stride]
@@ -378,6 +385,11 @@ int evd_voxel_forward(const evd_voxel* v, int precision, const float* pts, const
                       float* color, float* depth, float* acc, float* weights, float* feature,
                       void* workspace, size_t workspace_bytes, void* stream);
 size_t evd_voxel_forward_workspace_bytes(const evd_voxel* v, long R, int S);
+/* The per-sample part of VoxelNeRFBase.forward alone (voxnerf.py:210-221,240-254), inference: pts dev [R,S,3], viewdirs dev rows of
+ * vd_stride floats (one per ray), fts dev rows of ft_stride floats -> raw dev [R,S,4] = (sigma, sigmoid(colour)) and feature dev
+ * [R,S,geo] (NULL = not wanted), the per-sample geo rows.  Any level; the kernel evd_voxel_forward runs for the same arguments. */
+int evd_voxel_mlp(const evd_voxel* v, int precision, const float* pts, const float* viewdirs, int vd_stride, const float* fts, int ft_stride,
+                  long R, int S, float* raw, float* feature, void* stream);
 size_t evd_c2f_render_workspace_bytes(const evd_voxel* coarse, const evd_voxel* fine, const evd_render_cfg* cfg, long R);
 /* NeRFAll.render_rays for mode='c2f' (networks/renderer.py:182-217); arguments as evd_nerf_render_rays.
  * out->feature receives the fine level's per-sample geo features [R,S_final,geo_feat_dim] (what AWP consumes). */
@@ -399,7 +411,8 @@ int evd_voxel_tv_loss(const evd_voxel* v, float* out, void* stream);
 
 /* ---- training one PDRF level's sigma / colour networks -------------------------------------------------
  * Parameters live in one float32 arena, canonical order sigma_net.0.weight, sigma_net.1.weight, color_net.{0,1,2}.{weight,bias}
- * (reference nn.Linear layouts, voxnerf.py:60-84); evd_voxel_param_blocks writes the 8 offsets + the total and returns 8;
+ * (reference nn.Linear layouts, voxnerf.py:60-84); evd_voxel_param_blocks writes the 8 offsets + the total and returns 8
+ * (a generic level: sigma_net.0 .. num_layers-1, then color_net.l.{weight,bias}; num_layers + 2 num_layers_color blocks);
  * evd_voxel_load_params re-packs every weight stream of the level on the device (after optimizer.step()).
  * evd_voxel_mlp_train = the per-sample part of VoxelNeRFBase.forward (voxnerf.py:210-221,240-254): raw dev [R,S,4] =
  * (sigma, sigmoid(colour)), every layer's activations kept in `store` (evd_voxel_train_store_bytes); feature dev [R,S,geo]
@@ -413,8 +426,13 @@ int evd_voxel_tv_loss(const evd_voxel* v, float* out, void* stream);
  * level): the store of the fused AWP embedding AFTER evd_awp_embed_backward ran on the same samples -- its d geo fragments are added
  * to the geo features' gradient without ever becoming a float32 [R*S,128] tensor (below).
  * Built for EVD_PREC_F16 / EVD_PREC_BF16 and the float32-grade EVD_PREC_F16X3 (as evd_nerf_mlp_train; awp_store is a half-precision
- * coupling: in f16x3 the AWP consumer's gradient comes back as d_feature rows), both shipped levels (64/15/32 and 256/128/64). */
-typedef struct { float *sigma_w[2], *color_w[3], *color_b[3]; int accumulate; /* as in evd_nerf_grads */ } evd_voxel_grads;
+ * coupling: in f16x3 the AWP consumer's gradient comes back as d_feature rows), both shipped levels (64/15/32 and 256/128/64).
+ * A level of any other shape evd_voxel_create accepts trains in EVD_PREC_F16X3 alone: the forward is the inference kernel of that mode
+ * (raw bit-equal to evd_voxel_mlp) writing float32 rows to the store, the backward one exact-float32 wgrad and dgrad launch per layer
+ * with a fixed summation order (two calls give the same bits); no awp_store there.  Its backward workspace is sized by
+ * evd_voxel_backward_workspace_bytes_net (a standard level: evd_voxel_backward_workspace_bytes(); 0: NULL handle, or a precision the
+ * level does not train in); evd_voxel_train_store_bytes_prec answers 0 for such a precision too. */
+typedef struct { float *sigma_w[4], *color_w[4], *color_b[4]; int accumulate; /* sigma_net.l, color_net.l (unused layers NULL); as in evd_nerf_grads */ } evd_voxel_grads;
 int evd_voxel_geo_feat_dim(const evd_voxel* v);
 long evd_voxel_param_count(const evd_voxel* v);
 int evd_voxel_param_blocks(const evd_voxel* v, long* offsets, int capacity);
@@ -422,6 +440,7 @@ int evd_voxel_load_params(evd_voxel* v, const float* params, void* stream);
 size_t evd_voxel_train_store_bytes(const evd_voxel* v, long nsamp);         /* the f16 / bf16 size */
 size_t evd_voxel_train_store_bytes_prec(const evd_voxel* v, int precision, long nsamp);   /* EVD_PREC_F16X3: (hi, lo) fragments, twice that */
 size_t evd_voxel_backward_workspace_bytes(void);
+size_t evd_voxel_backward_workspace_bytes_net(const evd_voxel* v, int precision);
 int evd_voxel_mlp_train(const evd_voxel* v, int precision, const float* pts, const float* viewdirs, int vd_stride, const float* fts,
                         int ft_stride, long R, int S, float* raw, float* feature, void* store, size_t store_bytes, void* stream);
 int evd_voxel_mlp_backward(const evd_voxel* v, int precision, const float* d_raw, const float* raw, const float* d_feature,
