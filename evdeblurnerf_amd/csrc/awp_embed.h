@@ -25,7 +25,7 @@ constexpr int TRAILER_BYTES = 256;     // behind the tiles: word 0 = float bits 
                                        //                   word 1 = float bits of max |d geo| in true units
 }  // namespace awpstore
 
-inline long awp_tiles(long nsamp) { return cdiv(nsamp, 256L) * 8; }       // = evd_voxel_api.hip vox_tiles: both stores tile alike
+inline long awp_tiles(long nsamp) { return cdiv(nsamp, 256L) * 8; }       // = evd_voxel_train_api.hip vox_tiles: both stores tile alike
 
 // wgrad index maps (fragment column -> parameter row / column), offsets into one int32 array
 enum { AMAP_H = 0, AMAP_GEO = AMAP_H + AWP_W, AMAP_TOTAL = AMAP_GEO + AWP_IN };

@@ -4,6 +4,7 @@
 #include "nerf_mlp.h"
 #include "nerf_mlp_kernel.h"
 #include "nerf_net.h"
+#include "nerf_streams.h"
 #include "nerf_train.h"
 #include "nerf_train_generic.h"
 #include "pack.h"
@@ -113,21 +114,49 @@ int evd_device_count(void) {
 
 // Every stream keeps, next to its bytes, the index map element -> parameter arena (pack.h), so that new parameter values
 // are re-packed on the device (evd_nerf_load_params) with the arithmetic the host packer used at creation.
-static int upload_stream(evd_nerf::Packed& dst, const StreamBuilder& sb) { return dst.upload(sb); }
 
 // canonical parameter order of the arena: pts_linears[l].{weight, bias} for l < D, then views_linears.0, feature_linear,
-// alpha_linear, rgb_linear ({weight, bias} each)
-static void nerf_param_sizes(int D, int W, int skip, int L, int Lv, long* sz) {
-    const int IC = 3 * (1 + 2 * L), ICV = 3 * (1 + 2 * Lv);
+// alpha_linear, rgb_linear ({weight, bias} each; a missing bias = zeros); use_viewdirs=False: then output_linear.{weight, bias}.  Returns the
+// number of blocks
+static int nerf_param_blocks(const evd_nerf_desc* d, bool no_views, ParamBlock* blk) {
+    const int D = d->D, W = d->W, IC = 3 * (1 + 2 * d->multires), ICV = 3 * (1 + 2 * d->multires_views);
     for (int l = 0; l < D; ++l) {
-        sz[2 * l] = (long)W * (l == 0 ? IC : (l - 1 == skip ? W + IC : W));
-        sz[2 * l + 1] = W;
+        blk[2 * l] = {d->pts_w[l], (long)W * (l == 0 ? IC : (l - 1 == d->skip ? W + IC : W))};
+        blk[2 * l + 1] = {d->pts_b[l], W};
     }
-    long* h = sz + 2 * D;
-    h[0] = (long)(W / 2) * (W + ICV); h[1] = W / 2;      // views
-    h[2] = (long)W * W; h[3] = W;                        // feature
-    h[4] = W; h[5] = 1;                                  // alpha
-    h[6] = 3L * (W / 2); h[7] = 3;                       // rgb
+    ParamBlock* h = blk + 2 * D;
+    if (no_views) {
+        h[NB_OUTPUT] = {d->output_w, (long)d->output_ch * W}; h[NB_OUTPUT + 1] = {d->output_b, d->output_ch};
+        return 2 * D + 2;
+    }
+    h[NB_VIEWS] = {d->views_w, (long)(W / 2) * (W + ICV)}; h[NB_VIEWS + 1] = {d->views_b, W / 2};
+    h[NB_FEATURE] = {d->feature_w, (long)W * W}; h[NB_FEATURE + 1] = {d->feature_b, W};
+    h[NB_ALPHA] = {d->alpha_w, W}; h[NB_ALPHA + 1] = {d->alpha_b, 1};
+    h[NB_RGB] = {d->rgb_w, 3L * (W / 2)}; h[NB_RGB + 1] = {d->rgb_b, 3};
+    return 2 * D + 8;
+}
+
+// compensated float16 mode: its own streams (float16 + fp6 fragments) and row scales, pipelined kernel only -- the training forward's
+// (pipe_c) and the folded inference stream (pipe_cf), whose builder gives the layout and the maps over zeros: the values are always filled
+// on the device (nerf_fold_pack)
+static int nerf_streams_c(evd_nerf* n, const float* A) {
+    const int W = n->W, D = n->D, prec = EVD_PREC_F16C;
+    StreamBuilderC sc(PIPE_CB);
+    nerf_layers_c(sc, *n, A, false);
+    n->pipe_chunks[prec] = (int)(sc.bytes.size() / PIPE_CB);
+    if (n->pipe_chunks[prec] != nerf_mlp_c_chunks(W, D, n->skip, true))
+        return fail(EVD_E_INVALID, "evd_nerf_create: f16c stream has %d chunks, kernel expects %d", n->pipe_chunks[prec], nerf_mlp_c_chunks(W, D, n->skip, true));
+    int rc = n->pipe_c.upload(sc);
+    if (rc) return rc;
+    const long total = n->param_off[n->nparam_blocks], nfold = (long)(W / 2) * (W + 3 * (1 + 2 * n->multires_views)) + W / 2;
+    std::vector<float> ext((size_t)(total + nfold), 0.f);
+    StreamBuilderC sf(PIPE_CB);
+    nerf_layers_c(sf, *n, ext.data(), true);
+    n->fold_chunks = (int)(sf.bytes.size() / PIPE_CB);
+    if (n->fold_chunks != nerf_mlp_c_chunks(W, D, n->skip, false))
+        return fail(EVD_E_INVALID, "evd_nerf_create: folded f16c stream has %d chunks, kernel expects %d", n->fold_chunks, nerf_mlp_c_chunks(W, D, n->skip, false));
+    rc = n->pipe_cf.upload(sf);
+    return rc ? rc : n->fold_arena.alloc(ext.size() * sizeof(float));
 }
 
 int evd_nerf_create(const evd_nerf_desc* d, evd_nerf** out) {
@@ -135,215 +164,60 @@ int evd_nerf_create(const evd_nerf_desc* d, evd_nerf** out) {
     // frequency counts other than (PE_L, PE_LV) run in the generic kernel only (no pipelined / f16c / training streams)
     EVD_REQUIRE(d->multires >= 0 && d->multires <= PE_L_MAX && d->multires_views >= 0 && pe_ksteps(d->multires_views) <= 4,
                 "evd_nerf_create: multires %d / multires_views %d out of range (0..%d / 0..10)", d->multires, d->multires_views, PE_L_MAX);
-    const int L = d->multires, Lv = d->multires_views, VKS = pe_ksteps(Lv) <= 2 ? 2 : 4;
-    const bool standard = L == PE_L && Lv == PE_LV;
+    const bool standard = d->multires == PE_L && d->multires_views == PE_LV;
     EVD_REQUIRE(d->W == 256 || d->W == 128 || d->W == 64, "evd_nerf_create: netwidth %d not built (64, 128, 256)", d->W);
     EVD_REQUIRE(d->D >= 1 && d->D <= EVD_MAX_LAYERS, "evd_nerf_create: netdepth %d out of range", d->D);
     const bool no_views = !d->views_w && !d->feature_w && !d->alpha_w && !d->rgb_w && d->output_w;
     EVD_REQUIRE(no_views || (d->views_w && d->feature_w && d->alpha_w && d->rgb_w),
                 "evd_nerf_create: give either the view branch (views / feature / alpha / rgb) or output_linear (use_viewdirs=False)");
     EVD_REQUIRE(!no_views || (d->output_b && (d->output_ch == 4 || d->output_ch == 5)), "evd_nerf_create: output_linear needs its bias and output_ch 4 or 5");
-    const int W = d->W, T = W / 32, KS = W / 16, IC = 3 * (1 + 2 * L), ICV = 3 * (1 + 2 * Lv), D = d->D;
+    const int W = d->W, KS = W / 16, D = d->D;
     evd_nerf* n = new evd_nerf();
-    n->multires = L; n->multires_views = Lv;
+    n->multires = d->multires; n->multires_views = d->multires_views;
     n->D = D; n->W = W; n->skip = d->skip; n->rgb_act = d->rgb_act; n->sigma_act = d->sigma_act; n->rmnear = d->rmnear;
     n->no_views = no_views ? 1 : 0;
 
-    // host copy of every parameter in one arena (missing biases = zeros); the packers below read from it
-    long sz[2 * EVD_MAX_LAYERS + 8];
-    nerf_param_sizes(D, W, d->skip, L, Lv, sz);
-    n->nparam_blocks = 2 * D + 8;
-    if (no_views) {                     // canonical order: pts_linears[l].{weight, bias}, then output_linear.{weight, bias}
-        sz[2 * D] = (long)d->output_ch * W; sz[2 * D + 1] = d->output_ch;
-        n->nparam_blocks = 2 * D + 2;
-    }
-    long total = 0;
-    for (int i = 0; i < n->nparam_blocks; ++i) { n->param_off[i] = total; total += sz[i]; }
-    n->param_off[n->nparam_blocks] = total;
-    std::vector<float> arena((size_t)total, 0.f);
-    {
-        const float* srcs[2 * EVD_MAX_LAYERS + 8];
-        for (int l = 0; l < D; ++l) { srcs[2 * l] = d->pts_w[l]; srcs[2 * l + 1] = d->pts_b[l]; }
-        const float* heads[8] = {d->views_w, d->views_b, d->feature_w, d->feature_b, d->alpha_w, d->alpha_b, d->rgb_w, d->rgb_b};
-        for (int i = 0; i < 8; ++i) srcs[2 * D + i] = heads[i];
-        if (no_views) { srcs[2 * D] = d->output_w; srcs[2 * D + 1] = d->output_b; }
-        for (int i = 0; i < n->nparam_blocks; ++i)
-            if (srcs[i]) memcpy(arena.data() + n->param_off[i], srcs[i], sz[i] * sizeof(float));
-    }
+    // host copy of every parameter in one arena; the packers read from it
+    ParamBlock blk[2 * EVD_MAX_LAYERS + 8];
+    n->nparam_blocks = nerf_param_blocks(d, no_views, blk);
+    const std::vector<float> arena = build_arena(blk, n->nparam_blocks, n->param_off);
     const float* A = arena.data();
-    auto P = [&](int i) { return A + n->param_off[i]; };
-    auto pts_w = [&](int l) { return P(2 * l); };
-    const float *views_w = P(2 * D), *feature_w = no_views ? nullptr : P(2 * D + 2), *alpha_w = no_views ? nullptr : P(2 * D + 4), *rgb_w = no_views ? nullptr : P(2 * D + 6);
-    const float* output_w = P(2 * D);
     const int out_rows = d->output_ch < 4 ? d->output_ch : 4;       // raw2outputs reads channels 0..3
 
-    auto pe_col = [L](int j, int kk) { return pe_src_col(L, 8 * j + (kk & 7), kk >> 3); };
-    auto hid_col = [](int j, int kk) { return 16 * j + phi(kk); };
-    auto views_col = [&](int j, int kk) {
-        if (j < KS) return hid_col(j, kk);
-        const int c = pe_src_col(Lv, 8 * (j - KS) + (kk & 7), kk >> 3);
-        return c < 0 ? -1 : W + c;
-    };
-    // pdh < 0: the skip layer's k-steps are [pe_0..3 | h_0..h_{KS-1}] (generic kernel);
-    // else [h_0..h_{pdh-1} | pe_0..3 | h_pdh..h_{KS-1}] (pipelined kernel, nerf_mlp_kernel.h)
-    auto build = [&](StreamBuilder& sb, int pdh) {
-        sb.layer(pts_w(0), W, IC, T, PE_KS, true, pe_col);
-        for (int l = 1; l < D; ++l) {
-            if (l - 1 == d->skip) {
-                auto wide_col = [&](int j, int kk) {
-                    if (pdh < 0) return j < PE_KS ? pe_col(j, kk) : IC + hid_col(j - PE_KS, kk);
-                    if (j < pdh) return IC + hid_col(j, kk);
-                    if (j < pdh + PE_KS) return pe_col(j - pdh, kk);
-                    return IC + hid_col(j - PE_KS, kk);
-                };
-                sb.layer(pts_w(l), W, W + IC, T, PE_KS + KS, true, wide_col);
-            } else {
-                sb.layer(pts_w(l), W, W, T, KS, true, hid_col);
-            }
-        }
-        if (no_views) {
-            sb.layer(output_w, out_rows, W, 1, KS, true, hid_col);
-            return;
-        }
-        sb.layer(alpha_w, 1, W, 1, KS, false, hid_col);
-        sb.layer(feature_w, W, W, T, KS, false, hid_col);
-        sb.layer(views_w, W / 2, W + ICV, T / 2, KS + VKS, false, views_col);
-        sb.layer(rgb_w, 3, W / 2, 1, KS / 2, true, hid_col);
-    };
     int rc = EVD_OK;
     for (int prec = 0; prec < EVD_NUM_PREC && !rc; ++prec) {
-        if (prec == EVD_PREC_F16C) {      // compensated float16 mode: its own stream (float16 + fp6 fragments) and row scales; pipelined kernel only
-            n->nchunks[prec] = n->pipe_chunks[prec] = 0;
-            if (no_views || !standard || !nerf_mlp_c_chunks(W, D, d->skip, false)) continue;
-            // fold: the inference stream -- no feature layer, views_linears.0 replaced by the folded layer, whose elements live behind the
-            // parameters in the extended arena (k_fold_feature); base: the arena the element -> source maps index
-            auto build_c = [&](StreamBuilderC& sc, const float* base, bool fold) {
-                auto Pb = [&](int i) { return base + n->param_off[i]; };
-                sc.arena = base;
-                const int KB = KS / 4;
-                sc.layer(Pb(0), W, IC, T, PE_KS, 2, pe_col);
-                for (int l = 1; l < D; ++l) {
-                    if (l - 1 == d->skip) {       // blocks [h_0 .. h_{KB-2} | pe | h_{KB-1}]
-                        auto wide_col = [&](int j, int kk) {
-                            if (j < 4 * (KB - 1)) return IC + c_hid_col(j, kk);
-                            if (j < 4 * (KB - 1) + PE_KS) return pe_col(j - 4 * (KB - 1), kk);
-                            return IC + c_hid_col(j - PE_KS, kk);
-                        };
-                        sc.layer(Pb(2 * l), W, W + IC, T, PE_KS + KS, 2, wide_col);
-                    } else {
-                        sc.layer(Pb(2 * l), W, W, T, KS, 2, c_hid_col);
-                    }
-                }
-                sc.layer(Pb(2 * D + 4), 1, W, 1, KS, 1, c_hid_col);
-                if (!fold) sc.layer(Pb(2 * D + 2), W, W, T, KS, 2, c_hid_col);
-                sc.layer(fold ? base + total : Pb(2 * D), W / 2, W + ICV, T / 2, KS + PEV_KS, 2, [&](int j, int kk) {
-                    if (j < KS) return c_hid_col(j, kk);
-                    const int c = pe_src_col(Lv, 8 * (j - KS) + (kk & 7), kk >> 3);
-                    return c < 0 ? -1 : W + c;
-                });
-                sc.layer(Pb(2 * D + 6), 3, W / 2, 1, KS / 2, 1, c_hid_col);
-            };
-            StreamBuilderC sc(PIPE_CB);
-            build_c(sc, A, false);
-            n->pipe_chunks[prec] = (int)(sc.bytes.size() / PIPE_CB);
-            if (n->pipe_chunks[prec] != nerf_mlp_c_chunks(W, D, d->skip, true)) rc = fail(EVD_E_INVALID, "evd_nerf_create: f16c stream has %d chunks, kernel expects %d", n->pipe_chunks[prec], nerf_mlp_c_chunks(W, D, d->skip, true));
-            if (!rc) rc = n->pipe_c.upload(sc);
-            if (rc) continue;
-            // the folded stream: the builder gives the layout and the maps (over zeros); the values are always filled on the device (below)
-            const long nfold = (long)(W / 2) * (W + ICV) + W / 2;
-            std::vector<float> ext((size_t)(total + nfold), 0.f);
-            StreamBuilderC sf(PIPE_CB);
-            build_c(sf, ext.data(), true);
-            n->fold_chunks = (int)(sf.bytes.size() / PIPE_CB);
-            if (n->fold_chunks != nerf_mlp_c_chunks(W, D, d->skip, false)) rc = fail(EVD_E_INVALID, "evd_nerf_create: folded f16c stream has %d chunks, kernel expects %d", n->fold_chunks, nerf_mlp_c_chunks(W, D, d->skip, false));
-            if (!rc) rc = n->pipe_cf.upload(sf);
-            if (!rc) rc = n->fold_arena.alloc(ext.size() * sizeof(float));
+        n->nchunks[prec] = n->pipe_chunks[prec] = 0;
+        if (prec == EVD_PREC_F16C) {
+            if (!no_views && standard && nerf_mlp_c_chunks(W, D, d->skip, false)) rc = nerf_streams_c(n, A);
             continue;
         }
         StreamBuilder sb(prec);
         sb.arena = A;
-        build(sb, -1);
+        nerf_layers(sb, *n, A, out_rows, 0);
         n->nchunks[prec] = (int)(sb.bytes.size() / chunk_bytes(prec));
-        rc = upload_stream(n->stream[prec], sb);
-        n->pipe_chunks[prec] = 0;
+        rc = n->stream[prec].upload(sb);
         if (!rc && !no_views && standard && nerf_pipe_built(prec, W, D, d->skip)) {
-            StreamBuilder sp(prec, PIPE_CB);
-            sp.arena = A;
-            sp.group = nerf_group(prec);
-            build(sp, KS - 2 * nerf_group(prec));
+            StreamBuilder sp = pipe_builder(prec, A, nerf_group(prec));
+            nerf_layers(sp, *n, A, out_rows, KS - 2 * nerf_group(prec));
             n->pipe_chunks[prec] = (int)(sp.bytes.size() / PIPE_CB);
-            rc = upload_stream(n->pipe[prec], sp);
+            rc = n->pipe[prec].upload(sp);
         }
-        // training path (bf16 / f16 / split-f16 on the pipelined network): W^T streams of the dgrad chain, one per layer (nerf_train_kernel.h)
-        if (rc || !is_train_prec(prec) || !n->pipe_chunks[prec]) continue;
-        auto put = [&](int which, auto fill) {
-            StreamBuilder sb2(prec, PIPE_CB);
-            sb2.arena = A;
-            sb2.group = 1;
-            fill(sb2);
-            return upload_stream(n->bwd[prec][which], sb2);
-        };
-        rc = put(EVD_BWD_RGB, [&](StreamBuilder& b) { b.layer_transposed(rgb_w, 3, W / 2, 0, W / 2, nullptr, 0, T / 2, 1, true, [](int, int kk) { return kk < 3 ? kk : -1; }); });
-        if (!rc) rc = put(EVD_BWD_VIEWS, [&](StreamBuilder& b) { b.layer_transposed(views_w, W / 2, W + ICV, 0, W, nullptr, 0, T, KS / 2, true, hid_col); });
-        if (!rc) rc = put(EVD_BWD_HEAD, [&](StreamBuilder& b) {
-            b.layer_transposed(feature_w, W, W, 0, W, alpha_w, 1, T, KS + 1, true, [&](int j, int kk) { return j < KS ? hid_col(j, kk) : (kk == 0 ? W : -1); });
-        });
-        // encoding rows (for the gradient w.r.t. the rays): output row idx <-> encoding column so that the output fragments come out in
-        // the encoding's own arrangement (fragment j, position kk <-> pe_src_col(L, 8 j + (kk & 7), kk >> 3))
-        auto enc_row = [](int L_, int idx) { const int j = idx / 16, kk = phi_inv(idx % 16); return pe_src_col(L_, 8 * j + (kk & 7), kk >> 3); };
-        auto enc_layer = [&](StreamBuilder& b, const float* Wm, int in_dim, int col0, int L_, int tiles, int ksteps) {
-            b.layer_at(tiles, ksteps, true, [&](int t, int r) { const int c = enc_row(L_, 32 * t + r); return c < 0 ? -1 : col0 + c; }, hid_col,
-                       [=](int r, int c) { return Wm + (size_t)c * in_dim + r; });
-        };
-        if (!rc) rc = put(EVD_BWD_PE0, [&](StreamBuilder& b) { enc_layer(b, pts_w(0), IC, 0, PE_L, 2, KS); });
-        if (!rc && d->skip >= 0 && d->skip + 1 < D) rc = put(EVD_BWD_PESKIP, [&](StreamBuilder& b) { enc_layer(b, pts_w(d->skip + 1), W + IC, 0, PE_L, 2, KS); });
-        if (!rc) rc = put(EVD_BWD_DIR, [&](StreamBuilder& b) { enc_layer(b, views_w, W + ICV, W, PE_LV, 1, KS / 2); });
-        for (int l = 1; l < D && !rc; ++l) {
-            const bool wide = l - 1 == d->skip;
-            rc = put(EVD_BWD_HIDDEN1 + l - 1, [&](StreamBuilder& b) { b.layer_transposed(pts_w(l), W, wide ? W + IC : W, wide ? IC : 0, W, nullptr, 0, T, KS, true, hid_col); });
-        }
+        // training path (bf16 / f16 / split-f16 on the pipelined network)
+        if (!rc && is_train_prec(prec) && n->pipe_chunks[prec]) rc = nerf_wt_streams(*n, prec, A);
+    }
+    if (!rc) {
+        const std::vector<int> m = nerf_wgrad_maps(*n);
+        rc = n->wmaps.upload(m.data(), m.size() * sizeof(int));
     }
     if (rc) { evd_nerf_destroy(n); return rc; }
-    {   // wgrad index maps (nerf_train.h): fragment column (fragment j = i / 16, position kk = i % 16) -> parameter row / column
-        std::vector<int> m(MAP_TOTAL, -1);
-        for (int i = 0; i < 256; ++i) {
-            m[MAP_HID + i] = hid_col(i / 16, i % 16);
-            m[MAP_HID_SKIP + i] = IC + hid_col(i / 16, i % 16);
-        }
-        for (int i = 0; i < 64; ++i) m[MAP_PE + i] = pe_col(i / 16, i % 16);
-        for (int i = 0; i < 32; ++i) {
-            const int c = pe_src_col(Lv, 8 * (i / 16) + (i % 16 & 7), (i % 16) >> 3);
-            m[MAP_DIR + i] = c < 0 ? -1 : W + c;
-        }
-        for (int i = 0; i < 3; ++i) m[MAP_RGB + i] = i;
-        m[MAP_ALPHA] = 0;
-        if ((rc = n->wmaps.upload(m.data(), m.size() * sizeof(int)))) { evd_nerf_destroy(n); return rc; }
-    }
-    // biases, one 32-float row block per output tile, in stream order
-    std::vector<float> b;
-    std::vector<int32_t> bsrc;
-    auto push = [&](int block, int out_dim, int tiles) {
-        for (int i = 0; i < tiles * 32; ++i) {
-            b.push_back(i < out_dim ? P(block)[i] : 0.f);
-            bsrc.push_back(i < out_dim ? (int32_t)(n->param_off[block] + i) : -1);
-        }
-    };
-    for (int l = 0; l < D; ++l) push(2 * l + 1, W, T);
-    if (no_views) {
-        push(2 * D + 1, out_rows, 1);
-    } else {
-        push(2 * D + 5, 1, 1);
-        push(2 * D + 3, W, T);
-        push(2 * D + 1, W / 2, T / 2);
-        push(2 * D + 7, 3, 1);
-    }
-    rc = n->bias.upload(b.data(), b.size() * sizeof(float));
-    if (!rc) rc = n->bias_src.upload(bsrc.data(), bsrc.size() * sizeof(int32_t));
+    const BiasImage b = nerf_bias_image(*n, A, out_rows);
+    rc = b.upload(n->bias, n->bias_src);
     if (!rc && n->pipe_cf.data.p) {      // folded f16c stream: its bias block (no feature tiles, bfold as the views bias), then the device fill
-        const long nw = (long)(W / 2) * (W + ICV);
-        std::vector<int32_t> fsrc(bsrc.begin(), bsrc.begin() + (D * T + 1) * 32);
+        const int T = W / 32;
+        const long total = n->param_off[n->nparam_blocks], nw = (long)(W / 2) * (W + 3 * (1 + 2 * n->multires_views));
+        std::vector<int32_t> fsrc(b.src.begin(), b.src.begin() + (D * T + 1) * 32);
         for (int i = 0; i < (T / 2) * 32; ++i) fsrc.push_back((int32_t)(total + nw + i));
-        fsrc.insert(fsrc.end(), bsrc.end() - 32, bsrc.end());
+        fsrc.insert(fsrc.end(), b.src.end() - 32, b.src.end());
         rc = n->bias_f_src.upload(fsrc.data(), fsrc.size() * sizeof(int32_t));
         if (!rc) rc = n->bias_f.alloc(fsrc.size() * sizeof(float));
         DevBuf dev_params;

@@ -2,9 +2,8 @@
 // :98-100 (its forward), trained by run_nerf.py:593-601.
 #include "awp_embed.h"
 #include "evd_common.h"
-#include "mlp_pipe.h"
+#include "frag_layout.h"
 #include "nerf_mlp.h"
-#include "pack.h"
 #include "voxel_train.h"
 
 #include <cstdint>
@@ -40,57 +39,39 @@ int evd_awp_embed_create(const float* const* weights, const float* const* biases
                 AWP_IN, AWP_W, AWP_D, input_ch, width, depth);
     for (int l = 0; l < AWP_D; ++l) EVD_REQUIRE(weights[l] && biases[l], "evd_awp_embed_create: missing layer %d", l);
     evd_awp_embed* a = new evd_awp_embed();
-    long total = 0;
+    ParamBlock blk[2 * AWP_D];
     for (int l = 0; l < AWP_D; ++l) {
-        a->param_off[2 * l] = total; total += (long)AWP_W * (l == 0 ? AWP_IN : AWP_W);
-        a->param_off[2 * l + 1] = total; total += AWP_W;
+        blk[2 * l] = {weights[l], (long)AWP_W * (l == 0 ? AWP_IN : AWP_W)};
+        blk[2 * l + 1] = {biases[l], AWP_W};
     }
-    a->param_off[2 * AWP_D] = total;
-    std::vector<float> arena((size_t)total);
-    for (int l = 0; l < AWP_D; ++l) {
-        memcpy(arena.data() + a->param_off[2 * l], weights[l], sizeof(float) * AWP_W * (l == 0 ? AWP_IN : AWP_W));
-        memcpy(arena.data() + a->param_off[2 * l + 1], biases[l], sizeof(float) * AWP_W);
-    }
+    const std::vector<float> arena = build_arena(blk, 2 * AWP_D, a->param_off);
     const float* A = arena.data();
-    auto hid_col = [](int j, int kk) { return 16 * j + phi(kk); };
     int rc = EVD_OK;
     for (int i = 0; i < 2 && !rc; ++i) {
         const int prec = i == 0 ? EVD_PREC_BF16 : EVD_PREC_F16;
-        {   // forward stream, the layer table of awp_embed_kernel.h AwpNet: single-tile groups, 16 KiB chunks
-            StreamBuilder sb(prec, PIPE_CB);
-            sb.arena = A;
-            sb.group = 1;
-            for (int l = 0; l < AWP_D; ++l) {
-                const int in_dim = l == 0 ? AWP_IN : AWP_W;
-                sb.layer(A + a->param_off[2 * l], AWP_W, in_dim, AWP_W / 32, in_dim / 16, l == AWP_D - 1, hid_col);
-            }
-            if ((long)sb.bytes.size() != (long)AWP_NCHUNKS * PIPE_CB) { evd_awp_embed_destroy(a); return fail(EVD_E_INVALID, "evd_awp_embed_create: stream geometry"); }
-            rc = a->fwd[i].upload(sb);
+        StreamBuilder sb = pipe_builder(prec, A);       // forward stream, the layer table of awp_embed_kernel.h AwpNet
+        for (int l = 0; l < AWP_D; ++l) {
+            const int in_dim = l == 0 ? AWP_IN : AWP_W;
+            sb.layer(A + a->param_off[2 * l], AWP_W, in_dim, AWP_W / 32, in_dim / 16, l == AWP_D - 1, hid_col);
         }
+        if ((long)sb.bytes.size() != (long)AWP_NCHUNKS * PIPE_CB) { evd_awp_embed_destroy(a); return fail(EVD_E_INVALID, "evd_awp_embed_create: stream geometry"); }
+        rc = a->fwd[i].upload(sb);
         for (int l = 0; l < AWP_D && !rc; ++l) {        // W_l^T streams of the dgrad chain
             const int in_dim = l == 0 ? AWP_IN : AWP_W;
-            StreamBuilder sb(prec, PIPE_CB);
-            sb.arena = A;
-            sb.group = 1;
-            sb.layer_transposed(A + a->param_off[2 * l], AWP_W, in_dim, 0, in_dim, nullptr, 0, in_dim / 32, AWP_W / 16, true, hid_col);
-            rc = a->bwd[i][l].upload(sb);
+            rc = put_wt(a->bwd[i][l], prec, A, [&](StreamBuilder& b) {
+                b.layer_transposed(A + a->param_off[2 * l], AWP_W, in_dim, 0, in_dim, nullptr, 0, in_dim / 32, AWP_W / 16, true, hid_col);
+            });
         }
     }
     if (!rc) {
-        std::vector<float> b((size_t)AWP_D * AWP_W);
-        std::vector<int32_t> bsrc(b.size());
-        for (int l = 0; l < AWP_D; ++l)
-            for (int c = 0; c < AWP_W; ++c) {
-                b[(size_t)l * AWP_W + c] = A[a->param_off[2 * l + 1] + c];
-                bsrc[(size_t)l * AWP_W + c] = (int32_t)(a->param_off[2 * l + 1] + c);
-            }
-        rc = a->bias.upload(b.data(), b.size() * sizeof(float));
-        if (!rc) rc = a->bias_src.upload(bsrc.data(), bsrc.size() * sizeof(int32_t));
+        BiasImage b(A, a->param_off);
+        for (int l = 0; l < AWP_D; ++l) b.push(2 * l + 1, AWP_W, AWP_W / 32);
+        rc = b.upload(a->bias, a->bias_src);
     }
     if (!rc) {
         std::vector<int> m(AMAP_TOTAL, -1);
-        for (int i = 0; i < AWP_W; ++i) m[AMAP_H + i] = hid_col(i / 16, i % 16);
-        for (int i = 0; i < AWP_IN; ++i) m[AMAP_GEO + i] = hid_col(i / 16, i % 16);
+        fill_map(m, AMAP_H, AWP_W, hid_col);
+        fill_map(m, AMAP_GEO, AWP_IN, hid_col);
         rc = a->maps.upload(m.data(), m.size() * sizeof(int));
     }
     if (rc) { evd_awp_embed_destroy(a); return rc; }

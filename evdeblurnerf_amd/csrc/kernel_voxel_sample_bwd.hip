@@ -385,7 +385,7 @@ __device__ __forceinline__ void vbw_walk_plane64(float* __restrict__ gp, int c, 
 }
 
 // HALF: phase 2 re-gathers the grid values from the FLOAT16 copies (GridParams::plane_h / line_h) -- the values the forward of the
-// half-precision arithmetic modes interpolated (evd_voxel_api.hip grids_half_for), so the products d coef x value are the gradient of the function
+// half-precision arithmetic modes interpolated (voxel_net.h grids_half_for), so the products d coef x value are the gradient of the function
 // that forward computed; half the gather's loads and bytes, weight x value + sum as one v_fma_mix_f32 on the float16 value (as k_voxel_sample_m).
 template <bool DPTS, bool HALF>
 __global__ __launch_bounds__(64 * VBW_WAVES, 2) void k_voxel_sample_bwd_w(const GridParams g, const float* __restrict__ pts, long n,

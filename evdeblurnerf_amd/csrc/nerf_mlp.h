@@ -1,5 +1,5 @@
-// Layout contract between the host-side weight packer (nerf_pack.cpp part of evd_api.hip) and the fused
-// NeRF MLP kernel (kernel_nerf_mlp.hip).
+// Layout contract between the host-side weight packers (pack.h builders, the arrangements of frag_layout.h) and the fused
+// MLP kernels (kernel_nerf_mlp.hip first).
 //
 // The kernel computes every layer TRANSPOSED:  D[out_feature, sample] = W[out, in] * X[in, sample]
 //   A operand (32 x 16 per MFMA k-step) = a 32-row tile of the weight matrix       -> streamed through LDS

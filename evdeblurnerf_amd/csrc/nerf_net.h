@@ -26,7 +26,7 @@ struct evd_nerf {
     int fold_chunks = 0;
     Packed bwd[EVD_NUM_PREC][EVD_BWD_NSTREAMS];   // training (bf16 / f16, 8 x 256): W^T streams; HIDDEN1 + l - 1 = pts_linears[l]
     evd::DevBuf wmaps;                       // wgrad index maps (int32), nerf_train.h
-    int nparam_blocks;                       // 2 D + 8 parameter tensors, canonical order (evd_api.hip: nerf_param_sizes)
+    int nparam_blocks;                       // 2 D + 8 parameter tensors, canonical order (evd_api.hip: nerf_param_blocks)
     long param_off[2 * EVD_MAX_LAYERS + 9];  // arena offset of each, [nparam_blocks] = total
     evd::DevBuf params_f32;                  // generic training path (nerf_train_generic.h): device copy of the parameter arena, read in place by its backward
     evd::RepackBatch batch;                  // table of every fragment stream, for the one-launch re-pack of evd_nerf_load_params

@@ -1,4 +1,4 @@
-// Shared between the tri-plane level's kernel units (kernel_voxel*.hip: kernels + launchers) and evd_voxel_api.hip (C ABI); also the one
+// Shared between the tri-plane level's kernel units (kernel_voxel*.hip: kernels + launchers) and the evd_voxel_*api.hip units (C ABI, handle: voxel_net.h); also the one
 // place where the internal launchers of kernels_rays.hip / kernels_sample_pdf.hip that the c2f render calls are declared.
 #pragma once
 

@@ -36,7 +36,7 @@ static_assert(VS::D_PE == VS::D_FTS + 2 && VS::DIRPE == VS::GEO + 2, "output fra
 // as the B operand adds nothing to the other columns)
 constexpr int A_C2 = 0, A_C1 = A_C2 + 2, A_C0 = A_C1 + 4, A_SG = A_C0 + 4, A_L0 = A_SG + 2, A_BIAS = A_L0 + 6, NBLK = A_BIAS + 1;
 constexpr int B_C2 = 0, B_C1 = 1, B_C0 = 3;       // bias columns: colour_net.2, colour_net.1 (row tiles 0, 1), colour_net.0 (row tiles 0, 1)
-// W^T fragments in LDS: per layer [output tile][k-step] (the streams of evd_voxel_api.hip, group = 1)
+// W^T fragments in LDS: per layer [output tile][k-step] (the streams of voxel_streams.h voxel_wt_streams, group = 1)
 constexpr int W_C2 = 0, W_C1 = W_C2 + 2, W_C0 = W_C1 + 8, W_SG = W_C0 + 8, W_L0 = W_SG + 6, W_N = W_L0 + 12;
 constexpr int LDS_BYTES = W_N * 1024 + 4 * 4096;
 }  // namespace f64

@@ -3,7 +3,7 @@
 // (sigmoid).  Machinery and arithmetic: mlp_pipe_c.h (one float16 MFMA product + two block-scaled fp6 products of the operands' rounding
 // residuals, one wavefront of 32 samples per SIMD).  This is the mode the shipped (mode='c2f') configurations are rendered in when the
 // 1e-4 RGB bound has to hold on trained weights: the single-product float16 mode measures 3.8e-4 there (tools/trained_c2f.py).
-// No feature rows; the coarse 64-wide level runs in EVD_PREC_F16X3 next to it (evd_voxel_api.hip).
+// No feature rows; the coarse 64-wide level runs in EVD_PREC_F16X3 next to it (evd_voxel_render_api.hip).
 // TRAIN variant (round 4): the same arithmetic, and every completed input / hidden / geo block also goes to the activation store of the
 // single-product float16 mode (voxel_mlp_kernel.h VStore: float16 fragments in that mode's arrangement + the ReLU patterns as bit masks,
 // both taken from the COMPENSATED pre-activations), so that the level's backward is that mode's dgrad / wgrad chain unchanged.  This is
@@ -43,7 +43,7 @@ template <int HD, int G, int FT, bool TRAIN = false> struct VoxNetC {
 };
 
 // one input block from 64 float32 values of a row: B position q = 8 j + e of lane half h <-> value 16 j + 8 h + e (the natural k-step order
-// of evd_voxel_api.hip in0_col), all three representations
+// of voxel_streams.h voxel_layers_c), all three representations
 __device__ __forceinline__ void c_block_from_row(const float* f, XBlk& out) {
     f32x16 r[2];               // element i = 8 j + e of the block is pair i / 2, member i & 1 (mlp_pipe_c.h c_drain_pair)
 #pragma unroll
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(CCfg::NT, 1) void k_voxel_mlp_c(const VoxMlpParams 
     ST st;
     st.start_issue(p.wstream, smem, tid);
     float* bias = reinterpret_cast<float*>(smem + CCfg::RING);
-    // bias image (zeros for the sigma net, then the colour-net biases: p.bias = 512 zeros + colour biases, evd_voxel_api.hip) and row scales
+    // bias image (zeros for the sigma net, then the colour-net biases: p.bias = 512 zeros + colour biases, evd_voxel_api.hip evd_voxel_create) and row scales
     for (int i = tid; i < N::B_END; i += CCfg::NT) {
         bias[i] = i < N::B_C0 ? 0.f : p.bias[512 + (i - N::B_C0)];
         reinterpret_cast<unsigned*>(bias)[CCfg::BIAS_WORDS / 2 + i] = p.wscale[i];

@@ -1,7 +1,7 @@
 // Software-pipelined PDRF level network (fine: hidden 256, geo 128, 64 feature channels in; coarse: 64 / 15 / 32; reference
 // networks/pdrf/voxnerf.py:210-221,240-254 with the blurfactory dimensions): sigma net 127 -> 256 -> 1 + 128,
 // colour net 155 -> 256 -> 256 -> 3 (sigmoid), on the machinery of mlp_pipe.h.  One straight-line stream of 368
-// MFMAs per wavefront; layer table below.  Both levels read ONE packed stream per arithmetic mode (evd_voxel_api.hip `fwd`), in render
+// MFMAs per wavefront; layer table below.  Both levels read ONE packed stream per arithmetic mode (voxel_net.h `fwd`), in render
 // and in training.  Which kernel walks it:
 //   fine level     k_voxel_mlp_pipe: render (launch_voxel_pipe, FEAT with feature rows) and training forward (TRAIN)
 //   coarse level   render: k_voxel_mlp_resident from 65536 samples (round 6: the whole weight stream resident in LDS, persistent
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(NT, OCC) void k_voxel_mlp_pipe(const VoxMlpParams p
     }
 }
 
-// Inference on the software pipeline, either level, on the level's one forward stream (evd_voxel_api.hip `fwd`).  FEAT: the float32
+// Inference on the software pipeline, either level, on the level's one forward stream (voxel_net.h `fwd`).  FEAT: the float32
 // feature rows too (fine level).  The 64-wide coarse level comes here below 65536 samples (launch_voxel_resident_level); it is
 // prologue-bound, not MFMA-bound: 86 us per 4096 x 64 samples, the same as the generic kernel.
 // (Measured and dropped: 256-thread workgroups walking the same stream in 8 KiB chunks -- 72 KiB of LDS, two workgroups per CU
@@ -348,7 +348,7 @@ static int launch_voxel_resident_level(const VoxMlpParams& p, hipStream_t st) {
     const int cus = device_cus();
     const long groups = cdiv(p.nsamp, (long)C::SAMPLES);
     if constexpr (PREC == EVD_PREC_F16X3) {
-        // the coarse level of an f16c RENDER (p.rev_trig, evd_voxel_api.hip): sines as in that mode's fine-level kernel
+        // the coarse level of an f16c RENDER (p.rev_trig, evd_voxel_render_api.hip): sines as in that mode's fine-level kernel
         if (p.rev_trig) {
             EVD_SET_MAX_LDS((&k_voxel_mlp_resident<PREC, HD, G, FT, NT, false, false, true>), lds);
             hipLaunchKernelGGL((k_voxel_mlp_resident<PREC, HD, G, FT, NT, false, false, true>), dim3((unsigned)(groups < cus ? groups : cus)), dim3(NT), lds, st, p);

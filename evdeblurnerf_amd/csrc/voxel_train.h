@@ -1,4 +1,4 @@
-// Launchers / plans of the PDRF training kernels (kernel_voxel_train_*.hip), called by evd_voxel_api.hip.
+// Launchers / plans of the PDRF training kernels (kernel_voxel_train_*.hip), called by evd_voxel_train_api.hip.
 #pragma once
 
 #include "evd_common.h"
@@ -52,7 +52,7 @@ int launch_voxel_train_fwd_f16x3_hi(int HD, const VoxMlpParams& p, hipStream_t s
 int run_voxel_backward_f16(int HD, const VoxBwdPlan& b, hipStream_t st);
 int run_voxel_backward_bf16(int HD, const VoxBwdPlan& b, hipStream_t st);
 int run_voxel_backward_f16x3(int HD, const VoxBwdPlan& b, hipStream_t st);
-// prec: one of the modes the training kernels are built for (is_train_prec), checked by the callers (evd_voxel_api.hip vox_train_built)
+// prec: one of the modes the training kernels are built for (is_train_prec), checked by the callers (voxel_net.h vox_train_built)
 inline int launch_voxel_train_fwd_dispatch(int prec, int HD, const VoxMlpParams& p, hipStream_t st) {
     return prec == EVD_PREC_F16 ? launch_voxel_train_fwd_f16(HD, p, st)
            : prec == EVD_PREC_BF16 ? launch_voxel_train_fwd_bf16(HD, p, st) : launch_voxel_train_fwd_f16x3(HD, p, st);

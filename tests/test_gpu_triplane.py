@@ -33,7 +33,7 @@ F = 32
 
 # n_comp -> (is every component a multiple of 8, ct % 32 == 0 and ct <= 96, every component in {16, 32, 64})
 SHAPES = {"shipped": (64, 16, 16), "ct80": (32, 16, 32), "c12": (48, 12, 12), "ct128": (64, 32, 32), "c16": (16, 16, 16)}
-# a mode's level and whether its gather reads the float16 grid copies (evd_voxel_api.hip grids_half_for): f16c on the FINE level of a
+# a mode's level and whether its gather reads the float16 grid copies (voxel_net.h grids_half_for): f16c on the FINE level of a
 # c2f pair (a level fed by the previous one: ft_dim 64 > app_dim) reads them, on the coarse level it does not
 MODES = {"f32": ("fine", False), "f16x3": ("fine", False), "f16": ("fine", True), "bf16": ("fine", True), "f16c": ("fine", True),
          "f16c_coarse": ("coarse", False)}

@@ -1,4 +1,4 @@
-"""Every arm of the PDRF level inference pass (evd_voxel_forward -> voxel_level_forward, csrc/evd_voxel_api.hip) against the float64
+"""Every arm of the PDRF level inference pass (evd_voxel_forward -> voxel_level_forward, csrc/evd_voxel_render_api.hip) against the float64
 reference of tests/voxel_level_ref.py, at the sizes where its tiling, its column maps and its kernel thresholds change.
 
 Arms (the first field of a case id; voxel_level_ref.expected_arm re-derives it from the case's construction, and run() asserts what the

@@ -28,7 +28,7 @@ bounds            bound(X) = 4 E_q(X) + floor(X) + composite_ref's own E_X 2^-24
                            move the rows).
 Nothing measured on a kernel enters a bound.
 
-CASES is the arm matrix: every case names the arm of voxel_level_forward (csrc/evd_voxel_api.hip) it reaches, and expected_arm()
+CASES is the arm matrix: every case names the arm of voxel_level_forward (csrc/evd_voxel_render_api.hip) it reaches, and expected_arm()
 re-derives that arm from the case's construction alone, mirroring the dispatch.
 
 Layouts.  Per-sample (S <= 3): z = 0, 1, 2 on unit rays_d, one view direction per ray.  Per-ray: sorted uniform z in (0, 1) on N(0, 1)
@@ -177,7 +177,7 @@ def case(arm, level, mode, R, S, entry, bias=True, ft_scale=0.3, enc=(10, 4), co
 
 
 def expected_arm(c):
-    """the arm of voxel_level_forward a case reaches, from its construction (the dispatch of csrc/evd_voxel_api.hip restated)"""
+    """the arm of voxel_level_forward a case reaches, from its construction (the dispatch of csrc/evd_voxel_render_api.hip restated)"""
     coarse, n = c["level"] == "coarse", c["R"] * c["S"]
     rows = c["composite_feature"] or (c["entry"] == "forward" and c["mode"] != "f16c")
     mode, rev = c["mode"], False
