@@ -103,6 +103,14 @@ class SparseBlurParams(C.Structure):
                 ("linears1_w", _vp * 2), ("linears1_b", _vp * 2)]
 
 
+class ViewEmbedMlpDesc(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("n_img", "embed_dim", "W", "D")] + [("skip_mask", C.c_uint)]
+
+
+class ViewEmbedMlpParams(C.Structure):
+    _fields_ = [("table", _vp), ("w", _vp * 8), ("b", _vp * 8)]
+
+
 class AdamSegment(C.Structure):
     _fields_ = [("param", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("mirror_f32", _vp), ("mirror_f16", _vp), ("n", C.c_long), ("group", C.c_int), ("clip", C.c_int)]
 
@@ -148,6 +156,9 @@ SIGNATURES = {
                                      _vp, _S, _vp]),
     "evd_sparse_blur_backward": (_I, [C.POINTER(SparseBlurDesc), C.POINTER(SparseBlurParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _L, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _S, _vp]),
+    "evd_view_embed_mlp_workspace_bytes": (_S, [C.POINTER(ViewEmbedMlpDesc)]),
+    "evd_view_embed_mlp_forward": (_I, [C.POINTER(ViewEmbedMlpDesc), C.POINTER(ViewEmbedMlpParams), _vp, _vp]),
+    "evd_view_embed_mlp_backward": (_I, [C.POINTER(ViewEmbedMlpDesc), C.POINTER(ViewEmbedMlpParams), _vp, _vp, _vp, _S, _vp]),
     "evd_awp_feature_integration": (_I, [_vp, _vp, _vp, _L, _I, _I, _vp, _vp]),
     "evd_awp_feature_integration_bwd": (_I, [_vp, _vp, _vp, _vp, _L, _I, _I, _vp, _vp, _vp, _vp]),
     "evd_mam_local_forward": (_I, [_vp, _vp, _L, _I, _I, _I, _vp, _vp, _vp, _vp, _vp]),

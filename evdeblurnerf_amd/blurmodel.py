@@ -1,8 +1,8 @@
-"""Mirrors of the reference's blur kernel networks, with its ``ViewEmbedding`` (networks/embedding.py:6-32), as run_nerf.py:167-215 builds
-them: ``RigidBlurKernel`` for ``RigidBlurringModel`` (networks/dpnerf/blurmodel.py:9-173, kernel_type RBK) and ``SparseBlurKernel`` for
+"""Mirrors of the reference's blur kernel networks, with its ``ViewEmbedding`` and ``ViewEmbeddingMLP`` (networks/embedding.py:6-62), as
+run_nerf.py:167-215 builds them: ``RigidBlurKernel`` for ``RigidBlurringModel`` (networks/dpnerf/blurmodel.py:9-173, kernel_type RBK) and ``SparseBlurKernel`` for
 ``BlurModel`` (networks/pdrf/blurmodel.py:9-224, kernel_type DSK and PBE).  A module carries the reference's parameter names, shapes and
 initialisation, so a reference checkpoint's ``kernelsnet.*`` keys load; its forward and backward are launches of the library
-(evd_rigid_blur_* / evd_sparse_blur_*) that read the parameters in place."""
+(evd_rigid_blur_* / evd_sparse_blur_* / evd_view_embed_mlp_*) that read the parameters in place."""
 from __future__ import annotations
 
 import ctypes as C
@@ -34,6 +34,98 @@ class ViewEmbedding(nn.Module):
 
     def forward(self, x):
         return self.img_embed[x]
+
+
+class _ViewEmbedMlpFn(torch.autograd.Function):
+    """(img_embed, the D layers' weights and biases) -> feature table [n_img, W]"""
+
+    @staticmethod
+    def forward(ctx, desc, table, *net):
+        out = torch.empty((desc.n_img, desc.W), dtype=torch.float32, device=table.device)
+        prm = _view_embed_params(table, net)
+        L.check(L.lib().evd_view_embed_mlp_forward(C.byref(desc), C.byref(prm), L.ptr(out), L.stream_ptr()), "evd_view_embed_mlp_forward")
+        ctx.desc = desc
+        ctx.save_for_backward(table, *net)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        desc = ctx.desc
+        table, *net = ctx.saved_tensors
+        leaves = (table,) + tuple(net)
+        flat = torch.empty((sum(t.numel() for t in leaves),), dtype=torch.float32, device=table.device)
+        lib = L.lib()
+        need = int(lib.evd_view_embed_mlp_workspace_bytes(C.byref(desc)))
+        ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=table.device)
+        prm = _view_embed_params(table, net)
+        L.check(lib.evd_view_embed_mlp_backward(C.byref(desc), C.byref(prm), L.ptr(d_out.float().contiguous()), L.ptr(flat), L.ptr(ws), need,
+                                                L.stream_ptr()), "evd_view_embed_mlp_backward")
+        grads, o = [], 0
+        for t in leaves:                                         # the flat buffer sliced into the leaves' gradients
+            grads.append(flat[o:o + t.numel()].view(t.shape))
+            o += t.numel()
+        return (None, *grads)
+
+
+def _view_embed_params(table, net):
+    prm = L.ViewEmbedMlpParams()
+    for name, t in (("img_embed", table),) + tuple((f"view_embed_linears[{i // 2}]", t) for i, t in enumerate(net)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise L.EvdError(f"ViewEmbeddingMLP: parameter {name} must be contiguous float32")
+    prm.table = table.data_ptr()
+    for i in range(min(len(net) // 2, 8)):                       # (a deeper network is refused by the library: D)
+        prm.w[i], prm.b[i] = net[2 * i].data_ptr(), net[2 * i + 1].data_ptr()
+    return prm
+
+
+class ViewEmbeddingMLP(ViewEmbedding):
+    """networks/embedding.py:35-62 ('param_mlp': the per-image row through a ReLU MLP, the row concatenated in front of a skip layer's
+    output).  The MLP's input depends on the image only, so `feature_table()` evaluates it once per image on the device
+    (evd_view_embed_mlp_*); the blur kernel modules gather from that table by image id."""
+
+    def __init__(self, D, W, skips, num_embed, embed_dim, init_params="zero"):
+        super().__init__(num_embed, embed_dim, init_params)
+        self.D, self.W, self.skips, self.out_channels = D, W, skips, W
+        self.view_embed_linears = nn.ModuleList([nn.Linear(embed_dim, W)] +
+                                                [nn.Linear(W + embed_dim if i in skips else W, W) for i in range(D - 1)])
+
+    def _desc(self):
+        mask = sum(1 << int(i) for i in set(self.skips) if 0 <= int(i) < 32)
+        return L.ViewEmbedMlpDesc(n_img=self.img_embed.shape[0], embed_dim=self.img_embed.shape[1], W=self.W, D=len(self.view_embed_linears), skip_mask=mask)
+
+    def feature_table(self):
+        """[num_embed, W]: row i = the module's value for image i"""
+        net = tuple(t for m in self.view_embed_linears for t in (m.weight, m.bias))
+        return _ViewEmbedMlpFn.apply(self._desc(), self.img_embed, *net)
+
+    def forward(self, x):
+        return self.feature_table()[x]
+
+    @classmethod
+    def from_state_dict(cls, sd, prefix=""):
+        """the module that the tensors `<prefix>img_embed`, `<prefix>view_embed_linears.*` describe (not loaded): D, W and E from the shapes,
+        the skips from the layers that are E + W wide"""
+        num_embed, E = sd[prefix + "img_embed"].shape
+        D = len([k for k in sd if k.startswith(prefix + "view_embed_linears.") and k.endswith(".weight")])
+        W = sd[prefix + "view_embed_linears.0.weight"].shape[0]
+        skips = [i - 1 for i in range(1, D) if sd[f"{prefix}view_embed_linears.{i}.weight"].shape[1] == E + W]
+        return cls(D, W, skips, num_embed, E)
+
+
+def _embedding_from_args(args, n_imgs, who):
+    """run_nerf.py:168-175: the 'param' ViewEmbedding (None: the kernel module builds it) or the 'param_mlp' ViewEmbeddingMLP"""
+    kind = getattr(args, "kernel_img_embed_type", "param")
+    if kind == "param":
+        return None
+    if kind == "param_mlp":
+        return ViewEmbeddingMLP(D=args.kernel_img_mlp_depth, W=args.kernel_img_mlp_embed, skips=[args.kernel_img_mlp_skips], num_embed=n_imgs,
+                                embed_dim=args.kernel_img_embed, init_params=getattr(args, "kernel_img_embed_init", "zero"))
+    raise L.EvdError(f"{who}.from_args: kernel_img_embed_type {kind!r}: pass the embedding module as view_embed")
+
+
+def _feature_table(module):
+    """the table a blur kernel entry gathers from by image id: the 'param' rows themselves, or the 'param_mlp' module's per-image values"""
+    return module.feature_table() if type(module) is ViewEmbeddingMLP else module.img_embed
 
 
 class _RigidBlurFn(torch.autograd.Function):
@@ -91,8 +183,9 @@ def _params(table, net):
 
 class RigidBlurKernel(nn.Module):
     """RigidBlurringModel (networks/dpnerf/blurmodel.py:9-49,129-173).  `view_embed`: None builds the 'param' ViewEmbedding of
-    run_nerf.py:168-170 (n_imgs x embed_dim), whose rows the kernel gathers itself; any other module (the reference's
-    ViewEmbeddingMLP, :171-175) stays PyTorch in front of the kernel and hands it per-ray rows, as does a `feats` input."""
+    run_nerf.py:168-170 (n_imgs x embed_dim), whose rows the kernel gathers itself; a ViewEmbeddingMLP of this module ('param_mlp',
+    :171-175) is evaluated once per image and the kernel gathers from that table; a module of any other type stays PyTorch in front of
+    the kernel and hands it per-ray rows, as does a `feats` input."""
 
     def __init__(self, n_imgs, embed_dim=32, embed_init="zero", num_motion=9, D_r=1, W_r=32, D_v=1, W_v=32, D_w=1, W_w=32,
                  output_ch_r=3, output_ch_v=3, feat_ch=0, rv_window=0.1, use_origin=True, view_embed=None, use_view_embed=True):
@@ -124,16 +217,13 @@ class RigidBlurKernel(nn.Module):
 
     @classmethod
     def from_args(cls, args, n_imgs):
-        """the constructor call of run_nerf.py:168-170,204-215 ('param' embedding)"""
-        kind = getattr(args, "kernel_img_embed_type", "param")
-        if kind != "param":
-            raise L.EvdError(f"RigidBlurKernel.from_args: kernel_img_embed_type {kind!r}: pass the embedding module as view_embed")
+        """the constructor call of run_nerf.py:168-175,204-215 ('param' and 'param_mlp' embeddings)"""
         return cls(n_imgs, embed_dim=args.kernel_img_embed, embed_init=getattr(args, "kernel_img_embed_init", "zero"),
                    num_motion=args.kernel_ptnum - 1, D_r=args.kernel_rbk_se_r_depth, W_r=args.kernel_rbk_se_r_width,
                    D_v=args.kernel_rbk_se_v_depth, W_v=args.kernel_rbk_se_v_width, D_w=args.kernel_rbk_ccw_depth, W_w=args.kernel_rbk_ccw_width,
                    output_ch_r=args.kernel_rbk_se_r_output_ch, output_ch_v=args.kernel_rbk_se_v_output_ch,
                    feat_ch=getattr(args, "kernel_rbk_extra_feat_ch", 0), rv_window=args.kernel_rbk_se_rv_window,
-                   use_origin=args.kernel_rbk_use_origin)
+                   use_origin=args.kernel_rbk_use_origin, view_embed=_embedding_from_args(args, n_imgs, "RigidBlurKernel"))
 
     @classmethod
     def from_state_dict(cls, sd, rv_window=0.1, use_origin=True, prefix=""):
@@ -141,14 +231,15 @@ class RigidBlurKernel(nn.Module):
         sd = {k[len(prefix):]: torch.as_tensor(v) for k, v in sd.items() if k.startswith(prefix)}
         depth = lambda b: len([k for k in sd if k.startswith(f"{b}_branch.") and k.endswith(".weight")])
         n_imgs, embed_dim = sd["view_embed_module.img_embed"].shape
+        mlp = ViewEmbeddingMLP.from_state_dict(sd, "view_embed_module.") if "view_embed_module.view_embed_linears.0.weight" in sd else None
         M = sd["w_linear.weight"].shape[0] - 1
-        extra = sd["r_branch.0.weight"].shape[1] - embed_dim
+        extra = sd["r_branch.0.weight"].shape[1] - (mlp.out_channels if mlp else embed_dim)
         slots = M + 1 if use_origin else M
         if extra < 0 or extra % slots:
             raise L.EvdError("RigidBlurKernel.from_state_dict: branch input width does not fit the embedding")
         mod = cls(n_imgs, embed_dim=embed_dim, num_motion=M, D_r=depth("r"), W_r=sd["r_branch.0.weight"].shape[0], D_v=depth("v"),
                   W_v=sd["v_branch.0.weight"].shape[0], D_w=depth("w"), W_w=sd["w_branch.0.weight"].shape[0], feat_ch=extra // slots,
-                  rv_window=rv_window, use_origin=use_origin)
+                  rv_window=rv_window, use_origin=use_origin, view_embed=mlp)
         mod.load_state_dict(sd)
         return mod
 
@@ -163,9 +254,9 @@ class RigidBlurKernel(nn.Module):
         net = (self.r_branch[0].weight, self.r_branch[0].bias, self.v_branch[0].weight, self.v_branch[0].bias, self.w_branch[0].weight,
                self.w_branch[0].bias, self.r_linear.weight, self.r_linear.bias, self.v_linear.weight, self.v_linear.bias, self.w_linear.weight,
                self.w_linear.bias)
-        table_form = type(self.view_embed_module) is ViewEmbedding and self.use_view_embed and self.feat_ch == 0
+        table_form = type(self.view_embed_module) in (ViewEmbedding, ViewEmbeddingMLP) and self.use_view_embed and self.feat_ch == 0
         if table_form:
-            table = self.view_embed_module.img_embed
+            table = _feature_table(self.view_embed_module)
             ids = ids.to(torch.int64).contiguous()
             new_rays, weight, img_embed = _RigidBlurFn.apply(self._desc(table.shape[1], table.shape[0]), rays, ids, None, table, *net)
         else:
@@ -252,7 +343,8 @@ def init_linear_weights(m):
 class SparseBlurKernel(nn.Module):
     """BlurModel (networks/pdrf/blurmodel.py:9-224), kernel_type 'DSK' or 'PBE', under the reference's argument names and defaults.
     `view_embed`: None builds the 'param' ViewEmbedding of run_nerf.py:168-170 (num_img x view_embed_cnl, `embed_init`), whose rows the kernel
-    gathers itself; any other module stays PyTorch in front of the kernel and hands it per-ray rows.  `noise` of forward is the [R, P, 2]
+    gathers itself; a ViewEmbeddingMLP of this module ('param_mlp', :171-175; view_embed_cnl = its W) is evaluated once per image and the kernel
+    gathers from that table; a module of any other type stays PyTorch in front of the kernel and hands it per-ray rows.  `noise` of forward is the [R, P, 2]
     standard-normal draw the reference takes with randn_like (in eval mode too); None draws it on the device when random_hwindow > 0."""
     TILE_ROWS = 16            # a tile of the kernels holds TILE_ROWS // num_pt whole rays
     GRID_CAP = 128            # ... and at most this many workgroups share a batch's tiles
@@ -294,16 +386,15 @@ class SparseBlurKernel(nn.Module):
 
     @classmethod
     def from_args(cls, args, n_imgs, poses=None):
-        """the constructor call of run_nerf.py:168-170,184-203 ('param' embedding)"""
-        kind = getattr(args, "kernel_img_embed_type", "param")
-        if kind != "param":
-            raise L.EvdError(f"SparseBlurKernel.from_args: kernel_img_embed_type {kind!r}: pass the embedding module as view_embed")
+        """the constructor call of run_nerf.py:168-175,184-203 ('param' and 'param_mlp' embeddings)"""
+        view_embed = _embedding_from_args(args, n_imgs, "SparseBlurKernel")
         return cls(n_imgs, args.kernel_ptnum, args.kernel_hwindow, args.kernel_type, random_hwindow=args.kernel_random_hwindow,
                    in_embed=args.kernel_rand_embed, random_mode=args.kernel_random_mode, spatial_embed=args.kernel_spatial_embed,
                    depth_embed=args.kernel_depth_embed, num_hidden=args.kernel_num_hidden, num_wide=args.kernel_num_wide, feat_cnl=args.kernel_feat_cnl,
                    short_cut=args.kernel_shortcut, pattern_init_radius=args.kernel_pattern_init_radius, isglobal=args.kernel_isglobal,
                    optim_trans=args.kernel_global_trans, optim_spatialvariant_trans=args.kernel_spatialvariant_trans,
-                   view_embed_cnl=args.kernel_img_embed, embed_init=getattr(args, "kernel_img_embed_init", "zero"), poses=poses)
+                   view_embed_cnl=args.kernel_img_embed if view_embed is None else view_embed.out_channels,
+                   embed_init=getattr(args, "kernel_img_embed_init", "zero"), poses=poses, view_embed=view_embed)
 
     @classmethod
     def from_state_dict(cls, sd, kernel_type, kernel_hwindow, random_hwindow=0.25, in_embed=3, spatial_embed=0, isglobal=None, random_mode="input", prefix=""):
@@ -311,6 +402,8 @@ class SparseBlurKernel(nn.Module):
         size but the two embedding depths (and, when there is one image, isglobal): those are arguments."""
         sd = {k[len(prefix):]: torch.as_tensor(v) for k, v in sd.items() if k.startswith(prefix)}
         num_img, embed = sd["img_embed.img_embed"].shape
+        mlp = ViewEmbeddingMLP.from_state_dict(sd, "img_embed.") if "img_embed.view_embed_linears.0.weight" in sd else None
+        embed = mlp.out_channels if mlp else embed
         n_pat, num_pt, _ = sd["pattern_pos"].shape
         isglobal = (n_pat == 1 and num_img != 1) if isglobal is None else isglobal
         num_wide, in_cnl = sd["linears.0.weight"].shape
@@ -322,7 +415,7 @@ class SparseBlurKernel(nn.Module):
         mod = cls(num_img, num_pt, kernel_hwindow, kernel_type, random_hwindow=random_hwindow, in_embed=in_embed, random_mode=random_mode,
                   view_embed_cnl=embed, spatial_embed=spatial_embed, num_hidden=num_hidden, num_wide=num_wide, feat_cnl=feat_cnl if kernel_type == "PBE" else 15,
                   short_cut=sd["linears1.0.weight"].shape[1] > num_wide, isglobal=isglobal, optim_trans="pattern_trans" in sd,
-                  optim_spatialvariant_trans=sd["linears1.2.weight"].shape[0] == 5, poses=sd.get("poses"))
+                  optim_spatialvariant_trans=sd["linears1.2.weight"].shape[0] == 5, poses=sd.get("poses"), view_embed=mlp)
         mod.load_state_dict(sd)
         return mod
 
@@ -356,8 +449,8 @@ class SparseBlurKernel(nn.Module):
         else:
             feats = None
         trans = self.pattern_trans if self.optim_trans else None
-        if type(self.img_embed) is ViewEmbedding:
-            table = self.img_embed.img_embed
+        if type(self.img_embed) in (ViewEmbedding, ViewEmbeddingMLP):
+            table = _feature_table(self.img_embed)
             out = _SparseBlurFn.apply(self._desc(H, W, K, table.shape[1], table.shape[0]), ids, None, rays_x, rays_y, poses, noise, feats, self.pattern_pos,
                                       trans, table, *self._net())
             new_rays, weight, align, img_embed = out

@@ -158,6 +158,32 @@ int evd_sparse_blur_backward(const evd_sparse_blur_desc* d, const evd_sparse_blu
                              const float* rays_y, const float* poses, const float* noise, const float* feats, long R, const float* d_new_rays,
                              const float* d_weight, const float* d_align, const float* d_img_embed, float* grads, float* d_x, float* d_feats,
                              void* workspace, size_t workspace_bytes, void* stream);
+/* ViewEmbeddingMLP, networks/embedding.py:35-62 (built at run_nerf.py:171-175 for kernel_img_embed_type 'param_mlp'), evaluated once per
+ * IMAGE instead of once per ray: the module's input is a function of the image id only, so its values form a table [n_img, W] that
+ * evd_rigid_blur_* / evd_sparse_blur_* take as their `table` and gather from by ids.  Layer i is h = relu(w[i] h + b[i]); after a skip
+ * index i the next layer reads cat([embedding row, h]) (embedding columns first, :59-60), so its weight is [W, embed_dim + W].  Float32,
+ * the parameters are the module's own tensors in torch layout, read in place: nothing is packed and no handle is kept.
+ *   n_img 1..4096, embed_dim 1..128, W 1..128, D 1..8 layers; skip_mask bit i = skip index i: any set within 0..D-2, a bit >= D is inert
+ *   (the reference's default skips=[4] with D=4), bit D-1 is refused (the module would return embed_dim + W columns under an
+ *   out_channels of W).  Anything else: EVD_E_INVALID naming the field. */
+typedef struct {
+    int n_img, embed_dim, W, D;
+    unsigned skip_mask;
+} evd_view_embed_mlp_desc;
+typedef struct {
+    const float* table;                                      /* img_embed dev [n_img, embed_dim] */
+    const float *w[8], *b[8];                                /* view_embed_linears.{i}: dev [W, embed_dim | W | embed_dim + W], [W] */
+} evd_view_embed_mlp_params;
+/* networks/embedding.py:35-62: bytes of the backward's workspace (0 for an unsupported descriptor) */
+size_t evd_view_embed_mlp_workspace_bytes(const evd_view_embed_mlp_desc* d);
+/* networks/embedding.py:51-62 on every row of img_embed, one launch -> feature_table dev [n_img, W].  A row's value does not depend on
+ * its position in the table. */
+int evd_view_embed_mlp_forward(const evd_view_embed_mlp_desc* d, const evd_view_embed_mlp_params* p, float* feature_table, void* stream);
+/* torch.autograd of networks/embedding.py:51-62: two launches (the hidden layers are recomputed), no atomics, the same bits on every run.
+ * d_feature_table dev [n_img, W] -> grads dev: one flat float32 buffer in the params' order (table [n_img, embed_dim], then w[0], b[0],
+ * ...), overwritten.  An image whose d_feature_table row is zero gets a zero table row and adds nothing to the other gradients. */
+int evd_view_embed_mlp_backward(const evd_view_embed_mlp_desc* d, const evd_view_embed_mlp_params* p, const float* d_feature_table, float* grads,
+                                void* workspace, size_t workspace_bytes, void* stream);
 /* The NaN / Inf guard of render_rays, networks/renderer.py:259-263 (there: isnan().any() + isinf().any() per result key = two
  * host synchronisations per key).  Here one launch: ptrs host[n_keys] (device arrays), counts host[n_keys] (floats per array),
  * n_keys <= 16 -> flags dev [n_keys] (unsigned): bit 0 = the key contains a NaN, bit 1 = an Inf.  Nothing synchronises; the caller

@@ -1962,12 +1962,182 @@ def G39_sparse_blur():
     print(f"  wrote {os.path.relpath(path, ROOT)}  ({os.path.getsize(path) / 1024:.1f} KiB)")
 
 
+# --------------------------------------------------------------------------- G40: ViewEmbeddingMLP ('param_mlp'), alone and in front of both blur models
+VIEW_EMBED_CASES = {          # ViewEmbeddingMLP constructor arguments; R rays; M, use_origin of the rigid model behind it
+    "shipped": dict(D=4, W=32, skips=[4], n=34, E=32, seed=4001, R=24, M=9, use_origin=True),       # run_nerf.py's defaults: the skip never fires
+    "skip": dict(D=4, W=32, skips=[1], n=17, E=32, seed=4002, R=24, M=9, use_origin=True),
+    "odd": dict(D=3, W=20, skips=[0], n=7, E=24, seed=4003, R=37, M=4, use_origin=False),
+    "one": dict(D=1, W=7, skips=[4], n=1, E=5, seed=4004, R=5, M=2, use_origin=True),
+    "wide": dict(D=2, W=64, skips=[0], n=33, E=48, seed=4005, R=24, M=4, use_origin=True),
+}
+
+
+def _view_embed_module(c, sd, dtype):
+    from networks.embedding import ViewEmbeddingMLP
+    torch.manual_seed(c["seed"])
+    ve = ViewEmbeddingMLP(D=c["D"], W=c["W"], skips=c["skips"], num_embed=c["n"], embed_dim=c["E"], init_params="normal")
+    if sd is not None:
+        ve.load_state_dict({k: t(v) for k, v in sd.items()}, strict=True)
+    return ve.to(dtype)
+
+
+def _view_embed_alone(ve, ids, proj, dtype):
+    with torch.enable_grad():
+        rows = ve(t(ids)[:, 0])
+        named = list(ve.named_parameters())
+        g = torch.autograd.grad((rows * t(proj).to(dtype)).sum(), [p for _, p in named])
+    table = ve(torch.arange(ve.img_embed.shape[0]))
+    return dict(rows=n(rows), table=n(table)), {k: n(gi) for (k, _), gi in zip(named, g)}
+
+
+def _view_embed_fence(sd, c):
+    """the smallest |pre| / (sum |w||x| + |b|) of any unit, layer and image in float64, and that layer's threshold 2 D (K + 1) 2^-24"""
+    e = sd["img_embed"].astype(np.float64)
+    h, worst = e, (np.inf, 1.0)
+    for i in range(c["D"]):
+        w, b = sd[f"view_embed_linears.{i}.weight"].astype(np.float64), sd[f"view_embed_linears.{i}.bias"].astype(np.float64)
+        pre = h @ w.T + b
+        margin, thr = float((np.abs(pre) / (np.abs(h) @ np.abs(w).T + np.abs(b))).min()), 2.0 * c["D"] * (w.shape[1] + 1) * 2.0 ** -24
+        if margin / thr < worst[0] / worst[1]:
+            worst = (margin, thr)
+        h = np.maximum(pre, 0.0)
+        if i in c["skips"]:
+            h = np.concatenate([e, h], -1)
+    return worst
+
+
+def _record_errors(out, pre, o32, o64, g32, g64, skip_out=()):
+    for k in o32:
+        if k not in skip_out:
+            out[pre + "ref_f32_err.out." + k] = np.float64(np.abs(o32[k].astype(np.float64) - o64[k]).max())
+    for k in g32:
+        den = np.linalg.norm(g64[k])
+        out[pre + "ref_f32_err.g." + k] = np.float64(np.linalg.norm(g32[k].astype(np.float64) - g64[k]) / (den if den else 1.0))
+
+
+def G40_view_embed_mlp():
+    """ViewEmbeddingMLP (networks/embedding.py:35-62, built at run_nerf.py:171-175), the real module on the CPU, (a) alone: rows = module(ids)
+    and the table module(arange(n)), (b) in front of the real RigidBlurringModel (dpnerf/blurmodel.py:129-173), (c) in front of the real
+    BlurModel, kernel_type DSK (pdrf/blurmodel.py:109-224), in float32 and, with the same float32-valued parameters, in float64.  Five cases
+    (VIEW_EMBED_CASES), parameters drawn by torch.manual_seed(seed) with init_params='normal'; every batch leaves one image without a ray
+    (not the one-image case) and in 'odd' one image holds half of it.  Recorded per case: the parameters, ids, inputs and projections, the
+    float32 outputs and autograd gradients (behind the blur models: of img_embed and the rays) of the projected sums (G37's / G39's losses), (a)'s float64 twin, and ref_f32_err: the float32
+    results against the float64 ones (max abs per output, relative L2 per gradient tensor).  No ReLU may sit on the fence: in float64 every
+    |pre-activation| exceeds 2 D (K + 1) 2^-24 (sum |w||x| + |b|), else the case takes the next seed; (c) redraws its own network
+    as G39 does, until none of its hidden pre-activations and no argument of align's absolute values is within 1e-5 of its kink."""
+    from networks.dpnerf.blurmodel import RigidBlurringModel
+    from networks.pdrf.blurmodel import BlurModel
+    out = {}
+    for tag, case in VIEW_EMBED_CASES.items():
+        c = dict(case)
+        for attempt in range(20):
+            sd = {k: n(v).copy() for k, v in _view_embed_module(c, None, torch.float32).state_dict().items()}
+            margin, thr = _view_embed_fence(sd, c)
+            if margin >= thr:
+                break
+            print(f"   {tag}: seed {c['seed']}: margin {margin:.1e} below {thr:.1e}, next seed")
+            c["seed"] += 1
+        else:
+            raise AssertionError(f"{tag}: no seed keeps every ReLU off the fence")
+        rs = np.random.RandomState(c["seed"])
+        f32 = lambda *shape, s=1.0: (rs.standard_normal(shape) * s).astype(np.float32)
+        R, N, Wd, P = c["R"], c["n"], c["W"], c["M"] + int(c["use_origin"])
+        absent = 3 if N > 1 else -1                                           # image 3 has no ray in the batch
+        ids = rs.choice([i for i in range(N) if i != absent], size=(R, 1)).astype(np.int64)
+        if tag == "odd":
+            ids[rs.permutation(R)[:R // 2 + 1]] = 5                           # image 5 holds half of it
+        pre = tag + "."
+        out.update({pre + "sd." + k: v for k, v in sd.items()})
+        out.update({pre + "cfg": np.array([c["D"], Wd, c["E"], N, absent], np.int64), pre + "skips": np.array(c["skips"], np.int64),
+                    pre + "seed": np.int64(c["seed"]), pre + "ids": ids, pre + "fence": np.array([margin, thr], np.float64)})
+        # (a) alone
+        proj = f32(R, Wd)
+        o32, g32 = _view_embed_alone(_view_embed_module(c, sd, torch.float32), ids, proj, torch.float32)
+        o64, g64 = _view_embed_alone(_view_embed_module(c, sd, torch.float64), ids, proj, torch.float64)
+        assert all(v.dtype == np.float32 for v in o32.values()) and all(v.dtype == np.float64 for v in o64.values())
+        assert np.abs(o32["rows"] - o32["table"][ids[:, 0]]).max() < 1e-5           # (not bit for bit: the CPU's matmul depends on the row count)
+        out[pre + "alone.proj"] = proj
+        for name, d in (("out.", o32), ("out64.", {"table": o64["table"]}), ("g.", g32), ("g64.", g64)):          # (the float64 rows are table[ids])
+            out.update({pre + "alone." + name + k: v for k, v in d.items()})
+        _record_errors(out, pre + "alone.", o32, o64, g32, g64)
+        msg = [f"alone: table {out[pre + 'alone.ref_f32_err.out.table']:.1e}, gradients {max(float(out[pre + 'alone.ref_f32_err.g.' + k]) for k in g32):.1e}"]
+        # (b) in front of the rigid model
+        rays = W.synthetic_rays(c["seed"] % 100, R)
+        rproj = dict(new_rays=f32(R, P, 3, 2), weight=f32(R, c["M"] + 1), img_embed=f32(R, Wd))
+
+        def rigid(dtype):
+            ve = _view_embed_module(c, sd, torch.float32)
+            kern = RigidBlurringModel(feat_ch=0, num_motion=c["M"], D_r=1, W_r=16, D_v=1, W_v=16, D_w=1, W_w=16, output_ch_r=3, output_ch_v=3,
+                                      rv_window=0.1, use_origin=c["use_origin"], view_embed=ve, W=ve.out_channels)
+            return kern.to(dtype)
+        k32 = rigid(torch.float32)
+        k64 = rigid(torch.float64)
+        k64.load_state_dict({k: v.double() for k, v in k32.state_dict().items()})
+        o32, g32, _ = _rigid_blur_run(k32, rays, ids, rproj, torch.float32)
+        o64, g64, _ = _rigid_blur_run(k64, rays, ids, rproj, torch.float64)
+        assert all(v.dtype == np.float32 for v in o32.values()) and all(v.dtype == np.float64 for v in o64.values())
+        assert np.array_equal(o32["img_embed"], out[pre + "alone.out.rows"])
+        out.update({pre + "rigid.sd." + k: n(v).copy() for k, v in k32.state_dict().items() if not k.startswith("view_embed_module.")})
+        out.update({pre + "rigid.in.rays": rays, pre + "rigid.in.args": np.array([c["M"], int(c["use_origin"])], np.int64)})
+        own = lambda g_: {k: v for k, v in g_.items() if k.endswith("img_embed") or k == "rays"}      # (every tensor's error record is kept below; the arrays
+        for name, d in (("proj.", rproj), ("out.", o32), ("g.", own(g32))):                          # only where the composition ends: fixtures stay small)
+            out.update({pre + "rigid." + name + k: v for k, v in d.items()})
+        _record_errors(out, pre + "rigid.", o32, o64, g32, g64, skip_out=("img_embed",))
+        msg.append(f"rigid: new_rays {out[pre + 'rigid.ref_f32_err.out.new_rays']:.1e}, gradients {max(float(out[pre + 'rigid.ref_f32_err.g.' + k]) for k in g32):.1e}")
+        # (c) in front of the sparse model, kernel_type DSK
+        cfg = dict(SPARSE_BLUR_DEFAULTS, kernel_type="DSK", num_wide=32, num_hidden=2)
+        Pd = cfg["num_pt"]
+        in_cnl, wide = 2 * (1 + 2 * cfg["in_embed"]) + Wd, cfg["num_wide"]
+        for attempt in range(60):
+            rs2 = np.random.RandomState(c["seed"] + 50 + 100 * attempt)
+            d32 = lambda *shape, s=1.0: (rs2.standard_normal(shape) * s).astype(np.float32)
+            dsd = {"pattern_pos": d32(N, Pd, 2, s=0.5)}
+            for i in range(cfg["num_hidden"]):
+                fan = in_cnl if i == 0 else wide
+                dsd[f"linears.{2 * i}.weight"], dsd[f"linears.{2 * i}.bias"] = d32(wide, fan, s=(2.0 / (fan + wide)) ** 0.5), d32(wide, s=0.1)
+            dsd["linears1.0.weight"], dsd["linears1.0.bias"] = d32(wide, wide, s=(1.0 / wide) ** 0.5), d32(wide, s=0.1)
+            dsd["linears1.2.weight"], dsd["linears1.2.bias"] = d32(3, wide, s=0.5), d32(3, s=0.5)
+            dc = dict(ids=ids, rays_x=rs2.randint(0, 400, (R, 1)).astype(np.float32), rays_y=rs2.randint(0, 400, (R, 1)).astype(np.float32),
+                      poses=d32(R, 3, 4), noise=d32(R, Pd, 2), K=np.array([[350, 0, 200], [0, 350, 200], [0, 0, 1]], np.float32),
+                      proj=dict(new_rays=d32(R, Pd, 3, 2), weight=d32(R, Pd), img_embed=d32(R, Wd)))
+
+            def sparse(dtype):
+                kw = {k: v for k, v in cfg.items() if k not in ("kernel_type", "num_pt", "kernel_hwindow")}
+                kern = BlurModel(N, Pd, cfg["kernel_hwindow"], "DSK", _view_embed_module(c, sd, torch.float32), view_embed_cnl=Wd, **kw)
+                full = dict({k: t(v) for k, v in dsd.items()}, **{"img_embed." + k: t(v) for k, v in sd.items()})
+                kern.load_state_dict(full, strict=True)
+                return kern.to(dtype)
+            o32, g32, pre32 = _sparse_blur_run(sparse(torch.float32), dc, None, torch.float32)
+            o64, g64, pre64 = _sparse_blur_run(sparse(torch.float64), dc, None, torch.float64)
+            _, align_args = _sparse_blur_point0(dsd, cfg, dict(dc, ids=ids), pre64["x1"])
+            kink = min(pre32["pre_min"], pre64["pre_min"], float(np.abs(align_args).min()))
+            if kink >= 1e-5:
+                break
+            print(f"   {tag}: dsk: a value {kink:.1e} from a kink, redrawing")
+        else:
+            raise AssertionError(f"{tag}: dsk: no seed keeps the float32 / float64 comparison free of kink flips")
+        assert all(v.dtype == np.float32 for v in o32.values()) and all(v.dtype == np.float64 for v in o64.values())
+        assert np.array_equal(o32["img_embed"], out[pre + "alone.out.rows"])
+        out.update({pre + "dsk.cfg." + k: np.asarray(v) for k, v in cfg.items()})
+        out.update({pre + "dsk.sd." + k: v for k, v in dsd.items()})
+        out.update({pre + "dsk.in." + k: dc[k] for k in ("rays_x", "rays_y", "poses", "noise")})
+        out[pre + "dsk.in.K4"] = np.array([350, 350, 200, 200], np.float64)
+        for name, d in (("proj.", dc["proj"]), ("out.", o32), ("g.", own(g32))):
+            out.update({pre + "dsk." + name + k: v for k, v in d.items()})
+        _record_errors(out, pre + "dsk.", o32, o64, g32, g64, skip_out=("img_embed",))
+        msg.append(f"dsk: new_rays {out[pre + 'dsk.ref_f32_err.out.new_rays']:.1e}, gradients {max(float(out[pre + 'dsk.ref_f32_err.g.' + k]) for k in g32):.1e}")
+        print(f"   {tag}: seed {c['seed']}, margin {margin:.1e} (threshold {thr:.1e}); float32 error of the reference: " + "; ".join(msg))
+    path = os.path.join(OUT, "G40_view_embed_mlp.npz")
+    np.savez_compressed(path, **out)                                        # (keeps the float64 twin and error records)
+    print(f"  wrote {os.path.relpath(path, ROOT)}  ({os.path.getsize(path) / 1024:.1f} KiB)")
+
+
 ALL = [G1_embedder, G2_nerf_mlp, G3_nerf_raw2outputs, G4_voxel_raw2outputs, G5_sample_pdf, G6_rays,
        G7_render_nerf, G8_appfeature, G9_render_c2f, G10_rbk_weighted_sum, G11_crf, G12_egm_loss, G13_edi,
        G14_loss_assembly, G15_awp_feature_integration, G16_rbk_warp, G17_compute_successor, G18_nerf_grads, G19_c2f_grads, G20_loss_grads,
        G21_awp_sample_embed, G22_mam, G23_render_nerf_no_viewdirs, G24_render_other_multires, G25_pbe_composite_feature,
        G26_sample_events, G27_awp_per_ray, G28_image_batch, G29_pose_track, G30_c2f_grads_16k, G31_event_hops, G32_train_forward,
-       G33_train_trajectory, G34_event_tables, G35_llff_poses, G36_edi_prior, G37_rigid_blur, G38_lpips, G39_sparse_blur]
+       G33_train_trajectory, G34_event_tables, G35_llff_poses, G36_edi_prior, G37_rigid_blur, G38_lpips, G39_sparse_blur, G40_view_embed_mlp]
 
 if __name__ == "__main__":
     want = set(sys.argv[1:])
