@@ -2,15 +2,15 @@
 // SE3Field / RigidBody of utils/rigid_warping.py) and its backward.  The reference runs one gather, six small linears and a Python loop
 // over the motions of ~40 tensor ops each; autograd doubles that.  Here: one forward launch, two backward launches.
 //
-// A workgroup of four wavefronts takes tiles of 16 rays in grid-stride order.  Every matrix product is a set of 16 x 16 float32 MFMA
-// tiles (v_mfma_f32_16x16x4_f32, rb_tile below) with the ray as the N dimension, dealt to the wavefronts round robin; operands that
-// depend on the ray live in LDS, zero-padded to the tile, and the parameters are read in place in torch layout.  r / v go through LDS to
-// one lane per (ray, slot) for the SE(3) part (rigid_blur_se3.h).  The backward keeps nothing from the forward: it recomputes the hidden
-// layers, then forms, per tile, d heads -> d hidden -> d x on the matrix core, and the six weight gradients as products over the ray
-// dimension whose accumulators stay in registers across the workgroup's tiles (a bias gradient is the column a constant-one input adds).
-// They leave as per-workgroup partials; k_rigid_blur_reduce sums them over the workgroups in index order and forms the table's gradient
-// as the sum, in ray order, of the d x rows of each image.  No atomics: two runs give the same bits.
+// A float32 tile network (mfma_f32_tile.h holds the scheme and everything the family shares): a workgroup takes tiles of 16 rays in
+// grid-stride order, the ray is the N dimension of every product, dealt to the wavefronts round robin; operands that depend on the ray
+// live in LDS, the parameters are read in place in torch layout.  r / v go through LDS to one lane per (ray, slot) for the SE(3) part
+// (rigid_blur_se3.h).  The backward keeps nothing from the forward: it recomputes the hidden layers, then forms, per tile, d heads ->
+// d hidden -> d x on the matrix core, and the six weight gradients [W | b] = d Y^T [X | 1] (rb_products) with the family's resident
+// accumulators.  k_rigid_blur_reduce sums their partials and forms the table's gradient as the sum, in ray order, of the d x rows of
+// each image.
 #include <algorithm>
+#include <cstddef>
 
 #include "evd_common.h"
 #include "mfma_f32_tile.h"
@@ -18,17 +18,14 @@
 
 namespace evd {
 
-constexpr int RB_NT = 256;            // threads of a workgroup
-constexpr int RB_NW = RB_NT / 64;
-constexpr int RB_TR = 16;             // rays of a tile
+constexpr int RB_NT = MT_NT, RB_NW = MT_NW;
+constexpr int RB_TR = MT_TR;          // rays of a tile
 constexpr int RB_MAXC = 128, RB_MAXW = 64, RB_MAXM = 15;
 constexpr int RB_XS = 145;            // x row: C values, the constant one, zeros up to a multiple of 16 (<= 144), odd stride
 constexpr int RB_HS = 81;             // hidden row: W values, the constant one, zeros up to 80
 constexpr int RB_PS = 65;             // d pre-activation row
 constexpr int RB_OS = 49;             // head row (3 M <= 45, padded to 48)
 constexpr int RB_WS = 17;             // weight-head row (M + 1 <= 16)
-constexpr int RB_MAX_TILES = 3 * 4 * 9 + 2 * 3 * 5 + 5;        // weight-gradient tiles at the largest shape
-constexpr int RB_TPW = (RB_MAX_TILES + RB_NW - 1) / RB_NW;     // ... of one wavefront
 constexpr int RB_MAX_BLOCKS = 64;
 
 struct RbK {
@@ -44,7 +41,7 @@ struct RbK {
     // backward
     const float *d_new_rays, *d_weight, *d_img_embed;
     float *d_rays, *dx, *partial;
-    int tile_base[7], n_tiles;         // weight-gradient tiles of the six matrices, in the struct's order
+    MtMats mats;                       // the six weight-gradient products
 };
 
 struct RbSmem {
@@ -55,6 +52,32 @@ struct RbSmem {
     float dp[3][RB_TR][RB_PS];
     float dray[RB_TR][RB_MAXM + 1][6];
 };
+#define RB_OFF(field) ((int)(offsetof(RbSmem, field) / sizeof(float)))
+
+// The six weight-gradient products [W | b] = d Y^T [X | 1] (branches, then heads) and the twelve tensors behind pl.ten.end, in the flat
+// gradient's order: a bias is the column that the constant one behind X adds to its weight's product
+constexpr void rb_products(MtPlan& pl, int C, int W_r, int W_v, int W_w, int M) {
+    const int Wb[3] = {W_r, W_v, W_w};
+    for (int b = 0; b < 3; ++b) {
+        const MtMat m = pl.add_mat(Wb[b], C + 1, RB_OFF(dp) + b * RB_TR * RB_PS, RB_PS, RB_OFF(xs), RB_XS);
+        pl.add_tensor(Wb[b], C, m);
+        pl.add_tensor(Wb[b], 1, m, C);
+    }
+    for (int b = 0; b < 3; ++b) {
+        const int rows = b == 2 ? M + 1 : 3 * M;
+        const MtMat m = pl.add_mat(rows, Wb[b] + 1, b == 2 ? RB_OFF(ow) : RB_OFF(orv) + b * RB_TR * RB_OS, b == 2 ? RB_WS : RB_OS,
+                                   RB_OFF(hs) + b * RB_TR * RB_HS, RB_HS);
+        pl.add_tensor(rows, Wb[b], m);
+        pl.add_tensor(rows, 1, m, Wb[b]);
+    }
+}
+constexpr int rb_max_tiles() {
+    MtPlan pl{};
+    rb_products(pl, RB_MAXC, RB_MAXW, RB_MAXW, RB_MAXW, RB_MAXM);
+    return pl.mats.n_tiles;
+}
+constexpr int RB_MAX_TILES = rb_max_tiles();                   // weight-gradient tiles at the largest shape
+constexpr int RB_TPW = (RB_MAX_TILES + RB_NW - 1) / RB_NW;     // ... of one wavefront
 
 __device__ __forceinline__ const float* rb_branch_w(const RbK& k, int b) { return b == 0 ? k.p.r_branch_w : b == 1 ? k.p.v_branch_w : k.p.w_branch_w; }
 __device__ __forceinline__ const float* rb_branch_b(const RbK& k, int b) { return b == 0 ? k.p.r_branch_b : b == 1 ? k.p.v_branch_b : k.p.w_branch_b; }
@@ -72,7 +95,7 @@ __device__ __forceinline__ const float* rb_row(const RbK& k, long ray) {
 
 // x tile, hidden layers and heads of the 16 rays from ray0 on, left in s.xs / s.hs / s.orv / s.ow
 __device__ __forceinline__ void rb_networks(const RbK& k, RbSmem& s, long ray0, bool write_embed) {
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x, wv = tid >> 6;
     const int nx = 16 * ((k.C + 1 + 15) / 16);
     for (int i = tid; i < RB_TR * nx; i += RB_NT) {
         const int r = i / nx, c = i % nx;
@@ -95,36 +118,21 @@ __device__ __forceinline__ void rb_networks(const RbK& k, RbSmem& s, long ray0, 
     for (int job = wv; job < 12; job += RB_NW) {                     // hidden = relu(W x + b): (branch, 16 units) x 16 rays
         const int b = job >> 2, m0 = (job & 3) * 16, Wd = k.Wb[b];
         if (m0 >= Wd) continue;
-        rb_f4 acc = rb_tile(rb_zero(), rb_branch_w(k, b) + (long)m0 * k.C, k.C, 1, Wd - m0, k.C, &s.xs[0][0], RB_XS, 1);
-        const float* bias = rb_branch_b(k, b);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int m = m0 + 4 * (lane >> 4) + i;
-            if (m < Wd) s.hs[b][lane & 15][m] = act(EVD_ACT_RELU, acc[i] + bias[m]);
-        }
+        const mt_f4 acc = mt_tile(mt_zero(), rb_branch_w(k, b) + (long)m0 * k.C, k.C, 1, Wd - m0, k.C, &s.xs[0][0], RB_XS, 1);
+        mt_store_relu(&s.hs[b][0][0], RB_HS, acc, rb_branch_b(k, b), m0, Wd);
     }
     __syncthreads();
     for (int job = wv; job < 7; job += RB_NW) {                      // heads: r, v (3 M rows, x rv_window), weight logits (M + 1 rows)
         const int b = job < 3 ? 0 : job < 6 ? 1 : 2, m0 = (job - 3 * b) * 16, rows = rb_head_rows(k, b), Wd = k.Wb[b];
         if (m0 >= rows) continue;
-        rb_f4 acc = rb_tile(rb_zero(), rb_head_w(k, b) + (long)m0 * Wd, Wd, 1, rows - m0, Wd, &s.hs[b][0][0], RB_HS, 1);
+        const mt_f4 acc = mt_tile(mt_zero(), rb_head_w(k, b) + (long)m0 * Wd, Wd, 1, rows - m0, Wd, &s.hs[b][0][0], RB_HS, 1);
         const float* bias = rb_head_b(k, b);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int m = m0 + 4 * (lane >> 4) + i;
-            if (m < rows) {
-                const float y = acc[i] + bias[m];
-                if (b == 2) s.ow[lane & 15][m] = y;
-                else s.orv[b][lane & 15][m] = y * k.rv_window;
-            }
-        }
+        mt_each(acc, m0, rows, [&](int m, int n, float v) {
+            const float y = v + bias[m];
+            if (b == 2) s.ow[n][m] = y;
+            else s.orv[b][n][m] = y * k.rv_window;
+        });
     }
-    __syncthreads();
-}
-
-__device__ __forceinline__ void rb_zero_smem(RbSmem& s) {
-    float* f = reinterpret_cast<float*>(&s);
-    for (int i = threadIdx.x; i < (int)(sizeof(RbSmem) / sizeof(float)); i += RB_NT) f[i] = 0.f;
     __syncthreads();
 }
 
@@ -132,7 +140,7 @@ __global__ __launch_bounds__(RB_NT) void k_rigid_blur_fwd(RbK k) {
     __shared__ RbSmem s;
     const int tid = threadIdx.x;
     const long tiles = (k.R + RB_TR - 1) / RB_TR;
-    rb_zero_smem(s);
+    mt_zero_lds(s);
     for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const long ray0 = tile * RB_TR;
         rb_networks(k, s, ray0, true);
@@ -166,43 +174,16 @@ __global__ __launch_bounds__(RB_NT) void k_rigid_blur_fwd(RbK k) {
     }
 }
 
-// the matrix, tile row and tile column of weight-gradient tile t
-__device__ __forceinline__ void rb_decode(const RbK& k, int t, int& mat, int& mt, int& nt) {
-    mat = 0;
-#pragma unroll
-    for (int i = 1; i < 6; ++i) mat += t >= k.tile_base[i] ? 1 : 0;
-    const int b = mat % 3;
-    const int ncol = 1 + (mat < 3 ? k.C : k.Wb[b]);
-    const int ntl = (ncol + 15) / 16, local = t - k.tile_base[mat];
-    mt = local / ntl;
-    nt = local % ntl;
-}
-
 __global__ __launch_bounds__(RB_NT) void k_rigid_blur_bwd(RbK k) {
     __shared__ RbSmem s;
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x, wv = tid >> 6;
     const long tiles = (k.R + RB_TR - 1) / RB_TR;
-    rb_f4 wg[RB_TPW];
+    mt_f4 wg[RB_TPW];
 #pragma unroll
-    for (int i = 0; i < RB_TPW; ++i) wg[i] = rb_zero();
-    // per weight-gradient tile: float offsets in RbSmem of its d Y columns and its X columns, and the two row strides
+    for (int i = 0; i < RB_TPW; ++i) wg[i] = mt_zero();
     __shared__ int4 jobs[RB_MAX_TILES];
-    const float* sf = reinterpret_cast<const float*>(&s);
-    for (int t = tid; t < k.n_tiles; t += RB_NT) {
-        int mat, mt, nt;
-        rb_decode(k, t, mat, mt, nt);
-        const int b = mat % 3;
-        int4 j;
-        if (mat < 3) {
-            j.x = (int)(&s.dp[b][0][0] - sf); j.y = RB_PS; j.z = (int)(&s.xs[0][0] - sf); j.w = RB_XS;
-        } else {
-            j.x = (int)((b == 2 ? &s.ow[0][0] : &s.orv[b][0][0]) - sf); j.y = b == 2 ? RB_WS : RB_OS; j.z = (int)(&s.hs[b][0][0] - sf); j.w = RB_HS;
-        }
-        j.x += mt * 16;
-        j.z += nt * 16;
-        jobs[t] = j;
-    }
-    rb_zero_smem(s);
+    mt_jobs(jobs, k.mats, 0, RB_MAX_TILES);
+    mt_zero_lds(s);
     for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const long ray0 = tile * RB_TR;
         rb_networks(k, s, ray0, false);
@@ -265,100 +246,66 @@ __global__ __launch_bounds__(RB_NT) void k_rigid_blur_bwd(RbK k) {
             const int b = job >> 2, m0 = (job & 3) * 16, Wd = k.Wb[b], rows = rb_head_rows(k, b);
             if (m0 >= Wd) continue;
             const float* dout = b == 2 ? &s.ow[0][0] : &s.orv[b][0][0];
-            rb_f4 acc = rb_tile(rb_zero(), rb_head_w(k, b) + m0, 1, Wd, Wd - m0, rows, dout, b == 2 ? RB_WS : RB_OS, 1);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int m = m0 + 4 * (lane >> 4) + i;
-                if (m < Wd) s.dp[b][lane & 15][m] = s.hs[b][lane & 15][m] > 0.f ? acc[i] : 0.f;
-            }
+            const mt_f4 acc = mt_tile(mt_zero(), rb_head_w(k, b) + m0, 1, Wd, Wd - m0, rows, dout, b == 2 ? RB_WS : RB_OS, 1);
+            mt_gate_relu(&s.dp[b][0][0], RB_PS, &s.hs[b][0][0], RB_HS, acc, m0, Wd);
         }
         __syncthreads();
         // ---- d x = sum over the branches of W^T d pre (+ the gradient that arrives at img_embed)
         if (k.dx) {
             for (int job = wv; job < (k.C + 15) / 16; job += RB_NW) {
                 const int m0 = job * 16;
-                rb_f4 acc = rb_zero();
+                mt_f4 acc = mt_zero();
 #pragma unroll
-                for (int b = 0; b < 3; ++b) acc = rb_tile(acc, rb_branch_w(k, b) + m0, 1, k.C, k.C - m0, k.Wb[b], &s.dp[b][0][0], RB_PS, 1);
-                const long ray = ray0 + (lane & 15);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int m = m0 + 4 * (lane >> 4) + i;
-                    if (m < k.C && ray < k.R) k.dx[ray * k.C + m] = acc[i] + (k.d_img_embed ? k.d_img_embed[ray * k.C + m] : 0.f);
-                }
+                for (int b = 0; b < 3; ++b) acc = mt_tile(acc, rb_branch_w(k, b) + m0, 1, k.C, k.C - m0, k.Wb[b], &s.dp[b][0][0], RB_PS, 1);
+                mt_each(acc, m0, k.C, [&](int m, int n, float v) {
+                    const long ray = ray0 + n;
+                    if (ray < k.R) k.dx[ray * k.C + m] = v + (k.d_img_embed ? k.d_img_embed[ray * k.C + m] : 0.f);
+                });
             }
         }
         // ---- weight gradients: d Y^T [X | 1] over the tile's rays, both operands in LDS
-#pragma unroll
-        for (int i = 0; i < RB_TPW; ++i) {
-            const int t = wv + RB_NW * i;
-            if (t < k.n_tiles) {
-                const int4 j = jobs[t];
-                const float* dy = sf + j.x + (lane & 15);
-                const float* X = sf + j.z + (lane & 15);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int ray = 4 * u + (lane >> 4);
-                    wg[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(dy[ray * j.y], X[ray * j.w], wg[i], 0, 0, 0);
-                }
-            }
-            asm volatile("" ::: "memory");              // one tile's operands in flight at a time
-        }
+        mt_accumulate<RB_TPW, true>(wg, jobs, reinterpret_cast<const float*>(&s), k.mats.n_tiles, 0);
         __syncthreads();
     }
-#pragma unroll
-    for (int i = 0; i < RB_TPW; ++i) {
-        const int t = wv + RB_NW * i;
-        if (t < k.n_tiles) {
-            float* out = k.partial + ((long)blockIdx.x * k.n_tiles + t) * 256;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) out[(4 * (lane >> 4) + j) * 16 + (lane & 15)] = wg[i][j];
-        }
-    }
+    mt_store_partials(wg, k.partial, k.mats.n_tiles, 0);
 }
 
 struct RbReduce {
     const float *partial, *dx;
     const long* ids;
     float* grads;
-    long R, table_floats, total;
-    int C, Wb[3], M, n_blocks, n_tiles, tile_base[7];
-    long off[13];                       // offsets of the thirteen tensors in the flat gradient
+    long R, table_floats;
+    int C, n_blocks;
+    MtTensors ten;                      // the twelve network tensors behind the table
 };
 
 // One thread per gradient element.  Table: the d x rows of the image's rays in ray order (an image without rays gets zeros).  The
 // twelve network tensors: the workgroups' partial tiles in workgroup order.
 __global__ __launch_bounds__(256) void k_rigid_blur_reduce(RbReduce k) {
     const long e = blockIdx.x * 256L + threadIdx.x;
-    if (e >= k.total) return;
-    float a = 0.f;
-    if (e < k.table_floats) {
-        const long img = e / k.C;
-        const int c = e % k.C;
-        if (k.ids)                                   // (per-ray form: the table takes no part, its slot is zeros)
-            for (long r = 0; r < k.R; ++r)
-                if (k.ids[r] == img) a += k.dx[r * k.C + c];
-    } else {
-        int ti = 1;
-#pragma unroll
-        for (int i = 2; i < 13; ++i) ti += e >= k.off[i] ? 1 : 0;
-        const int mat = (ti - 1) >> 1, b = mat % 3, bias = (ti - 1) & 1;
-        const int ncol = mat < 3 ? k.C : k.Wb[b];
-        const long local = e - k.off[ti];
-        const int m = bias ? (int)local : (int)(local / ncol), n = bias ? ncol : (int)(local % ncol);
-        const int ntl = (ncol + 1 + 15) / 16;
-        const long t = k.tile_base[mat] + (m >> 4) * ntl + (n >> 4);
-        const float* p = k.partial + t * 256 + (m & 15) * 16 + (n & 15);
-        for (int g = 0; g < k.n_blocks; ++g) a += p[(long)g * k.n_tiles * 256];
-    }
-    k.grads[e] = a;
+    if (e >= k.ten.end) return;
+    if (e < k.table_floats)                          // (per-ray form: the table takes no part, its slot is zeros)
+        k.grads[e] = k.ids ? mt_rows_of_image_sum(k.ids, k.R, e / k.C, k.dx, k.C, (int)(e % k.C)) : 0.f;
+    else
+        k.grads[e] = mt_reduce_sum(k.ten, k.partial, k.n_blocks, e);
 }
 
 struct RbPlan {
     RbK k;
-    long off[14];
+    RbReduce r;
     int blocks;
 };
+
+static int rb_blocks(long R) { return (int)std::min<long>(cdiv(R, RB_TR), RB_MAX_BLOCKS); }
+
+// workspace of evd_rigid_blur_backward: the d x rows (table form) | the workgroups' partial weight-gradient tiles
+struct RbWs { float *dx, *partial; };
+static size_t rb_layout(const RbPlan& pl, long R, void* workspace, RbWs* L) {
+    FloatSlots ws(workspace);
+    L->dx = ws.take((size_t)R * pl.k.C);
+    L->partial = ws.take(mt_partial_floats(rb_blocks(R), pl.k.mats.n_tiles));
+    return ws.bytes();
+}
 
 static int rb_plan(const char* who, const evd_rigid_blur_desc* d, const evd_rigid_blur_params* p, const float* rays, const long* ids, const float* x,
                    long R, RbPlan* out) {
@@ -371,7 +318,7 @@ static int rb_plan(const char* who, const evd_rigid_blur_desc* d, const evd_rigi
     EVD_REQUIRE(d->M >= 1 && d->M <= RB_MAXM, "%s: num_motion %d outside 1..%d", who, d->M, RB_MAXM);
     EVD_REQUIRE(R >= 0 && d->n_img >= 0, "%s: negative size", who);
     RbK& k = out->k;
-    memset(&k, 0, sizeof(k));
+    memset(out, 0, sizeof(*out));
     k.C = d->C;
     k.Wb[0] = d->W_r; k.Wb[1] = d->W_v; k.Wb[2] = d->W_w;
     k.M = d->M;
@@ -380,19 +327,17 @@ static int rb_plan(const char* who, const evd_rigid_blur_desc* d, const evd_rigi
     k.n_img = d->n_img;
     k.rv_window = d->rv_window;
     k.R = R;
-    int t = 0;
-    for (int mat = 0; mat < 6; ++mat) {
-        const int b = mat % 3, rows = mat < 3 ? k.Wb[b] : (b == 2 ? k.M + 1 : 3 * k.M), ncol = 1 + (mat < 3 ? k.C : k.Wb[b]);
-        k.tile_base[mat] = t;
-        t += (int)(cdiv(rows, 16) * cdiv(ncol, 16));
-    }
-    k.tile_base[6] = k.n_tiles = t;
-    long o = 0;
-    const long sizes[13] = {(long)k.n_img * k.C, (long)k.Wb[0] * k.C, k.Wb[0], (long)k.Wb[1] * k.C, k.Wb[1], (long)k.Wb[2] * k.C, k.Wb[2],
-                            3L * k.M * k.Wb[0], 3L * k.M, 3L * k.M * k.Wb[1], 3L * k.M, (long)(k.M + 1) * k.Wb[2], k.M + 1};
-    for (int i = 0; i < 13; ++i) { out->off[i] = o; o += sizes[i]; }
-    out->off[13] = o;
-    out->blocks = (int)std::min<long>(cdiv(R, RB_TR), RB_MAX_BLOCKS);
+    MtPlan mp{};
+    mp.ten.end = (long)k.n_img * k.C;                                  // the table's gradient comes first
+    rb_products(mp, k.C, k.Wb[0], k.Wb[1], k.Wb[2], k.M);
+    const int rc = mt_check(who, mp, RB_MAX_TILES);
+    if (rc != EVD_OK) return rc;
+    k.mats = mp.mats;
+    out->r.ten = mp.ten;
+    out->r.table_floats = (long)k.n_img * k.C;
+    out->r.C = k.C;
+    out->r.R = R;
+    out->blocks = rb_blocks(R);
     if (R == 0) return EVD_OK;
     EVD_REQUIRE(p && rays, "%s: null parameters / rays", who);
     EVD_REQUIRE(ids ? (p->table != nullptr && d->n_img >= 1) : x != nullptr, "%s: needs ids and the table, or per-ray feature rows", who);
@@ -414,8 +359,8 @@ extern "C" {
 size_t evd_rigid_blur_workspace_bytes(const evd_rigid_blur_desc* d, long R) {
     RbPlan pl;
     if (rb_plan("evd_rigid_blur_workspace_bytes", d, nullptr, nullptr, nullptr, nullptr, R < 0 ? -1 : 0, &pl) != EVD_OK) return 0;
-    const long blocks = std::min<long>(cdiv(R, RB_TR), RB_MAX_BLOCKS);
-    return sizeof(float) * ((size_t)R * d->C + (size_t)blocks * pl.k.n_tiles * 256);
+    RbWs L;
+    return rb_layout(pl, R, nullptr, &L);
 }
 
 int evd_rigid_blur_forward(const evd_rigid_blur_desc* d, const evd_rigid_blur_params* p, const float* rays, const long* ids, const float* x, long R,
@@ -440,38 +385,28 @@ int evd_rigid_blur_backward(const evd_rigid_blur_desc* d, const evd_rigid_blur_p
     int rc = rb_plan("evd_rigid_blur_backward", d, p, rays, ids, x, R, &pl);
     if (rc != EVD_OK) return rc;
     EVD_REQUIRE(grads, "evd_rigid_blur_backward: null gradient buffer");
-    RbReduce rk;
-    memset(&rk, 0, sizeof(rk));
+    RbReduce& rk = pl.r;
     rk.grads = grads;
-    rk.R = R;
-    rk.table_floats = pl.off[1];
-    rk.total = pl.off[13];
-    rk.C = pl.k.C;
-    rk.M = pl.k.M;
-    for (int i = 0; i < 3; ++i) rk.Wb[i] = pl.k.Wb[i];
-    for (int i = 0; i < 7; ++i) rk.tile_base[i] = pl.k.tile_base[i];
-    for (int i = 0; i < 13; ++i) rk.off[i] = pl.off[i];
-    rk.n_tiles = pl.k.n_tiles;
     rk.ids = ids;
     if (R > 0) {
         EVD_REQUIRE(d_new_rays && d_weight, "evd_rigid_blur_backward: null d new_rays / d weight");
-        const size_t need = evd_rigid_blur_workspace_bytes(d, R);
+        RbWs L;
+        const size_t need = rb_layout(pl, R, workspace, &L);
         if (!workspace || workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_rigid_blur_backward: workspace %zu < %zu bytes", workspace_bytes, need);
-        float* ws = static_cast<float*>(workspace);
         pl.k.d_new_rays = d_new_rays;
         pl.k.d_weight = d_weight;
         pl.k.d_img_embed = d_img_embed;
         pl.k.d_rays = d_rays;
-        pl.k.dx = ids ? ws : d_x;
-        pl.k.partial = ws + (size_t)R * d->C;
+        pl.k.dx = ids ? L.dx : d_x;
+        pl.k.partial = L.partial;
         k_rigid_blur_bwd<<<pl.blocks, RB_NT, 0, as_stream(stream)>>>(pl.k);
         EVD_LAUNCH_CHECK();
-        rk.partial = pl.k.partial;
-        rk.dx = ws;
+        rk.partial = L.partial;
+        rk.dx = L.dx;
         rk.n_blocks = pl.blocks;
     }
-    if (rk.total > 0) {
-        k_rigid_blur_reduce<<<(unsigned)cdiv(rk.total, 256), 256, 0, as_stream(stream)>>>(rk);
+    if (rk.ten.end > 0) {
+        k_rigid_blur_reduce<<<(unsigned)cdiv(rk.ten.end, 256), 256, 0, as_stream(stream)>>>(rk);
         EVD_LAUNCH_CHECK();
     }
     return EVD_OK;

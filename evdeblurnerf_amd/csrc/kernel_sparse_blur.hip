@@ -2,15 +2,14 @@
 // The reference runs about 60 small tensor ops each way on R P rows; here the network and the rays are one forward launch (DSK's align, a
 // mean over the batch, takes a second launch of one workgroup) and the backward is two launches.
 //
-// kernel_rigid_blur.hip's scheme.  A workgroup of four wavefronts takes tiles in grid-stride order; a tile is 16 rows = T = 16 / P whole
-// rays with all their P points, so the softmax over a ray's points and the ray's shared columns never leave the tile.  Every matrix product
-// is a set of 16 x 16 float32 MFMA tiles (rb_tile) with the row as the N dimension, dealt to the wavefronts round robin; the rows, the
-// hidden layers and the backward's d pre-activations live in zero-padded LDS arrays, and the parameters are read in place in torch layout.
-// The backward keeps nothing from the forward: it recomputes the rows and the hidden layers, walks d out -> d hidden -> d row on the matrix
-// core, and forms the weight gradients as products over the row dimension whose accumulators stay in registers across the workgroup's tiles
-// (a bias gradient is the product with a column of ones).  They leave as per-workgroup partials; k_sparse_blur_reduce sums them over the
-// workgroups in index order and forms the per-image sums of pattern_pos, pattern_trans and the embedding table in ray order.  No atomics:
-// two runs give the same bits.  sinf / cosf / tanhf / expf are the accurate ones.
+// A float32 tile network (mfma_f32_tile.h holds the scheme and everything the family shares).  A workgroup takes tiles in grid-stride
+// order; a tile is 16 rows = T = 16 / P whole rays with all their P points, so the softmax over a ray's points and the ray's shared columns
+// never leave the tile.  The row is the N dimension of every product, dealt to the wavefronts round robin; the rows, the hidden layers and
+// the backward's d pre-activations live in zero-padded LDS arrays, and the parameters are read in place in torch layout.  The backward
+// keeps nothing from the forward: it recomputes the rows and the hidden layers, walks d out -> d hidden -> d row on the matrix core, and
+// forms the weight gradients (sb_products; a bias gradient is the product with a column of ones) with the family's resident accumulators.
+// k_sparse_blur_reduce sums their partials and forms the per-image sums of pattern_pos, pattern_trans and the embedding table in ray order.
+// sinf / cosf / tanhf / expf are the accurate ones.
 #include <algorithm>
 #include <cstddef>
 
@@ -19,22 +18,13 @@
 
 namespace evd {
 
-constexpr int SB_NT = 256;            // threads of a workgroup
-constexpr int SB_NW = SB_NT / 64;
-constexpr int SB_ROWS = 16;           // rows of a tile
+constexpr int SB_NT = MT_NT, SB_NW = MT_NW;
+constexpr int SB_ROWS = MT_TR;        // rows of a tile
 constexpr int SB_MAXIN = 127, SB_MAXW = 64, SB_MAXP = 16, SB_MAXH = 4, SB_MAXL = 4;
 constexpr int SB_XS = 129;            // row: up to 127 values, zeros up to a multiple of 16, odd stride
 constexpr int SB_HS = 65;             // hidden row / d pre-activation row
 constexpr int SB_OS = 17;             // output row (3 or 5 values, padded to 16)
-constexpr int SB_MATS = 2 * SB_MAXH + 3 + 2;                                  // weight and bias of each layer, linears1.0 in two column parts
-constexpr int SB_MAX_TILES = (4 * 8 + 4) + 3 * (4 * 4 + 4) + (4 * 8 + 4 * 4 + 4) + (4 + 1);      // weight-gradient tiles at the largest shape
-constexpr int SB_TPW = (SB_MAX_TILES + SB_NW - 1) / SB_NW;                    // ... of one wavefront
 constexpr int SB_MAX_BLOCKS = 128;
-constexpr int SB_TENSORS = 2 * SB_MAXH + 4;
-
-struct SbMat {                        // one weight-gradient product d Y^T X: its tiles and, as float offsets in SbSmem, its operands
-    int tile_base, ntl, dy_off, dy_stride, x_off, x_stride;
-};
 
 struct SbK {
     evd_sparse_blur_params p;
@@ -49,8 +39,7 @@ struct SbK {
     // backward
     const float *d_new_rays, *d_weight, *d_align, *d_img_embed;
     float *dxe, *dpp, *dpt, *d_feats, *partial;
-    SbMat mats[SB_MATS];
-    int n_mats, n_tiles;
+    MtMats mats;                       // the weight-gradient products
 };
 
 struct SbSmem {
@@ -61,6 +50,34 @@ struct SbSmem {
     float one[SB_ROWS][SB_OS];                      // column 0: 1 for a row of the batch
     float pos[SB_ROWS][2], dpos[SB_ROWS][2];        // input_pos and the gradient that reaches it past the network
 };
+#define SB_OFF(field) ((int)(offsetof(SbSmem, field) / sizeof(float)))
+
+// The weight-gradient products d Y^T X (weight and bias of each layer, linears1.0 with the short cut in two column parts) and the
+// network tensors behind pl.ten.end, in the flat gradient's order
+constexpr void sb_products(MtPlan& pl, int nh, int Wd, int in_cnl, int sc, int n_out) {
+    const int layer = SB_ROWS * SB_HS;
+    for (int l = 0; l <= nh; ++l) {                                  // linears, then linears1.0
+        const int dy = SB_OFF(dp) + l * layer, hx = SB_OFF(hs) + (l - 1) * layer;
+        if (l == 0) {
+            pl.add_tensor(Wd, in_cnl, pl.add_mat(Wd, in_cnl, dy, SB_HS, SB_OFF(xs), SB_XS));
+        } else if (l == nh && sc) {
+            const MtMat wx = pl.add_mat(Wd, in_cnl, dy, SB_HS, SB_OFF(xs), SB_XS);
+            pl.add_tensor(Wd, in_cnl + Wd, wx, 0, in_cnl, pl.add_mat(Wd, Wd, dy, SB_HS, hx, SB_HS));
+        } else {
+            pl.add_tensor(Wd, Wd, pl.add_mat(Wd, Wd, dy, SB_HS, hx, SB_HS));
+        }
+        pl.add_tensor(Wd, 1, pl.add_mat(Wd, 1, dy, SB_HS, SB_OFF(one), SB_OS));
+    }
+    pl.add_tensor(n_out, Wd, pl.add_mat(n_out, Wd, SB_OFF(o), SB_OS, SB_OFF(hs) + nh * layer, SB_HS));      // linears1.2
+    pl.add_tensor(n_out, 1, pl.add_mat(n_out, 1, SB_OFF(o), SB_OS, SB_OFF(one), SB_OS));
+}
+constexpr int sb_max_tiles() {
+    MtPlan pl{};
+    sb_products(pl, SB_MAXH, SB_MAXW, SB_MAXIN, 1, 5);
+    return pl.mats.n_tiles;
+}
+constexpr int SB_MAX_TILES = sb_max_tiles();                                  // weight-gradient tiles at the largest shape
+constexpr int SB_TPW = (SB_MAX_TILES + SB_NW - 1) / SB_NW;                    // ... of one wavefront
 
 // image id of a ray, -1 outside [0, n)
 __device__ __forceinline__ long sb_id(const SbK& k, long ray, int n) {
@@ -68,25 +85,9 @@ __device__ __forceinline__ long sb_id(const SbK& k, long ray, int n) {
     return id >= 0 && id < n ? id : -1;
 }
 
-__device__ __forceinline__ void sb_zero_smem(SbSmem& s) {
-    float* f = reinterpret_cast<float*>(&s);
-    for (int i = threadIdx.x; i < (int)(sizeof(SbSmem) / sizeof(float)); i += SB_NT) f[i] = 0.f;
-    __syncthreads();
-}
-
-// hidden = relu(A x + b) for one 16-unit tile of a layer, accumulated by the caller
-__device__ __forceinline__ void sb_store_relu(float (*h)[SB_HS], rb_f4 acc, const float* bias, int m0, int Wd) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m0 + 4 * (lane >> 4) + i;
-        if (m < Wd) h[lane & 15][m] = act(EVD_ACT_RELU, acc[i] + bias[m]);
-    }
-}
-
 // rows, hidden layers and outputs of the tile's 16 rows from ray0 on, left in s.xs / s.hs / s.o / s.pos / s.one
 __device__ __forceinline__ void sb_network(const SbK& k, SbSmem& s, long ray0, bool write_embed) {
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x, wv = tid >> 6;
     const int nx = 16 * ((k.in_cnl + 15) / 16), rows = k.T * k.P;
     if (tid < 2 * SB_ROWS) {                                        // canonical position and its embedding: one lane per (row, component)
         const int r = tid >> 1, c = tid & 1, pnt = r % k.P;
@@ -145,8 +146,8 @@ __device__ __forceinline__ void sb_network(const SbK& k, SbSmem& s, long ray0, b
         const int K = l == 0 ? k.in_cnl : k.Wd, st = l == 0 ? SB_XS : SB_HS;
         for (int job = wv; job < mt; job += SB_NW) {
             const int m0 = job * 16;
-            rb_f4 acc = rb_tile(rb_zero(), k.p.linears_w[l] + (long)m0 * K, K, 1, k.Wd - m0, K, in, st, 1);
-            sb_store_relu(s.hs[l], acc, k.p.linears_b[l], m0, k.Wd);
+            mt_f4 acc = mt_tile(mt_zero(), k.p.linears_w[l] + (long)m0 * K, K, 1, k.Wd - m0, K, in, st, 1);
+            mt_store_relu(&s.hs[l][0][0], SB_HS, acc, k.p.linears_b[l], m0, k.Wd);
         }
         __syncthreads();
     }
@@ -154,19 +155,15 @@ __device__ __forceinline__ void sb_network(const SbK& k, SbSmem& s, long ray0, b
     for (int job = wv; job < mt; job += SB_NW) {
         const int m0 = job * 16;
         const float* w = k.p.linears1_w[0] + (long)m0 * ldw;
-        rb_f4 acc = rb_zero();
-        if (k.sc) acc = rb_tile(acc, w, ldw, 1, k.Wd - m0, k.in_cnl, &s.xs[0][0], SB_XS, 1);
-        acc = rb_tile(acc, w + (ldw - k.Wd), ldw, 1, k.Wd - m0, k.Wd, &s.hs[k.nh - 1][0][0], SB_HS, 1);
-        sb_store_relu(s.hs[k.nh], acc, k.p.linears1_b[0], m0, k.Wd);
+        mt_f4 acc = mt_zero();
+        if (k.sc) acc = mt_tile(acc, w, ldw, 1, k.Wd - m0, k.in_cnl, &s.xs[0][0], SB_XS, 1);
+        acc = mt_tile(acc, w + (ldw - k.Wd), ldw, 1, k.Wd - m0, k.Wd, &s.hs[k.nh - 1][0][0], SB_HS, 1);
+        mt_store_relu(&s.hs[k.nh][0][0], SB_HS, acc, k.p.linears1_b[0], m0, k.Wd);
     }
     __syncthreads();
     if (wv == 0) {                                                  // linears1.2: 3 or 5 outputs
-        rb_f4 acc = rb_tile(rb_zero(), k.p.linears1_w[1], k.Wd, 1, k.n_out, k.Wd, &s.hs[k.nh][0][0], SB_HS, 1);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int m = 4 * (lane >> 4) + i;
-            if (m < k.n_out) s.o[lane & 15][m] = acc[i] + k.p.linears1_b[1][m];
-        }
+        const mt_f4 acc = mt_tile(mt_zero(), k.p.linears1_w[1], k.Wd, 1, k.n_out, k.Wd, &s.hs[k.nh][0][0], SB_HS, 1);
+        mt_each(acc, 0, k.n_out, [&](int m, int n, float v) { s.o[n][m] = v + k.p.linears1_b[1][m]; });
     }
     __syncthreads();
 }
@@ -211,7 +208,7 @@ __global__ __launch_bounds__(SB_NT) void k_sparse_blur_fwd(SbK k) {
     __shared__ SbSmem s;
     const int tid = threadIdx.x;
     const long tiles = (k.R + k.T - 1) / k.T;
-    sb_zero_smem(s);
+    mt_zero_lds(s);
     for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const long ray0 = tile * k.T;
         sb_network(k, s, ray0, true);
@@ -265,33 +262,20 @@ __device__ __forceinline__ float sb_sign(float v) { return v > 0.f ? 1.f : v < 0
 // d hidden = A^T d next through the ReLU, one 16-unit tile: A[m][j] = w[m + j lda]
 __device__ __forceinline__ void sb_back(const SbK& k, float (*dp)[SB_HS], const float (*h)[SB_HS], const float* w, int lda, int m0, int K, const float* dnext,
                                         int dstride) {
-    const int lane = threadIdx.x & 63;
-    rb_f4 acc = rb_tile(rb_zero(), w + m0, 1, lda, k.Wd - m0, K, dnext, dstride, 1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m0 + 4 * (lane >> 4) + i;
-        if (m < k.Wd) dp[lane & 15][m] = h[lane & 15][m] > 0.f ? acc[i] : 0.f;
-    }
+    const mt_f4 acc = mt_tile(mt_zero(), w + m0, 1, lda, k.Wd - m0, K, dnext, dstride, 1);
+    mt_gate_relu(&dp[0][0], SB_HS, &h[0][0], SB_HS, acc, m0, k.Wd);
 }
 
 __global__ __launch_bounds__(SB_NT) void k_sparse_blur_bwd(SbK k) {
     __shared__ SbSmem s;
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x, wv = tid >> 6;
     const long tiles = (k.R + k.T - 1) / k.T;
-    rb_f4 wg[SB_TPW];
+    mt_f4 wg[SB_TPW];
 #pragma unroll
-    for (int i = 0; i < SB_TPW; ++i) wg[i] = rb_zero();
-    // per weight-gradient tile: float offsets in SbSmem of its d Y columns and its X columns, and the two row strides
+    for (int i = 0; i < SB_TPW; ++i) wg[i] = mt_zero();
     __shared__ int4 jobs[SB_MAX_TILES];
-    const float* sf = reinterpret_cast<const float*>(&s);
-    for (int t = tid; t < k.n_tiles; t += SB_NT) {
-        int mat = 0;
-        for (int i = 1; i < k.n_mats; ++i) mat += t >= k.mats[i].tile_base ? 1 : 0;
-        const SbMat& m = k.mats[mat];
-        const int local = t - m.tile_base;
-        jobs[t] = make_int4(m.dy_off + (local / m.ntl) * 16, m.dy_stride, m.x_off + (local % m.ntl) * 16, m.x_stride);
-    }
-    sb_zero_smem(s);
+    mt_jobs(jobs, k.mats, 0, SB_MAX_TILES);
+    mt_zero_lds(s);
     const int mt = (k.Wd + 15) / 16, oq = k.n_out - 3, ow = k.n_out - 1, ldw = (k.sc ? k.in_cnl : 0) + k.Wd;
     for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const long ray0 = tile * k.T;
@@ -350,32 +334,14 @@ __global__ __launch_bounds__(SB_NT) void k_sparse_blur_bwd(SbK k) {
             __syncthreads();
         }
         // ---- weight gradients: d Y^T X over the tile's rows, both operands in LDS
-#pragma unroll
-        for (int i = 0; i < SB_TPW; ++i) {
-            const int t = wv + SB_NW * i;
-            if (t < k.n_tiles) {
-                const int4 j = jobs[t];
-                const float* dy = sf + j.x + (lane & 15);
-                const float* X = sf + j.z + (lane & 15);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int row = 4 * u + (lane >> 4);
-                    wg[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(dy[row * j.y], X[row * j.w], wg[i], 0, 0, 0);
-                }
-            }
-            asm volatile("" ::: "memory");              // one tile's operands in flight at a time
-        }
+        mt_accumulate<SB_TPW, true>(wg, jobs, reinterpret_cast<const float*>(&s), k.mats.n_tiles, 0);
         __syncthreads();
         // ---- d row = W0^T d pre0 (+ the short cut's part), in place of the row: its gradient-bearing columns only
         for (int job = wv; job < (k.ng + 15) / 16; job += SB_NW) {
             const int m0 = job * 16;
-            rb_f4 acc = rb_tile(rb_zero(), k.p.linears_w[0] + m0, 1, k.in_cnl, k.ng - m0, k.Wd, &s.dp[0][0][0], SB_HS, 1);
-            if (k.sc) acc = rb_tile(acc, k.p.linears1_w[0] + m0, 1, ldw, k.ng - m0, k.Wd, &s.dp[k.nh][0][0], SB_HS, 1);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int m = m0 + 4 * (lane >> 4) + i;
-                if (m < k.ng) s.xs[lane & 15][m] = acc[i];
-            }
+            mt_f4 acc = mt_tile(mt_zero(), k.p.linears_w[0] + m0, 1, k.in_cnl, k.ng - m0, k.Wd, &s.dp[0][0][0], SB_HS, 1);
+            if (k.sc) acc = mt_tile(acc, k.p.linears1_w[0] + m0, 1, ldw, k.ng - m0, k.Wd, &s.dp[k.nh][0][0], SB_HS, 1);
+            mt_each(acc, m0, k.ng, [&](int m, int n, float v) { s.xs[n][m] = v; });
         }
         __syncthreads();
         if (tid < 2 * SB_ROWS) {                                    // d pattern_pos rows: through the embedding, input_pos and tanh
@@ -408,79 +374,59 @@ __global__ __launch_bounds__(SB_NT) void k_sparse_blur_bwd(SbK k) {
         }
         __syncthreads();
     }
-#pragma unroll
-    for (int i = 0; i < SB_TPW; ++i) {
-        const int t = wv + SB_NW * i;
-        if (t < k.n_tiles) {
-            float* out = k.partial + ((long)blockIdx.x * k.n_tiles + t) * 256;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) out[(4 * (lane >> 4) + j) * 16 + (lane & 15)] = wg[i][j];
-        }
-    }
+    mt_store_partials(wg, k.partial, k.mats.n_tiles, 0);
 }
-
-struct SbTensor {                       // a network tensor in the flat gradient: columns [0, split) come from part a's tiles, the rest from part b's
-    long off;
-    int width, split, base_a, ntl_a, base_b, ntl_b;
-};
 
 struct SbReduce {
     const float *partial, *dxe, *dpp, *dpt;
     const long* ids;
     float* grads;
-    long R, pat_floats, trans_floats, table_floats, total;
-    int C, P, isglobal, table_form, n_blocks, n_tiles, n_tensors;
-    SbTensor ten[SB_TENSORS];
+    long R, pat_floats, trans_floats, table_floats;
+    int C, P, isglobal, table_form, n_blocks;
+    MtTensors ten;                      // the network tensors behind pattern_pos, pattern_trans and the table
 };
 
 // One thread per gradient element.  pattern_pos, pattern_trans, table: the rows of the image's rays in ray order (an image without rays
 // gets zeros).  The network tensors: the workgroups' partial tiles in workgroup order.
 __global__ __launch_bounds__(256) void k_sparse_blur_reduce(SbReduce k) {
     const long e = blockIdx.x * 256L + threadIdx.x;
-    if (e >= k.total) return;
-    float a = 0.f;
+    if (e >= k.ten.end) return;
     const long net0 = k.pat_floats + k.trans_floats + k.table_floats;
     if (e < k.pat_floats + k.trans_floats) {
         const float* rows = e < k.pat_floats ? k.dpp : k.dpt;
         const long l = e < k.pat_floats ? e : e - k.pat_floats;
-        const long img = l / (k.P * 2);
-        const int pc = (int)(l % (k.P * 2));
-        for (long r = 0; r < k.R; ++r)
-            if (k.isglobal || k.ids[r] == img) a += rows[r * k.P * 2 + pc];
+        k.grads[e] = mt_rows_of_image_sum(k.ids, k.R, l / (k.P * 2), rows, k.P * 2, (int)(l % (k.P * 2)), k.isglobal);
     } else if (e < net0) {
-        const long l = e - k.pat_floats - k.trans_floats, img = l / k.C;
-        const int c = (int)(l % k.C);
-        if (k.table_form)
-            for (long r = 0; r < k.R; ++r)
-                if (k.ids[r] == img) a += k.dxe[r * k.C + c];
+        const long l = e - k.pat_floats - k.trans_floats;
+        k.grads[e] = k.table_form ? mt_rows_of_image_sum(k.ids, k.R, l / k.C, k.dxe, k.C, (int)(l % k.C)) : 0.f;
     } else {
-        int ti = 0;
-        for (int i = 1; i < k.n_tensors; ++i) ti += e >= k.ten[i].off ? 1 : 0;
-        const SbTensor& t = k.ten[ti];
-        const long local = e - t.off;
-        const int m = (int)(local / t.width);
-        int n = (int)(local % t.width);
-        long tile;
-        if (n < t.split) {
-            tile = t.base_a + (m >> 4) * t.ntl_a + (n >> 4);
-        } else {
-            n -= t.split;
-            tile = t.base_b + (m >> 4) * t.ntl_b + (n >> 4);
-        }
-        const float* p = k.partial + tile * 256 + (m & 15) * 16 + (n & 15);
-        for (int g = 0; g < k.n_blocks; ++g) a += p[(long)g * k.n_tiles * 256];
+        k.grads[e] = mt_reduce_sum(k.ten, k.partial, k.n_blocks, e);
     }
-    k.grads[e] = a;
 }
 
 struct SbPlan {
     SbK k;
     SbReduce r;
     int blocks;
-    size_t ws_floats;                   // d embedding rows | d pattern_pos rows | d pattern_trans rows | partials (the forward: 2 R align terms)
 };
 
-#define SB_OFF(field) ((int)(offsetof(SbSmem, field) / sizeof(float)))
+// workspace of evd_sparse_blur_backward: d embedding rows | d pattern_pos rows | d pattern_trans rows | the workgroups' partial tiles
+struct SbWs { float *dxe, *dpp, *dpt, *partial; };
+static size_t sb_layout(const SbPlan& pl, void* workspace, SbWs* L) {
+    const SbK& k = pl.k;
+    FloatSlots ws(workspace);
+    L->dxe = ws.take((size_t)k.R * k.C);
+    L->dpp = ws.take(2 * (size_t)k.R * k.P);
+    L->dpt = ws.take(2 * (size_t)k.R * k.P);
+    L->partial = ws.take(mt_partial_floats(pl.blocks, k.mats.n_tiles));
+    return ws.bytes();
+}
+// workspace of evd_sparse_blur_forward (DSK): the rays' terms of align's two means
+static size_t sb_layout_fwd(const SbPlan& pl, void* workspace, float** align_terms) {
+    FloatSlots ws(workspace);
+    *align_terms = ws.take(2 * (size_t)pl.k.R);
+    return ws.bytes();
+}
 
 static int sb_plan(const char* who, const evd_sparse_blur_desc* d, long R, SbPlan* out) {
     EVD_REQUIRE(d, "%s: null descriptor", who);
@@ -524,51 +470,14 @@ static int sb_plan(const char* who, const evd_sparse_blur_desc* d, long R, SbPla
     k.fx = d->fx; k.fy = d->fy; k.cx = d->cx; k.cy = d->cy;
     k.inv2R = R > 0 ? (float)(1.0 / (2.0 * (double)R)) : 0.f;
     k.R = R;
-    // the weight-gradient products, in the flat gradient's order; each tensor of the reduce names the products its columns come from
     SbReduce& r = out->r;
-    int t = 0, nm = 0, nt = 0;
-    long o = (long)k.n_pat * k.P * 2 * (d->optim_trans ? 2 : 1) + (long)k.n_img * k.C;
-    auto add_mat = [&](int rows, int cols, int dy_off, int dy_stride, int x_off, int x_stride) {
-        SbMat& m = k.mats[nm++];
-        m.tile_base = t; m.ntl = (int)cdiv(cols, 16); m.dy_off = dy_off; m.dy_stride = dy_stride; m.x_off = x_off; m.x_stride = x_stride;
-        t += (int)cdiv(rows, 16) * m.ntl;
-        return m;
-    };
-    auto add_tensor = [&](int rows, int width, const SbMat& a, int split, const SbMat* b) {
-        SbTensor& x = r.ten[nt++];
-        x.off = o; x.width = width; x.split = split; x.base_a = a.tile_base; x.ntl_a = a.ntl;
-        x.base_b = b ? b->tile_base : 0; x.ntl_b = b ? b->ntl : 1;
-        o += (long)rows * width;
-    };
-    for (int l = 0; l < k.nh; ++l) {
-        const int cols = l == 0 ? k.in_cnl : k.Wd;
-        const SbMat w = add_mat(k.Wd, cols, SB_OFF(dp) + l * SB_ROWS * SB_HS, SB_HS, l == 0 ? SB_OFF(xs) : SB_OFF(hs) + (l - 1) * SB_ROWS * SB_HS, l == 0 ? SB_XS : SB_HS);
-        add_tensor(k.Wd, cols, w, cols, nullptr);
-        const SbMat b = add_mat(k.Wd, 1, SB_OFF(dp) + l * SB_ROWS * SB_HS, SB_HS, SB_OFF(one), SB_OS);
-        add_tensor(k.Wd, 1, b, 1, nullptr);
-    }
-    {
-        const int dy = SB_OFF(dp) + k.nh * SB_ROWS * SB_HS, hx = SB_OFF(hs) + (k.nh - 1) * SB_ROWS * SB_HS;
-        if (k.sc) {
-            const SbMat wx = add_mat(k.Wd, k.in_cnl, dy, SB_HS, SB_OFF(xs), SB_XS);
-            const SbMat wh = add_mat(k.Wd, k.Wd, dy, SB_HS, hx, SB_HS);
-            add_tensor(k.Wd, k.in_cnl + k.Wd, wx, k.in_cnl, &wh);
-        } else {
-            const SbMat wh = add_mat(k.Wd, k.Wd, dy, SB_HS, hx, SB_HS);
-            add_tensor(k.Wd, k.Wd, wh, k.Wd, nullptr);
-        }
-        const SbMat b = add_mat(k.Wd, 1, dy, SB_HS, SB_OFF(one), SB_OS);
-        add_tensor(k.Wd, 1, b, 1, nullptr);
-        const SbMat w2 = add_mat(k.n_out, k.Wd, SB_OFF(o), SB_OS, SB_OFF(hs) + k.nh * SB_ROWS * SB_HS, SB_HS);
-        add_tensor(k.n_out, k.Wd, w2, k.Wd, nullptr);
-        const SbMat b2 = add_mat(k.n_out, 1, SB_OFF(o), SB_OS, SB_OFF(one), SB_OS);
-        add_tensor(k.n_out, 1, b2, 1, nullptr);
-    }
-    k.n_mats = nm;
-    k.n_tiles = t;
-    r.n_tensors = nt;
-    r.n_tiles = t;
-    r.total = o;
+    MtPlan mp{};
+    mp.ten.end = (long)k.n_pat * k.P * 2 * (d->optim_trans ? 2 : 1) + (long)k.n_img * k.C;      // pattern_pos, pattern_trans, the table come first
+    sb_products(mp, k.nh, k.Wd, k.in_cnl, k.sc, k.n_out);
+    const int rc = mt_check(who, mp, SB_MAX_TILES);
+    if (rc != EVD_OK) return rc;
+    k.mats = mp.mats;
+    r.ten = mp.ten;
     r.pat_floats = (long)k.n_pat * k.P * 2;
     r.trans_floats = d->optim_trans ? r.pat_floats : 0;
     r.table_floats = (long)k.n_img * k.C;
@@ -577,7 +486,6 @@ static int sb_plan(const char* who, const evd_sparse_blur_desc* d, long R, SbPla
     r.isglobal = k.isglobal;
     r.R = R;
     out->blocks = (int)std::min<long>(cdiv(R, k.T), SB_MAX_BLOCKS);
-    out->ws_floats = (size_t)R * k.C + 4 * (size_t)R * k.P + (size_t)out->blocks * t * 256;
     return EVD_OK;
 }
 
@@ -612,7 +520,8 @@ extern "C" {
 size_t evd_sparse_blur_workspace_bytes(const evd_sparse_blur_desc* d, long R) {
     SbPlan pl;
     if (R < 0 || sb_plan("evd_sparse_blur_workspace_bytes", d, R, &pl) != EVD_OK) return 0;
-    return sizeof(float) * pl.ws_floats;
+    SbWs L;
+    return sb_layout(pl, nullptr, &L);
 }
 
 int evd_sparse_blur_forward(const evd_sparse_blur_desc* d, const evd_sparse_blur_params* p, const long* ids, const float* x, const float* rays_x,
@@ -626,13 +535,12 @@ int evd_sparse_blur_forward(const evd_sparse_blur_desc* d, const evd_sparse_blur
     if (rc != EVD_OK) return rc;
     EVD_REQUIRE(new_rays && weight && img_embed && (align || pl.k.pbe), "evd_sparse_blur_forward: null output");
     if (!pl.k.pbe) {
-        const size_t need = sizeof(float) * 2 * (size_t)R;
+        const size_t need = sb_layout_fwd(pl, workspace, &pl.k.align_terms);
         if (!workspace || workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_sparse_blur_forward: workspace %zu < %zu bytes", workspace_bytes, need);
     }
     pl.k.new_rays = new_rays;
     pl.k.weight = weight;
     pl.k.img_embed = img_embed;
-    pl.k.align_terms = static_cast<float*>(workspace);
     k_sparse_blur_fwd<<<pl.blocks, SB_NT, 0, as_stream(stream)>>>(pl.k);
     EVD_LAUNCH_CHECK();
     if (!pl.k.pbe) {
@@ -659,19 +567,19 @@ int evd_sparse_blur_backward(const evd_sparse_blur_desc* d, const evd_sparse_blu
         if (rc != EVD_OK) return rc;
         EVD_REQUIRE(d_new_rays && d_weight, "evd_sparse_blur_backward: null d new_rays / d weight");
         EVD_REQUIRE(!d_feats || pl.k.F > 0, "evd_sparse_blur_backward: d feats with feat_cnl 0");
-        const size_t need = sizeof(float) * pl.ws_floats;
+        SbWs L;
+        const size_t need = sb_layout(pl, workspace, &L);
         if (!workspace || workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_sparse_blur_backward: workspace %zu < %zu bytes", workspace_bytes, need);
-        float* ws = static_cast<float*>(workspace);
         SbK& k = pl.k;
         k.d_new_rays = d_new_rays;
         k.d_weight = d_weight;
         k.d_align = d_align;
         k.d_img_embed = d_img_embed;
         k.d_feats = d_feats;
-        k.dxe = x && d_x ? d_x : ws;
-        k.dpp = ws + (size_t)R * k.C;
-        k.dpt = k.dpp + 2 * (size_t)R * k.P;
-        k.partial = k.dpt + 2 * (size_t)R * k.P;
+        k.dxe = x && d_x ? d_x : L.dxe;
+        k.dpp = L.dpp;
+        k.dpt = L.dpt;
+        k.partial = L.partial;
         k_sparse_blur_bwd<<<pl.blocks, SB_NT, 0, as_stream(stream)>>>(k);
         EVD_LAUNCH_CHECK();
         rk.partial = k.partial;
@@ -680,8 +588,8 @@ int evd_sparse_blur_backward(const evd_sparse_blur_desc* d, const evd_sparse_blu
         rk.dpt = k.dpt;
         rk.n_blocks = pl.blocks;
     }
-    if (rk.total > 0) {
-        k_sparse_blur_reduce<<<(unsigned)cdiv(rk.total, 256), 256, 0, as_stream(stream)>>>(rk);
+    if (rk.ten.end > 0) {
+        k_sparse_blur_reduce<<<(unsigned)cdiv(rk.ten.end, 256), 256, 0, as_stream(stream)>>>(rk);
         EVD_LAUNCH_CHECK();
     }
     return EVD_OK;

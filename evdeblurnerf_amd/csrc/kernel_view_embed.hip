@@ -3,15 +3,14 @@
 // the module per ray (a gather, D addmm + relu + cat and their autograd on R rows); its input is a function of the image id only, so the
 // blur kernel entries take the table this file produces as their `table` and gather from it themselves.
 //
-// kernel_rigid_blur.hip's scheme: a workgroup of four wavefronts takes tiles of 16 images; every product is a set of 16 x 16 float32 MFMA
-// tiles (rb_tile, mfma_f32_tile.h) with the image as the N dimension, dealt to the wavefronts round robin; the embedding rows and the
-// hidden rows live in LDS behind a constant one and zeros up to the tile, the parameters are read in place in torch layout.  A skip
-// layer's input is never assembled: its product is the sum of the embedding columns' and the hidden columns' products.  The backward keeps
-// nothing from the forward: it recomputes the hidden rows, runs d pre-activation down the layers (the embedding columns of layer 0 and of
-// every skip layer add into one d img_embed accumulator in registers), and forms the weight gradients -- a bias is the column the
-// constant one adds -- as MFMA products over the image dimension whose accumulators stay in registers across the workgroup's tiles.  A
-// workgroup holds at most VE_CHUNK such tiles; a wider network spreads them over blockIdx.y, each of which recomputes the rows.  They leave
-// as per-workgroup partials that k_view_embed_reduce sums in workgroup order.  No atomics: two runs give the same bits.
+// A float32 tile network (mfma_f32_tile.h holds the scheme and everything the family shares): a workgroup takes tiles of 16 images, the
+// image is the N dimension of every product, dealt to the wavefronts round robin; the embedding rows and the hidden rows live in LDS
+// behind a constant one and zeros up to the tile, the parameters are read in place in torch layout.  A skip layer's input is never
+// assembled: its product is the sum of the embedding columns' and the hidden columns' products.  The backward keeps nothing from the
+// forward: it recomputes the hidden rows, runs d pre-activation down the layers (the embedding columns of layer 0 and of every skip layer
+// add into one d img_embed accumulator in registers), and forms the weight gradients (ve_products; a bias is the column the constant
+// one adds) with the family's resident accumulators.  A workgroup holds at most VE_CHUNK such tiles; a wider network spreads them over
+// blockIdx.y, each of which recomputes the rows.  k_view_embed_reduce sums the partials.
 #include <algorithm>
 
 #include "evd_common.h"
@@ -19,9 +18,8 @@
 
 namespace evd {
 
-constexpr int VE_NT = 256;            // threads of a workgroup
-constexpr int VE_NW = VE_NT / 64;
-constexpr int VE_TR = 16;             // images of a tile
+constexpr int VE_NT = MT_NT, VE_NW = MT_NW;
+constexpr int VE_TR = MT_TR;          // images of a tile
 constexpr int VE_MAXN = 4096, VE_MAXE = 128, VE_MAXW = 128, VE_MAXD = 8;
 constexpr int VE_CHUNK = 64;          // weight-gradient tiles of one workgroup
 constexpr int VE_TPW = VE_CHUNK / VE_NW;                         // ... of one wavefront
@@ -37,18 +35,13 @@ struct VeK {
     float* out;                        // forward: feature table
     const float* d_out;                // backward
     float *d_table, *partial;
-    int tile_base[VE_MAXD + 1], n_tiles;
+    MtMats mats;                       // the weight-gradient products
 };
 
 __host__ __device__ inline int ve_pad16(int n) { return (n + 15) & ~15; }
 // layer i reads the embedding columns in front of its hidden columns
-__host__ __device__ inline bool ve_skip_in(unsigned skip, int i) { return i > 0 && ((skip >> (i - 1)) & 1u); }
+__host__ __device__ constexpr bool ve_skip_in(unsigned skip, int i) { return i > 0 && ((skip >> (i - 1)) & 1u); }
 __host__ __device__ inline int ve_in_width(int E, int W, unsigned skip, int i) { return i == 0 ? E : ve_skip_in(skip, i) ? E + W : W; }
-// column tiles of layer i's weight gradient: ce over the embedding row (with its constant one in layer 0), ch over [hidden row | 1]
-__host__ __device__ inline void ve_col_tiles(int E, int W, unsigned skip, int i, int& ce, int& ch) {
-    ce = i == 0 ? ve_pad16(E + 1) / 16 : ve_skip_in(skip, i) ? ve_pad16(E) / 16 : 0;
-    ch = i == 0 ? 0 : ve_pad16(W + 1) / 16;
-}
 
 __device__ __forceinline__ const float* ve_pick(const float* const (&a)[VE_MAXD], int i) {
     const float* r = a[0];
@@ -56,28 +49,57 @@ __device__ __forceinline__ const float* ve_pick(const float* const (&a)[VE_MAXD]
     for (int j = 1; j < VE_MAXD; ++j) r = i == j ? a[j] : r;
     return r;
 }
+// LDS, as float offsets: the embedding rows at 0, the outputs of layers 0 .. D - 2, the d pre-activations of layers 0 .. D - 1
+__host__ __device__ constexpr int ve_hs_off(const VeK& k, int i) { return VE_TR * k.ES + i * VE_TR * k.HS; }
+__host__ __device__ constexpr int ve_dp_off(const VeK& k, int i) { return ve_hs_off(k, k.D - 1) + i * VE_TR * k.PS; }
 __device__ __forceinline__ float* ve_es(const VeK& k, float* s) { return s; }
-__device__ __forceinline__ float* ve_hs(const VeK& k, float* s, int i) { return s + VE_TR * k.ES + i * VE_TR * k.HS; }
-__device__ __forceinline__ float* ve_dp(const VeK& k, float* s, int i) { return s + VE_TR * k.ES + (k.D - 1) * VE_TR * k.HS + i * VE_TR * k.PS; }
+__device__ __forceinline__ float* ve_hs(const VeK& k, float* s, int i) { return s + ve_hs_off(k, i); }
+__device__ __forceinline__ float* ve_dp(const VeK& k, float* s, int i) { return s + ve_dp_off(k, i); }
 
-__device__ __forceinline__ void ve_zero_smem(float* s, int floats) {
-    for (int i = threadIdx.x; i < floats; i += VE_NT) s[i] = 0.f;
-    __syncthreads();
+// The weight-gradient products of the layers and their tensors w[0], b[0], ... in the flat gradient's order.  Layer 0: d pre^T [embedding
+// row | 1].  Layer i > 0: d pre^T [hidden row | 1], behind the product with the embedding row where the layer reads it; its weight's
+// columns come from both, its bias is the column of the constant one.
+constexpr void ve_products(MtPlan& pl, const VeK& k) {
+    for (int i = 0; i < k.D; ++i) {
+        const int dy = ve_dp_off(k, i);
+        if (i == 0) {
+            const MtMat e = pl.add_mat(k.W, k.E + 1, dy, k.PS, 0, k.ES);
+            pl.add_tensor(k.W, k.E, e);
+            pl.add_tensor(k.W, 1, e, k.E);
+        } else if (ve_skip_in(k.skip, i)) {
+            const MtMat e = pl.add_mat(k.W, k.E, dy, k.PS, 0, k.ES), h = pl.add_mat(k.W, k.W + 1, dy, k.PS, ve_hs_off(k, i - 1), k.HS);
+            pl.add_tensor(k.W, k.E + k.W, e, 0, k.E, h);
+            pl.add_tensor(k.W, 1, h, k.W);
+        } else {
+            const MtMat h = pl.add_mat(k.W, k.W + 1, dy, k.PS, ve_hs_off(k, i - 1), k.HS);
+            pl.add_tensor(k.W, k.W, h);
+            pl.add_tensor(k.W, 1, h, k.W);
+        }
+    }
 }
+constexpr int ve_max_tiles() {
+    VeK k{};
+    k.E = VE_MAXE; k.W = VE_MAXW; k.D = VE_MAXD; k.skip = (1u << (VE_MAXD - 1)) - 1u;
+    MtPlan pl{};
+    ve_products(pl, k);
+    return pl.mats.n_tiles;
+}
+constexpr int VE_MAX_TILES = ve_max_tiles();                     // weight-gradient tiles at the largest shape, over all blockIdx.y
+static_assert(VE_CHUNK % VE_NW == 0, "a chunk is dealt evenly to the wavefronts");
 
 // W_i h of units m0 .. m0 + 15 of layer i for the tile's 16 images (the bias is added by the caller)
-__device__ __forceinline__ rb_f4 ve_pre(const VeK& k, float* s, int i, int m0) {
+__device__ __forceinline__ mt_f4 ve_pre(const VeK& k, float* s, int i, int m0) {
     const int kin = ve_in_width(k.E, k.W, k.skip, i);
     const float* w = ve_pick(k.p.w, i) + (long)m0 * kin;
-    rb_f4 acc = rb_zero();
-    if (i == 0 || ve_skip_in(k.skip, i)) acc = rb_tile(acc, w, kin, 1, k.W - m0, k.E, ve_es(k, s), k.ES, 1);
-    if (i > 0) acc = rb_tile(acc, w + (kin - k.W), kin, 1, k.W - m0, k.W, ve_hs(k, s, i - 1), k.HS, 1);
+    mt_f4 acc = mt_zero();
+    if (i == 0 || ve_skip_in(k.skip, i)) acc = mt_tile(acc, w, kin, 1, k.W - m0, k.E, ve_es(k, s), k.ES, 1);
+    if (i > 0) acc = mt_tile(acc, w + (kin - k.W), kin, 1, k.W - m0, k.W, ve_hs(k, s, i - 1), k.HS, 1);
     return acc;
 }
 
 // embedding rows of the 16 images from img0 on and the outputs of layers 0 .. D - 2, left in LDS
 __device__ __forceinline__ void ve_hidden(const VeK& k, float* s, int img0) {
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x, wv = tid >> 6;
     const int ne = k.ES - 1;
     float* es = ve_es(k, s);
     for (int i = tid; i < VE_TR * ne; i += VE_NT) {
@@ -92,14 +114,7 @@ __device__ __forceinline__ void ve_hidden(const VeK& k, float* s, int img0) {
     for (int l = 0; l + 1 < k.D; ++l) {
         const float* bias = ve_pick(k.p.b, l);
         float* h = ve_hs(k, s, l);
-        for (int m0 = 16 * wv; m0 < k.W; m0 += 16 * VE_NW) {
-            const rb_f4 acc = ve_pre(k, s, l, m0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int m = m0 + 4 * (lane >> 4) + j;
-                if (m < k.W) h[(lane & 15) * k.HS + m] = act(EVD_ACT_RELU, acc[j] + bias[m]);
-            }
-        }
+        for (int m0 = 16 * wv; m0 < k.W; m0 += 16 * VE_NW) mt_store_relu(h, k.HS, ve_pre(k, s, l, m0), bias, m0, k.W);
         __syncthreads();
     }
 }
@@ -108,21 +123,18 @@ extern __shared__ float ve_smem[];
 
 __global__ __launch_bounds__(VE_NT) void k_view_embed_fwd(VeK k) {
     float* s = ve_smem;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, L = k.D - 1;
+    const int wv = threadIdx.x >> 6, L = k.D - 1;
     const int tiles = (k.n_img + VE_TR - 1) / VE_TR;
-    ve_zero_smem(s, VE_TR * (k.ES + L * k.HS));
+    mt_zero_lds(s, VE_TR * (k.ES + L * k.HS));
     const float* bias = ve_pick(k.p.b, L);
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int img0 = tile * VE_TR;
         ve_hidden(k, s, img0);
         for (int m0 = 16 * wv; m0 < k.W; m0 += 16 * VE_NW) {
-            const rb_f4 acc = ve_pre(k, s, L, m0);
-            const int img = img0 + (lane & 15);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int m = m0 + 4 * (lane >> 4) + j;
-                if (m < k.W && img < k.n_img) k.out[(long)img * k.W + m] = act(EVD_ACT_RELU, acc[j] + bias[m]);
-            }
+            mt_each(ve_pre(k, s, L, m0), m0, k.W, [&](int m, int n, float v) {
+                const int img = img0 + n;
+                if (img < k.n_img) k.out[(long)img * k.W + m] = act(EVD_ACT_RELU, v + bias[m]);
+            });
         }
         __syncthreads();
     }
@@ -130,31 +142,16 @@ __global__ __launch_bounds__(VE_NT) void k_view_embed_fwd(VeK k) {
 
 __global__ __launch_bounds__(VE_NT) void k_view_embed_bwd(VeK k) {
     float* s = ve_smem;
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, L = k.D - 1;
+    const int wv = threadIdx.x >> 6, L = k.D - 1;
     const int tiles = (k.n_img + VE_TR - 1) / VE_TR;
     const int floats = VE_TR * (k.ES + L * k.HS + k.D * k.PS);
     const int chunk0 = blockIdx.y * VE_CHUNK;
-    rb_f4 wg[VE_TPW];
+    mt_f4 wg[VE_TPW];
 #pragma unroll
-    for (int i = 0; i < VE_TPW; ++i) wg[i] = rb_zero();
-    // per weight-gradient tile of this workgroup: float offsets in LDS of its d pre-activation columns and its input columns, and the input's row stride
+    for (int i = 0; i < VE_TPW; ++i) wg[i] = mt_zero();
     int4* jobs = reinterpret_cast<int4*>(s + floats);
-    if (tid < VE_CHUNK && chunk0 + tid < k.n_tiles) {
-        const int t = chunk0 + tid;
-        int i = 0;
-#pragma unroll
-        for (int j = 1; j < VE_MAXD; ++j) i += (j < k.D && t >= k.tile_base[j]) ? 1 : 0;
-        int ce, ch;
-        ve_col_tiles(k.E, k.W, k.skip, i, ce, ch);
-        const int local = t - k.tile_base[i], mt = local / (ce + ch), c = local % (ce + ch);
-        int4 j;
-        j.x = (int)(ve_dp(k, s, i) - s) + 16 * mt;
-        j.y = c < ce ? 16 * c : (int)(ve_hs(k, s, i - 1) - s) + 16 * (c - ce);
-        j.z = c < ce ? k.ES : k.HS;
-        j.w = 0;
-        jobs[tid] = j;
-    }
-    ve_zero_smem(s, floats);
+    mt_jobs(jobs, k.mats, chunk0, VE_CHUNK);
+    mt_zero_lds(s, floats);
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int img0 = tile * VE_TR;
         ve_hidden(k, s, img0);
@@ -163,20 +160,17 @@ __global__ __launch_bounds__(VE_NT) void k_view_embed_bwd(VeK k) {
             const float* bias = ve_pick(k.p.b, L);
             float* dp = ve_dp(k, s, L);
             for (int m0 = 16 * wv; m0 < k.W; m0 += 16 * VE_NW) {
-                const rb_f4 acc = ve_pre(k, s, L, m0);
-                const int img = img0 + (lane & 15);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int m = m0 + 4 * (lane >> 4) + j;
-                    if (m < k.W) dp[(lane & 15) * k.PS + m] = (img < k.n_img && acc[j] + bias[m] > 0.f) ? k.d_out[(long)img * k.W + m] : 0.f;
-                }
+                mt_each(ve_pre(k, s, L, m0), m0, k.W, [&](int m, int n, float v) {
+                    const int img = img0 + n;
+                    dp[n * k.PS + m] = (img < k.n_img && v + bias[m] > 0.f) ? k.d_out[(long)img * k.W + m] : 0.f;
+                });
             }
         }
         __syncthreads();
         // ---- d input = W^T d pre: the hidden columns through the ReLU below, the embedding columns into d img_embed
-        rb_f4 de[VE_EJ];
+        mt_f4 de[VE_EJ];
 #pragma unroll
-        for (int q = 0; q < VE_EJ; ++q) de[q] = rb_zero();
+        for (int q = 0; q < VE_EJ; ++q) de[q] = mt_zero();
         for (int i = L; i >= 0; --i) {
             const int kin = ve_in_width(k.E, k.W, k.skip, i);
             const float* w = ve_pick(k.p.w, i);
@@ -185,101 +179,49 @@ __global__ __launch_bounds__(VE_NT) void k_view_embed_bwd(VeK k) {
 #pragma unroll
                 for (int q = 0; q < VE_EJ; ++q) {
                     const int m0 = 16 * (wv + VE_NW * q);
-                    if (m0 < k.E) de[q] = rb_tile(de[q], w + m0, 1, kin, k.E - m0, k.W, dp, k.PS, 1);
+                    if (m0 < k.E) de[q] = mt_tile(de[q], w + m0, 1, kin, k.E - m0, k.W, dp, k.PS, 1);
                 }
             }
             if (i > 0) {
                 const float* h = ve_hs(k, s, i - 1);
                 float* dlow = ve_dp(k, s, i - 1);
                 for (int m0 = 16 * wv; m0 < k.W; m0 += 16 * VE_NW) {
-                    const rb_f4 acc = rb_tile(rb_zero(), w + (kin - k.W) + m0, 1, kin, k.W - m0, k.W, dp, k.PS, 1);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int m = m0 + 4 * (lane >> 4) + j;
-                        if (m < k.W) dlow[(lane & 15) * k.PS + m] = h[(lane & 15) * k.HS + m] > 0.f ? acc[j] : 0.f;
-                    }
+                    const mt_f4 acc = mt_tile(mt_zero(), w + (kin - k.W) + m0, 1, kin, k.W - m0, k.W, dp, k.PS, 1);
+                    mt_gate_relu(dlow, k.PS, h, k.HS, acc, m0, k.W);
                 }
                 __syncthreads();
             }
         }
         if (blockIdx.y == 0) {
-            const int img = img0 + (lane & 15);
 #pragma unroll
-            for (int q = 0; q < VE_EJ; ++q) {
-                const int m0 = 16 * (wv + VE_NW * q);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int m = m0 + 4 * (lane >> 4) + j;
-                    if (m < k.E && img < k.n_img) k.d_table[(long)img * k.E + m] = de[q][j];
-                }
-            }
+            for (int q = 0; q < VE_EJ; ++q)
+                mt_each(de[q], 16 * (wv + VE_NW * q), k.E, [&](int m, int n, float v) {
+                    if (img0 + n < k.n_img) k.d_table[(long)(img0 + n) * k.E + m] = v;
+                });
         }
         // ---- weight gradients: d pre^T [input | 1] over the tile's images, both operands in LDS
-#pragma unroll
-        for (int i = 0; i < VE_TPW; ++i) {
-            const int t = wv + VE_NW * i;
-            if (chunk0 + t < k.n_tiles) {
-                const int4 j = jobs[t];
-                const float* dy = s + j.x + (lane & 15);
-                const float* X = s + j.y + (lane & 15);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int img = 4 * u + (lane >> 4);
-                    wg[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(dy[img * k.PS], X[img * j.z], wg[i], 0, 0, 0);
-                }
-            }
-        }
+        mt_accumulate<VE_TPW, false>(wg, jobs, s, k.mats.n_tiles, chunk0);
         __syncthreads();
     }
-#pragma unroll
-    for (int i = 0; i < VE_TPW; ++i) {
-        const int t = chunk0 + wv + VE_NW * i;
-        if (t < k.n_tiles) {
-            float* out = k.partial + ((long)blockIdx.x * k.n_tiles + t) * 256;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) out[(4 * (lane >> 4) + j) * 16 + (lane & 15)] = wg[i][j];
-        }
-    }
+    mt_store_partials(wg, k.partial, k.mats.n_tiles, chunk0);
 }
 
 struct VeReduce {
     const float* partial;
     float* grads;                       // behind the table's gradient
-    long total, off[2 * VE_MAXD + 1];   // offsets of w[0], b[0], ... in it
-    int E, W, D, n_blocks, n_tiles, tile_base[VE_MAXD + 1];
-    unsigned skip;
+    int n_blocks;
+    MtTensors ten;                      // w[0], b[0], ... in it
 };
 
 // One thread per element of the weight and bias gradients: the workgroups' partial tiles in workgroup order.
 __global__ __launch_bounds__(256) void k_view_embed_reduce(VeReduce k) {
     const long e = blockIdx.x * 256L + threadIdx.x;
-    if (e >= k.total) return;
-    int ti = 0;
-#pragma unroll
-    for (int i = 1; i < 2 * VE_MAXD; ++i) ti += (i < 2 * k.D && e >= k.off[i]) ? 1 : 0;
-    const int layer = ti >> 1, bias = ti & 1;
-    const int kin = ve_in_width(k.E, k.W, k.skip, layer);
-    int ce, ch;
-    ve_col_tiles(k.E, k.W, k.skip, layer, ce, ch);
-    const long local = e - k.off[ti];
-    const int m = bias ? (int)local : (int)(local / kin);
-    int n = bias ? (layer == 0 ? k.E : k.W) : (int)(local % kin), c;       // column within the embedding part or within [hidden | 1]
-    if (layer == 0 || (!bias && ve_skip_in(k.skip, layer) && n < k.E)) {
-        c = n >> 4;
-    } else {
-        if (!bias && ve_skip_in(k.skip, layer)) n -= k.E;
-        c = ce + (n >> 4);
-    }
-    const long t = k.tile_base[layer] + (m >> 4) * (ce + ch) + c;
-    const float* p = k.partial + t * 256 + (m & 15) * 16 + (n & 15);
-    float a = 0.f;
-    for (int g = 0; g < k.n_blocks; ++g) a += p[(long)g * k.n_tiles * 256];
-    k.grads[e] = a;
+    if (e < k.ten.end) k.grads[e] = mt_reduce_sum(k.ten, k.partial, k.n_blocks, e);
 }
 
 struct VePlan {
     VeK k;
-    long off[2 * VE_MAXD + 1];          // offsets of w[0], b[0], ... behind the table in the flat gradient
+    VeReduce r;
     int blocks, chunks;
     size_t lds_fwd, lds_bwd;
 };
@@ -293,7 +235,7 @@ static int ve_plan(const char* who, const evd_view_embed_mlp_desc* d, VePlan* ou
     EVD_REQUIRE(!((d->skip_mask >> (d->D - 1)) & 1u), "%s: skip_mask names the last layer %d: its output would be embed_dim + W wide, not the W "
                 "that out_channels promises (networks/embedding.py:44,59-60)", who, d->D - 1);
     VeK& k = out->k;
-    memset(&k, 0, sizeof(k));
+    memset(out, 0, sizeof(*out));
     k.n_img = d->n_img;
     k.E = d->embed_dim;
     k.W = d->W;
@@ -302,22 +244,14 @@ static int ve_plan(const char* who, const evd_view_embed_mlp_desc* d, VePlan* ou
     k.ES = ve_pad16(k.E + 1) + 1;
     k.HS = ve_pad16(k.W + 1) + 1;
     k.PS = ve_pad16(k.W) + 1;
-    int t = 0;
-    long o = 0;
-    for (int i = 0; i < k.D; ++i) {
-        int ce, ch;
-        ve_col_tiles(k.E, k.W, k.skip, i, ce, ch);
-        k.tile_base[i] = t;
-        t += ve_pad16(k.W) / 16 * (ce + ch);
-        out->off[2 * i] = o;
-        o += (long)k.W * ve_in_width(k.E, k.W, k.skip, i);
-        out->off[2 * i + 1] = o;
-        o += k.W;
-    }
-    k.tile_base[k.D] = k.n_tiles = t;
-    out->off[2 * k.D] = o;
+    MtPlan mp{};
+    ve_products(mp, k);
+    const int rc = mt_check(who, mp, VE_MAX_TILES);
+    if (rc != EVD_OK) return rc;
+    k.mats = mp.mats;
+    out->r.ten = mp.ten;
     out->blocks = (int)std::min<long>(cdiv(k.n_img, VE_TR), VE_MAX_BLOCKS);
-    out->chunks = (int)cdiv(k.n_tiles, VE_CHUNK);
+    out->chunks = (int)cdiv(k.mats.n_tiles, VE_CHUNK);
     out->lds_fwd = sizeof(float) * VE_TR * (k.ES + (k.D - 1) * k.HS);
     out->lds_bwd = out->lds_fwd + sizeof(float) * VE_TR * k.D * k.PS + sizeof(int4) * VE_CHUNK;
     return EVD_OK;
@@ -334,7 +268,7 @@ struct VeWs { float* partial; };
 static const size_t VE_WS_SLACK = 256;     // alignment slack for an unaligned caller pointer
 static size_t ve_layout(const VePlan& pl, void* workspace, VeWs* L) {
     Workspace ws(workspace);
-    L->partial = ws.take<float>((size_t)pl.blocks * pl.k.n_tiles * 256);
+    L->partial = ws.take<float>(mt_partial_floats(pl.blocks, pl.k.mats.n_tiles));
     return ws.used() + VE_WS_SLACK;
 }
 
@@ -385,20 +319,11 @@ int evd_view_embed_mlp_backward(const evd_view_embed_mlp_desc* d, const evd_view
     EVD_SET_MAX_LDS(k_view_embed_bwd, VE_MAX_LDS);
     k_view_embed_bwd<<<dim3(pl.blocks, pl.chunks), VE_NT, pl.lds_bwd, as_stream(stream)>>>(pl.k);
     EVD_LAUNCH_CHECK();
-    VeReduce rk;
-    memset(&rk, 0, sizeof(rk));
+    VeReduce& rk = pl.r;
     rk.partial = L.partial;
     rk.grads = grads + table_floats;
-    rk.total = pl.off[2 * pl.k.D];
-    for (int i = 0; i <= 2 * pl.k.D; ++i) rk.off[i] = pl.off[i];
-    for (int i = 0; i <= pl.k.D; ++i) rk.tile_base[i] = pl.k.tile_base[i];
-    rk.E = pl.k.E;
-    rk.W = pl.k.W;
-    rk.D = pl.k.D;
-    rk.skip = pl.k.skip;
     rk.n_blocks = pl.blocks;
-    rk.n_tiles = pl.k.n_tiles;
-    k_view_embed_reduce<<<(unsigned)cdiv(rk.total, 256), 256, 0, as_stream(stream)>>>(rk);
+    k_view_embed_reduce<<<(unsigned)cdiv(rk.ten.end, 256), 256, 0, as_stream(stream)>>>(rk);
     EVD_LAUNCH_CHECK();
     return EVD_OK;
 }

@@ -72,11 +72,11 @@ def forward(params, rays, x, M, use_origin, rv_window):
     return warp(rays, r, v, M, use_origin), weight
 
 
-def run(params, rays, ids, M, use_origin, rv_window, proj_new_rays, proj_weight, proj_img_embed=None, x=None):
-    """float64 outputs and gradients of  sum(new_rays * proj_new_rays) + sum(weight * proj_weight) (+ sum(img_embed * proj_img_embed))
+def run(params, rays, ids, M, use_origin, rv_window, proj_new_rays, proj_weight, proj_img_embed=None, x=None, dtype=torch.float64):
+    """outputs and gradients, in `dtype`, of  sum(new_rays * proj_new_rays) + sum(weight * proj_weight) (+ sum(img_embed * proj_img_embed))
     on float32-valued inputs.  ids: image ids [R] (table form) or None with per-ray rows x.
     -> dict(new_rays, weight, img_embed, grads {name: array}, d_rays, d_x (per-ray form))"""
-    T = lambda a: torch.tensor(a, dtype=torch.float64)
+    T = lambda a: torch.tensor(a, dtype=dtype)
     p = {k: T(v).requires_grad_(True) for k, v in params.items()}
     rays_t = T(rays).requires_grad_(True)
     if ids is not None:

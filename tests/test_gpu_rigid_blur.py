@@ -161,6 +161,59 @@ def test_backward_twice_gives_the_same_bits_and_more_tiles_than_workgroups():
     assert not g1[RR.PARAM_KEYS[0]][RR.ABSENT_IMAGE].any()
 
 
+def _widest():
+    """-> module, its parameters, rays, ids, proj, M at the widest shape (test_widest_shape_against_float64)"""
+    from evdeblurnerf_amd.blurmodel import RigidBlurKernel
+    rs = np.random.RandomState(37)
+    C, Wd, M, R, n_img = 128, 64, 15, 17, 3
+    mod = RigidBlurKernel(n_img, embed_dim=C, num_motion=M, W_r=Wd, W_v=Wd, W_w=Wd, use_origin=True, rv_window=0.1).to(DEV)
+    assert {k for k, _ in mod.named_parameters()} == set(RR.PARAM_KEYS)
+    params = {}
+    for k, p in mod.named_parameters():
+        scale = 1.0 if k == RR.PARAM_KEYS[0] else 0.5 if k.endswith("bias") else 1.0 / np.sqrt(p.shape[1])
+        params[k] = (rs.standard_normal(tuple(p.shape)) * scale).astype(np.float32)
+        with torch.no_grad():
+            p.copy_(torch.tensor(params[k]))
+    rays = rs.standard_normal((R, 3, 2)).astype(np.float32)
+    ids = rs.choice([0, 2], R).astype(np.int64)                       # image 1 has no ray
+    proj = dict(new_rays=rs.standard_normal((R, M + 1, 3, 2)).astype(np.float32), weight=rs.standard_normal((R, M + 1)).astype(np.float32),
+                img_embed=rs.standard_normal((R, C)).astype(np.float32))
+    return mod, params, rays, ids, proj, M
+
+
+def test_widest_shape_against_float64():
+    """The largest weight-gradient job table the kernel is built for (embed_dim 128, hidden widths 64, num_motion 15: 143 tiles), on two tiles
+    of rays, the second holding one ray, with an image that has no ray.  Seeded normal table, rays and parameters (weights / sqrt(fan in),
+    biases x 0.5, so the ReLU gates are mixed).  No fixture records the reference's float32 error here, so the bound is measured: the
+    restatement in float32 against itself in float64 on the same inputs, times 4 for a different summation order; outputs get the floor
+    2^-23 max|value|."""
+    mod, params, rays, ids, proj, M = _widest()
+    out1, g1, d1 = _run(mod, None, rays, ids, proj)
+    out2, g2, d2 = _run(mod, None, rays, ids, proj)
+    for k in g1:
+        assert np.array_equal(g1[k], g2[k]), k
+    assert np.array_equal(d1, d2) and all(np.array_equal(out1[k], out2[k]) for k in out1)
+    args = (params, rays, ids, M, True, 0.1, proj["new_rays"], proj["weight"], proj["img_embed"])
+    ref, f32 = RR.run(*args), RR.run(*args, dtype=torch.float32)
+    errs, bounds = {}, {}
+    for k in ("new_rays", "weight"):
+        errs[k] = float(np.abs(out1[k] - ref[k]).max())
+        bounds[k] = max(FACTOR * float(np.abs(f32[k].astype(np.float64) - ref[k]).max()), 2.0 ** -23 * float(np.abs(ref[k]).max()))
+    gerr = {k: RR.rel_l2(g1[k], ref["grads"][k]) for k in RR.PARAM_KEYS}
+    gbound = {k: FACTOR * RR.rel_l2(f32["grads"][k], ref["grads"][k]) for k in RR.PARAM_KEYS}
+    gerr["rays"], gbound["rays"] = RR.rel_l2(d1, ref["d_rays"]), FACTOR * RR.rel_l2(f32["d_rays"], ref["d_rays"])
+    for k, e in errs.items():
+        print(f"widest {k}: {e:.2e} (bound {bounds[k]:.2e})")
+    for k, e in gerr.items():
+        print(f"widest d {k}: {e:.2e} of the norm (bound {gbound[k]:.2e})")
+    assert np.array_equal(out1["img_embed"], params[RR.PARAM_KEYS[0]][ids])
+    assert not g1[RR.PARAM_KEYS[0]][1].any() and g1[RR.PARAM_KEYS[0]][[0, 2]].any(1).all()
+    for k, e in errs.items():
+        assert e <= bounds[k], (k, e, bounds[k])
+    for k, e in gerr.items():
+        assert e <= gbound[k], (k, e, gbound[k])
+
+
 @pytest.mark.parametrize("kw,what", [(dict(D_r=2), "depth"), (dict(W_v=65), "width"), (dict(num_motion=16), "num_motion"), (dict(embed_dim=129), "feature")])
 def test_rejected_shapes(kw, what):
     from evdeblurnerf_amd._lib import EvdError

@@ -156,6 +156,53 @@ def test_backward_twice_gives_the_same_bits_and_more_tiles_than_workgroups():
     assert not g1["img_embed.img_embed"][SR.ABSENT_IMAGE].any() and not g1["pattern_pos"][SR.ABSENT_IMAGE].any()
 
 
+def _widest():
+    """-> module, cfg, its parameters, the batch at the widest shape (test_widest_shape_against_float64)"""
+    from evdeblurnerf_amd.blurmodel import SparseBlurKernel
+    rs = np.random.RandomState(39)
+    P, C, R, n_img = 5, 113, 4, 3
+    cfg = dict(kernel_type="DSK", num_pt=P, kernel_hwindow=10, random_hwindow=0.25, in_embed=3, spatial_embed=0, feat_cnl=0, num_hidden=4, num_wide=64,
+               short_cut=1, isglobal=0, optim_trans=0, optim_spatialvariant_trans=1)
+    mod = SparseBlurKernel(n_img, P, 10, "DSK", view_embed_cnl=C, num_hidden=4, num_wide=64, short_cut=True, optim_spatialvariant_trans=True).to(DEV)
+    assert {k for k, _ in mod.named_parameters()} == set(SR.param_keys(cfg)) and mod.linears[0].in_features == 127
+    params = {}
+    for k, p in mod.named_parameters():
+        scale = 0.5 if k.endswith("bias") else 1.0 / np.sqrt(p.shape[1]) if k.endswith("weight") else 1.0
+        params[k] = (rs.standard_normal(tuple(p.shape)) * scale).astype(np.float32)
+        with torch.no_grad():
+            p.copy_(torch.tensor(params[k]))
+    poses = np.concatenate([np.eye(3, dtype=np.float32)[None].repeat(R, 0) + 0.02 * rs.standard_normal((R, 3, 3)).astype(np.float32),
+                            0.1 * rs.standard_normal((R, 3, 1)).astype(np.float32)], -1)
+    b = dict(ids=np.array([0, 2, 2, 0], np.int64), rays_x=rs.uniform(0, 400, (R, 1)).astype(np.float32), rays_y=rs.uniform(0, 400, (R, 1)).astype(np.float32),
+             poses=poses, noise=rs.standard_normal((R, P, 2)).astype(np.float32), feats=None,
+             proj=dict(new_rays=rs.standard_normal((R, P, 3, 2)).astype(np.float32), weight=rs.standard_normal((R, P)).astype(np.float32),
+                       img_embed=rs.standard_normal((R, C)).astype(np.float32)))
+    return mod, cfg, params, b
+
+
+def test_widest_shape_against_float64():
+    """The largest weight-gradient job table the kernel is built for (row width 127 = 14 + embed_cnl 113, num_hidden 4, num_wide 64, the short cut,
+    5 outputs: 153 tiles), DSK with 5 points, on two tiles of 3 rays, the second holding one, with an image that has no ray.  Seeded normal
+    table, poses, noise and parameters (weights / sqrt(fan in), biases x 0.5, so the ReLU gates are mixed).  No fixture records the reference's
+    float32 error here, so the records _check takes its bounds from are measured: the restatement in float32 against itself in float64 on the
+    same inputs."""
+    mod, cfg, params, b = _widest()
+    poses = b["poses"]
+    out1, g1 = _run(mod, b)
+    out2, g2 = _run(mod, b)
+    for k in g1:
+        assert np.array_equal(g1[k], g2[k]), k
+    assert all(np.array_equal(out1[k], out2[k]) for k in out1)
+    K4 = (float(KMAT[0, 0]), float(KMAT[1, 1]), float(KMAT[0, 2]), float(KMAT[1, 2]))
+    args = (params, cfg, 400, 400, K4, b["ids"], b["rays_x"], b["rays_y"], poses, b["noise"], b["proj"])
+    ref, f32 = SR.run(*args), SR.run(*args, dtype=torch.float32)
+    c = dict(err_out={k: float(np.abs(f32[k].astype(np.float64) - ref[k]).max()) for k in ("new_rays", "weight", "align")},
+             err_g={k: SR.rel_l2(f32["grads"][k], ref["grads"][k]) for k in ref["grads"]})
+    _check("widest", c, out1, g1, ref, per_tensor=True)
+    assert np.array_equal(out1["img_embed"], params["img_embed.img_embed"][b["ids"]])
+    assert not g1["img_embed.img_embed"][1].any() and not g1["pattern_pos"][1].any()
+
+
 def test_per_ray_form_equals_the_table_form():
     """x = table[ids] through the Function: the same outputs and network gradients bit for bit (the same arithmetic on the same rows), and
     d x = the rows whose per-image sums are the table's gradient"""
