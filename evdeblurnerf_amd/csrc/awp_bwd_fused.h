@@ -18,6 +18,7 @@ constexpr int KW = AWP_W / 16, KIN = AWP_IN / 16;
 // accumulator blocks [row tile][column tile] per layer, top layer first; then the shared bias block (column 2 (3 - l) + row tile)
 constexpr int A_L3 = 0, A_L2 = 4, A_L1 = 8, A_BIAS = 12, NBLK = 13;
 constexpr int acc0(int l) { return l == 3 ? A_L3 : l == 2 ? A_L2 : A_L1; }
+constexpr int bcol(int l) { return 2 * (3 - l); }
 // W^T fragments in LDS: layers 3, 2, 1 [2 output tiles][4 k-steps], layer 0 [4 output tiles][4 k-steps]
 constexpr int W_L3 = 0, W_L2 = 8, W_L1 = 16, W_L0 = 24, W_N = 40;
 constexpr int wt0(int l) { return l == 3 ? W_L3 : l == 2 ? W_L2 : l == 1 ? W_L1 : W_L0; }
@@ -45,82 +46,15 @@ __global__ __launch_bounds__(256, 1) void k_awp_bwd_fused(const AwpBwdFusedParam
     pipe_fp16_saturate<PREC>();
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), n = lane & 31, h = lane >> 5;
 #pragma unroll
-    for (int l = 0; l < AWP_D; ++l) {
-        const int cnt = (l == 0 ? 16 : 8) * 64;
-        for (int i = tid; i < cnt; i += 256) *reinterpret_cast<f32x4*>(wl + wt0(l) * 1024 + i * 16) = *reinterpret_cast<const f32x4*>(p.wt[l] + (long)i * 16);
-    }
+    for (int l = 0; l < AWP_D; ++l) bt_stage_wt(wl, wt0(l), p.wt[l], l == 0 ? 16 : 8, tid);
     __syncthreads();
-    auto WT = [&](int f) -> W4 { return *reinterpret_cast<const W4*>(wl + f * 1024 + lane * 16); };
-    const unsigned one = half_one_pair<PREC>();
-    auto selectors = [&](W4& sel0, W4& sel1) {
-        int nn = n, hh = h;
-        asm volatile("" : "+v"(nn), "+v"(hh));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int kk = 8 * hh + 2 * e;
-            sel0.w[e] = (nn == kk ? (one & 0xffffu) : 0u) | (nn == kk + 1 ? (one & 0xffff0000u) : 0u);
-            sel1.w[e] = (nn == 16 + kk ? (one & 0xffffu) : 0u) | (nn == 17 + kk ? (one & 0xffff0000u) : 0u);
-        }
-    };
-    auto ones = [&](int c) {
-        int nn = n;
-        asm volatile("" : "+v"(nn));
-        const unsigned v = nn == c ? one : 0u;
-        return W4{{v, v, v, v}};
-    };
     f32x16 acc[NBLK];
 #pragma unroll
     for (int b = 0; b < NBLK; ++b)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[b][i] = 0.f;
-    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const float scale = grad_scale(p.words[0], false);
     auto ld = [&](long t, int slot) -> W4 { return *reinterpret_cast<const W4*>(p.store + t * TILE_BYTES + (long)slot * 1024 + lane * 16); };
-    auto prod = [&](f32x16& a, const W4 (&yt)[2], const W4 (&xt)[2]) {
-        a = mfma_half<PREC>(yt[0], xt[0], a);
-        a = mfma_half<PREC>(yt[1], xt[1], a);
-    };
-    auto bias = [&](int c, const W4 (&yt)[2]) {
-        const W4 o = ones(c);
-        acc[A_BIAS] = mfma_half<PREC>(yt[0], o, acc[A_BIAS]);
-        acc[A_BIAS] = mfma_half<PREC>(yt[1], o, acc[A_BIAS]);
-    };
-    auto frags = [&](const f32x16& d, W4& o0, W4& o1) {
-        typename O::B o2[2];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) O::template set_pair<false>(o2[k >> 2], k & 3, d[2 * k], d[2 * k + 1]);
-        o0 = __builtin_bit_cast(W4, o2[0]);
-        o1 = __builtin_bit_cast(W4, o2[1]);
-    };
-    auto mask = [&](W4& g, const W4& a) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) g.w[e] = mask_word(g.w[e], a.w[e]);
-    };
-    // one 64 -> 64 layer l (3, 2, 1): wgrad of (gradient g, input activations x), dgrad to the input's gradient, masked by x
-    auto layer = [&](int l, const W4 (&g)[4], const W4 (&x)[4], W4 (&gout)[4]) {
-        W4 yt[2][2], xt[2], sel0, sel1;
-        selectors(sel0, sel1);
-#pragma unroll
-        for (int yb = 0; yb < 2; ++yb) transpose_block<PREC>(g[2 * yb], g[2 * yb + 1], sel0, sel1, yt[yb]);
-#pragma unroll
-        for (int xb = 0; xb < 2; ++xb) {
-            transpose_block<PREC>(x[2 * xb], x[2 * xb + 1], sel0, sel1, xt);
-#pragma unroll
-            for (int yb = 0; yb < 2; ++yb) prod(acc[acc0(l) + 2 * yb + xb], yt[yb], xt);
-        }
-#pragma unroll
-        for (int yb = 0; yb < 2; ++yb) bias(2 * (3 - l) + yb, yt[yb]);
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            f32x16 d = zero16;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) d = mfma_half<PREC>(WT(wt0(l) + 4 * r + j), g[j], d);
-            frags(d, gout[2 * r], gout[2 * r + 1]);
-            mask(gout[2 * r], x[2 * r]);
-            mask(gout[2 * r + 1], x[2 * r + 1]);
-        }
-    };
-
     const long nw = (long)gridDim.x * 4;
     long t = (long)blockIdx.x * 4 + wave;
     const long last = p.tiles - 1;
@@ -165,16 +99,16 @@ __global__ __launch_bounds__(256, 1) void k_awp_bwd_fused(const AwpBwdFusedParam
                 O::template set_pair<false>(b, 2, hi[0] * scale, hi[1] * scale);
                 O::template set_pair<false>(b, 3, hi[2] * scale, hi[3] * scale);
                 g3[j] = __builtin_bit_cast(W4, b);
-                mask(g3[j], e3[j]);
+                bt_mask<PREC>(g3[j], e3[j]);
             }
         }
-        layer(3, g3, e2, g2);
+        bt_layer64<PREC>(acc, acc0(3), A_BIAS, bcol(3), wl, wt0(3), lane, g3, e2, g2);
         if (t + nw < p.tiles) load_top(t + nw);
         asm volatile("" ::: "memory");
-        layer(2, g2, e1, g1);
+        bt_layer64<PREC>(acc, acc0(2), A_BIAS, bcol(2), wl, wt0(2), lane, g2, e1, g1);
         if (t + nw < p.tiles) load4(e2, t + nw, E0 + 2 * KW);
         asm volatile("" ::: "memory");
-        layer(1, g1, e0, g0);
+        bt_layer64<PREC>(acc, acc0(1), A_BIAS, bcol(1), wl, wt0(1), lane, g1, e0, g0);
         // ---- layer 0: d e0 leaves for its wgrad; d geo = W_0^T d e0 (no activation below the geo features) ------------------------------
         if (t + nw < p.tiles) load4(e1, t + nw, E0 + KW);
         asm volatile("" ::: "memory");
@@ -184,11 +118,9 @@ __global__ __launch_bounds__(256, 1) void k_awp_bwd_fused(const AwpBwdFusedParam
             for (int j = 0; j < 4; ++j) *reinterpret_cast<W4*>(out + (long)(D_E0 + j) * 1024) = g0[j];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                f32x16 d = zero16;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) d = mfma_half<PREC>(WT(W_L0 + 4 * r + j), g0[j], d);
+                const f32x16 d = bt_dgrad64<PREC>(wl, W_L0, r, lane, g0);
                 W4 o0, o1;
-                frags(d, o0, o1);
+                bt_frags<PREC>(d, o0, o1);
                 *reinterpret_cast<W4*>(out + (long)(D_GEO + 2 * r) * 1024) = o0;
                 *reinterpret_cast<W4*>(out + (long)(D_GEO + 2 * r + 1) * 1024) = o1;
                 float nan_probe = 0.f;               // fmaxf drops a NaN (and inf - inf): record it as +inf, like k_mam_local_bwd does for |d h_local|
@@ -205,21 +137,7 @@ __global__ __launch_bounds__(256, 1) void k_awp_bwd_fused(const AwpBwdFusedParam
         const unsigned mb = __float_as_uint(gmax * grad_scale(p.words[0], true));
         if (mb > *reinterpret_cast<volatile unsigned*>(p.words + 1)) atomicMax(p.words + 1, mb);
     }
-    float* part = p.partial + (long)blockIdx.x * NBLK * 1024;
-#pragma unroll
-    for (int b = 0; b < NBLK; ++b) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 v = {acc[b][4 * q], acc[b][4 * q + 1], acc[b][4 * q + 2], acc[b][4 * q + 3]};
-            *reinterpret_cast<f32x4*>(fold + wave * 1024 + lane * 16 + 4 * q) = v;
-        }
-        __syncthreads();
-        f32x4 s = *reinterpret_cast<const f32x4*>(fold + wave * 256 + lane * 4);
-#pragma unroll
-        for (int w = 1; w < 4; ++w) s += *reinterpret_cast<const f32x4*>(fold + w * 1024 + wave * 256 + lane * 4);
-        *reinterpret_cast<f32x4*>(part + b * 1024 + wave * 256 + lane * 4) = s;
-        __syncthreads();
-    }
+    bt_fold4(acc, fold, p.partial + (long)blockIdx.x * NBLK * 1024, wave, lane);
 }
 
 }  // namespace evd

@@ -139,8 +139,7 @@ __global__ __launch_bounds__(256) void k_awp_rows_to_frags(const float* __restri
     O::template set_pair<false>(b, 1, lo[2] * s, lo[3] * s);
     O::template set_pair<false>(b, 2, hi[0] * s, hi[1] * s);
     O::template set_pair<false>(b, 3, hi[2] * s, hi[3] * s);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) b.w[e] = mask_word(b.w[e], act.w[e]);
+    O::mask_act(b, __builtin_bit_cast(typename O::B, act));
     act_store(a, dlast + j, b);
 }
 

@@ -20,8 +20,7 @@ struct BwdChain : BwdPlanBase {
     hipStream_t st;                     // the caller's stream
     BwdChain(const BwdPlanBase& b, long tile_bytes_, hipStream_t st_) : BwdPlanBase(b), tile_bytes(tile_bytes_), st(st_) {}
 
-    // workgroups of a wgrad launch: the NeRF and the PDRF levels / the fused steps and the AWP embedding
-    int wgrad_grid() const { return (int)(cdiv(tiles, (long)WGRAD_TPI) < wgrad_blocks ? cdiv(tiles, (long)WGRAD_TPI) : wgrad_blocks); }
+    // workgroups of a wgrad launch or a fused step: one sample tile per iteration, grid-stride
     int tile_grid() const { return (int)(tiles < wgrad_blocks ? tiles : wgrad_blocks); }
 
     // *ws = the stream of a wgrad: the side stream, behind everything issued so far on the caller's stream (the producer of the

@@ -52,20 +52,6 @@ struct VoxBwdFusedParams {
     int d_fts_stride;
 };
 
-// one stored fragment (one 32 x 16 block) transposed: transpose_block with an all-zero second fragment, one MFMA
-template <int PREC> __device__ __forceinline__ void transpose_single(const W4& f0, const W4& sel0, W4 (&t)[2]) {
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const f32x16 d = mfma_half<PREC>(f0, sel0, zero);
-    typename POps<PREC>::B b;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) POps<PREC>::template set_pair<false>(b, e, d[8 * q + 2 * e], d[8 * q + 2 * e + 1]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) t[q].w[e] = b.w[e];
-    }
-}
-
 template <int PREC>
 __global__ __launch_bounds__(256, 1) void k_voxel_bwd_fused64(const VoxBwdFusedParams p) {
     using namespace f64;
@@ -80,31 +66,11 @@ __global__ __launch_bounds__(256, 1) void k_voxel_bwd_fused64(const VoxBwdFusedP
         constexpr int w0[VBWD_NSTREAMS + 1] = {W_C2, W_C1, W_C0, W_SG, W_L0, W_N};
         static_assert(VBWD_C2 == 0 && VBWD_C1 == 1 && VBWD_C0 == 2 && VBWD_SIGGEO == 3 && VBWD_L0 == 4, "stream order");
 #pragma unroll
-        for (int k = 0; k < VBWD_NSTREAMS; ++k)
-            for (int i = tid; i < (w0[k + 1] - w0[k]) * 64; i += 256)
-                *reinterpret_cast<f32x4*>(wl + w0[k] * 1024 + i * 16) = *reinterpret_cast<const f32x4*>(p.wt[k] + (long)i * 16);
+        for (int k = 0; k < VBWD_NSTREAMS; ++k) bt_stage_wt(wl, w0[k], p.wt[k], w0[k + 1] - w0[k], tid);
     }
     __syncthreads();
-    auto WT = [&](int f) -> W4 { return *reinterpret_cast<const W4*>(wl + f * 1024 + lane * 16); };
-    // transposition selectors (k_wgrad): sel0[kk][n] = (n == kk), sel1[kk][n] = (n == 16 + kk); re-made where they are used (a dozen VALU
-    // instructions) instead of living in registers next to 304 accumulators; `ones(c)`: the bias column at position c
-    const unsigned one = half_one_pair<PREC>();
-    auto selectors = [&](W4& sel0, W4& sel1) {
-        int nn = n, hh = h;
-        asm volatile("" : "+v"(nn), "+v"(hh));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int kk = 8 * hh + 2 * e;
-            sel0.w[e] = (nn == kk ? (one & 0xffffu) : 0u) | (nn == kk + 1 ? (one & 0xffff0000u) : 0u);
-            sel1.w[e] = (nn == 16 + kk ? (one & 0xffffu) : 0u) | (nn == 17 + kk ? (one & 0xffff0000u) : 0u);
-        }
-    };
-    auto ones = [&](int c) {
-        int nn = n;
-        asm volatile("" : "+v"(nn));
-        const unsigned v = nn == c ? one : 0u;
-        return W4{{v, v, v, v}};
-    };
+    // (the transposition selectors and the bias columns are re-made where they are used -- bwd_tile.h -- instead of living in registers next
+    // to 304 accumulators)
     f32x16 acc[NBLK];
 #pragma unroll
     for (int b = 0; b < NBLK; ++b)
@@ -115,29 +81,6 @@ __global__ __launch_bounds__(256, 1) void k_voxel_bwd_fused64(const VoxBwdFusedP
     constexpr long TB = VS::TILE_BYTES;
 
     auto ld = [&](long t, int slot) -> W4 { return *reinterpret_cast<const W4*>(p.store + t * TB + (long)slot * 1024 + lane * 16); };
-    // wgrad of one (gradient block, activation block) pair: both already transposed
-    auto prod = [&](f32x16& a, const W4 (&yt)[2], const W4 (&xt)[2]) {
-        a = mfma_half<PREC>(yt[0], xt[0], a);
-        a = mfma_half<PREC>(yt[1], xt[1], a);
-    };
-    auto bias = [&](int c, const W4 (&yt)[2]) {
-        const W4 o = ones(c);
-        acc[A_BIAS] = mfma_half<PREC>(yt[0], o, acc[A_BIAS]);
-        acc[A_BIAS] = mfma_half<PREC>(yt[1], o, acc[A_BIAS]);
-    };
-    // 32 output rows of a dgrad layer (accumulator d) as the two fragments of the next gradient, masked by the stored activations m0, m1
-    auto frags = [&](const f32x16& d, W4& o0, W4& o1) {
-        typename O::B o2[2];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) O::template set_pair<false>(o2[k >> 2], k & 3, d[2 * k], d[2 * k + 1]);
-        o0 = __builtin_bit_cast(W4, o2[0]);
-        o1 = __builtin_bit_cast(W4, o2[1]);
-    };
-    auto mask = [&](W4& g, const W4& a) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) g.w[e] = mask_word(g.w[e], a.w[e]);
-    };
-
     const long nw = (long)gridDim.x * 4;
     long t = (long)blockIdx.x * 4 + wave;
     const long last = p.tiles - 1;
@@ -186,20 +129,20 @@ __global__ __launch_bounds__(256, 1) void k_voxel_bwd_fused64(const VoxBwdFusedP
         }
         {
             W4 yt[2], xt[2], sel0, sel1;
-            selectors(sel0, sel1);
-            transpose_single<PREC>(gcol, sel0, yt);
+            bt_selectors<PREC, true>(n, h, sel0, sel1);
+            transpose_block<PREC, true>(gcol, gcol, sel0, sel1, yt);         // the gradient is ONE fragment (3 of its 16 rows in use)
 #pragma unroll
             for (int xb = 0; xb < 2; ++xb) {
                 transpose_block<PREC>(c1[2 * xb], c1[2 * xb + 1], sel0, sel1, xt);
-                prod(acc[A_C2 + xb], yt, xt);
+                bt_prod<PREC>(acc[A_C2 + xb], yt, xt);
             }
-            bias(B_C2, yt);
+            bt_bias<PREC, true>(acc[A_BIAS], yt, n, B_C2);
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
-                const f32x16 d = mfma_half<PREC>(WT(W_C2 + r), gcol, zero16);
-                frags(d, gc1[2 * r], gc1[2 * r + 1]);
-                mask(gc1[2 * r], c1[2 * r]);
-                mask(gc1[2 * r + 1], c1[2 * r + 1]);
+                const f32x16 d = mfma_half<PREC>(bt_wt(wl, W_C2 + r, lane), gcol, zero16);
+                bt_frags<PREC>(d, gc1[2 * r], gc1[2 * r + 1]);
+                bt_mask<PREC>(gc1[2 * r], c1[2 * r]);
+                bt_mask<PREC>(gc1[2 * r + 1], c1[2 * r + 1]);
             }
         }
         // ---- phase 2: colour_net.1 ------------------------------------------------------------------------------------------
@@ -207,55 +150,19 @@ __global__ __launch_bounds__(256, 1) void k_voxel_bwd_fused64(const VoxBwdFusedP
         for (int j = 0; j < 4; ++j) hid[j] = ld(t, VS::HID + j);
         asm volatile("" ::: "memory");
         W4 gc0[4];
-        {
-            W4 yt[2][2], xt[2], sel0, sel1;
-            selectors(sel0, sel1);
-#pragma unroll
-            for (int yb = 0; yb < 2; ++yb) transpose_block<PREC>(gc1[2 * yb], gc1[2 * yb + 1], sel0, sel1, yt[yb]);
-#pragma unroll
-            for (int xb = 0; xb < 2; ++xb) {
-                transpose_block<PREC>(c0[2 * xb], c0[2 * xb + 1], sel0, sel1, xt);
-#pragma unroll
-                for (int yb = 0; yb < 2; ++yb) prod(acc[A_C1 + 2 * yb + xb], yt[yb], xt);
-            }
-#pragma unroll
-            for (int yb = 0; yb < 2; ++yb) bias(B_C1 + yb, yt[yb]);
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                f32x16 d = zero16;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) d = mfma_half<PREC>(WT(W_C1 + 4 * r + j), gc1[j], d);
-                frags(d, gc0[2 * r], gc0[2 * r + 1]);
-                mask(gc0[2 * r], c0[2 * r]);
-                mask(gc0[2 * r + 1], c0[2 * r + 1]);
-            }
-        }
+        bt_layer64<PREC>(acc, A_C1, A_BIAS, B_C1, wl, W_C1, lane, gc1, c0, gc0);
         // ---- phase 3: colour_net.0 on cat([geo, PE(dirs)]) ------------------------------------------------------------------
 #pragma unroll
         for (int j = 0; j < 6; ++j) in0[j] = ld(t, VS::IN0 + j);
         asm volatile("" ::: "memory");
         W4 dgeo0;
         {
-            W4 yt[2][2], xt[2], sel0, sel1;
-            selectors(sel0, sel1);
-#pragma unroll
-            for (int yb = 0; yb < 2; ++yb) transpose_block<PREC>(gc0[2 * yb], gc0[2 * yb + 1], sel0, sel1, yt[yb]);
-#pragma unroll
-            for (int xb = 0; xb < 2; ++xb) {
-                transpose_block<PREC>(gd[2 * xb], gd[2 * xb + 1], sel0, sel1, xt);
-#pragma unroll
-                for (int yb = 0; yb < 2; ++yb) prod(acc[A_C0 + 2 * yb + xb], yt[yb], xt);
-            }
-#pragma unroll
-            for (int yb = 0; yb < 2; ++yb) bias(B_C0 + yb, yt[yb]);
+            bt_wgrad64<PREC, 2, true>(acc, A_C0, A_BIAS, B_C0, lane, gc0, gd);
             char* out = p.store + t * TB + lane * 16;
 #pragma unroll
-            for (int r = 0; r < 2; ++r) {        // output tile 0: d geo (15 rows: its second fragment is zero), tile 1: d PE(dirs)
-                f32x16 d = zero16;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) d = mfma_half<PREC>(WT(W_C0 + 4 * r + j), gc0[j], d);
+            for (int r = 0; r < 2; ++r) {        // output tile 0: d geo (15 rows: its second fragment is zero), tile 1: d PE(dirs); no activation to mask by
                 W4 o0, o1;
-                frags(d, o0, o1);
+                bt_frags<PREC>(bt_dgrad64<PREC>(wl, W_C0, r, lane, gc0), o0, o1);
                 if (r == 0) dgeo0 = o0;
                 else {
                     *reinterpret_cast<W4*>(out + (long)(VS::D_DIRPE) * 1024) = o0;
@@ -269,44 +176,32 @@ __global__ __launch_bounds__(256, 1) void k_voxel_bwd_fused64(const VoxBwdFusedP
         W4 dhid[4];
         {
             W4 yt[2], xt[2], sel0, sel1;
-            selectors(sel0, sel1);
+            bt_selectors<PREC, true>(n, h, sel0, sel1);
             transpose_block<PREC>(dgeo0, gsig, sel0, sel1, yt);          // rows 0..15: geo positions, rows 16..31: the sigma fragment
 #pragma unroll
             for (int xb = 0; xb < 2; ++xb) {
                 transpose_block<PREC>(hid[2 * xb], hid[2 * xb + 1], sel0, sel1, xt);
-                prod(acc[A_SG + xb], yt, xt);
+                bt_prod<PREC>(acc[A_SG + xb], yt, xt);
             }
 #pragma unroll
             for (int r = 0; r < 2; ++r) {        // k-steps of the stream: geo_0, geo_1 (all padding for 15 channels), sigma
-                f32x16 d = mfma_half<PREC>(WT(W_SG + 3 * r), dgeo0, zero16);
-                d = mfma_half<PREC>(WT(W_SG + 3 * r + 2), gsig, d);
-                frags(d, dhid[2 * r], dhid[2 * r + 1]);
-                mask(dhid[2 * r], hid[2 * r]);
-                mask(dhid[2 * r + 1], hid[2 * r + 1]);
+                f32x16 d = mfma_half<PREC>(bt_wt(wl, W_SG + 3 * r, lane), dgeo0, zero16);
+                d = mfma_half<PREC>(bt_wt(wl, W_SG + 3 * r + 2, lane), gsig, d);
+                bt_frags<PREC>(d, dhid[2 * r], dhid[2 * r + 1]);
+                bt_mask<PREC>(dhid[2 * r], hid[2 * r]);
+                bt_mask<PREC>(dhid[2 * r + 1], hid[2 * r + 1]);
             }
         }
         // ---- phase 5: sigma_net.0 on cat([fts, PE(pts)]) ---------------------------------------------------------------------
         if (t + nw < p.tiles) load2(t + nw);
         asm volatile("" ::: "memory");
         {
-            W4 yt[2][2], xt[2], sel0, sel1;
-            selectors(sel0, sel1);
-#pragma unroll
-            for (int yb = 0; yb < 2; ++yb) transpose_block<PREC>(dhid[2 * yb], dhid[2 * yb + 1], sel0, sel1, yt[yb]);
-#pragma unroll
-            for (int xb = 0; xb < 3; ++xb) {
-                transpose_block<PREC>(in0[2 * xb], in0[2 * xb + 1], sel0, sel1, xt);
-#pragma unroll
-                for (int yb = 0; yb < 2; ++yb) prod(acc[A_L0 + 3 * yb + xb], yt[yb], xt);
-            }
+            bt_wgrad64<PREC, 3, false>(acc, A_L0, A_BIAS, 0, lane, dhid, in0);
             char* out = p.store + t * TB + lane * 16;
 #pragma unroll
             for (int r = 0; r < 3; ++r) {        // output tile 0: d fts, tiles 1, 2: d PE(pts)
-                f32x16 d = zero16;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) d = mfma_half<PREC>(WT(W_L0 + 4 * r + j), dhid[j], d);
                 W4 o0, o1;
-                frags(d, o0, o1);
+                bt_frags<PREC>(bt_dgrad64<PREC>(wl, W_L0, r, lane, dhid), o0, o1);
                 if (r == 0 && p.d_fts) {         // the feature gradient leaves as the float32 rows the tri-plane scatter reads (k_frags_to_rows' output)
                     const long smp = t * 32 + n;
                     if (smp < p.nsamp) frag_pair_to_row<PREC>(o0, o1, p.d_fts + smp * p.d_fts_stride, h, grad_scale(*p.maxbits, true));
@@ -318,21 +213,7 @@ __global__ __launch_bounds__(256, 1) void k_voxel_bwd_fused64(const VoxBwdFusedP
         }
     }
     // ---- the workgroup's four accumulator sets folded through LDS: one partial block set per workgroup ----------------------------
-    float* part = p.partial + (long)blockIdx.x * NBLK * 1024;
-#pragma unroll
-    for (int b = 0; b < NBLK; ++b) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 v = {acc[b][4 * q], acc[b][4 * q + 1], acc[b][4 * q + 2], acc[b][4 * q + 3]};
-            *reinterpret_cast<f32x4*>(fold + wave * 1024 + lane * 16 + 4 * q) = v;
-        }
-        __syncthreads();
-        f32x4 s = *reinterpret_cast<const f32x4*>(fold + wave * 256 + lane * 4);
-#pragma unroll
-        for (int w = 1; w < 4; ++w) s += *reinterpret_cast<const f32x4*>(fold + w * 1024 + wave * 256 + lane * 4);
-        *reinterpret_cast<f32x4*>(part + b * 1024 + wave * 256 + lane * 4) = s;
-        __syncthreads();
-    }
+    bt_fold4(acc, fold, p.partial + (long)blockIdx.x * NBLK * 1024, wave, lane);
 }
 
 // the shared bias block: column c of the workgroups' partial blocks summed -> the bias gradient it belongs to (rows through an index map)

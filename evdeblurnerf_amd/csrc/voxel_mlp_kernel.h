@@ -28,7 +28,7 @@ template <int HD, int G, int FT> struct VStore {
     // gradient slots; D_GEO is followed by the 2 direction-encoding gradient fragments, D_FTS by the 4 point-encoding ones (both
     // produced by the same dgrad layer as their neighbours, in the encodings' own fragment arrangement)
     // (M_C1 sits right behind G_COL: the fused backward of color_net.1 fetches [d colour fragment | c1's ReLU bits] as ONE pair of
-    // DMA pieces and forms d c1 from them in registers, nerf_train_kernel.h k_wgrad_dgrad YGEN)
+    // DMA pieces and forms d c1 from them in registers, nerf_bwd_fused.h FusedLayer YGEN)
     static constexpr int G_COL = FWD_END, M_C1 = G_COL + 1, G_SIG = M_C1 + 1, D_C1 = G_SIG + 1, D_C0 = D_C1 + KS, D_GEO = D_C0 + KS, D_DIRPE = D_GEO + 2 * GT,
                          D_HID = D_DIRPE + PEV_KS, D_FTS = D_HID + KS, D_PE = D_FTS + 2 * ((FT + 31) / 32),
                          M_HID = D_PE + PE_KS, M_C0 = M_HID + 1,      // ReLU patterns as bit masks (mlp_pipe.h frag_bits)

@@ -196,7 +196,7 @@ template <int PREC> static int voxel_backward_fused64(const BwdChain& c, const V
 }
 
 // The per-layer sequence.  The 256-wide layers of the fine level run wgrad(l) and dgrad(l) in one launch in the half-precision modes
-// (FUSABLE; nerf_train_kernel.h k_wgrad_dgrad) when the layer's weight gradient is wanted; every other layer issues its wgrad before the
+// (FUSABLE; nerf_bwd_fused.h k_wgrad_dgrad) when the layer's weight gradient is wanted; every other layer issues its wgrad before the
 // dgrad that reads the same arrays (BwdChain::wgrad).
 template <int PREC, int HD, int G, int FT> static int voxel_backward_layers(const BwdChain& c, const VoxBwdPlan& b) {
     typedef VStore<HD, G, FT> VS;
@@ -205,7 +205,7 @@ template <int PREC, int HD, int G, int FT> static int voxel_backward_layers(cons
     hipStream_t st = c.st;
     const BwdSwitches& sw = bwd_switches();
     const VoxBwdGrads& g = b.grads;
-    const int wb = c.wgrad_grid();
+    const int wb = c.tile_grid();
     auto dgrad = [&](int stream, int in_slot, int extra_slot, int mask_slot, int out_slot) { return c.dgrad_params(b.wt[stream], in_slot, extra_slot, mask_slot, out_slot); };
     int rc;
     hipLaunchKernelGGL((k_voxel_grad_frags<PREC>), dim3((unsigned)cdiv(b.tiles * 64, 256L)), dim3(256), 0, st, b.d_raw, b.raw, b.nsamp, b.maxbits, b.store,

@@ -1,4 +1,4 @@
-// Probe: what rate does the TRAFFIC of k_wgrad_dgrad (nerf_train_kernel.h) reach without its arithmetic?  The kernel reads, per 32-sample
+// Probe: what rate does the TRAFFIC of k_wgrad_dgrad (nerf_bwd_fused.h) reach without its arithmetic?  The kernel reads, per 32-sample
 // tile, 16 KiB of gradient fragments + 16 KiB of activation fragments by LDS-DMA (8 wavefronts x 4 x global_load_lds_dwordx4 of 1 KiB)
 // into a 3-deep ring and writes 16 KiB of d X; 256 persistent workgroups of 512 threads walk the tiles with a grid stride.  Measured in
 // the iteration it moves 48 KiB per tile at ~4.3 TB/s.  Variants:
