@@ -15,8 +15,9 @@ from evdeblurnerf_amd import weights as W
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 
-# fragment slots of the embedding's store (csrc/awp_embed.h, namespace awpstore)
-A_GEO, A_E0, A_D_E0, A_D_GEO, A_TILE_FRAGS = 0, 8, 24, 40, 48
+# fragment slots of the embedding's store and its decoder: tests/store_decode.py
+from store_decode import A_GEO, A_E0, A_D_E0, A_D_GEO, A_TILE_FRAGS, adecode, phi  # noqa: E402,F401
+
 AABB = ((-1.5, -1.5, -1.0), (1.5, 1.5, 1.0))
 
 
@@ -26,25 +27,9 @@ def O():
     return oracle
 
 
-def phi(kk):
-    return 8 * ((kk & 7) >> 2) + 4 * (kk >> 3) + (kk & 3)
-
-
 def rel_l2(a, b):
     a, b = torch.as_tensor(a).double().reshape(-1), torch.as_tensor(b).double().reshape(-1)
     return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
-
-
-def adecode(store, nsamp, slot, nfrag, dtype):
-    """fragments [slot, slot + nfrag) of every tile of an awp store -> [nsamp, 16 nfrag], channel 16 j + phi(kk)"""
-    tiles = (store.numel() - 256) // (A_TILE_FRAGS * 1024)
-    v = store[:tiles * A_TILE_FRAGS * 1024].view(tiles, A_TILE_FRAGS, 64, 16)[:, slot:slot + nfrag].contiguous().view(dtype).float()
-    v = v.view(tiles, nfrag, 2, 32, 8)
-    out = torch.zeros((tiles, 32, nfrag * 16), dtype=torch.float32, device=store.device)
-    for h in range(2):
-        for e in range(8):
-            out[:, :, torch.arange(nfrag) * 16 + phi(8 * h + e)] = v[:, :, h, :, e].permute(0, 2, 1)
-    return out.reshape(tiles * 32, nfrag * 16)[:nsamp]
 
 
 def _embed(prec="f16", seed=211):

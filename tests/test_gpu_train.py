@@ -8,29 +8,11 @@ from evdeblurnerf_amd import weights as W
 
 pytestmark = pytest.mark.gpu
 
-# fragment slots of the activation store (csrc/nerf_mlp.h, namespace astore)
-PE, DIR, H0, F, HV, FWD_END = 0, 4, 6, 134, 150, 158
-G_RGB, G_ALPHA, D_HV, D_F, D_H0, TILE_FRAGS = 158, 159, 160, 168, 184, 331
-
-
-def phi(kk):
-    return 8 * ((kk & 7) >> 2) + 4 * (kk >> 3) + (kk & 3)
-
-
+# fragment slots of the activation store and the store decoders: tests/store_decode.py
+from store_decode import (PE, DIR, H0, F, HV, FWD_END, G_RGB, G_ALPHA, D_HV, D_F, D_H0, TILE_FRAGS,  # noqa: E402,F401
+                          decode, phi, vdecode)
 from torch_restatement import (TorchNerf, TorchVoxLevel, embed, torch_appfeature as _torch_appfeature, torch_tv as _torch_tv,  # noqa: E402
                                vox_composite as _torch_vox_composite)
-
-
-def decode(store, nsamp, slot, nfrag, dtype):
-    """fragments [slot, slot + nfrag) of every tile -> [nsamp, 16 * nfrag] in the hidden-channel arrangement (channel 16 j + phi(kk))"""
-    tiles = store.numel() // (TILE_FRAGS * 1024)
-    v = store.view(tiles, TILE_FRAGS, 64, 16)[:, slot:slot + nfrag].contiguous().view(dtype).float()   # [tiles, nfrag, lane, 8]
-    v = v.view(tiles, nfrag, 2, 32, 8)                                                                  # lane = n + 32 h
-    out = torch.zeros((tiles, 32, nfrag * 16), dtype=torch.float32, device=store.device)
-    for h in range(2):
-        for e in range(8):
-            out[:, :, torch.arange(nfrag) * 16 + phi(8 * h + e)] = v[:, :, h, :, e].permute(0, 2, 1)
-    return out.reshape(tiles * 32, nfrag * 16)[:nsamp]
 
 
 def make_inputs(R, S, seed):
@@ -348,16 +330,6 @@ def test_triplane_sample_and_tv_backward_match_torch_autograd():
     ref2 = _torch_appfeature([sd2[f"app_plane.{i}"].cpu().double() for i in range(3)], [sd2[f"app_line.{i}"].cpu().double() for i in range(3)],
                              sd2["basis_mat.weight"].cpu().double(), torch.tensor(pts, dtype=torch.float64), AABB)
     assert (out2.detach().cpu().double() - ref2).abs().max().item() < 1e-4
-
-
-def vdecode(store, nsamp, tile_frags, slot, nfrag, dtype):
-    tiles = store.numel() // (tile_frags * 1024)
-    v = store.view(tiles, tile_frags, 64, 16)[:, slot:slot + nfrag].contiguous().view(dtype).float().view(tiles, nfrag, 2, 32, 8)
-    out = torch.zeros((tiles, 32, nfrag * 16), dtype=torch.float32, device=store.device)
-    for h in range(2):
-        for e in range(8):
-            out[:, :, torch.arange(nfrag) * 16 + phi(8 * h + e)] = v[:, :, h, :, e].permute(0, 2, 1)
-    return out.reshape(tiles * 32, nfrag * 16)[:nsamp]
 
 
 @pytest.mark.parametrize("prec,tol", [("f16", 4e-3), ("bf16", 3e-2)])
