@@ -146,6 +146,8 @@ SIGNATURES = {
     "evd_sample_events_track": (_I, [_vp, _L, _I, _vp, _L, _vp, C.POINTER(PoseTrack), _vp, _vp, _L, _fp, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "evd_interpolate_poses": (_I, [C.POINTER(PoseTrack), _vp, _L, _vp, _vp]),
     "evd_image_batch": (_I, [_vp, _L, _vp, _vp, _vp, _I, _I, _I, _fp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "evd_image_batch_draw": (_I, [_I, _I, _L, C.c_ulonglong, _L, _L, C.POINTER(_I), C.POINTER(_I), _I, _vp, _vp, _vp, _vp, _I, _I, _I, _fp,
+                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "evd_rbk_warp": (_I, [_vp, _vp, _vp, _L, _I, _I, _vp, _vp, _vp]),
     "evd_rigid_blur_workspace_bytes": (_S, [C.POINTER(RigidBlurDesc), _L]),
     "evd_rigid_blur_forward": (_I, [C.POINTER(RigidBlurDesc), C.POINTER(RigidBlurParams), _vp, _vp, _vp, _L, _vp, _vp, _vp, _vp]),

@@ -880,6 +880,24 @@ int evd_image_batch(const long long* ray_ids, long n, const float* images, const
                     int W, const float* K, float* rays, float* rays_x, float* rays_y, long long* images_idx, float* rgbsf, float* poses_out,
                     float* rgbsf_pts0, int* invalid, void* stream);
 
+/* The same batch with its ray ids drawn in the launch (run_nerf.py:61-68): one kernel, nothing read back.  The generator is the
+ * library's own, counter-based on (seed, epoch, batch): the same triple gives the same ids bit for bit; torch's streams are not reproduced.
+ *   mode 0 "random"  BatchSampler(RandomSampler) with drop_last: row j of batch b is the value at position b N + j of a keyed bijection
+ *                    of [0, n_img H W) -- a 6-round Feistel network over the next power of four, round function murmur3's 32-bit
+ *                    finaliser of (half ^ key(seed, epoch, round)), cycle-walked into the range.  No id twice within the epoch's
+ *                    floor(n_rays / N) batches; batch must lie inside the epoch.  chosen_images / live_counts / perm are not read.
+ *   mode 1 "images"  data/sampler_image_batch.py: `same` distinct images, N / same distinct unused pixels of each.  The caller chooses
+ *                    the images and keeps the counts (host int[same] each: image id, pixels it has left this epoch, >= N / same);
+ *                    perm is dev int32 [n_img, H W], every row a permutation of [0, H W) (any; the identity to start), whose first
+ *                    live_count entries are the unused pixels.  One wavefront per image removes N / same of them by partial
+ *                    Fisher-Yates into the rows' dead tails; a new epoch only resets the caller's counts.  Rows s N / same .. of the batch
+ *                    belong to chosen_images[s].  assemble 0 advances perm only (to replay an epoch's draws; outputs may be NULL).
+ *   outputs as evd_image_batch, plus ray_ids dev int64 [N].  rgbsf_pts0 / poses_out may be NULL. */
+int evd_image_batch_draw(int mode, int assemble, long N, unsigned long long seed, long epoch, long batch, const int* chosen_images,
+                         const int* live_counts, int same, int* perm, const float* images, const float* pts0_images, const float* poses,
+                         int n_img, int H, int W, const float* K, long long* ray_ids, float* rays, float* rays_x, float* rays_y,
+                         long long* images_idx, float* rgbsf, float* poses_out, float* rgbsf_pts0, void* stream);
+
 /* ---------------------------------------------------------------- test-set pass: image metrics, 8-bit frames
  * compute_img_metric(im1t, im2t, 'mse' | 'psnr' | 'ssim', margin, mask), utils/metrics.py:18-100 (called at run_nerf.py:685-687,704), for a
  * whole batch in one main launch plus a fixed-order finish launch: scikit-image 0.19.2's mean_squared_error, peak_signal_noise_ratio and
