@@ -123,6 +123,15 @@ class LpipsDesc(C.Structure):
     _fields_ = [("conv_w", _fp * 5), ("conv_b", _fp * 5), ("lin", _fp * 5), ("shift", C.c_float * 3), ("scale", C.c_float * 3)]
 
 
+class LpipsNetDesc(C.Structure):
+    """evd_lpips_net_desc: net = LPIPS_NET_ALEX / LPIPS_NET_VGG16, heads = 0 for the baseline without linear heads"""
+    _fields_ = [("net", C.c_int), ("heads", C.c_int), ("conv_w", _fp * 13), ("conv_b", _fp * 13), ("lin", _fp * 5), ("shift", C.c_float * 3),
+                ("scale", C.c_float * 3)]
+
+
+LPIPS_NET_ALEX, LPIPS_NET_VGG16 = 0, 1
+
+
 class RenderOut(C.Structure):
     _fields_ = [(k, _vp) for k in ("rgb", "depth", "acc", "z_vals", "weights", "rgb0", "depth0", "acc0", "z_std",
                                    "z_vals0", "weights0", "feature", "raw")] + [("feature_kind", C.c_int)]
@@ -283,9 +292,13 @@ SIGNATURES = {
     "evd_frame_map": (_I, [_vp, _vp, _I, _I, _I, _L, _vp, _I, _vp, _vp, _vp]),
     "evd_frame_colormap": (_I, [_vp, _L, _vp, _vp, _vp]),
     "evd_lpips_create": (_I, [C.POINTER(LpipsDesc), C.POINTER(_vp)]),
+    "evd_lpips_create_net": (_I, [C.POINTER(LpipsNetDesc), C.POINTER(_vp)]),
     "evd_lpips_destroy": (None, [_vp]),
+    "evd_lpips_min_side": (_I, [_I]),
     "evd_lpips_workspace_bytes": (_S, [_I, _I, _I]),
+    "evd_lpips_model_workspace_bytes": (_S, [_vp, _I, _I, _I, _I]),
     "evd_lpips": (_I, [_vp, _vp, _vp, _I, _I, _I, _vp, _vp, _S, _vp]),
+    "evd_lpips_spatial": (_I, [_vp, _vp, _vp, _I, _I, _I, _vp, _vp, _vp, _S, _vp]),
     "evd_adam_create": (_I, [C.POINTER(AdamSegment), _I, _I, C.POINTER(_vp)]),
     "evd_adam_destroy": (None, [_vp]),
     "evd_adam_workspace_bytes": (_S, [_vp]),

@@ -5,11 +5,12 @@ call (evd_img_metrics) without a host copy; scikit-image is not needed.  The ari
 One deliberate deviation: with a mask, every image is multiplied by its own mask.  The reference multiplies the whole batch by every earlier
 image's mask inside its loop (:77-78); the two agree for a batch of one and for identical binary masks.
 
-LPIPS (:92-95, networks/lpips/lpips.py) is built as the reference's ``LPIPS()`` call uses it -- AlexNet backbone, version 0.1, linear heads,
-spatial average, eval mode -- on the device in float32 (evd_lpips).  Its WEIGHTS ARE THE CALLER'S: the AlexNet backbone's pretrained
-weights are not part of the reference checkout (torchvision downloads them), so ``LPIPS`` is built from two state dicts or files the
-user already has, nothing is ever downloaded, and ``compute_img_metric(..., 'lpips')`` works once a model is installed with
-``set_lpips``.  vgg / squeeze, the spatial map, the baseline without heads and any backward are not built."""
+LPIPS (:92-95, networks/lpips/lpips.py) runs on the device in float32 (evd_lpips, evd_lpips_spatial), eval mode: the AlexNet backbone (the
+reference's ``LPIPS()`` call) or VGG-16 (``net='vgg'``, the variant most papers report), version 0.1 or 0.0, with the linear heads or as
+the baseline without them (``lpips=False``), as the spatial average or as the spatial map (``spatial=True``).  Its WEIGHTS ARE THE
+CALLER'S: a backbone's pretrained weights are not part of the reference checkout (torchvision downloads them), so ``LPIPS`` is built from
+state dicts or files the user already has, nothing is ever downloaded, and ``compute_img_metric(..., 'lpips')`` works once a model is
+installed with ``set_lpips``.  net='squeeze', dropout in training mode, pnet_tune and any backward are not built."""
 from __future__ import annotations
 
 import ctypes
@@ -19,6 +20,7 @@ import torch
 
 from . import _lib as L
 from .losses import img2mse  # noqa: F401  (utils/metrics.py:7)
+from .weights import LPIPS_VGG16
 
 TILE_H, TILE_W = 16, 32          # EVD_IMG_METRICS_TILE_H / _W of include/evdnerf.h: the kernel's tile of output pixels
 PHOTOMETRIC = ("mse", "ssim", "psnr", "lpips")
@@ -79,13 +81,32 @@ def img_metrics(pred, target, margin=0, mask=None, format=None):
 
 
 class LPIPS:
-    """The reference's ``LPIPS()`` (net='alex', version='0.1', lpips=True, spatial=False, eval mode: dropout is the identity) on the device.
-    alexnet: torchvision's AlexNet state dict (``features.{0,3,6,8,10}.{weight,bias}``; other keys such as ``classifier.*`` are ignored);
-    lin: the linear heads (``lin{0..4}.model.1.weight``, the keys of the reference's weights/v0.1/alex.pth).  The library packs them once."""
+    """The reference's ``LPIPS(net, version, lpips, spatial)`` in eval mode (dropout is the identity) on the device.
+    backbone: torchvision's state dict of the backbone -- AlexNet ``features.{0,3,6,8,10}.{weight,bias}`` for net='alex', VGG-16
+    ``features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.{weight,bias}`` for net='vgg' / 'vgg16'; other keys such as ``classifier.*`` are ignored;
+    lin: the linear heads (``lin{0..4}.model.1.weight``, the keys of the reference's weights/v0.1/{alex,vgg}.pth), required with lpips=True and
+    ignored with lpips=False (the baseline: the plain channel sum);
+    version: '0.1', or '0.0' without the scaling layer;
+    spatial: the call returns the per-pixel map [B, 1, H, W] instead of the per-image value.  The library packs the weights once."""
     CONV = ((0, 3, 64, 11), (3, 64, 192, 5), (6, 192, 384, 3), (8, 384, 256, 3), (10, 256, 256, 3))       # features index, Cin, Cout, kernel
+    CONV_VGG = tuple((idx, ci, co, 3) for idx, ci, co in LPIPS_VGG16)
+    CHNS = {"alex": (64, 192, 384, 256, 256), "vgg": (64, 128, 256, 512, 512)}                          # lpips.py:159-164
     SHIFT, SCALE = (-.030, -.088, -.188), (.458, .448, .450)                                             # ScalingLayer, lpips.py:245-252
 
-    def __init__(self, alexnet, lin):
+    def __init__(self, backbone, lin=None, net="alex", version="0.1", lpips=True, spatial=False):
+        if net == "squeeze":
+            raise NotImplementedError("LPIPS: net='squeeze' is not built: its fire modules have 16-, 32- and 48-channel layers, channel "
+                                      "concatenation and ceil-mode pools, none of which fit the convolution kernel's 64-column tile")
+        if net not in ("alex", "vgg", "vgg16"):
+            raise L.EvdError(f"LPIPS: net '{net}'; 'alex', 'vgg' or 'vgg16'")
+        if version not in ("0.1", "0.0"):
+            raise L.EvdError(f"LPIPS: version '{version}'; '0.1' or '0.0' (the original release without the scaling layer)")
+        if lpips and lin is None:
+            raise L.EvdError("LPIPS: lpips=True needs the linear heads (lin); lpips=False is the baseline without them")
+        net = "alex" if net == "alex" else "vgg"
+        name = "the AlexNet" if net == "alex" else "the VGG-16"
+        self.net, self.version, self.lpips, self.spatial = net, version, bool(lpips), bool(spatial)
+
         def take(sd, key, shape, what):
             if key not in sd:
                 raise L.EvdError(f"LPIPS: {what} state dict has no '{key}'")
@@ -95,32 +116,36 @@ class LPIPS:
             return v.reshape(shape).contiguous()
 
         keep = []
-        desc = L.LpipsDesc()
-        for l, (idx, ci, co, k) in enumerate(self.CONV):
-            w = take(alexnet, f"features.{idx}.weight", (co, ci, k, k), "the AlexNet")
-            b = take(alexnet, f"features.{idx}.bias", (co,), "the AlexNet")
-            h = take(lin, f"lin{l}.model.1.weight", (1, co, 1, 1), "the linear-head")
-            keep += [w, b, h]
+        desc = L.LpipsNetDesc()
+        desc.net, desc.heads = (L.LPIPS_NET_ALEX if net == "alex" else L.LPIPS_NET_VGG16), int(self.lpips)
+        for l, (idx, ci, co, k) in enumerate(self.CONV if net == "alex" else self.CONV_VGG):
+            w = take(backbone, f"features.{idx}.weight", (co, ci, k, k), name)
+            b = take(backbone, f"features.{idx}.bias", (co,), name)
+            keep += [w, b]
             desc.conv_w[l] = ctypes.cast(w.data_ptr(), L._fp)
             desc.conv_b[l] = ctypes.cast(b.data_ptr(), L._fp)
+        for l, co in enumerate(self.CHNS[net] if self.lpips else ()):
+            h = take(lin, f"lin{l}.model.1.weight", (1, co, 1, 1), "the linear-head")
+            keep.append(h)
             desc.lin[l] = ctypes.cast(h.data_ptr(), L._fp)
-        for c in range(3):
-            desc.shift[c], desc.scale[c] = self.SHIFT[c], self.SCALE[c]
+        for c in range(3):                                           # version 0.0: no scaling layer; (x - 0) / 1 is exact
+            desc.shift[c], desc.scale[c] = (self.SHIFT[c], self.SCALE[c]) if version == "0.1" else (0.0, 1.0)
         self._lib = L.lib()
         self._h = ctypes.c_void_p()
-        L.check(self._lib.evd_lpips_create(ctypes.byref(desc), ctypes.byref(self._h)), "evd_lpips_create")
+        L.check(self._lib.evd_lpips_create_net(ctypes.byref(desc), ctypes.byref(self._h)), "evd_lpips_create_net")
 
     @classmethod
-    def from_files(cls, alexnet_path, lin_path):
-        """Both files are read with torch.load(..., map_location='cpu', weights_only=True); nothing is downloaded."""
-        return cls(torch.load(alexnet_path, map_location="cpu", weights_only=True), torch.load(lin_path, map_location="cpu", weights_only=True))
+    def from_files(cls, backbone_path, lin_path=None, **kwargs):
+        """The files are read with torch.load(..., map_location='cpu', weights_only=True); nothing is downloaded."""
+        lin = None if lin_path is None else torch.load(lin_path, map_location="cpu", weights_only=True)
+        return cls(torch.load(backbone_path, map_location="cpu", weights_only=True), lin, **kwargs)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
             self._lib.evd_lpips_destroy(h)
 
-    def _run(self, im1, im2, format):
+    def _inputs(self, im1, im2, format):
         p = _bhwc(im1, format)
         t = _bhwc(im2, format).to(p.device)
         if not p.is_cuda:
@@ -128,21 +153,38 @@ class LPIPS:
         if p.shape != t.shape:
             raise L.EvdError(f"LPIPS: shapes {tuple(p.shape)} and {tuple(t.shape)} differ")
         B, H, W = (int(v) for v in p.shape[:3])
-        need = int(self._lib.evd_lpips_workspace_bytes(B, H, W))
-        ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=p.device)
+        need = int(self._lib.evd_lpips_model_workspace_bytes(self._h, B, H, W, int(self.spatial)))
+        return p, t, B, H, W, need, torch.empty((max(need, 1),), dtype=torch.uint8, device=p.device)
+
+    def _run(self, im1, im2, format):
+        if self.spatial:
+            raise L.EvdError("LPIPS: a spatial model returns a map per image, not a value: build one with spatial=False for the mean")
+        p, t, B, H, W, need, ws = self._inputs(im1, im2, format)
         out = torch.empty((6 * B + 1,), dtype=torch.float64, device=p.device)
         L.check(self._lib.evd_lpips(self._h, L.ptr(p), L.ptr(t), B, H, W, L.ptr(out), L.ptr(ws), need, L.stream_ptr()), "evd_lpips")
         return out, B
 
+    def _run_spatial(self, im1, im2, format, layers):
+        p, t, B, H, W, need, ws = self._inputs(im1, im2, format)
+        out = torch.empty((B, 1, H, W), dtype=torch.float32, device=p.device)
+        per = torch.empty((B, 5, H, W), dtype=torch.float32, device=p.device) if layers else None
+        L.check(self._lib.evd_lpips_spatial(self._h, L.ptr(p), L.ptr(t), B, H, W, L.ptr(out), L.ptr(per), L.ptr(ws), need, L.stream_ptr()),
+                "evd_lpips_spatial")
+        return out, per
+
     def __call__(self, im1, im2, format=None, retPerLayer=False):
         """im1, im2 in (0, 1), laid out as compute_img_metric takes them -> the [B] float64 device tensor of per-image values, and with
         retPerLayer the [B, 5] per-layer terms (each layer's own term: the reference's list carries the total in slot 0 because its sum adds
-        in place).  No host copy, no synchronisation."""
+        in place).  A spatial model returns the float32 map [B, 1, H, W] (the reference's shape), and with retPerLayer the five upsampled
+        per-layer maps [B, 5, H, W].  No host copy, no synchronisation."""
+        if self.spatial:
+            out, per = self._run_spatial(im1, im2, format, retPerLayer)
+            return (out, per) if retPerLayer else out
         out, B = self._run(im1, im2, format)
         return (out[:B], out[B + 1:].view(B, 5)) if retPerLayer else out[:B]
 
     def mean(self, im1, im2, format=None):
-        """the batch mean, summed image by image (0-dim float64 device tensor)"""
+        """the batch mean, summed image by image (0-dim float64 device tensor); not for a spatial model"""
         out, B = self._run(im1, im2, format)
         return out[B]
 
@@ -155,6 +197,8 @@ def set_lpips(model):
     filled by hand because the weights are the caller's); None removes it."""
     if model is not None and not isinstance(model, LPIPS):
         raise L.EvdError(f"set_lpips: an evdeblurnerf_amd.metrics.LPIPS or None, got {type(model).__name__}")
+    if model is not None and getattr(model, "spatial", False):
+        raise L.EvdError("set_lpips: a spatial LPIPS model returns maps; compute_img_metric needs one built with spatial=False")
     _LPIPS[0] = model
 
 
@@ -168,7 +212,7 @@ def compute_img_metric(im1t, im2t, metric="mse", margin=0, mask=None, format=Non
     if metric == "lpips":
         if _LPIPS[0] is None:
             raise NotImplementedError("compute_img_metric: 'lpips' needs the LPIPS backbone's pretrained weights, which are not part of the "
-                                      "reference checkout and cannot be fetched: build metrics.LPIPS from the AlexNet and linear-head weights "
+                                      "reference checkout and cannot be fetched: build metrics.LPIPS from the backbone and linear-head weights "
                                       "you have and install it with metrics.set_lpips; 'mse', 'psnr' and 'ssim' run on the device")
         return float(_LPIPS[0].mean(im1t, im2t, format=format))
     return float(img_metrics(im1t, im2t, margin=margin, mask=mask, format=format)[metric + "_mean"])

@@ -145,6 +145,23 @@ def make_lpips_alexnet_state_dict(seed: int, gain: float = 1.4, bias_bound: floa
     return sd
 
 
+LPIPS_VGG16 = ((0, 3, 64), (2, 64, 64), (5, 64, 128), (7, 128, 128), (10, 128, 256), (12, 256, 256), (14, 256, 256), (17, 256, 512),
+               (19, 512, 512), (21, 512, 512), (24, 512, 512), (26, 512, 512), (28, 512, 512))                # features index, Cin, Cout (all 3 x 3)
+
+
+def make_lpips_vgg16_state_dict(seed: int, bias_std: float = 0.05):
+    """``features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.{weight,bias}`` of torchvision's VGG-16, the LPIPS backbone of net='vgg'
+    (networks/lpips/pretrained_networks.py:98-136), as a SYNTHETIC stand-in for the pretrained weights nobody may ship: weights normal with
+    std sqrt(2 / fan_in) (the variance a ReLU stack preserves), biases normal with std bias_std.  About half of the units are alive at each of
+    the five taps and the per-layer LPIPS terms on random frames stay above 1e-5 (tools/gen_golden.py G43 asserts both)."""
+    rs = np.random.RandomState(seed)
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for idx, ci, co in LPIPS_VGG16:
+        sd[f"features.{idx}.weight"] = (rs.standard_normal((co, ci, 3, 3)) * math.sqrt(2.0 / (ci * 9))).astype(np.float32)
+        sd[f"features.{idx}.bias"] = (rs.standard_normal((co,)) * bias_std).astype(np.float32)
+    return sd
+
+
 def synthetic_frame_pairs(seed: int, B: int, H: int, W: int, lo: float = 0.0, hi: float = 1.0, noise: float = 0.15):
     """Predicted and target frames [B, H, W, 3] for the image-metric goldens: uniform [lo, hi) frames and a noisy copy, clipped to [0, 1]
     unless the range leaves it (the case that exercises the metrics' clamp)."""

@@ -970,44 +970,80 @@ int evd_frame_map(const float* x, const float* y, int source, int scope, int n_f
 int evd_frame_colormap(const unsigned char* g, long n, const unsigned char* lut, unsigned char* out, void* stream);
 
 /* LPIPS, the fourth metric of the test-set pass: compute_img_metric(im1t, im2t, 'lpips'), utils/metrics.py:92-95 (called at run_nerf.py:688),
- * i.e. networks/lpips/lpips.py LPIPS(net='alex', version='0.1', lpips=True, spatial=False) in eval mode, float32 throughout.
- * The WEIGHTS ARE THE CALLER'S: torchvision's pretrained AlexNet `features` (not part of the reference checkout; torchvision downloads
- * them) and the linear heads of the reference's weights/v0.1/alex.pth.  The library ships none and fetches nothing.
+ * i.e. networks/lpips/lpips.py LPIPS(net, version, lpips, spatial) in eval mode, float32 throughout.  Built: net = 'alex' and 'vgg' ('vgg16'),
+ * version 0.1 and 0.0, with the linear heads (lpips=True) and the baseline without them (lpips=False), the spatial average (evd_lpips) and
+ * the spatial map (evd_lpips_spatial).
+ * The WEIGHTS ARE THE CALLER'S: torchvision's pretrained AlexNet / VGG-16 `features` (not part of the reference checkout; torchvision
+ * downloads them) and the linear heads of the reference's weights/v0.1/{alex,vgg}.pth.  The library ships none and fetches nothing.
+ * evd_lpips_desc / evd_lpips_create: the AlexNet backbone with heads (the reference's default LPIPS() call):
  *   conv_w[l], conv_b[l]  host float32, torchvision's features.{0,3,6,8,10}.{weight,bias}: [Cout, Cin, kh, kw] / [Cout] with
  *                         (Cout, Cin, k) = (64, 3, 11), (192, 64, 5), (384, 192, 3), (256, 384, 3), (256, 256, 3)
  *   lin[l]                host float32 [Cout of layer l]: lin{l}.model.1.weight (a 1 x 1 convolution without bias)
  *   shift, scale          the ScalingLayer's constants (lpips.py:245-252)
- * Host pointers are read during evd_lpips_create only (as for every _create entry); the handle owns packed device copies ([K, Cout] with
- * K = (ky, kx, c), the layout of the implicit-GEMM kernel) and is destroyed with evd_lpips_destroy.
+ * evd_lpips_net_desc / evd_lpips_create_net: any built backbone, with or without heads:
+ *   net                   EVD_LPIPS_NET_ALEX (5 convolutions as above) or EVD_LPIPS_NET_VGG16: the 13 convolutions of features[0:30],
+ *                         features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.{weight,bias}, all 3 x 3 / pad 1, Cout = 64, 64, 128, 128, 256 x 3,
+ *                         512 x 3, 512 x 3, a 2 x 2 / stride 2 floor pool in front of convolutions 2, 4, 7 and 10, taps after convolutions
+ *                         1, 3, 6, 9 and 12 (relu1_2, 2_2, 3_3, 4_3, 5_3; 64, 128, 256, 512, 512 channels).  Entries past the backbone's
+ *                         convolutions are not read.
+ *   heads                 non-zero: lin[t] is the head of tap t (lpips=True); 0: the baseline, the plain channel sum of the squared
+ *                         difference (lpips=False, lpips.py:219-223), lin is not read
+ *   shift, scale          as above; version 0.0 (no scaling layer) is shift 0, scale 1, which are exact
+ * Host pointers are read during a _create call only (as for every _create entry); the handle owns packed device copies ([K, Cout] with
+ * K = (ky, kx, c), the layout of the implicit-GEMM kernel), remembers its backbone and is destroyed with evd_lpips_destroy.
  * evd_lpips:
- *   pred, target  dev float32 [B, H, W, 3] in (0, 1); conv1 maps them on load, clamp(2 x - 1, -1, 1) (utils/metrics.py:48-49), then
- *                 (x - shift) / scale, and pads with zeros by predicate.  H, W >= EVD_LPIPS_MIN_SIDE: the smallest side at which the
- *                 second 3 x 3 / stride 2 pool still has one output.
+ *   pred, target  dev float32 [B, H, W, 3] in (0, 1); the first convolution maps them on load, clamp(2 x - 1, -1, 1)
+ *                 (utils/metrics.py:48-49), then (x - shift) / scale, and pads with zeros by predicate.  H, W >= evd_lpips_min_side(net):
+ *                 the smallest side at which the backbone's last pool still has one output (EVD_LPIPS_MIN_SIDE for AlexNet's second
+ *                 3 x 3 / stride 2 pool, EVD_LPIPS_VGG_MIN_SIDE for VGG's four 2 x 2 pools); 0 for an unknown backbone.
  *   out           dev float64 [6 B + 1]: the per-image values [B], their mean over the batch (summed image by image), then the per-layer
  *                 terms [B, 5]; value[b] = sum_l term[b, l], term[b, l] = mean over the layer's pixels of
  *                 sum_c lin_c (f0_c / (n0 + 1e-10) - f1_c / (n1 + 1e-10))^2 with n = sqrt(sum_c f_c^2); an all-zero feature vector gives 0.
- *   workspace     evd_lpips_workspace_bytes(B, H, W) bytes (0 for sizes the entry rejects): two activation buffers and the partials.
+ *   workspace     evd_lpips_model_workspace_bytes(m, B, H, W, 0) bytes (0 for a null handle and for sizes the entry rejects): two
+ *                 activation buffers and the partials.  evd_lpips_workspace_bytes(B, H, W) is the same for an AlexNet handle.
+ * evd_lpips_spatial (spatial=True): per tap the per-pixel distance d (the same float64 arithmetic) goes to a float64 map; every output pixel
+ * reads the five maps bilinearly as nn.Upsample(size=(H, W), mode='bilinear', align_corners=False) does (lpips.py:134-136: source
+ * coordinate (dst + 0.5) in / out - 0.5, clamped below at 0, the upper neighbour clamped to the last index), adds them in layer order in
+ * float64 and rounds once.
+ *   map           dev float32 [B, H, W]
+ *   layer_maps    dev float32 [B, 5, H, W], the five upsampled maps, or null
+ *   workspace     evd_lpips_model_workspace_bytes(m, B, H, W, 1) bytes: two activation buffers and the five maps
  * Predicted and target frames of the whole batch go through every layer in ONE launch (M = 2 B h w rows of the implicit GEMM on
  * v_mfma_f32_32x32x2_f32: exact float32 products).  The features are float32; the normalisation, the distance and every sum after it
  * are float64, workgroup partials summed in a fixed order without floating-point atomics: two runs give the same bits, an image's
- * value does not depend on the rest of the batch, and identical frames give exactly 0.  No allocation, no host copy, no
- * synchronisation; asynchronous on `stream`.
- * Not built: net = 'vgg' / 'squeeze', spatial maps, the baseline without heads (lpips=False), version 0.0, dropout in training mode,
- * any backward. */
+ * value (and map) does not depend on the rest of the batch, and identical frames give exactly 0 (an all-zero map).  No allocation, no
+ * host copy, no synchronisation; asynchronous on `stream`.
+ * Not built: net = 'squeeze' (fire modules of 16, 32 and 48 channels, channel concatenation and ceil-mode pools fit neither the 64-column
+ * tile nor the one-tap K tile), dropout in training mode, pnet_tune, any backward. */
 #define EVD_LPIPS_MIN_SIDE 31
+#define EVD_LPIPS_VGG_MIN_SIDE 16
 #define EVD_LPIPS_LAYERS 5
-typedef struct evd_lpips_model evd_lpips_model;     /* opaque: packed backbone weights, heads, scaling constants (a type cannot share the
-                                                      * entry's name evd_lpips in C) */
+#define EVD_LPIPS_MAX_CONVS 13
+#define EVD_LPIPS_NET_ALEX 0
+#define EVD_LPIPS_NET_VGG16 1
+typedef struct evd_lpips_model evd_lpips_model;     /* opaque: backbone id, packed backbone weights, heads, scaling constants (a type
+                                                      * cannot share the entry's name evd_lpips in C) */
 typedef struct {
     const float *conv_w[EVD_LPIPS_LAYERS], *conv_b[EVD_LPIPS_LAYERS];
     const float* lin[EVD_LPIPS_LAYERS];
     float shift[3], scale[3];
 } evd_lpips_desc;
+typedef struct {
+    int net, heads;
+    const float *conv_w[EVD_LPIPS_MAX_CONVS], *conv_b[EVD_LPIPS_MAX_CONVS];
+    const float* lin[EVD_LPIPS_LAYERS];
+    float shift[3], scale[3];
+} evd_lpips_net_desc;
 int evd_lpips_create(const evd_lpips_desc* desc, evd_lpips_model** out);
+int evd_lpips_create_net(const evd_lpips_net_desc* desc, evd_lpips_model** out);
 void evd_lpips_destroy(evd_lpips_model* m);
+int evd_lpips_min_side(int net);
 size_t evd_lpips_workspace_bytes(int B, int H, int W);
+size_t evd_lpips_model_workspace_bytes(const evd_lpips_model* m, int B, int H, int W, int spatial);
 int evd_lpips(const evd_lpips_model* m, const float* pred, const float* target, int B, int H, int W, double* out, void* workspace, size_t workspace_bytes,
               void* stream);
+int evd_lpips_spatial(const evd_lpips_model* m, const float* pred, const float* target, int B, int H, int W, float* map, float* layer_maps,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- optimizer step (run_nerf.py:593-613)
  * clip_grad_norm_ + torch.optim.Adam(amsgrad=False, maximize=False).step() over any number of float32 arrays in ONE launch, with the

@@ -2132,12 +2132,145 @@ def G40_view_embed_mlp():
     print(f"  wrote {os.path.relpath(path, ROOT)}  ({os.path.getsize(path) / 1024:.1f} KiB)")
 
 
+# --------------------------------------------------------------------------- G43: LPIPS, VGG-16 backbone, spatial map, baseline, version 0.0
+LPIPS_VGG_BACKBONE_SEED = 4300
+LPIPS_VGG_CASES = {           # B, H, W, seed of the frames, value range of the predicted frames, keep the per-layer maps
+    "min": (1, 16, 16, 4301, 0.0, 1.0, True),         # the last tap is 1 x 1
+    "wide": (1, 16, 33, 4302, 0.0, 1.0, True),
+    "tall": (1, 33, 16, 4303, 0.0, 1.0, True),
+    "odd": (3, 37, 50, 4304, 0.0, 1.0, False),        # floor pools drop a row or column at several levels; M no multiple of the 128-row tile
+    "clamp": (2, 20, 27, 4305, -0.3, 1.3, True),      # values outside (0, 1): the clamp matters
+    "two": (2, 40, 56, 4306, 0.0, 1.0, False),
+    "square": (1, 24, 24, 4307, 0.0, 1.0, True),
+    "rect": (2, 18, 29, 4308, 0.0, 1.0, True),
+}
+LPIPS_VGG_V00_CASE = "tall"
+
+
+def _lpips_vgg_reference_models():
+    """the reference's real LPIPS class with net='vgg' and its own linear heads (weights/v0.1/vgg.pth); torchvision is absent, so a stub
+    `torchvision.models.vgg16` hands it the `features` stack of the public VGG-16 architecture (configuration D: 3 x 3 convolutions of
+    64, 64, M, 128, 128, M, 256 x 3, M, 512 x 3, M, 512 x 3, M channels, M = MaxPool2d(2, 2)) built from torch.nn and loaded with the
+    seed-derived stand-in weights.  Returns the module and a factory of models."""
+    import types
+    from torch import nn
+
+    def vgg16(pretrained=True, **kw):
+        layers, ci = [], 3
+        for v in (64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512, "M"):
+            if v == "M":
+                layers.append(nn.MaxPool2d(kernel_size=2, stride=2))
+            else:
+                layers += [nn.Conv2d(ci, v, kernel_size=3, padding=1), nn.ReLU(inplace=True)]
+                ci = v
+        feats = nn.Sequential(*layers)
+        sd = W.make_lpips_vgg16_state_dict(LPIPS_VGG_BACKBONE_SEED)
+        feats.load_state_dict({k[len("features."):]: t(v) for k, v in sd.items()})
+        return types.SimpleNamespace(features=feats)
+
+    tv = types.ModuleType("torchvision")
+    tv.models = types.ModuleType("torchvision.models")
+    sys.modules.setdefault("torchvision", tv)
+    sys.modules.setdefault("torchvision.models", tv.models)
+    sys.modules["torchvision"].models = sys.modules["torchvision.models"]
+    sys.modules["torchvision.models"].vgg16 = vgg16
+    from networks.lpips import lpips as lp
+    return lp, lambda **kw: lp.LPIPS(net="vgg", verbose=False, **kw)
+
+
+def _lpips_maps_run(lp, model, pred, target, dtype):
+    """map [B, H, W] and the five upsampled per-layer maps [B, 5, H, W] of a spatial model, one call per image as in _lpips_run.  The
+    per-layer maps are copied as upsample returns them: the reference's in-place sum leaves the total in slot 0 of its list."""
+    seen = []
+    orig = lp.upsample
+
+    def recording(*a, **k):
+        r = orig(*a, **k)
+        seen.append(r.detach().clone())
+        return r
+
+    lp.upsample = recording
+    try:
+        im1 = (t(pred) * 2 - 1).clamp(-1, 1).permute(0, 3, 1, 2).to(dtype)
+        im2 = (t(target) * 2 - 1).clamp(-1, 1).permute(0, 3, 1, 2).to(dtype)
+        maps, layers = [], []
+        for i in range(im1.shape[0]):
+            del seen[:]
+            v = model(im1[i:i + 1], im2[i:i + 1])
+            assert len(seen) == 5 and v.dtype == dtype and tuple(v.shape) == (1, 1) + tuple(im1.shape[2:])
+            maps.append(n(v)[0, 0].astype(np.float64))
+            layers.append(np.stack([n(x)[0, 0].astype(np.float64) for x in seen]))
+    finally:
+        lp.upsample = orig
+    return np.stack(maps), np.stack(layers)
+
+
+def G43_lpips_vgg():
+    """LPIPS(net='vgg') of the reference on the CPU, float32 and the same module in .double().  Per case, for the heads (lpips=True, no
+    prefix) and the baseline (lpips=False, prefix `base.`): value [B], per-layer terms [B, 5] and ref_f32_err = |f32 - f64| / f64 of both;
+    with spatial=True the map [B, H, W], the five upsampled per-layer maps [B, 5, H, W] (f64.layer_maps, dropped from the two larger cases
+    for the fixture's size) and ref_f32_err.map [B] = max |f32 - f64| over the map / max of the float64 map.  One case also with
+    version='0.0' (prefix `v00.`; no scaling layer, the heads of v0.1).  Stored beside them: the reference's linear heads (1472 floats of weights/v0.1/vgg.pth), the scaling
+    layer's shift and scale, and each case's (B, H, W, seed, lo, hi); the backbone weights and the frames are derived from seeds on both
+    sides (evdeblurnerf_amd.weights) and not stored."""
+    import copy
+    lp, make = _lpips_vgg_reference_models()
+    head = make()
+    out = {f"lin{l}": n(getattr(head, f"lin{l}").model[1].weight).reshape(-1).copy() for l in range(5)}
+    assert sum(v.size for v in out.values()) == 1472 and all((v >= 0).all() for v in out.values())
+    out["shift"] = n(head.scaling_layer.shift).reshape(3).copy()
+    out["scale"] = n(head.scaling_layer.scale).reshape(3).copy()
+    out["backbone_seed"] = np.int64(LPIPS_VGG_BACKBONE_SEED)
+    out["cases"] = np.array(list(LPIPS_VGG_CASES))
+    out["v00_case"] = np.array(LPIPS_VGG_V00_CASE)
+    # the reference checkout has no weights/v0.0: version 0.0 (no scaling layer) runs with the heads of v0.1
+    v01 = os.path.join(os.path.dirname(lp.__file__), "weights", "v0.1", "vgg.pth")
+    variants = {"": dict(), "base.": dict(lpips=False), "v00.": dict(version="0.0", model_path=v01)}
+    models = {}
+    for pre, kw in variants.items():
+        for spatial in (False, True):
+            m32 = make(spatial=spatial, **kw)
+            models[pre, spatial] = (m32, copy.deepcopy(m32).double())
+    for tag, (B, H, Wd, seed, lo, hi, keep_layers) in LPIPS_VGG_CASES.items():
+        pred, target = W.synthetic_frame_pairs(seed, B, H, Wd, lo, hi)
+        out.update({tag + ".args": np.array([B, H, Wd, seed], np.int64), tag + ".range": np.array([lo, hi], np.float64)})
+        # the stand-in initialisation keeps every tap alive: about half of the units, as a trained backbone's ReLUs do
+        m64 = models["", False][1]
+        x = m64.scaling_layer((t(pred) * 2 - 1).clamp(-1, 1).permute(0, 3, 1, 2).double())
+        alive = [float((f > 0).double().mean()) for f in m64.net.forward(x)]
+        assert all(0.3 <= a <= 0.7 for a in alive), (tag, alive)
+        for vpre, kw in variants.items():
+            if vpre == "v00." and tag != LPIPS_VGG_V00_CASE:
+                continue
+            pre = tag + "." + vpre
+            v32, t32 = _lpips_run(lp, models[vpre, False][0], pred, target, torch.float32)
+            v64, t64 = _lpips_run(lp, models[vpre, False][1], pred, target, torch.float64)
+            assert t64.min() > 1e-6, (pre, t64)
+            m32, l32 = _lpips_maps_run(lp, models[vpre, True][0], pred, target, torch.float32)
+            m64_, l64 = _lpips_maps_run(lp, models[vpre, True][1], pred, target, torch.float64)
+            assert np.allclose(m64_.mean(axis=(1, 2)), v64, rtol=0.5) and m64_.shape == (B, H, Wd) and l64.shape == (B, 5, H, Wd)
+            out.update({pre + "f32.value": v32, pre + "f32.terms": t32, pre + "f64.value": v64, pre + "f64.terms": t64,
+                        pre + "ref_f32_err.value": np.abs(v32 - v64) / v64, pre + "ref_f32_err.terms": np.abs(t32 - t64) / t64,
+                        pre + "f64.map": m64_,
+                        pre + "ref_f32_err.map": np.abs(m32 - m64_).max(axis=(1, 2)) / m64_.max(axis=(1, 2)),
+                        pre + "ref_f32_err.layer_maps": np.abs(l32 - l64).max(axis=(2, 3)) / l64.max(axis=(2, 3))})
+            if keep_layers:
+                out[pre + "f64.layer_maps"] = l64
+            print(f"   {pre[:-1]}: value {v64}, terms {t64.min():.1e} .. {t64.max():.1e}, alive {min(alive):.2f} .. {max(alive):.2f}; float32 error "
+                  f"of the reference: value {out[pre + 'ref_f32_err.value'].max():.1e}, terms {out[pre + 'ref_f32_err.terms'].max():.1e}, "
+                  f"map {out[pre + 'ref_f32_err.map'].max():.1e}, layer maps {out[pre + 'ref_f32_err.layer_maps'].max():.1e}")
+    path = os.path.join(OUT, "G43_lpips_vgg.npz")
+    np.savez_compressed(path, **out)                                        # (keeps the float64 records)
+    print(f"  wrote {os.path.relpath(path, ROOT)}  ({os.path.getsize(path) / 1024:.1f} KiB)")
+
+
 ALL = [G1_embedder, G2_nerf_mlp, G3_nerf_raw2outputs, G4_voxel_raw2outputs, G5_sample_pdf, G6_rays,
        G7_render_nerf, G8_appfeature, G9_render_c2f, G10_rbk_weighted_sum, G11_crf, G12_egm_loss, G13_edi,
        G14_loss_assembly, G15_awp_feature_integration, G16_rbk_warp, G17_compute_successor, G18_nerf_grads, G19_c2f_grads, G20_loss_grads,
        G21_awp_sample_embed, G22_mam, G23_render_nerf_no_viewdirs, G24_render_other_multires, G25_pbe_composite_feature,
        G26_sample_events, G27_awp_per_ray, G28_image_batch, G29_pose_track, G30_c2f_grads_16k, G31_event_hops, G32_train_forward,
-       G33_train_trajectory, G34_event_tables, G35_llff_poses, G36_edi_prior, G37_rigid_blur, G38_lpips, G39_sparse_blur, G40_view_embed_mlp]
+       G33_train_trajectory, G34_event_tables, G35_llff_poses, G36_edi_prior, G37_rigid_blur, G38_lpips, G39_sparse_blur, G40_view_embed_mlp,
+       G43_lpips_vgg]
 
 if __name__ == "__main__":
     want = set(sys.argv[1:])
