@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void k_mam_local_fwd(const float* __restrict__
     for (int p = wave; p < P; p += 4) {
         float m = -INFINITY;
         for (int s = lane; s < S; s += 64) m = fmaxf(m, A[p * S + s]);
-        for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        m = wave_max(m);
         float t = 0.f;
         for (int s = lane; s < S; s += 64) t += __expf(A[p * S + s] - m);
         t = wave_sum_dpp(t);
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void k_mam_local_fwd_r(const float* __restrict
     for (int p = wave; p < P; p += 4) {      // the softmax along the samples: one wavefront per sub-exposure
         float m = -INFINITY;
         for (int s = lane; s < S; s += 64) m = fmaxf(m, A[p * S + s]);
-        for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        m = wave_max(m);
         float t = 0.f;
         for (int s = lane; s < S; s += 64) t += __expf(A[p * S + s] - m);
         t = wave_sum_dpp(t);
@@ -257,7 +257,7 @@ __device__ __forceinline__ void mam_bwd_fold_du(const MamBwdLds& m, float4 du, f
 __device__ __forceinline__ void mam_bwd_fold_absmax(const MamBwdLds& m, float amax, unsigned* absmax) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     if (!absmax) return;
-    for (int o = 32; o; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+    amax = wave_max(amax);
     __syncthreads();
     if (lane == 0) m.red[wave] = amax;
     __syncthreads();

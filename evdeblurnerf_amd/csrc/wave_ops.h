@@ -21,6 +21,11 @@ __device__ __forceinline__ T wave_sum(T v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
     return v;
 }
+// maximum over the 64 lanes
+__device__ __forceinline__ float wave_max(float v) {
+    for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
 // bitwise OR over the 64 lanes
 __device__ __forceinline__ unsigned wave_or(unsigned v) {
 #pragma unroll

@@ -676,7 +676,9 @@ int evd_mam_local_backward(const float* h_local, const float* u, const float* al
  * batch mean / UNBIASED variance into them with bn_momentum and adds 1 to *bn_num_batches (int64, may be NULL); training == 0 uses the
  * running estimates.  saved_y, saved_xg dev [R,P,32] and saved_stats dev [64] (mean, 1/sqrt(var + eps)) are kept for the backward;
  * saved_rays dev [R, evd_awp_tail_saved_floats(d)] (optional in both calls) takes every ray's forward state -- 55 KB per ray at P = 10,
- * S = 128 -- so that the backward does not run the forward a second time (measured: a third of its time). */
+ * S = 128 -- so that the backward does not run the forward a second time (measured: a third of its time).
+ * workspace: evd_awp_tail_workspace_bytes(d, R, backward) bytes, any alignment; fewer -> EVD_E_WORKSPACE, nothing is written.  The size
+ * queries return -1 (evd_awp_tail_param_count, _saved_floats) / 0 (_workspace_bytes) for a descriptor outside the ranges above. */
 typedef struct {
     int P, S, VF, dir_freqs, n_mot, training;
     float bn_eps, bn_momentum;

@@ -6,7 +6,8 @@
              larger workspace: bit for bit for the forward and once-per-dataset entries; for the pipelined backwards and the two scatter
              entries (float atomics, wavefront order) within the bound the entry's own test holds it to against its reference
   undersized need - 1 bytes -> EVD_E_WORKSPACE, the error text names the workspace, outputs and workspace untouched
-The shapes are the smallest at which the layouts differ: 3 rays, 8 (+ 4) samples, 24 backward samples, 0 / 5 events on a 3 x 2 sensor."""
+The shapes are the smallest at which the layouts differ: 3 rays, 8 (+ 4) samples, 24 backward samples, 0 / 5 events on a 3 x 2 sensor, the
+AWP tail (evd_awp_tail_forward / _backward) on 3 rays x 2 sub-exposures x 5 samples."""
 import ctypes as C
 import functools
 from types import SimpleNamespace
@@ -354,6 +355,79 @@ def test_awp_embed_backward():
     # tests/test_gpu_awp.py test_sample_embed_backward_matches_torch_autograd: relative L2 < 4e-3 per tensor in f16
     guard_band(lib.evd_awp_embed_backward_workspace_bytes(), run,
                compare=lambda o, r: rel_l2_all(o, r, 4e-3, "test_gpu_awp.py::test_sample_embed_backward_matches_torch_autograd"))
+
+
+# ---- the AWP tail --------------------------------------------------------------------------------------------------------------------
+TAIL_P, TAIL_S, TAIL_VF, TAIL_F, TAIL_NMOT = 2, 5, 3, 2, 2
+
+
+def tail_case():
+    """3 rays x 2 sub-exposures x 5 samples, view_feature 3 + 15 direction columns, two motion layers, training mode; the parameter
+    tensors in the order include/evdnerf.h documents"""
+    lib, P, S, VF = L.lib(), TAIL_P, TAIL_S, TAIL_VF
+    desc = L.AwpTailDesc(P=P, S=S, VF=VF, dir_freqs=TAIL_F, n_mot=TAIL_NMOT, training=1, bn_eps=1e-5, bn_momentum=0.1)
+    in0 = 64 + VF + 3 + 6 * TAIL_F
+    sizes = [32 * in0, 32, 32 * 32, 32, 32 * 64, 32, 16 * 32, 16 * 32, 16 * 32, 16 * 16, 16 * 16, 32 * 32, 32, 32, P * 32, P]
+    assert lib.evd_awp_tail_num_params(TAIL_NMOT) == len(sizes) and lib.evd_awp_tail_param_count(C.byref(desc)) == sum(sizes)
+    rs = np.random.RandomState(21)
+    params = [T_((0.2 * rs.standard_normal(n)).astype(np.float32)) for n in sizes]
+    arr = (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
+    ins = dict(h=(R, P, 64), vf=(R, VF), rd=(R * P, 3), hi=(R, P, 64), hs=(R, S, 64), d_out=(R, P))
+    ins = {k: T_(rs.standard_normal(sh).astype(np.float32)) for k, sh in ins.items()}
+    return lib, desc, params, arr, ins, sum(sizes)
+
+
+def tail_forward_run(lib, desc, arr, ins):
+    nsaved = lib.evd_awp_tail_saved_floats(C.byref(desc))
+
+    def run(ws, nbytes):
+        o = dict(out=filled((R, TAIL_P)), y=filled((R, TAIL_P, 32)), xg=filled((R, TAIL_P, 32)), stats=filled((64,)), rays=filled((R, nsaved)),
+                 run_mean=filled((32,)), run_var=filled((32,)), num_batches=filled((1,), torch.int64))
+        rc = lib.evd_awp_tail_forward(C.byref(desc), arr, L.ptr(ins["h"]), L.ptr(ins["vf"]), L.ptr(ins["rd"]), L.ptr(ins["hi"]), L.ptr(ins["hs"]), R,
+                                      L.ptr(o["run_mean"]), L.ptr(o["run_var"]), L.ptr(o["num_batches"]), L.ptr(o["out"]), L.ptr(o["y"]), L.ptr(o["xg"]),
+                                      L.ptr(o["stats"]), L.ptr(o["rays"]), C.c_void_p(ws), nbytes, L.stream_ptr())
+        torch.cuda.synchronize()
+        return rc, o
+    return run
+
+
+def test_awp_tail_sizes_equal_their_slot_lists():
+    lib, desc, params, arr, ins, total = tail_case()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    for R_ in (0, 1, 3, 7, 1000):
+        grid, nblk = min(max(R_, 1), cus), (R_ + 7) // 8           # a workgroup per ray up to one per CU; eight rays per finish workgroup
+        assert lib.evd_awp_tail_workspace_bytes(C.byref(desc), R_, 0) == al(grid * 64 * 8) + 256, R_          # bn_part (double) + slack
+        want = al(R_ * TAIL_P * 32 * 4) + al(nblk * (64 + TAIL_P * 32 + TAIL_P) * 4) + al(grid * ((total + 3) & ~3) * 4) + 256      # dz | partB | partA + slack
+        assert lib.evd_awp_tail_workspace_bytes(C.byref(desc), R_, 1) == want, R_
+    assert lib.evd_awp_tail_workspace_bytes(None, 3, 0) == 0 and lib.evd_awp_tail_workspace_bytes(C.byref(desc), -1, 1) == 0
+
+
+def test_awp_tail_forward():
+    lib, desc, params, arr, ins, total = tail_case()
+    def compare(out, ref):
+        # no atomics: bit for bit.  saved_rays is a copy of the ray's LDS block, padding included (row pads, 16-byte rounding of the arrays):
+        # those floats are whatever the LDS held, so the block is checked by test_awp_tail_backward, which computes from it
+        for name in ref:
+            assert name == "rays" or same_bits(out[name], ref[name]), f"{name} differs from the aligned call"
+    guard_band(lib.evd_awp_tail_workspace_bytes(C.byref(desc), R, 0), tail_forward_run(lib, desc, arr, ins), compare=compare)
+
+
+def test_awp_tail_backward():
+    lib, desc, params, arr, ins, total = tail_case()
+    fwd_need = int(lib.evd_awp_tail_workspace_bytes(C.byref(desc), R, 0))
+    fws = torch.empty((fwd_need,), dtype=torch.uint8, device=DEV)
+    rc, f = tail_forward_run(lib, desc, arr, ins)(fws.data_ptr(), fwd_need)
+    assert rc == 0, lib.evd_last_error()
+
+    def run(ws, nbytes):
+        o = dict(d_h=filled((R, TAIL_P, 64)), d_vf=filled((R, TAIL_VF)), d_rd=filled((R * TAIL_P, 3)), d_hi=filled((R, TAIL_P, 64)), d_hs=filled((R, TAIL_S, 64)),
+                 d_params=filled((total,)))
+        rc = lib.evd_awp_tail_backward(C.byref(desc), arr, L.ptr(ins["h"]), L.ptr(ins["vf"]), L.ptr(ins["rd"]), L.ptr(ins["hi"]), L.ptr(ins["hs"]), R, L.ptr(f["y"]),
+                                       L.ptr(f["xg"]), L.ptr(f["stats"]), L.ptr(f["rays"]), L.ptr(ins["d_out"]), L.ptr(o["d_h"]), L.ptr(o["d_vf"]), L.ptr(o["d_rd"]),
+                                       L.ptr(o["d_hi"]), L.ptr(o["d_hs"]), L.ptr(o["d_params"]), C.c_void_p(ws), nbytes, L.stream_ptr())
+        torch.cuda.synchronize()
+        return rc, o
+    guard_band(lib.evd_awp_tail_workspace_bytes(C.byref(desc), R, 1), run)          # no atomics: bit for bit
 
 
 # ---- the two scatter entries -------------------------------------------------------------------------------------------------------

@@ -24,7 +24,8 @@ def _time(fn, iters=20):
     return e0.elapsed_time(e1) / iters * 1e3
 
 
-def run(R=1024, P=10, S=128, VF=32):
+def run(R=1024, P=10, S=128, VF=32, iters=20, legs=("kernels", "torch")):
+    """iters: timed calls per window (an A/B of two libraries wants windows of half a second: a few thousand, and the kernels leg alone)"""
     from awp_standin import RefLikeAWP
     from evdeblurnerf_amd.awp import FusedAWP
     torch.manual_seed(1)
@@ -38,7 +39,7 @@ def run(R=1024, P=10, S=128, VF=32):
     vf, rd, proj = t(rs.standard_normal((R, VF))), t(rs.standard_normal((R * P, 3))), t(rs.standard_normal((R, P)))
     out = {}
     res = {}
-    for tag, kern in (("kernels", True), ("torch", False)):
+    for tag, kern in ((leg, leg == "kernels") for leg in legs):
         m = copy.deepcopy(base)
         fused = FusedAWP(m, tail_kernels=kern)
         ins = [x.clone().requires_grad_(True) for x in (h, rd, hi, hs, vf)]
@@ -56,8 +57,8 @@ def run(R=1024, P=10, S=128, VF=32):
             torch.autograd.grad((o * proj).sum(), ins + ps)
 
         with torch.no_grad():
-            t_f = _time(fwd)
-        t_fb = _time(both)
+            t_f = _time(fwd, iters)
+        t_fb = _time(both, iters)
         o = fwd()
         res[tag] = (o.detach(), torch.autograd.grad((o * proj).sum(), ins + ps))
         out[tag] = {"forward_us": t_f, "forward_backward_us": t_fb}
