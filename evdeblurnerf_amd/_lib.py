@@ -227,6 +227,10 @@ SIGNATURES = {
     "evd_voxel_mlp_train": (_I, [_vp, _I, _vp, _vp, _I, _vp, _I, _L, _I, _vp, _vp, _vp, _S, _vp]),
     "evd_voxel_geo_feat_dim": (_I, [_vp]),
     "evd_voxel_mlp_backward": (_I, [_vp, _I, _vp, _vp, _vp, _vp, _S, _L, _I, _vp, _S, C.POINTER(VoxelGrads), _vp, _I, _vp, _vp, _I, _vp, _vp, _vp, _S, _vp]),
+    "evd_voxel_color_rows_store_bytes": (_S, [_vp, _L]),
+    "evd_voxel_color_rows_backward_workspace_bytes": (_S, [_vp, _L]),
+    "evd_voxel_color_rows_train": (_I, [_vp, _vp, _vp, _I, _L, _vp, _vp, _S, _vp]),
+    "evd_voxel_color_rows_backward": (_I, [_vp, _vp, _vp, _vp, _I, _L, _vp, _S, C.POINTER(VoxelGrads), _vp, _vp, _vp, _S, _vp]),
     "evd_voxel_grid_sizes": (_I, [_vp, C.POINTER(C.c_long)]),
     "evd_voxel_get_grids": (_I, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp]),
     "evd_voxel_load_grids": (_I, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp]),
@@ -244,6 +248,7 @@ SIGNATURES = {
                              _vp, _vp, _vp, _vp, _vp, _vp, _I, _vp, _vp]),
     "evd_raw2outputs_bwd": (_I, [_vp, _vp, _vp, _I, _L, _I, _I, _I, _I, _I, _I, _I, _I, _F, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "evd_raw2outputs_bwd_rays": (_I, [_vp, _vp, _vp, _I, _L, _I, _I, _I, _I, _I, _I, _I, _I, _F, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _I, _vp]),
+    "evd_raw2outputs_feat_bwd": (_I, [_vp, _I, _I, _vp, _I, _I, _vp, _vp, _I, _vp, _I, _F, _L, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _I, _vp]),
     "evd_sample_pdf_merge": (_I, [_vp, _vp, _L, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp]),
     "evd_nerf_render_workspace_bytes": (_S, [C.POINTER(RenderCfg), _L]),
     "evd_nerf_render_rays": (_I, [_vp, _vp, C.POINTER(RenderCfg), _vp, _L, _vp, _vp, _vp, _vp,

@@ -1,6 +1,7 @@
 // C-ABI entry points of a PDRF level's inference pass and of the mode='c2f' renderer (reference networks/pdrf/voxnerf.py,
 // networks/renderer.py:182-217): the tri-plane gather, the level networks on the handle's streams (voxel_net.h), feature merging.
 #include "voxel_net.h"
+#include "voxel_color_rows.h"
 
 using namespace evd;
 
@@ -44,50 +45,6 @@ size_t evd_voxel_forward_workspace_bytes(const evd_voxel* v, long R, int S) { Vo
 static __global__ __launch_bounds__(256) void k_act_inplace(float* __restrict__ x, long n, int code) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) x[i] = act(code, x[i]);
-}
-
-// colour network of a composite_feature level, per RAY (voxnerf.py:231-239): h = cat([feature_map, PE(dirs)]) -> Linear + ReLU
-// (num_layers_color - 1 times) -> Linear -> sigmoid.  A wavefront per ray, a lane per hidden unit (HD <= 256: up to 4 units per lane);
-// the weights are the reference's float32 [out, in] rows, read through the caches (7 k MACs per ray: nothing to optimise).
-static __global__ __launch_bounds__(256) void k_color_rows(const float* __restrict__ cnet, const float* __restrict__ fm, const float* __restrict__ viewdirs,
-                                                           int vd_stride, long R, int G, int HD, int Lv, float* __restrict__ color) {
-    __shared__ float in[4][160], h0[4][256], h1[4][256];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long r = (long)blockIdx.x * 4 + w;
-    const int icv = 3 * (1 + 2 * Lv), nin = G + icv;
-    const float *w0 = cnet, *b0 = w0 + (long)HD * nin, *w1 = b0 + HD, *b1 = w1 + (long)HD * HD, *w2 = b1 + HD, *b2 = w2 + 3L * HD;
-    if (r < R) {
-        for (int i = lane; i < nin; i += 64) {
-            float x;
-            if (i < G) x = fm[r * G + i];
-            else {
-                const int c = i - G;              // embedding.py:88-98: [x, sin(x f0), cos(x f0), sin(x f1), ...], 3 values each
-                const float d = viewdirs[r * vd_stride + c % 3];
-                x = c < 3 ? d : ((c - 3) / 3 % 2 == 0 ? sinf(d * (float)(1 << ((c - 3) / 6))) : cosf(d * (float)(1 << ((c - 3) / 6))));
-            }
-            in[w][i] = x;
-        }
-    }
-    __syncthreads();
-    if (r < R)
-        for (int j = lane; j < HD; j += 64) {
-            float s = b0[j];
-            for (int i = 0; i < nin; ++i) s = fmaf(w0[(long)j * nin + i], in[w][i], s);
-            h0[w][j] = fmaxf(s, 0.f);
-        }
-    __syncthreads();
-    if (r < R)
-        for (int j = lane; j < HD; j += 64) {
-            float s = b1[j];
-            for (int i = 0; i < HD; ++i) s = fmaf(w1[(long)j * HD + i], h0[w][i], s);
-            h1[w][j] = fmaxf(s, 0.f);
-        }
-    __syncthreads();
-    if (r < R && lane < 3) {
-        float s = b2[lane];
-        for (int i = 0; i < HD; ++i) s = fmaf(w2[(long)lane * HD + i], h1[w][i], s);
-        color[r * 3 + lane] = 1.f / (1.f + expf(-s));            // torch.sigmoid(h) voxnerf.py:239
-    }
 }
 
 // The network of a level's inference pass: picks the kernel and, with it, the stream of the handle it reads (p.wstream / p.nchunks).
@@ -158,8 +115,8 @@ static int voxel_pass(const evd_voxel* v, int precision, const float* pts, const
         // composite written to `color` here is overwritten by the per-ray colour network below
         if ((rc = evd_raw2outputs(raw, z, rays_d, rd_stride, R, S, 4, 0, 1, 3, v->rgb_act, v->sigma_act, 0, thr, noise,
                                   color, nullptr, acc, weights, depth, crows, v->geo, cmap, stream))) return rc;
-        hipLaunchKernelGGL(k_color_rows, dim3((unsigned)cdiv(R, 4L)), dim3(256), 0, st, (const float*)v->cnet.p, cmap, viewdirs, vd_stride, R, v->geo,
-                           v->hidden_dim, v->multires_views, color);
+        hipLaunchKernelGGL(k_color_rows<false>, dim3((unsigned)cdiv(R, 4L)), dim3(256), 0, st, (const float*)v->cnet.p, cmap, viewdirs, vd_stride, R, v->geo,
+                           v->hidden_dim, v->multires_views, color, (float*)nullptr, (float*)nullptr);
         EVD_LAUNCH_CHECK();
         return EVD_OK;
     }

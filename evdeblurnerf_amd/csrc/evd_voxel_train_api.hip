@@ -40,7 +40,11 @@ size_t evd_voxel_backward_workspace_bytes_net(const evd_voxel* v, int precision)
 int evd_voxel_mlp_train(const evd_voxel* v, int precision, const float* pts, const float* viewdirs, int vd_stride, const float* fts, int ft_stride,
                         long R, int S, float* raw, float* feature, void* store, size_t store_bytes, void* stream) {
     EVD_REQUIRE(v && pts && viewdirs && fts && raw && store, "evd_voxel_mlp_train: null argument");
-    EVD_REQUIRE(!v->composite_feature, "evd_voxel_mlp_train: composite_feature levels (kernel_type PBE) are built for inference only");
+    // a composite_feature level (kernel_type PBE) runs these kernels unchanged: raw and the geo rows before their activation leave as
+    // `feature`, the composite and the colour network follow per ray (evd_raw2outputs_feat_bwd, evd_voxel_color_rows_train)
+    EVD_REQUIRE(!v->composite_feature || (std_coarse(v) && (precision == EVD_PREC_F16X3 || precision == EVD_PREC_F16 || precision == EVD_PREC_BF16)),
+                "evd_voxel_mlp_train: a composite_feature level trains as the standard coarse level (64/15/32) in precision f16x3 / f16 / bf16 "
+                "(f16c / f16m keep no float32 feature rows)");
     if (const int rc = refuse_generic_mode(v, precision, "evd_voxel_mlp_train")) return rc;
     EVD_REQUIRE(vox_train_built(v, precision), "evd_voxel_mlp_train: the training path is built for precision f16 / bf16 / f16x3 / f16c / f16m");
     EVD_REQUIRE(R >= 0 && S >= 1 && ft_stride >= v->ft_dim && ft_stride % 4 == 0, "evd_voxel_mlp_train: bad shape");

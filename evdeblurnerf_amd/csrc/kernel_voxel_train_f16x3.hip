@@ -6,7 +6,7 @@ namespace evd {
 
 int launch_voxel_train_fwd_f16x3(int HD, const VoxMlpParams& p, hipStream_t st) {
     if (HD == 256) return p.feature ? launch_voxel_train_fwd<EVD_PREC_F16X3, 256, 128, 64, true>(p, st) : launch_voxel_train_fwd<EVD_PREC_F16X3, 256, 128, 64>(p, st);
-    if (p.feature) return fail(EVD_E_INVALID, "evd_voxel_mlp_train: the feature output is built for the fine level (geo 128)");
+    if (p.feature) return launch_voxel_train_fwd64_rows<EVD_PREC_F16X3>(p, st);      // (the 15 geo rows, read back out of the store)
     return launch_voxel_train_fwd<EVD_PREC_F16X3, 64, 15, 32>(p, st);
 }
 

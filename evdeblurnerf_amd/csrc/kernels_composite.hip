@@ -8,6 +8,7 @@
 //   k_composite_rows       C == 4, S <= 256                            SPL consecutive ones   act_fast    expf     act() made it VALU-bound (wave_ops.h)
 //   k_composite_il         C == 4, S <= 256, the renderer's layouts    l, 64 + l, ...         act_fast    __expf   hardware exp2: |error of alpha| <= 1e-7
 //   k_composite_rows_bwd   backward of the C == 4 forms                SPL consecutive ones   act         expf     recomputes k_composite's values
+//   k_composite_feat_bwd   backward of the G-channel feature composite SPL consecutive ones   act         expf     (+ the [S, G] row block in contiguous pieces)
 //   k_weighted_channels    sum_s w x: colour maps with n_rgb != 3, feature maps
 //
 // The arithmetic of a sample inside the row is written once (composite_dist, composite_density, composite_alpha).  What a form does to
@@ -418,6 +419,150 @@ __global__ __launch_bounds__(256) void k_composite_rows_bwd(const float* __restr
     }
 }
 
+// Backward of the FEATURE composite (composite_feature levels, voxnerf.py:223-229): fmap_c = sum_i w_i act(rows_ic) over G geo channels,
+// the density from channel sigma_ch of raw [R, S, C].  k_composite_rows_bwd's scan (a wavefront per ray, SPL consecutive samples per lane,
+// forward quantities recomputed) between two passes over the ray's [S, G] row block, which is what moves the bytes (S (8 G + 24) per ray):
+//   A  the block is read in CONTIGUOUS pieces of whole samples (<= 64 samples, <= 1024 floats: element e of a piece by lane e mod 64; a
+//      lane-per-sample walk would stride by the 4 G bytes of a row) into LDS, then lane l sums g_fmap . act(rows) of the piece's sample l
+//      in channel order -> dot_i
+//   B  G_i = dot_i + g_depth z_i + g_acc + g_w_i, d density and d rays_d exactly as k_composite_rows_bwd; w_i is left in LDS
+//   C  d rows_ic = g_fmap_c w_i act'(rows_ic), written in the same contiguous order; the rows come from LDS when the ray is one piece
+//      (S = 64, G = 15: 960 floats), else they are read again (the second read of a ray's few KiB is served by the caches)
+// Without g_fmap, A is skipped and C writes zeros.  The four wavefronts of a workgroup share nothing but the barriers, so every
+// wavefront runs the full trip counts (a ragged last workgroup works on row R - 1 again and stores nothing).
+template <int SPL>
+__global__ __launch_bounds__(256) void k_composite_feat_bwd(const float* __restrict__ raw, int C, int sigma_ch, const float* __restrict__ rows, int G,
+                                                            int rows_act, const float* __restrict__ z, const float* __restrict__ rays_d,
+                                                            int rd_stride, long R, int S, int sigma_act, float rmnear,
+                                                            const float* __restrict__ noise, const float* __restrict__ g_fmap,
+                                                            const float* __restrict__ g_depth, const float* __restrict__ g_acc,
+                                                            const float* __restrict__ g_w, float* __restrict__ d_raw, float* __restrict__ d_rows,
+                                                            float* __restrict__ d_rays_d, int d_rd_stride) {
+    constexpr int TILE = 1024;
+    __shared__ float s_tile[4][TILE], s_dot[4][256], s_w[4][256], s_g[4][128];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long r_own = blockIdx.x * 4L + wv;
+    const bool live = r_own < R;
+    const long r = live ? r_own : R - 1;
+    const int TS = min(64, TILE / G);                        // samples per piece
+    const bool single = S <= TS;
+    const float* rw = rows + r * (long)S * G;
+    float* tile = s_tile[wv];
+    // ---- A
+    if (g_fmap) {
+        for (int c = lane; c < G; c += 64) s_g[wv][c] = g_fmap[r * G + c];
+        for (int s0 = 0; s0 < S; s0 += TS) {
+            const int ns = min(TS, S - s0), ne = ns * G;
+            if (s0) __syncthreads();                         // the piece before this one has been summed
+            for (int e = lane; e < ne; e += 64) tile[e] = rw[(long)s0 * G + e];
+            __syncthreads();
+            if (lane < ns) {
+                float dsum = 0.f;
+                for (int c = 0; c < G; ++c) dsum = fmaf(s_g[wv][c], act(rows_act, tile[lane * G + c]), dsum);
+                s_dot[wv][s0 + lane] = dsum;
+            }
+        }
+        __syncthreads();
+    }
+    // ---- B
+    const int i0 = lane * SPL;
+    const float* zz = z + r * (long)S;
+    float sr[SPL], zi[SPL + 1], gw[SPL], dot[SPL];
+#pragma unroll
+    for (int j = 0; j < SPL; ++j) {
+        const int i = min(i0 + j, S - 1);
+        sr[j] = raw[(r * (long)S + i) * C + sigma_ch];
+        zi[j] = zz[i];
+        gw[j] = g_w ? g_w[r * (long)S + i] : 0.f;
+        dot[j] = g_fmap ? s_dot[wv][i] : 0.f;
+    }
+    const float* d = rays_d + r * rd_stride;
+    const float norm = ray_norm(d);
+    const float gd = g_depth ? g_depth[r] : 0.f;
+    const float ga = g_acc ? g_acc[r] : 0.f;
+    zi[SPL] = dpp_f32<0x130>(0.f, zi[0]);
+    float alpha[SPL], om[SPL], dist[SPL], spre[SPL], mask[SPL], densm[SPL];
+#pragma unroll
+    for (int j = 0; j < SPL; ++j) {
+        const int i = i0 + j;
+        dist[j] = 0.f; spre[j] = 0.f; mask[j] = 1.f; densm[j] = 0.f;
+        if (i < S - 1) {
+            dist[j] = composite_dist(zi[j], zi[j + 1], norm);
+            spre[j] = sr[j] + (noise ? noise[r * (long)(S - 1) + i] : 0.f);
+            if (rmnear > 0.f) mask[j] = rmnear_mask(zi[j + 1], rmnear);
+            densm[j] = composite_density<ACT_IEEE>(sigma_act, spre[j], zi[j + 1], rmnear);
+            alpha[j] = composite_alpha<EXP_IEEE>(densm[j], dist[j]);
+        } else {
+            alpha[j] = i == S - 1 ? 1.f : 0.f;
+        }
+        om[j] = i < S ? __fadd_rn(-alpha[j], 1.f) : 1.f;
+    }
+    float local = om[0];
+#pragma unroll
+    for (int j = 1; j < SPL; ++j) local *= om[j];
+    const float incl = wave_scan_mul_dpp(local);
+    float T = dpp_f32<0x138>(1.f, incl);
+    float w[SPL], Gv[SPL], Tn[SPL], lsum = 0.f;
+#pragma unroll
+    for (int j = 0; j < SPL; ++j) {
+        w[j] = (i0 + j < S) ? alpha[j] * T : 0.f;
+        T *= om[j];
+        Tn[j] = T;                                          // T_{i+1}
+        Gv[j] = dot[j] + gd * zi[j] + ga + gw[j];
+        lsum += Gv[j] * w[j];
+        if (i0 + j < S) s_w[wv][i0 + j] = w[j];
+    }
+    const float pre_incl = wave_scan_add_dpp(lsum);
+    const float total = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pre_incl), 63));
+    float run = pre_incl - lsum;
+    float dn = 0.f;
+#pragma unroll
+    for (int j = 0; j < SPL; ++j) {
+        const int i = i0 + j;
+        run += Gv[j] * w[j];
+        if (i < S) {
+            float ds = 0.f;
+            if (i < S - 1) {
+                const float suffix = total - run;            // sum_{j > i} G_j w_j
+                const float q = dist[j] * (Gv[j] * Tn[j] - suffix);
+                ds = q * mask[j] * act_grad(sigma_act, spre[j]);
+                dn += q * densm[j];
+            }
+            if (live) {
+                float* o = d_raw + (r * (long)S + i) * C;
+                if (C == 4) {
+                    *reinterpret_cast<float4*>(o) = make_float4(sigma_ch == 0 ? ds : 0.f, sigma_ch == 1 ? ds : 0.f, sigma_ch == 2 ? ds : 0.f, sigma_ch == 3 ? ds : 0.f);
+                } else {
+                    for (int c = 0; c < C; ++c) o[c] = c == sigma_ch ? ds : 0.f;
+                }
+            }
+        }
+    }
+    if (d_rays_d) {
+        dn = wave_sum_dpp(dn);
+        if (lane == 0 && live) {
+            const float k = dn / (norm * norm);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d_rays_d[r * d_rd_stride + c] = k * d[c];
+        }
+    }
+    __syncthreads();                                         // s_w is complete
+    // ---- C
+    float* dr = d_rows + r * (long)S * G;
+    const int ne = S * G, qi = 64 / G, qc = 64 % G;
+    int i = lane / G, c = lane % G;
+    for (int e = lane; e < ne; e += 64) {
+        float v = 0.f;
+        if (g_fmap) {
+            const float x = single ? tile[e] : rw[e];
+            v = s_g[wv][c] * s_w[wv][i] * act_grad(rows_act, x);
+        }
+        if (live) dr[e] = v;
+        i += qi; c += qc;
+        if (c >= G) { c -= G; ++i; }
+    }
+}
+
 // out[r, f] = sum_s w[r, s] * x[r, s, ch0 + f] (optionally through an activation): used for n_rgb != 3 colour
 // maps (PBE 15-channel features, voxnerf.py:226) and for feature compositing (nerf.py:119).  One block per ray.
 __global__ void k_weighted_channels(const float* __restrict__ x, const float* __restrict__ w, long R, int S, int Cx, int ch0,
@@ -513,6 +658,24 @@ int evd_raw2outputs_bwd_rays(const float* raw, const float* z, const float* rays
                                                                           white_bkgd, rmnear_thresh, noise, g_map, g_depth, g_acc, g_weights, d_raw, d_rays_d, d_rays_d_stride)
     EVD_BY_CHUNKS(S, EVD_BWD);
 #undef EVD_BWD
+    EVD_LAUNCH_CHECK();
+    return EVD_OK;
+}
+
+int evd_raw2outputs_feat_bwd(const float* raw, int C, int sigma_ch, const float* rows, int G, int rows_act, const float* z,
+                             const float* rays_d, int rays_d_stride, const float* noise, int sigma_act, float rmnear_thresh, long R, int S,
+                             const float* g_fmap, const float* g_depth, const float* g_acc, const float* g_weights,
+                             float* d_raw, float* d_rows, float* d_rays_d, int d_rays_d_stride, void* stream) {
+    EVD_REQUIRE(raw && rows && z && rays_d && d_raw && d_rows && R >= 0, "evd_raw2outputs_feat_bwd: bad arguments");
+    EVD_REQUIRE(G >= 1 && G <= 128 && S >= 1 && S <= 256, "evd_raw2outputs_feat_bwd: built for 1..128 feature channels and 1..256 samples (got G=%d S=%d)", G, S);
+    EVD_REQUIRE(C >= 1 && sigma_ch >= 0 && sigma_ch < C && rays_d_stride >= 3, "evd_raw2outputs_feat_bwd: channel layout out of range");
+    EVD_REQUIRE(!d_rays_d || d_rays_d_stride >= 3, "evd_raw2outputs_feat_bwd: d_rays_d needs a row stride >= 3");
+    if (R == 0) return EVD_OK;
+    hipStream_t st = as_stream(stream);
+#define EVD_FBWD(SPL) k_composite_feat_bwd<SPL><<<(unsigned)cdiv(R, 4), 256, 0, st>>>(raw, C, sigma_ch, rows, G, rows_act, z, rays_d, rays_d_stride, R, S, sigma_act, \
+                                                                                     rmnear_thresh, noise, g_fmap, g_depth, g_acc, g_weights, d_raw, d_rows, d_rays_d, d_rays_d_stride)
+    EVD_BY_CHUNKS(S, EVD_FBWD);
+#undef EVD_FBWD
     EVD_LAUNCH_CHECK();
     return EVD_OK;
 }

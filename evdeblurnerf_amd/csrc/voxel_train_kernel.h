@@ -67,11 +67,49 @@ template <int PREC> int BwdChain::frags_to_rows(int slot, int nfrag, float* rows
     return EVD_OK;
 }
 
-// float32 gradient rows (the per-sample geo features' gradient, from the AWP consumer) added into gradient fragments: fragment j,
-// position kk <-> channel 16 j + phi(kk); rows are scaled by the loss scale first
+// activation fragments -> float32 rows [n, nch] (no scale): the geo rows of the 64-wide level, whose training forward writes no rows
+// itself (voxel_mlp_kernel.h: rows leave the pipelined kernel 32 channels at a time) -- in the half-precision modes they are the rounded
+// values the level's colour layer consumed
+template <int PREC>
+__global__ __launch_bounds__(256) void k_act_frags_to_rows(const char* __restrict__ store, long tile_bytes, int slot, int nfrag, long nsamp,
+                                                           float* __restrict__ rows, int nch) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const long tile = idx / (64 * nfrag);
+    const int j = (int)((idx / 64) % nfrag), lane = idx & 63, n = lane & 31, h = lane >> 5;
+    const long smp = tile * 32 + n;
+    if (smp >= nsamp) return;
+    float fv[8];
+    frag_values<PREC>(store + tile * tile_bytes + lane * 16, slot + j, fv);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int ch = 16 * j + phi(8 * h + e);
+        if (ch < nch) rows[smp * (long)nch + ch] = fv[e];
+    }
+}
+// the geo rows of a training forward that kept its activations in p.act, into p.feature
+template <int PREC, int HD, int G, int FT> static int voxel_geo_rows_from_store(const VoxMlpParams& p, hipStream_t st) {
+    typedef VStore<HD, G, FT> VS;
+    constexpr int NF = (G + 15) / 16;
+    const long tiles = cdiv(p.nsamp, 256L) * 8;
+    hipLaunchKernelGGL((k_act_frags_to_rows<PREC>), dim3((unsigned)cdiv(tiles * 64 * NF, 256L)), dim3(256), 0, st, (const char*)p.act, VS::tile_bytes(PREC), VS::GEO, NF,
+                       p.nsamp, p.feature, G);
+    EVD_LAUNCH_CHECK();
+    return EVD_OK;
+}
+// the 64-wide level's training forward with the geo rows wanted (a composite_feature level composites them per ray)
+template <int PREC> static int launch_voxel_train_fwd64_rows(const VoxMlpParams& p, hipStream_t st) {
+    VoxMlpParams q = p;
+    q.feature = nullptr;
+    const int rc = launch_voxel_train_fwd<PREC, 64, 15, 32>(q, st);
+    return rc ? rc : voxel_geo_rows_from_store<PREC, 64, 15, 32>(p, st);
+}
+
+// float32 gradient rows (the per-sample geo features' gradient, from the AWP consumer or the feature composite of a composite_feature
+// level) added into gradient fragments: fragment j, position kk <-> channel 16 j + phi(kk), channels < nch (the 64-wide level's 15 geo
+// channels leave one position of their fragment as it is); rows are scaled by the loss scale first
 template <int PREC>
 __global__ __launch_bounds__(256) void k_rows_add_to_frags(char* __restrict__ store, long tile_bytes, int slot, int nfrag, long nsamp,
-                                                           const unsigned* __restrict__ maxbits, const float* __restrict__ rows, int stride) {
+                                                           const unsigned* __restrict__ maxbits, const float* __restrict__ rows, int stride, int nch) {
     typedef POps<PREC> O;
     pipe_fp16_saturate<PREC>();
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -84,7 +122,10 @@ __global__ __launch_bounds__(256) void k_rows_add_to_frags(char* __restrict__ st
     float v[8];
     frag_values<PREC>(a, slot + j, v);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] += rows[smp * (long)stride + 16 * j + phi(8 * h + e)] * s;
+    for (int e = 0; e < 8; ++e) {
+        const int ch = 16 * j + phi(8 * h + e);
+        if (ch < nch) v[e] += rows[smp * (long)stride + ch] * s;
+    }
     typename O::B b;
 #pragma unroll
     for (int e = 0; e < 4; ++e) O::template set_pair<false>(b, e, v[2 * e], v[2 * e + 1]);
@@ -251,9 +292,9 @@ template <int PREC, int HD, int G, int FT> static int voxel_backward_layers(cons
     }
     if (!c0_fused && (rc = launch_dgrad<PREC, KS, GT + 1, KS, false, 0>(dgrad(VBWD_C0, VS::D_C0, -1, -1, VS::D_GEO), b.tiles, st))) return rc;   // d geo | d PE(dirs)
     if (b.d_feature) {          // + the gradient of the geo features as an output of the level (voxnerf.py:221, consumed by AWP)
-        if (G % 16) return fail(EVD_E_INVALID, "evd_voxel_mlp_backward: d_feature is built for the fine level (geo 128)");
-        hipLaunchKernelGGL((k_rows_add_to_frags<PREC>), dim3((unsigned)cdiv(b.tiles * 64 * (G / 16), 256L)), dim3(256), 0, st, b.store, VS::tile_bytes(PREC), VS::D_GEO,
-                           G / 16, b.nsamp, b.maxbits, b.d_feature, G);
+        constexpr int NF = (G + 15) / 16;
+        hipLaunchKernelGGL((k_rows_add_to_frags<PREC>), dim3((unsigned)cdiv(b.tiles * 64 * NF, 256L)), dim3(256), 0, st, b.store, VS::tile_bytes(PREC), VS::D_GEO,
+                           NF, b.nsamp, b.maxbits, b.d_feature, G, G);
         EVD_LAUNCH_CHECK();
     }
     if (b.awp_store) {          // + the gradient that reached the geo features through the fused AWP embedding (awp_embed_kernel.h)

@@ -220,9 +220,9 @@ class NeRFAll:
         else:
             from .voxnerf import VoxelNeRFRayFeatures, VoxelNeRFSampleFeatures
             # kernel_type PBE: the coarse level composites its geo features and runs its colour network per ray (renderer.py:30-34,
-            # voxnerf.py:223-239) -- built for inference (render / coarse_render).  The blur model that consumes them is built
-            # (blurmodel.SparseBlurKernel, kernel_type PBE, takes feats and returns their gradient); the training forward still needs the
-            # differentiable composite-feature coarse render in front of it (_check_kernel_type)
+            # voxnerf.py:223-239), in inference (render / coarse_render) and under autograd (VoxelNeRFBase.forward_train,
+            # coarse_render_train).  composite_feature is fixed here, at construction, as in the reference: a model that is relabelled
+            # kernel_type PBE afterwards has no such level and its training call keeps raising (_check_kernel_type)
             ic = 3 * (1 + 2 * args.multires)
             rm = _args_get(args, "render_rmnearplane", 0)
             self.mlp_coarse = VoxelNeRFRayFeatures(
@@ -462,8 +462,11 @@ class NeRFAll:
         rays_d = rb[:, 3:6].contiguous()
         pts0 = points(rb, z0)
         ft0 = coarse.sample_train(pts0, pc["grids"], self.train_precision)
-        raw0 = coarse.mlp_train(pc["net"], pts0, vd, ft0, self.train_precision)
-        rgb0, _, acc0, w0, depth0 = coarse.raw2outputs(raw0, z0, rays_d, is_train=True, noise=noise0)
+        if coarse.composite_feature:         # kernel_type PBE: rgb0 is the per-ray colour of the composited features (voxnerf.py:223-239)
+            rgb0, depth0, acc0, w0, _ = coarse.forward_train(pc["net"], pts0, vd, ft0, z0, rays_d, self.train_precision, noise=noise0)
+        else:
+            raw0 = coarse.mlp_train(pc["net"], pts0, vd, ft0, self.train_precision)
+            rgb0, _, acc0, w0, depth0 = coarse.raw2outputs(raw0, z0, rays_d, is_train=True, noise=noise0)
         if Ni <= 0:
             return {"rgb_map": rgb0, "depth_map": depth0, "acc_map": acc0, "weights": w0, "z_vals": z0}
         zs, zm, order, zstd = sample_pdf_merge(z0, w0.detach(), Ni, det=(perturb == 0.), u=u, want_order=True)
@@ -490,6 +493,33 @@ class NeRFAll:
         if feat is not None:
             ret["depth_feature"] = feat                    # the fine level's per-sample geo features (renderer.py:253-256), for AWP
         return ret
+
+    def coarse_render_train(self, ray_batch, params_coarse, N_samples, lindisp=False, perturb=0., white_bkgd=False, raw_noise_std=0., *,
+                            t_rand=None, noise0=None):
+        """coarse_render_rays (renderer.py:525-592) of a composite_feature coarse level under autograd: the coarse level alone on N_samples
+        stratified samples -> (rgb_map [R, 3], feat [R, geo]), with gradients to params_coarse and to the ray batch.  The stratified draw
+        t_rand [R, S] and the density noise noise0 [R, S - 1] as coarse_render_rays draws them when they are not passed."""
+        if self.mode != "c2f" or not self.mlp_coarse.composite_feature:
+            raise NotImplementedError("coarse_render_train is the differentiable composite-feature coarse render of a mode='c2f' model "
+                                      "constructed with kernel_type='PBE'")
+        rb = ray_batch.contiguous().float()
+        R, S = rb.shape[0], int(N_samples)
+        f32 = dict(dtype=torch.float32, device=rb.device)
+        cfg = self._cfg(0, 0, 1.0, False, 0., 1., S, 0, lindisp, perturb, white_bkgd)
+        cfg.is_train = 1
+        if perturb > 0. and t_rand is None:
+            t_rand = torch.rand((R, S), **f32)
+        if raw_noise_std > 0. and noise0 is None:
+            noise0 = torch.randn((R, S - 1), **f32) * raw_noise_std
+        z0 = torch.empty((R, S), **f32)
+        tr = t_rand.contiguous().float() if t_rand is not None else None
+        L.check(L.lib().evd_sample_z(C.byref(cfg), L.ptr(rb), 11, R, L.ptr(tr), L.ptr(z0), L.stream_ptr()), "evd_sample_z")
+        coarse, pc = self.mlp_coarse, params_coarse
+        pts0 = points(rb, z0)
+        ft0 = coarse.sample_train(pts0, pc["grids"], self.train_precision)
+        rgb, _, _, _, feat = coarse.forward_train(pc["net"], pts0, rb[:, 8:11].contiguous(), ft0, z0, rb[:, 3:6].contiguous(), self.train_precision,
+                                                  noise=noise0)
+        return rgb, feat
 
     @staticmethod
     def ray_batch_train(H, W, K, rays, ndc=True, near=0., far=1.):
@@ -521,12 +551,27 @@ class NeRFAll:
         -> ray packing -> render_rays_train -> [composition with the kernel's weights] ; returns the reference's
         (rgb, rgb0, other_loss, other_tensors).  Gradients reach params_coarse / params_fine (trainable_parameters) and, through
         the rays, the kernelsnet (a PyTorch module, as in the reference).  kw: lindisp, perturb, white_bkgd, raw_noise_std and the
-        explicit random draws of render_rays_train; kernel_noise: the DSK kernel's explicit [R, P, 2] draw (SparseBlurKernel.forward's `noise`)."""
+        explicit random draws of render_rays_train; kernel_noise: the DSK kernel's explicit [R, P, 2] draw (SparseBlurKernel.forward's `noise`).
+        kernel_type PBE (renderer.py:286-302,342-343,356-357,372-373): the kernel runs twice -- stage 0 without features, whose rays go
+        through coarse_render_train (explicit draws: t_rand_stage0 [R P, S], noise_stage0 [R P, S - 1]); stage 1 with that render's
+        composited features as `feats`.  kernel_noise_stage0: the stage-0 call's own [R, P, 2] draw."""
         other_loss, other_tensors = {}, {}
         use_kernel = self.kernelsnet is not None and not force_naive
+        t_rand_stage0, noise_stage0, kernel_noise0 = kw.pop("t_rand_stage0", None), kw.pop("noise_stage0", None), kw.pop("kernel_noise_stage0", None)
+        pbe, features, extra0 = False, None, {}
         if use_kernel:
             self._check_kernel_type()
-            new_rays, weight1, align_loss, extra1 = self.kernelsnet(H, W, K, rays, rays_info, feats=None, return_img_embed=self.use_awp,
+            pbe = self.kernel_type == "PBE"
+            if pbe:
+                new_rays0, weight0, _, extra0 = self.kernelsnet(H, W, K, rays, rays_info, **({} if kernel_noise0 is None else {"noise": kernel_noise0}))
+                extra0 = {f"stage0_{k}": v for k, v in extra0.items()}
+                rb0 = self.ray_batch_train(H, W, K, new_rays0.reshape(-1, 3, 2), ndc, near, far)
+                rgb0_s0, features = self.coarse_render_train(rb0, params_coarse, N_samples, kw.get("lindisp", False), kw.get("perturb", 0.),
+                                                             kw.get("white_bkgd", False), kw.get("raw_noise_std", 0.), t_rand=t_rand_stage0,
+                                                             noise0=noise_stage0)
+                rgb0_pts_s0 = rgb0_s0.reshape(new_rays0.shape[0], new_rays0.shape[1], 3)
+                rgb0_s0 = torch.sum(rgb0_pts_s0 * weight0[..., None], dim=1)
+            new_rays, weight1, align_loss, extra1 = self.kernelsnet(H, W, K, rays, rays_info, feats=features, return_img_embed=self.use_awp,
                                                                     **({} if kernel_noise is None else {"noise": kernel_noise}))
             ray_num, pt_num = new_rays.shape[:2]
             flat_rays = new_rays.reshape(-1, 3, 2)
@@ -555,9 +600,14 @@ class NeRFAll:
                 rgb0_pts = rgb0.reshape(ray_num, pt_num, 3)
                 rgb0 = (rgb0_pts * weight1[..., None]).sum(1)
                 other_tensors["stage1_rgb1_pts0"] = rgb0_pts[:, 0]
+                if pbe:
+                    rgb0 = (rgb0_s0 + rgb0) / 2                                 # renderer.py:342-343,356-357
             if align_loss is not None:
                 other_loss["align"] = align_loss.reshape(1, 1)
+            other_tensors.update(extra0)
             other_tensors.update({f"stage1_{k}": v for k, v in extra1.items()})
+            if pbe:
+                other_tensors["stage0_rgb_pts0"] = rgb0_pts_s0[:, 0]
         else:
             other_tensors["stage1_rgb_pts0"] = rgb
             if rgb0 is not None:
@@ -937,7 +987,23 @@ class NeRFAll:
         if self.kernelsnet is not None and not force_baseline:
             self._check_kernel_type()
             from .losses import weighted_sum
-            new_rays, weight1, align_loss, extra1 = self.kernelsnet(H, W, K, rays, rays_info, feats=None, return_img_embed=self.use_awp,
+            pbe, features, extra0 = self.kernel_type == "PBE", None, {}
+            if pbe:                                        # renderer.py:289-299: stage 0, then the coarse level's composited features
+                kn0 = kwargs.get("kernel_noise_stage0")
+                new_rays0, weight0, _, extra0 = self.kernelsnet(H, W, K, rays, rays_info, **({} if kn0 is None else {"noise": kn0}))
+                extra0 = {f"stage0_{k}": v for k, v in extra0.items()}
+                ckw = dict(kwargs)
+                ckw.pop("kernel_noise_stage0", None)
+                for k, k0 in (("t_rand", "t_rand_stage0"), ("noise0", "noise_stage0")):
+                    ckw.pop(k, None)
+                    if kwargs.get(k0) is not None:
+                        ckw[k] = kwargs[k0]
+                rgb0_s0, features = self.coarse_render(H, W, K, chunk, new_rays0.reshape(-1, 3, 2), **ckw)
+                rgb0_pts_s0 = rgb0_s0.reshape(new_rays0.shape[0], new_rays0.shape[1], 3)
+                rgb0_s0 = torch.sum(rgb0_pts_s0 * weight0[..., None], dim=1)
+            for k in ("t_rand_stage0", "noise_stage0", "kernel_noise_stage0"):
+                kwargs.pop(k, None)
+            new_rays, weight1, align_loss, extra1 = self.kernelsnet(H, W, K, rays, rays_info, feats=features, return_img_embed=self.use_awp,
                                                                     **({} if kernel_noise is None else {"noise": kernel_noise}))
             extra1 = {f"stage1_{k}": v for k, v in extra1.items()}
             ray_num, pt_num = new_rays.shape[:2]
@@ -951,11 +1017,16 @@ class NeRFAll:
                 other_tensors["rgb_awp"] = weighted_sum(rgb, ccw_fine)
             rgb_out = weighted_sum(rgb, weight1)
             rgb1 = weighted_sum(extras["rgb0"], weight1) if N_importance > 0 else None
+            if pbe and rgb1 is not None:
+                rgb1 = (rgb0_s0 + rgb1) / 2                                     # renderer.py:342-343,356-357
             self._tv(other_loss, N_importance)
             if align_loss is not None:
                 other_loss["align"] = align_loss.reshape(1, 1)
+            other_tensors.update(extra0)
             other_tensors.update(extra1)
             if return_pts0_rgb:
+                if pbe:
+                    other_tensors["stage0_rgb_pts0"] = rgb0_pts_s0[:, 0]
                 other_tensors["stage1_rgb_pts0"] = rgb_pts[:, 0]
                 if N_importance > 0:
                     other_tensors["stage1_rgb1_pts0"] = rgb1_pts[:, 0]
@@ -969,13 +1040,23 @@ class NeRFAll:
 
     def _check_kernel_type(self):
         """RBK (blurmodel.RigidBlurKernel) and DSK (blurmodel.SparseBlurKernel) compose the P renders of a pixel with the kernel's weights
-        (renderer.py:299,332-354).  PBE's kernel reads the coarse level's composited features of the pixel's own ray first (:286-302)."""
+        (renderer.py:299,332-354).  PBE's kernel reads the coarse level's composited features of the pixel's own ray first (:286-302): it
+        runs on a mode='c2f' model CONSTRUCTED with kernel_type='PBE', whose coarse level has composite_feature (renderer.py:30-34 fixes it
+        there).  A model relabelled afterwards has no such level, and the NeRF network's composited feature is not built under autograd."""
         if self.kernel_type == "PBE":
-            raise NotImplementedError("kernel_type PBE in training needs the differentiable composite-feature coarse render, which is not built: "
-                                      "coarse_render returns the features, but no gradient reaches the coarse level through them "
-                                      "(blurmodel.SparseBlurKernel itself takes feats and returns their gradient)")
+            if getattr(self, "mode", None) != "c2f":
+                raise NotImplementedError("kernel_type PBE in training needs the differentiable composite-feature coarse render, which is built "
+                                          "for mode='c2f' (the PDRF coarse level), not for mode='nerf'")
+            if not getattr(getattr(self, "mlp_coarse", None), "composite_feature", False):
+                raise NotImplementedError("kernel_type PBE in training needs the composite-feature coarse render of a coarse level built with "
+                                          "composite_feature: construct the model with kernel_type='PBE' (this one was built without and "
+                                          "relabelled)")
+            if getattr(self, "train_precision", None) in ("f16c", "f16m"):
+                raise NotImplementedError(f"kernel_type PBE trains in precision f16x3 / f16 / bf16: the mixed mode {self.train_precision} keeps no "
+                                          "float32 feature rows of the coarse level (composite-feature coarse render)")
+            return
         if self.kernel_type not in ("RBK", "DSK"):
-            raise NotImplementedError(f"kernel_type {self.kernel_type!r}: RBK and DSK are built")
+            raise NotImplementedError(f"kernel_type {self.kernel_type!r}: RBK, DSK and PBE are built")
 
     def _tv(self, other_loss, N_importance):
         """TV regulariser of the tri-planes, renderer.py:361-365 / :385-389."""

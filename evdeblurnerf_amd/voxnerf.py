@@ -181,6 +181,129 @@ class _VoxelMLP(torch.autograd.Function):
                 d_dirs.reshape(R, S, 3).sum(1) if d_dirs is not None else None, None, None, None)
 
 
+class _FeatComposite(torch.autograd.Function):
+    """The feature composite of a composite_feature level (kernel_type PBE, voxnerf.py:223-229) under autograd: raw [R, S, 4] (its sigma
+    channel), the geo rows [R, S, G] BEFORE rgb_activate -> (feature map [R, G], density, acc, weights, depth).  Forward: the kernels of the
+    inference pass (evd_raw2outputs with the activated rows riding along as the feature); backward: evd_raw2outputs_feat_bwd, which
+    recomputes the scan -- d raw (sigma channel, zeros elsewhere), d rows and d rays_d."""
+
+    @staticmethod
+    def forward(ctx, raw, rows, z, rd, noise, rows_act, sigma_act, thr):
+        R, S, G = rows.shape
+        f32 = dict(dtype=torch.float32, device=raw.device)
+        fmap, dens, acc = torch.empty((R, G), **f32), torch.empty((R, max(S - 1, 0)), **f32), torch.empty((R,), **f32)
+        wts, depth = torch.empty((R, S), **f32), torch.empty((R,), **f32)
+        if rows_act not in (L.ACT["relu"], L.ACT["none"]):
+            raise NotImplementedError("composite_feature training: rgb_activate relu or none (voxnerf.py:172)")
+        act_rows = torch.relu(rows) if rows_act == L.ACT["relu"] else rows
+        L.check(L.lib().evd_raw2outputs(L.ptr(raw), L.ptr(z), L.ptr(rd), rd.shape[-1], R, S, 4, 0, 1, 3, rows_act, sigma_act, 0, thr, L.ptr(noise),
+                                        None, L.ptr(dens), L.ptr(acc), L.ptr(wts), L.ptr(depth), L.ptr(act_rows), G, L.ptr(fmap), L.stream_ptr()),
+                "evd_raw2outputs")
+        ctx.save_for_backward(raw, rows, z, rd, noise)
+        ctx.cfg = (rows_act, sigma_act, thr)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(dens)
+        return fmap, dens, acc, wts, depth
+
+    @staticmethod
+    def backward(ctx, g_fmap, g_dens, g_acc, g_w, g_depth):
+        raw, rows, z, rd, noise = ctx.saved_tensors
+        rows_act, sigma_act, thr = ctx.cfg
+        R, S, G = rows.shape
+        c = lambda t: t.contiguous().float() if t is not None else None
+        g_fmap, g_acc, g_w, g_depth = c(g_fmap), c(g_acc), c(g_w), c(g_depth)
+        d_raw, d_rows = torch.empty_like(raw), torch.empty_like(rows)
+        d_rd = torch.empty_like(rd) if ctx.needs_input_grad[3] else None
+        L.check(L.lib().evd_raw2outputs_feat_bwd(L.ptr(raw), 4, 0, L.ptr(rows), G, rows_act, L.ptr(z), L.ptr(rd), rd.shape[-1], L.ptr(noise), sigma_act, thr,
+                                                 R, S, L.ptr(g_fmap), L.ptr(g_depth), L.ptr(g_acc), L.ptr(g_w), L.ptr(d_raw), L.ptr(d_rows), L.ptr(d_rd),
+                                                 rd.shape[-1], L.stream_ptr()), "evd_raw2outputs_feat_bwd")
+        return d_raw, d_rows, None, d_rd, None, None, None, None
+
+
+class _Raw2OutputsFeat(torch.autograd.Function):
+    """VoxelNeRFBase.raw2outputs on raw = [sigma | geo rows] (Cc = 1 + G channels, voxnerf.py:223-229): the forward call and bits of the
+    inference arm; the backward splits raw into the two operands of evd_raw2outputs_feat_bwd and joins their gradients again."""
+
+    @staticmethod
+    def forward(ctx, raw, z, rd, noise, rows_act, sigma_act, thr):
+        R, S, Cc = raw.shape
+        f32 = dict(dtype=torch.float32, device=raw.device)
+        fmap, dens, acc = torch.empty((R, Cc - 1), **f32), torch.empty((R, S - 1), **f32), torch.empty((R,), **f32)
+        wts, depth = torch.empty((R, S), **f32), torch.empty((R,), **f32)
+        L.check(L.lib().evd_raw2outputs(L.ptr(raw), L.ptr(z), L.ptr(rd), rd.shape[-1], R, S, Cc, 0, 1, Cc - 1, rows_act, sigma_act, 0, thr, L.ptr(noise),
+                                        L.ptr(fmap), L.ptr(dens), L.ptr(acc), L.ptr(wts), L.ptr(depth), None, 0, None, L.stream_ptr()), "evd_raw2outputs")
+        ctx.save_for_backward(raw, z, rd, noise)
+        ctx.cfg = (rows_act, sigma_act, thr)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(dens)
+        return fmap, dens, acc, wts, depth
+
+    @staticmethod
+    def backward(ctx, g_fmap, g_dens, g_acc, g_w, g_depth):
+        raw, z, rd, noise = ctx.saved_tensors
+        rows_act, sigma_act, thr = ctx.cfg
+        R, S, Cc = raw.shape
+        c = lambda t: t.contiguous().float() if t is not None else None
+        g_fmap, g_acc, g_w, g_depth = c(g_fmap), c(g_acc), c(g_w), c(g_depth)
+        rows = raw[..., 1:].contiguous()
+        d_raw, d_rows = torch.empty_like(raw), torch.empty_like(rows)
+        d_rd = torch.empty_like(rd) if ctx.needs_input_grad[2] else None
+        L.check(L.lib().evd_raw2outputs_feat_bwd(L.ptr(raw), Cc, 0, L.ptr(rows), Cc - 1, rows_act, L.ptr(z), L.ptr(rd), rd.shape[-1], L.ptr(noise), sigma_act,
+                                                 thr, R, S, L.ptr(g_fmap), L.ptr(g_depth), L.ptr(g_acc), L.ptr(g_w), L.ptr(d_raw), L.ptr(d_rows), L.ptr(d_rd),
+                                                 rd.shape[-1], L.stream_ptr()), "evd_raw2outputs_feat_bwd")
+        d_raw[..., 1:] = d_rows                                # (the kernel wrote d sigma into channel 0 and zeros behind it)
+        return d_raw, None, d_rd, None, None, None, None
+
+
+class _ColorRows(torch.autograd.Function):
+    """The per-ray colour network of a composite_feature level (voxnerf.py:231-239) under autograd: feature map [R, G], viewdirs [R, 3] ->
+    colour [R, 3] (the inference pass's bits) with gradients to the flat parameter tensor (its color_net blocks; the sigma blocks of this
+    node's gradient are zero -- the per-sample node _VoxelMLP supplies them and autograd adds the two), the map and the view directions.
+    evd_voxel_color_rows_train / _backward; float32 in every mode, bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, flat, fmap, viewdirs, net):
+        fm, vd = fmap.contiguous().float(), viewdirs.contiguous().float()
+        R = fm.shape[0]
+        nb = int(L.lib().evd_voxel_color_rows_store_bytes(net._h, R))
+        if nb == 0 and R > 0:
+            raise L.EvdError(f"the per-ray colour network trains on the standard coarse level (hidden 64, geo 15, three colour layers) with "
+                             f"composite_feature, not on hidden {net.hidden_dim} / geo {net.geo_feat_dim} / {net.num_layers_color} colour layers")
+        store = torch.empty((nb,), dtype=torch.uint8, device=fm.device)
+        color = torch.empty((R, 3), dtype=torch.float32, device=fm.device)
+        L.check(L.lib().evd_voxel_color_rows_train(net._h, L.ptr(fm), L.ptr(vd), vd.shape[-1], R, L.ptr(color), L.ptr(store), nb, L.stream_ptr()),
+                "evd_voxel_color_rows_train")
+        ctx.net, ctx.store, ctx.fm, ctx.vd = net, store, fm, vd
+        ctx.accum = getattr(flat, "_evd_accum", None)
+        return color
+
+    @staticmethod
+    def backward(ctx, g_color):
+        L.note_backward()
+        net, need = ctx.net, ctx.needs_input_grad
+        g = g_color.contiguous().float()
+        R = g.shape[0]
+        acc = ctx.accum() if (ctx.accum is not None and need[0] and not torch.is_grad_enabled()) else None
+        net.param_blocks()
+        flat = acc if acc is not None else torch.zeros((net._nparam,), dtype=torch.float32, device=g.device)
+        gs, base = L.VoxelGrads(), flat.data_ptr()
+        gs.accumulate = int(acc is not None)
+        for key, shape, off in net.param_blocks():
+            name, idx, kind = key.split(".")
+            if name != "color_net" or (kind == "bias" and not net.has_color_bias):
+                continue
+            (gs.color_w if kind == "weight" else gs.color_b)[int(idx)] = base + 4 * off
+        d_map = torch.empty_like(ctx.fm)
+        d_vd = torch.empty((R, 3), dtype=torch.float32, device=g.device) if need[2] else None
+        nw = int(L.lib().evd_voxel_color_rows_backward_workspace_bytes(net._h, R))
+        ws = torch.empty((nw,), dtype=torch.uint8, device=g.device)
+        L.check(L.lib().evd_voxel_color_rows_backward(net._h, L.ptr(g), L.ptr(ctx.fm), L.ptr(ctx.vd), ctx.vd.shape[-1], R, L.ptr(ctx.store), ctx.store.numel(),
+                                                      C.byref(gs), L.ptr(d_map), L.ptr(d_vd), L.ptr(ws), nw, L.stream_ptr()), "evd_voxel_color_rows_backward")
+        ctx.store = None
+        _bwd_done(net)
+        return (None if acc is not None else flat), d_map, d_vd, None
+
+
 class _VoxelTV(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, *grids):
@@ -282,14 +405,8 @@ class VoxelNeRFBase:
             noise = torch.randn((R, S - 1), dtype=torch.float32, device=raw.device) * raw_noise_std
         nz = noise.contiguous().float() if noise is not None else None
         thr = float(self.render_rmnearplane) / 128.0 if (not is_train and self.render_rmnearplane > 0) else 0.0
-        if Cc != 4:           # composite_feature=True (PBE): raw = [sigma | geo features], the map has Cc - 1 channels (:223-229); forward only
-            f32 = dict(dtype=torch.float32, device=raw.device)
-            fmap, dens, acc = torch.empty((R, Cc - 1), **f32), torch.empty((R, S - 1), **f32), torch.empty((R,), **f32)
-            wts, depth = torch.empty((R, S), **f32), torch.empty((R,), **f32)
-            L.check(L.lib().evd_raw2outputs(L.ptr(raw.detach()), L.ptr(z), L.ptr(rd), rd.shape[-1], R, S, Cc, 0, 1, Cc - 1, L.ACT[self.rgb_activate],
-                                            L.ACT[self.sigma_activate], 0, thr, L.ptr(nz), L.ptr(fmap), L.ptr(dens), L.ptr(acc), L.ptr(wts), L.ptr(depth),
-                                            None, 0, None, L.stream_ptr()), "evd_raw2outputs")
-            return fmap, dens, acc, wts, depth
+        if Cc != 4:           # composite_feature=True (PBE): raw = [sigma | geo features], the map has Cc - 1 channels (:223-229)
+            return _Raw2OutputsFeat.apply(raw, z, rd, nz, L.ACT[self.rgb_activate], L.ACT[self.sigma_activate], thr)
         rgb, dens, acc, wts, depth = _Raw2Outputs.apply(raw, z, rd, nz, 0, 1, L.ACT[self.rgb_activate], L.ACT[self.sigma_activate], False, thr)
         return rgb, dens, acc, wts, depth
 
@@ -439,6 +556,25 @@ class VoxelNeRFBase:
             self.load_params(flat)
         _fwd_noted(self)
         return _VoxelMLP.apply(flat, fts, pts, viewdirs, self, precision or self.precision, want_feature)
+
+    def forward_train(self, flat, pts, viewdirs, fts, z_vals, rays_d, precision=None, noise=None):
+        """VoxelNeRFBase.forward of a composite_feature level (kernel_type PBE) in training, the reference's order (voxnerf.py:223-239):
+        per-sample sigma and geo rows -> rgb_activate -> composite -> per-ray colour network.  -> (color [R, 3], depth, acc, weights,
+        feature map [R, geo]) with autograd to the flat parameter tensor (both nodes that read it), the sampled features, the points,
+        viewdirs and rays_d.  The per-sample colours the level's kernels also compute are not used: their d raw channels are zero."""
+        prec = precision or self.precision
+        if not self.composite_feature:
+            raise L.EvdError("forward_train is the training form of a composite_feature level; other levels: mlp_train + raw2outputs")
+        if prec in ("f16c", "f16m"):
+            raise NotImplementedError(f"a composite_feature level (kernel_type PBE) trains in precision f16x3 / f16 / bf16: the mixed mode {prec} keeps "
+                                      "no float32 feature rows of the coarse level")
+        raw, rows = self.mlp_train(flat, pts, viewdirs, fts, prec, want_feature=True)
+        z, rd = z_vals.contiguous().float(), rays_d.contiguous().float()
+        nz = noise.contiguous().float() if noise is not None else None
+        fmap, _, acc, wts, depth = _FeatComposite.apply(raw, rows, z, rd, nz, L.ACT[self.rgb_activate], L.ACT[self.sigma_activate], 0.0)
+        _fwd_noted(self)
+        color = _ColorRows.apply(flat, fmap, viewdirs, self)
+        return color, depth, acc, wts, fmap
 
     # ---- training the grids (the library's channel-last layout; a permute away from the state dict) ---------------------
     def grid_params(self):

@@ -342,6 +342,16 @@ int evd_raw2outputs_bwd_rays(const float* raw, const float* z, const float* rays
                              int sigma_ch, int rgb_ch0, int n_rgb, int rgb_act, int sigma_act, int white_bkgd, float rmnear_thresh,
                              const float* noise, const float* g_map, const float* g_depth, const float* g_acc, const float* g_weights,
                              float* d_raw, float* d_rays_d, int d_rays_d_stride, void* stream);
+/* Backward of the FEATURE composite of a composite_feature level (kernel_type PBE, voxnerf.py:223-229): the map is
+ * fmap[r,c] = sum_i w_i act(rows[r,i,c]) over the G geo channels, the density is channel sigma_ch of raw dev [R,S,C].
+ * rows dev [R,S,G] are the geo rows BEFORE the activation rows_act (relu on the coarse level, none is legal).  g_fmap dev [R,G],
+ * g_depth dev [R], g_acc dev [R], g_weights dev [R,S]: any may be NULL (= zero).  Writes d_raw dev [R,S,C] (channel sigma_ch = dL/d sigma,
+ * every other channel zero), d_rows dev [R,S,G] (every element) and, where wanted, d_rays_d as evd_raw2outputs_bwd_rays does.
+ * The forward quantities are recomputed; G in 1..128, S in 1..256. */
+int evd_raw2outputs_feat_bwd(const float* raw, int C, int sigma_ch, const float* rows, int G, int rows_act, const float* z,
+                             const float* rays_d, int rays_d_stride, const float* noise, int sigma_act, float rmnear_thresh, long R, int S,
+                             const float* g_fmap, const float* g_depth, const float* g_acc, const float* g_weights,
+                             float* d_raw, float* d_rows, float* d_rays_d, int d_rays_d_stride, void* stream);
 
 /* sample_pdf, utils/rays.py:149-193, called as in renderer.py:200-201,230-231 with bins = z_mid and
  * weights[...,1:-1]: z dev [R,S], weights dev [R,S] -> z_samples dev [R,N].  det != 0 => u = linspace;
@@ -405,7 +415,8 @@ int evd_voxel_sample_prec(const evd_voxel* v, int precision, const float* pts, l
 /* VoxelNeRFBase.forward, voxnerf.py:210-259.  pts dev [R,S,3], viewdirs dev rows of vd_stride floats,
  * fts dev [R,S,F] -> color [R,3], depth [R], acc [R], weights [R,S], feature [R,S,geo].
  * A level created with composite_feature != 0 (kernel_type PBE, voxnerf.py:223-239) composites its geo features first and runs the
- * colour network per ray: `feature` is then the COMPOSITED map [R,geo].  Inference only; the workspace query includes its scratch. */
+ * colour network per ray: `feature` is then the COMPOSITED map [R,geo].  This entry is the inference pass (the workspace query includes its scratch); the two
+ * per-ray steps train through evd_raw2outputs_feat_bwd and evd_voxel_color_rows_train / _backward below. */
 int evd_voxel_forward(const evd_voxel* v, int precision, const float* pts, const float* viewdirs, int vd_stride, const float* fts, int F,
                       const float* z, const float* rays_d, int rays_d_stride, long R, int S, int is_train,
                       float* color, float* depth, float* acc, float* weights, float* feature,
@@ -442,7 +453,9 @@ int evd_voxel_tv_loss(const evd_voxel* v, float* out, void* stream);
  * evd_voxel_load_params re-packs every weight stream of the level on the device (after optimizer.step()).
  * evd_voxel_mlp_train = the per-sample part of VoxelNeRFBase.forward (voxnerf.py:210-221,240-254): raw dev [R,S,4] =
  * (sigma, sigmoid(colour)), every layer's activations kept in `store` (evd_voxel_train_store_bytes); feature dev [R,S,geo]
- * (NULL = not wanted; fine level) = the per-sample geo features AWP consumes (voxnerf.py:221), whose gradient
+ * (NULL = not wanted; the fine level, and a coarse level with composite_feature) = the per-sample geo features AWP consumes
+ * (voxnerf.py:221) or, on a composite_feature level (kernel_type PBE), the rows BEFORE rgb_activate that evd_raw2outputs composites per
+ * ray (voxnerf.py:223-229; f16x3 / f16 / bf16 -- in the half-precision modes the rounded values the store keeps), whose gradient
  * evd_voxel_mlp_backward takes back as d_feature (NULL = none).
  * evd_voxel_mlp_backward: d_raw, raw dev [R,S,4] -> parameter gradients (overwritten) and d_fts dev [R*S, d_fts_stride]
  * (columns 0 .. ft_dim-1 overwritten; NULL = not wanted), the gradient of the sampled features that evd_voxel_sample_bwd
@@ -473,6 +486,22 @@ int evd_voxel_mlp_backward(const evd_voxel* v, int precision, const float* d_raw
                            const void* awp_store, size_t awp_store_bytes, long R, int S, void* store, size_t store_bytes, const evd_voxel_grads* grads, float* d_fts, int d_fts_stride, const float* pts,
                            const float* viewdirs, int vd_stride, float* d_pts, float* d_dirs, void* workspace,
                            size_t workspace_bytes, void* stream);
+/* The per-RAY colour network of a composite_feature level (voxnerf.py:231-239) for training, float32 in every mode as at inference.
+ * evd_voxel_color_rows_train: fmap dev [R,geo] (the composited map), viewdirs dev rows of vd_stride floats -> color dev [R,3], the bits
+ * evd_voxel_forward writes for the same map, and the two hidden activations kept in `store` (evd_voxel_color_rows_store_bytes).
+ * evd_voxel_color_rows_backward: g_color dev [R,3] -> d_map dev [R,geo], d_viewdirs dev [R,3] through the direction encoding (NULL = not
+ * wanted) and the gradients of color_net.l.{weight,bias} through grads->color_w / color_b (NULL pointer = skipped; sigma_w is not read);
+ * grads->accumulate != 0 adds into the caller's buffers instead of writing.  Each workgroup sums its rays' terms in ray order and the
+ * workgroups' partial sums (in `workspace`, evd_voxel_color_rows_backward_workspace_bytes) are folded in workgroup order: two calls give
+ * the same bits.  Built for the standard coarse level (hidden 64, geo 15, three colour layers, multires_views 0..4); a 256/128
+ * composite level is refused with EVD_E_INVALID. */
+size_t evd_voxel_color_rows_store_bytes(const evd_voxel* v, long R);
+size_t evd_voxel_color_rows_backward_workspace_bytes(const evd_voxel* v, long R);
+int evd_voxel_color_rows_train(const evd_voxel* v, const float* fmap, const float* viewdirs, int vd_stride, long R, float* color,
+                               void* store, size_t store_bytes, void* stream);
+int evd_voxel_color_rows_backward(const evd_voxel* v, const float* g_color, const float* fmap, const float* viewdirs, int vd_stride, long R,
+                                  const void* store, size_t store_bytes, const evd_voxel_grads* grads, float* d_map, float* d_viewdirs,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- training the PDRF grids (scatter-add into the tri-planes) -----------------------------------------
  * The library keeps planes / lines CHANNEL-LAST: plane[i] [grid[m1]][grid[m0]][C_i] (reference app_plane.i is [1,C,H,W],

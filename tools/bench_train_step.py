@@ -49,7 +49,7 @@ def main():
     ap.add_argument("--pixels", type=int, default=1024)
     ap.add_argument("--events", type=int, default=4096)
     ap.add_argument("--P", type=int, default=10)
-    ap.add_argument("--kernel", choices=["standin", "torch", "device", "dsk", "dsk-torch"], default="standin",
+    ap.add_argument("--kernel", choices=["standin", "torch", "device", "dsk", "dsk-torch", "pbe"], default="standin",
                     help="the blur kernel network: standin = RigidKernel above (what bench.py times), torch = RigidBlurringModel's function as PyTorch ops "
                          "(tools/rigid_blur_torch.py), device = the library's kernels (evdeblurnerf_amd.blurmodel.RigidBlurKernel); 34 images, widths 32; "
                          "dsk = kernel_type DSK at the options.py defaults on the library's kernels (blurmodel.SparseBlurKernel; pass --P 5), dsk-torch = the "
@@ -90,11 +90,13 @@ def run(a):
     blur_info = None
     if kernel_kind == "standin":
         kern = RigidKernel(a.P).to(dev)
-    elif kernel_kind in ("dsk", "dsk-torch"):
+    elif kernel_kind in ("dsk", "dsk-torch", "pbe"):
         from evdeblurnerf_amd.blurmodel import SparseBlurKernel
-        args.kernel_type = "DSK"
+        # pbe: kernel_type PBE -- the model is CONSTRUCTED with it (composite_feature coarse level); the kernel runs twice per iteration and a
+        # coarse pass over the stage-0 rays feeds the second call (renderer.py:286-302); pass --P 5
+        args.kernel_type = "PBE" if kernel_kind == "pbe" else "DSK"
         torch.manual_seed(0)
-        kern = SparseBlurKernel(34, a.P, 10, "DSK", embed_init="normal").to(dev)
+        kern = SparseBlurKernel(34, a.P, 10, args.kernel_type, embed_init="normal").to(dev)
         if kernel_kind == "dsk-torch":
             sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
             from sparse_blur_torch import TorchSparseBlur
