@@ -54,6 +54,10 @@ class AwpEmbedGrads(C.Structure):
     _fields_ = [("w", _vp * 4), ("b", _vp * 4)]
 
 
+class AwpEmbedF32Grads(C.Structure):
+    _fields_ = [("w", _vp * 8), ("b", _vp * 8)]
+
+
 class AwpTailDesc(C.Structure):
     _fields_ = [("P", C.c_int), ("S", C.c_int), ("VF", C.c_int), ("dir_freqs", C.c_int), ("n_mot", C.c_int), ("training", C.c_int),
                 ("bn_eps", C.c_float), ("bn_momentum", C.c_float)]
@@ -190,6 +194,14 @@ SIGNATURES = {
     "evd_awp_embed_backward_workspace_bytes": (_S, []),
     "evd_awp_embed_forward": (_I, [_vp, _I, _vp, _vp, _vp, _S, _L, _vp, _vp, _S, _vp]),
     "evd_awp_embed_backward": (_I, [_vp, _I, _vp, _L, _vp, _S, C.POINTER(AwpEmbedGrads), _vp, _vp, _vp, _S, _vp]),
+    "evd_awp_embed_f32_create": (_I, [C.POINTER(_fp), C.POINTER(_fp), _I, _I, _I, C.POINTER(_vp)]),
+    "evd_awp_embed_f32_destroy": (None, [_vp]),
+    "evd_awp_embed_f32_param_count": (_L, [_vp]),
+    "evd_awp_embed_f32_load_params": (_I, [_vp, _vp, _vp]),
+    "evd_awp_embed_f32_store_bytes": (_S, [_vp, _L]),
+    "evd_awp_embed_f32_backward_workspace_bytes": (_S, []),
+    "evd_awp_embed_f32_forward": (_I, [_vp, _vp, _L, _L, _vp, _vp, _S, _vp]),
+    "evd_awp_embed_f32_backward": (_I, [_vp, _vp, _vp, _L, _L, _vp, _S, C.POINTER(AwpEmbedF32Grads), _vp, _vp, _S, _vp]),
     "evd_probe_mfma_rate": (_I, [_I, _I, C.POINTER(C.c_double), _vp]),
     "evd_device_count": (_I, []),
     "evd_get_rays": (_I, [_I, _I, _fp, _fp, _I, _vp, _vp, _vp]),
@@ -217,6 +229,10 @@ SIGNATURES = {
     "evd_nerf_backward_workspace_bytes": (_S, []),
     "evd_nerf_backward_workspace_bytes_net": (_S, [_vp, _I]),
     "evd_nerf_mlp_backward": (_I, [_vp, _I, _vp, _L, _I, _vp, _S, C.POINTER(NerfGrads), _vp, _vp, _I, _vp, _vp, _vp, _S, _vp]),
+    "evd_nerf_train_feature_store_bytes": (_S, [_vp, _I, _L]),
+    "evd_nerf_backward_feature_workspace_bytes": (_S, [_vp, _I]),
+    "evd_nerf_mlp_train_feature": (_I, [_vp, _I, _vp, _vp, _L, _I, _vp, _I, _vp, _S, C.POINTER(C.c_long), C.POINTER(C.c_long), _vp]),
+    "evd_nerf_mlp_backward_feature": (_I, [_vp, _I, _vp, _vp, _L, _I, _L, _I, _vp, _S, C.POINTER(NerfGrads), _vp, _vp, _vp, _S, _vp]),
     "evd_voxel_param_count": (_L, [_vp]),
     "evd_voxel_param_blocks": (_I, [_vp, C.POINTER(C.c_long), _I]),
     "evd_voxel_load_params": (_I, [_vp, _vp, _vp]),

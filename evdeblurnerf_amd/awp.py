@@ -123,6 +123,45 @@ class _SampleEmbed(torch.autograd.Function):
         return d_src, gflat, None, None
 
 
+class _SampleEmbedF32(torch.autograd.Function):
+    """evd_awp_embed_f32_forward / _backward: the embedding on float32 rows [n, input_ch] (input_ch 64 / 128 / 256: the per-sample feature
+    of a mode='nerf' network), exact float32 on the matrix cores, a bit-reproducible backward.  The rows are read in place -- a view of
+    the NeRF network's activation store is not copied -- and again by the backward."""
+
+    @staticmethod
+    def forward(ctx, src, flat, embed):
+        lib = L.lib()
+        if src.shape[-1] != embed.input_ch:
+            raise L.EvdError(f"the AWP sample embedding reads {embed.input_ch} channels per sample, the rows given have {src.shape[-1]}")
+        rows = src.detach().reshape(-1, embed.input_ch)
+        if rows.dtype != torch.float32 or not rows.is_contiguous() or rows.data_ptr() % 16:
+            rows = rows.float().clone(memory_format=torch.contiguous_format)
+        n, dev = rows.shape[0], rows.device
+        nb = int(lib.evd_awp_embed_f32_store_bytes(embed._h, n))
+        store = torch.empty((nb,), dtype=torch.uint8, device=dev)
+        h_local = torch.empty((n, embed.width), dtype=torch.float32, device=dev)
+        L.check(lib.evd_awp_embed_f32_forward(embed._h, L.ptr(rows), embed.input_ch, n, L.ptr(h_local), L.ptr(store), nb, L.stream_ptr()),
+                "evd_awp_embed_f32_forward")
+        ctx.embed, ctx.store, ctx.rows, ctx.n, ctx.src_shape = embed, store, rows, n, src.shape
+        return h_local
+
+    @staticmethod
+    def backward(ctx, d_h):
+        embed, lib, n = ctx.embed, L.lib(), ctx.n
+        g = d_h.contiguous().float()
+        gflat = torch.zeros((embed.nparam,), dtype=torch.float32, device=g.device)
+        gs, base = L.AwpEmbedF32Grads(), gflat.data_ptr()
+        for l, (wo, bo) in enumerate(embed.offsets):
+            gs.w[l], gs.b[l] = base + 4 * wo, base + 4 * bo
+        d_rows = torch.empty((n, embed.input_ch), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[0] else None
+        nb = int(lib.evd_awp_embed_f32_backward_workspace_bytes())
+        ws = torch.empty((nb,), dtype=torch.uint8, device=g.device)
+        L.check(lib.evd_awp_embed_f32_backward(embed._h, L.ptr(g), L.ptr(ctx.rows), embed.input_ch, n, L.ptr(ctx.store), ctx.store.numel(),
+                                               C.byref(gs), L.ptr(d_rows), L.ptr(ws), nb, L.stream_ptr()), "evd_awp_embed_f32_backward")
+        ctx.store = ctx.rows = None
+        return (d_rows.reshape(ctx.src_shape) if d_rows is not None else None), gflat, None
+
+
 class _MamLocal(torch.autograd.Function):
     """evd_mam_local_forward / _backward: h_local [R P, S, 64], u [64] -> (h_inter [R, P, 64], h_intra [R, S, 64]), the softmax-weighted
     sums of h_local along the samples / along the sub-exposures with the logits u . h_local (mam.py:29-33 before the 64 -> 32 map)."""
@@ -280,19 +319,28 @@ def _dir_freqs(fn):
 
 
 class SampleFeatureEmbed:
-    """sample_feature_embed_layer (awp.py:36-37) as a library handle: weights[l] [64, in_l], biases[l] [64] (nn.Linear layouts)."""
+    """sample_feature_embed_layer (awp.py:36-37) as a library handle: weights[l] [64, in_l], biases[l] [64] (nn.Linear layouts).
+
+    input_ch 128, depth 4 in precision f16 / bf16: the fused half-precision kernel (evd_awp_embed_*), which can read the fine PDRF level's
+    geo fragments.  Every other shape the library builds (input_ch 64 / 128 / 256 -- a mode='nerf' network's netwidth, run_nerf.py:223 --
+    width 64, depth 1..8), and precision="f32" for any of them: the float32 rows path (evd_awp_embed_f32_*, self.generic)."""
 
     def __init__(self, weights, biases, precision="f16"):
         ws = [torch.as_tensor(w).detach().float().cpu().contiguous() for w in weights]
         bs = [torch.as_tensor(b).detach().float().cpu().contiguous() for b in biases]
         self.depth, self.width, self.input_ch, self.precision = len(ws), ws[0].shape[0], ws[0].shape[1], precision
+        self.generic = precision == "f32" or (self.input_ch, self.width, self.depth) != (128, 64, 4)
         fp = C.POINTER(C.c_float)
         wa = (fp * len(ws))(*[C.cast(w.data_ptr(), fp) for w in ws])
         ba = (fp * len(bs))(*[C.cast(b.data_ptr(), fp) for b in bs])
         h = C.c_void_p()
-        L.check(L.lib().evd_awp_embed_create(wa, ba, self.input_ch, self.width, self.depth, C.byref(h)), "evd_awp_embed_create")
+        if self.generic:
+            L.check(L.lib().evd_awp_embed_f32_create(wa, ba, self.input_ch, self.width, self.depth, C.byref(h)), "evd_awp_embed_f32_create")
+            self.nparam = int(L.lib().evd_awp_embed_f32_param_count(h))
+        else:
+            L.check(L.lib().evd_awp_embed_create(wa, ba, self.input_ch, self.width, self.depth, C.byref(h)), "evd_awp_embed_create")
+            self.nparam = int(L.lib().evd_awp_embed_param_count(h))
         self._h = h
-        self.nparam = int(L.lib().evd_awp_embed_param_count(h))
         self.offsets, off = [], 0
         for w, b in zip(ws, bs):
             self.offsets.append((off, off + w.numel()))
@@ -302,19 +350,27 @@ class SampleFeatureEmbed:
     def __del__(self):
         h = getattr(self, "_h", None)
         if h and L is not None and getattr(L, "lib", None) is not None:     # module globals may be gone at interpreter shutdown
-            L.lib().evd_awp_embed_destroy(h)
+            (L.lib().evd_awp_embed_f32_destroy if self.generic else L.lib().evd_awp_embed_destroy)(h)
             self._h = None
 
     def load_params(self, flat):
         f = flat.detach().contiguous().float()
         if f.numel() != self.nparam:
             raise L.EvdError(f"flat parameter tensor has {f.numel()} elements, the embedding {self.nparam}")
+        if self.generic:
+            L.check(L.lib().evd_awp_embed_f32_load_params(self._h, L.ptr(f), L.stream_ptr()), "evd_awp_embed_f32_load_params")
+            return
         L.check(L.lib().evd_awp_embed_load_params(self._h, L.ptr(f), L.stream_ptr()), "evd_awp_embed_load_params")
 
     def __call__(self, flat, geo):
         """flat: the parameters W0, b0, W1, b1, ... (re-packed into the library's streams before the launch); geo: GeoFragments or a
         float32 tensor [..., 128] -> h_local [n, 64] with autograd to flat and to the geo features"""
         self.load_params(flat)
+        if self.generic:
+            if isinstance(geo, GeoFragments):
+                raise L.EvdError("the float32 rows path of SampleFeatureEmbed reads a float32 tensor [..., input_ch]; the fragment coupling is "
+                                 "built for input_ch 128, depth 4 in f16 / bf16 only")
+            return _SampleEmbedF32.apply(geo, flat, self)
         if isinstance(geo, GeoFragments):
             # the fragments are the level's own half-precision MFMA operands: reading a bf16 store as f16 (or the reverse) would
             # reinterpret the bits silently -- the C entry can only check the store's size
@@ -368,7 +424,9 @@ class FusedAWP(torch.nn.Module):
                                      (tail_kernels=True and the reference's structure; else the wrapped module's own layers)
 
     `depth_feature` is the GeoFragments handle NeRFAll.forward_train passes when its awpnet is a FusedAWP (a float32 tensor
-    [R P, S, 128] is accepted too)."""
+    [R P, S, 128] is accepted too).  A proposal whose embedding reads 64 / 128 / 256 channels of a float32 tensor -- mode='nerf', where
+    depth_feature is the NeRF network's per-sample feature [R P, S, netwidth] -- runs the embedding on float32 rows
+    (SampleFeatureEmbed.generic, evd_awp_embed_f32_*) and everything behind it on the same kernels."""
 
     def __init__(self, awpnet, precision="f16", graph_per_ray=False, tail_kernels=True):
         """tail_kernels (default): the per-ray remainder (awp.py:89-95, 104-117, mam.py:35-53) on evd_awp_tail_forward / _backward -- two

@@ -4,6 +4,8 @@
 // the float16 / bfloat16 MFMA fragments the level's training forward already keeps for its own backward (voxel_mlp_kernel.h
 // VStore::GEO), so the reference's depth_feature tensor [R P, S, 128] (renderer.py:253-256,314) is never written.
 // Shared between the kernels (awp_embed_kernel.h) and the C ABI (evd_awp_api.hip).
+// This is the ONE shape of the fused half-precision kernel; the embedding of a mode='nerf' model's proposal (input_ch 64 / 128 / 256 on
+// float32 rows, depth 1..8) is awp_embed_generic.h.
 #pragma once
 
 #include "evd_common.h"

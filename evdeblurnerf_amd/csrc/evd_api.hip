@@ -202,6 +202,14 @@ int evd_nerf_create(const evd_nerf_desc* d, evd_nerf** out) {
             n->pipe_chunks[prec] = (int)(sp.bytes.size() / PIPE_CB);
             rc = n->pipe[prec].upload(sp);
         }
+        if (!rc && prec == EVD_PREC_F16X3 && n->pipe_chunks[prec]) {        // (see nerf_net.h stream_pd)
+            StreamBuilder sd(prec);
+            sd.arena = A;
+            n->pd_pdh = KS - 2 * nerf_group(prec);
+            nerf_layers(sd, *n, A, out_rows, n->pd_pdh);
+            n->pd_chunks = (int)(sd.bytes.size() / chunk_bytes(prec));
+            rc = n->stream_pd.upload(sd);
+        }
         // training path (bf16 / f16 / split-f16 on the pipelined network)
         if (!rc && is_train_prec(prec) && n->pipe_chunks[prec]) rc = nerf_wt_streams(*n, prec, A);
     }
@@ -227,7 +235,8 @@ int evd_nerf_create(const evd_nerf_desc* d, evd_nerf** out) {
         dev_params.release();
     }
     // generic training path (nerf_train_generic.h): its backward reads the float32 parameters in place
-    if (!rc && nerf_generic_trains(n, EVD_PREC_F16X3)) rc = n->params_f32.upload(arena.data(), arena.size() * sizeof(float));
+    // (every view-branch network: the entries with a feature output run that path for the pipelined network too)
+    if (!rc && (nerf_generic_trains(n, EVD_PREC_F16X3) || nerf_feature_trains(n, EVD_PREC_F16X3))) rc = n->params_f32.upload(arena.data(), arena.size() * sizeof(float));
     if (rc) { evd_nerf_destroy(n); return rc; }
     *out = n;
     return EVD_OK;
@@ -240,6 +249,7 @@ void evd_nerf_destroy(evd_nerf* n) {
         n->pipe[i].release();
         for (int k = 0; k < EVD_BWD_NSTREAMS; ++k) n->bwd[i][k].release();
     }
+    n->stream_pd.release();
     n->wmaps.release();
     n->batch.release();
     n->bias.release();
@@ -273,6 +283,7 @@ int evd_nerf_load_params(evd_nerf* net, const float* params, void* stream) {
         all.push_back(&net->pipe[i]);
         for (int k = 0; k < EVD_BWD_NSTREAMS; ++k) all.push_back(&net->bwd[i][k]);
     }
+    all.push_back(&net->stream_pd);
     if ((rc = repack_batch(net->batch, all, params, st))) return rc;
     if ((rc = repack_stream_c(net->pipe_c, params, st))) return rc;
     const long nb = (long)(net->bias.bytes / sizeof(float));

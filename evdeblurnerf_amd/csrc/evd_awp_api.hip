@@ -1,6 +1,7 @@
 // C-ABI entry points of the fused AWP sample-feature embedding: reference networks/dpnerf/awp.py:36-37 (the module list),
 // :98-100 (its forward), trained by run_nerf.py:593-601.
 #include "awp_embed.h"
+#include "awp_embed_generic.h"
 #include "evd_common.h"
 #include "frag_layout.h"
 #include "nerf_mlp.h"
@@ -9,6 +10,13 @@
 #include <cstdint>
 
 using namespace evd;
+
+// the embedding on float32 rows (awp_embed_generic.h): the parameters as one float32 arena on the device, read in place by every launch
+struct evd_awp_embed_f32 {
+    int input_ch, depth;
+    long param_off[2 * AWPG_MAX_D + 1];      // W0, b0, W1, b1, ...; [2 depth] = total
+    DevBuf params;
+};
 
 struct evd_awp_embed {
     long param_off[2 * AWP_D + 1];           // W0, b0, W1, b1, ... in the flat parameter arena; [8] = total
@@ -151,6 +159,104 @@ int evd_awp_embed_backward(const evd_awp_embed* a, int precision, const float* d
     b.wgrad_blocks = AWP_WGRAD_BLOCKS;
     b.d_geo_rows = d_geo_rows;
     return precision == EVD_PREC_F16 ? run_awp_backward_f16(b, as_stream(stream)) : run_awp_backward_bf16(b, as_stream(stream));
+}
+
+// ---- float32 rows, input_ch 64 / 128 / 256 (awp_embed_generic.h) -------------------------------------------------------------------------
+
+void evd_awp_embed_f32_destroy(evd_awp_embed_f32* a) {
+    if (!a) return;
+    a->params.release();
+    delete a;
+}
+
+int evd_awp_embed_f32_create(const float* const* weights, const float* const* biases, int input_ch, int width, int depth, evd_awp_embed_f32** out) {
+    EVD_REQUIRE(weights && biases && out, "evd_awp_embed_f32_create: null argument");
+    EVD_REQUIRE(awpg_shape_ok(input_ch, width, depth), "evd_awp_embed_f32_create: built for input_ch 64 / 128 / 256, W_sam %d, D_sam 1..%d, got %d / %d / %d",
+                AWPG_W, AWPG_MAX_D, input_ch, width, depth);
+    for (int l = 0; l < depth; ++l) EVD_REQUIRE(weights[l] && biases[l], "evd_awp_embed_f32_create: missing layer %d", l);
+    evd_awp_embed_f32* a = new evd_awp_embed_f32();
+    a->input_ch = input_ch; a->depth = depth;
+    ParamBlock blk[2 * AWPG_MAX_D];
+    for (int l = 0; l < depth; ++l) {
+        blk[2 * l] = {weights[l], (long)AWPG_W * (l == 0 ? input_ch : AWPG_W)};
+        blk[2 * l + 1] = {biases[l], AWPG_W};
+    }
+    const std::vector<float> arena = build_arena(blk, 2 * depth, a->param_off);
+    if (int rc = a->params.upload(arena.data(), arena.size() * sizeof(float))) { evd_awp_embed_f32_destroy(a); return rc; }
+    *out = a;
+    return EVD_OK;
+}
+
+long evd_awp_embed_f32_param_count(const evd_awp_embed_f32* a) { return a ? a->param_off[2 * a->depth] : 0; }
+
+int evd_awp_embed_f32_load_params(evd_awp_embed_f32* a, const float* params, void* stream) {
+    EVD_REQUIRE(a && params, "evd_awp_embed_f32_load_params: null argument");
+    EVD_HIP(hipMemcpyAsync(a->params.p, params, a->params.bytes, hipMemcpyDeviceToDevice, as_stream(stream)));
+    return EVD_OK;
+}
+
+size_t evd_awp_embed_f32_store_bytes(const evd_awp_embed_f32* a, long nsamp) {
+    return (!a || nsamp < 0) ? 0 : (size_t)AwpGenStore(nsamp, a->depth).total() * sizeof(float);
+}
+
+size_t evd_awp_embed_f32_backward_workspace_bytes(void) { WgradWs L; return wgrad_layout(GEN_WS_FLOATS * sizeof(float), nullptr, &L); }
+
+static bool rows_ok(const float* rows, long ld, int input_ch) { return ld >= input_ch && ld % 4 == 0 && ((uintptr_t)rows & 15) == 0; }
+
+int evd_awp_embed_f32_forward(const evd_awp_embed_f32* a, const float* rows, long rows_stride, long nsamp, float* h_local, void* store,
+                              size_t store_bytes, void* stream) {
+    EVD_REQUIRE(a && rows && h_local && store && nsamp >= 0, "evd_awp_embed_f32_forward: null argument");
+    EVD_REQUIRE(rows_ok(rows, rows_stride, a->input_ch), "evd_awp_embed_f32_forward: rows of %ld floats for %d channels (a multiple of 4, 16-byte aligned)",
+                rows_stride, a->input_ch);
+    if (nsamp == 0) return EVD_OK;
+    const size_t need = evd_awp_embed_f32_store_bytes(a, nsamp);
+    if (store_bytes < need) return fail(EVD_E_WORKSPACE, "evd_awp_embed_f32_forward: store %zu < %zu bytes", store_bytes, need);
+    const AwpGenStore gs(nsamp, a->depth);
+    float* S = (float*)store;
+    const float* P = (const float*)a->params.p;
+    for (int l = 0; l < a->depth; ++l) {
+        GenLinear g;
+        g.X = l == 0 ? rows : S + gs.h(l - 1); g.ldx = l == 0 ? rows_stride : AWPG_W;
+        g.Wm = P + a->param_off[2 * l]; g.bias = P + a->param_off[2 * l + 1];
+        g.out = S + gs.h(l); g.out2 = l == a->depth - 1 ? h_local : nullptr; g.nsamp = nsamp;
+        if (int rc = launch_gen_linear_relu(l == 0 ? a->input_ch : AWPG_W, g, as_stream(stream))) return rc;
+    }
+    return EVD_OK;
+}
+
+int evd_awp_embed_f32_backward(const evd_awp_embed_f32* a, const float* d_h_local, const float* rows, long rows_stride, long nsamp, void* store,
+                               size_t store_bytes, const evd_awp_embed_f32_grads* grads, float* d_rows, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    EVD_REQUIRE(a && d_h_local && rows && store && grads && workspace && nsamp >= 0, "evd_awp_embed_f32_backward: null argument");
+    EVD_REQUIRE(rows_ok(rows, rows_stride, a->input_ch) && rows_stride <= INT32_MAX,
+                "evd_awp_embed_f32_backward: rows of %ld floats for %d channels (a multiple of 4, 16-byte aligned)", rows_stride, a->input_ch);
+    if (nsamp == 0) return EVD_OK;
+    const size_t need_store = evd_awp_embed_f32_store_bytes(a, nsamp);
+    if (store_bytes < need_store) return fail(EVD_E_WORKSPACE, "evd_awp_embed_f32_backward: store %zu < %zu bytes", store_bytes, need_store);
+    WgradWs ws;
+    const size_t need = wgrad_layout(GEN_WS_FLOATS * sizeof(float), workspace, &ws);
+    if (workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_awp_embed_f32_backward: workspace %zu < %zu bytes", workspace_bytes, need);
+    hipStream_t st = as_stream(stream);
+    const AwpGenStore gs(nsamp, a->depth);
+    float* S = (float*)store;
+    const float* P = (const float*)a->params.p;
+    const int D = a->depth, W = AWPG_W;
+    float *cur = S + gs.g(0), *oth = S + gs.g(1);
+    // d pre-activation of the last layer: d h_local where its ReLU passed
+    if (int rc = launch_gen_rows_in(d_h_local, W, S + gs.h(D - 1), nsamp, W, cur, st)) return rc;
+    GenChain c{nsamp, ws.partial, 0, st, "evd_awp_embed_f32_backward"};
+    for (int l = D - 1; l >= 0; --l) {          // cur = d pre-activation of layer l
+        const float* wl = P + a->param_off[2 * l];
+        if (l == 0) {
+            c.wgrad(cur, W, W, rows, (int)rows_stride, a->input_ch, grads->w[0], a->input_ch, 0, grads->b[0]);
+            if (d_rows) c.dgrad(W, cur, W, wl, a->input_ch, 0, a->input_ch, d_rows, a->input_ch, nullptr, 0, nullptr, nullptr, 0);
+            break;
+        }
+        c.wgrad(cur, W, W, S + gs.h(l - 1), W, W, grads->w[l], W, 0, grads->b[l]);
+        c.dgrad(W, cur, W, wl, W, 0, W, oth, W, S + gs.h(l - 1), W, nullptr, nullptr, 0);
+        float* t = cur; cur = oth; oth = t;
+    }
+    return c.rc;
 }
 
 }  // extern "C"

@@ -146,4 +146,66 @@ int evd_nerf_mlp_backward(const evd_nerf* net, int precision, const float* d_raw
            : precision == EVD_PREC_BF16 ? run_nerf_backward_bf16(b, as_stream(stream)) : run_nerf_backward_f16x3(b, as_stream(stream));
 }
 
+// ---- the training entries with a per-sample feature output (the proposal's depth_feature, renderer.py:238-257): generic kernels only ----
+#define EVD_FEATURE_REFUSAL(entry)                                                                                                      \
+    entry ": the feature output under training is built for precision f16x3 on view-branch networks (use_viewdirs=False networks and "  \
+          "every other precision: not built)"
+
+size_t evd_nerf_train_feature_store_bytes(const evd_nerf* net, int precision, long nsamp) {
+    return (net && nsamp >= 0 && nerf_feature_trains(net, precision)) ? nerf_generic_store_bytes(net, nsamp) : 0;
+}
+
+size_t evd_nerf_backward_feature_workspace_bytes(const evd_nerf* net, int precision) {
+    WgradWs L;
+    return (net && nerf_feature_trains(net, precision)) ? wgrad_layout(wgrad_partial_bytes(true), nullptr, &L) : 0;
+}
+
+int evd_nerf_mlp_train_feature(const evd_nerf* net, int precision, const float* ray_batch, const float* z, long R, int S, float* raw, int feature_kind,
+                               void* store, size_t store_bytes, long* feature_offset, long* feature_stride, void* stream) {
+    EVD_REQUIRE(net && ray_batch && z && raw && store && feature_offset && feature_stride, "evd_nerf_mlp_train_feature: null argument");
+    EVD_REQUIRE(nerf_feature_trains(net, precision), EVD_FEATURE_REFUSAL("evd_nerf_mlp_train_feature"));
+    EVD_REQUIRE(feature_kind == 1 || feature_kind == 2, "evd_nerf_mlp_train_feature: feature_kind %d (1 = after_linear, 2 = before_linear)", feature_kind);
+    EVD_REQUIRE(R >= 0 && S >= 1, "evd_nerf_mlp_train_feature: bad shape R=%ld S=%d", R, S);
+    const long nsamp = R * (long)S;
+    const GenStore gs(nsamp, net->D, net->W);
+    *feature_offset = feature_kind == 1 ? gs.f() : gs.h(net->D - 1);
+    *feature_stride = net->W;
+    if (R == 0) return EVD_OK;
+    const size_t need = nerf_generic_store_bytes(net, nsamp);
+    if (store_bytes < need) return fail(EVD_E_WORKSPACE, "evd_nerf_mlp_train_feature: store %zu < %zu bytes", store_bytes, need);
+    MlpParams g{};
+    // the pipelined network: the stream with that kernel's order of additions in the skip layer, so that raw has the bits of evd_nerf_mlp_train
+    const bool pd = net->pd_chunks > 0;
+    g.wstream = (const char*)(pd ? net->stream_pd.data.p : net->stream[EVD_PREC_F16X3].data.p);
+    g.bias = (const float*)net->bias.p;
+    g.ray_batch = ray_batch; g.z = z; g.nsamp = nsamp; g.S = S; g.ncol = 11;
+    g.D = net->D; g.skip = net->skip; g.nchunks = pd ? net->pd_chunks : net->nchunks[EVD_PREC_F16X3]; g.nbias = (int)(net->bias.bytes / sizeof(float));
+    g.raw = raw; g.act = (char*)store; g.pe_l = net->multires; g.pe_lv = net->multires_views;
+    return launch_nerf_train_fwd_generic(net->W, g, as_stream(stream), pd ? net->pd_pdh : 0);
+}
+
+int evd_nerf_mlp_backward_feature(const evd_nerf* net, int precision, const float* d_raw, const float* d_feature, long d_feature_stride, int feature_kind,
+                                  long R, int S, void* store, size_t store_bytes, const evd_nerf_grads* grads, float* d_pts, float* d_dirs,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    EVD_REQUIRE(net && d_raw && store && grads && workspace, "evd_nerf_mlp_backward_feature: null argument");
+    EVD_REQUIRE(nerf_feature_trains(net, precision), EVD_FEATURE_REFUSAL("evd_nerf_mlp_backward_feature"));
+    EVD_REQUIRE(feature_kind == 1 || feature_kind == 2, "evd_nerf_mlp_backward_feature: feature_kind %d (1 = after_linear, 2 = before_linear)", feature_kind);
+    EVD_REQUIRE(!d_feature || (d_feature_stride >= net->W && d_feature_stride <= INT32_MAX),
+                "evd_nerf_mlp_backward_feature: d_feature rows of %ld floats, the feature has %d", d_feature_stride, net->W);
+    EVD_REQUIRE(R >= 0 && S >= 1, "evd_nerf_mlp_backward_feature: bad shape R=%ld S=%d", R, S);
+    if (R == 0) return EVD_OK;
+    const long nsamp = R * (long)S;
+    const size_t need_store = nerf_generic_store_bytes(net, nsamp);
+    if (store_bytes < need_store) return fail(EVD_E_WORKSPACE, "evd_nerf_mlp_backward_feature: store %zu < %zu bytes", store_bytes, need_store);
+    WgradWs ws;
+    const size_t need = wgrad_layout(wgrad_partial_bytes(true), workspace, &ws);
+    if (workspace_bytes < need) return fail(EVD_E_WORKSPACE, "evd_nerf_mlp_backward_feature: workspace %zu < %zu bytes", workspace_bytes, need);
+    GenBwdPlan g;
+    g.net = net; g.d_raw = d_raw; g.nsamp = nsamp; g.store = (float*)store;
+    g.partial = ws.partial; g.grads = plan_grads(net, grads);
+    g.accumulate = grads->accumulate ? 1 : 0; g.d_pts = d_pts; g.d_dirs = d_dirs;
+    g.d_feature = d_feature; g.ldf = (int)d_feature_stride; g.feature_kind = feature_kind;
+    return run_nerf_backward_generic(g, as_stream(stream));
+}
+
 }  // extern "C"

@@ -10,7 +10,9 @@ namespace evd {
 // Forward: k_nerf_mlp_generic<EVD_PREC_F16X3, W, VKS> (kernel_nerf_mlp.hip) -- the same stream, the same layer<> calls in the same
 // order, hence the same raw bit for bit -- with every layer's output written as a float32 row of the store (layer<>'s feat_row).
 // A kernel of its own and not a switch in k_nerf_mlp_generic: the inference kernels' code objects stay what they were.
-template <int W, int VKS>
+// PDH: where the point encoding's k-steps sit in the skip layer, [h_0 .. h_{PDH-1} | pe | h_PDH .. h_{KS-1}] (nerf_streams.h nerf_layers).  0: the
+// generic stream; KS - 2: evd_nerf::stream_pd, the pipelined kernel's order of additions, for the pipelined network's forward with a feature.
+template <int W, int VKS, int PDH = 0>
 __global__ __launch_bounds__(mlp_threads(EVD_PREC_F16X3), 1) void k_nerf_train_fwd_generic(const MlpParams p) {
     constexpr int PREC = EVD_PREC_F16X3;
     typedef Ops<PREC> O;
@@ -70,9 +72,11 @@ __global__ __launch_bounds__(mlp_threads(EVD_PREC_F16X3), 1) void k_nerf_train_f
         if (l - 1 == p.skip) {      // h = cat([input_pts, h]) feeds this layer (nerf.py:137-138)
             B wide[PE_KS + KS];
 #pragma unroll
-            for (int j = 0; j < PE_KS; ++j) wide[j] = stash[j * 64];
+            for (int j = 0; j < PDH; ++j) wide[j] = act[j];
 #pragma unroll
-            for (int j = 0; j < KS; ++j) wide[PE_KS + j] = act[j];
+            for (int j = 0; j < PE_KS; ++j) wide[PDH + j] = stash[j * 64];
+#pragma unroll
+            for (int j = PDH; j < KS; ++j) wide[PE_KS + j] = act[j];
             layer<PREC, PE_KS + KS, T, true, OUT_B, 0, true>(st, wide, nxt, nullptr, bias, lane, hrow, W);
         } else {
             layer<PREC, KS, T, true, OUT_B, 0, true>(st, act, nxt, nullptr, bias, lane, hrow, W);
@@ -115,20 +119,24 @@ __global__ __launch_bounds__(mlp_threads(EVD_PREC_F16X3), 1) void k_nerf_train_f
     }
 }
 
-template <int W, int VKS>
+template <int W, int VKS, int PDH = 0>
 static int launch_fwd(const MlpParams& p, hipStream_t st) {
     constexpr int PREC = EVD_PREC_F16X3, NT = mlp_threads(PREC);
     const long blocks = cdiv(p.nsamp, NT / 2);
     const size_t lds = MlpLds<PREC>::TOTAL;
-    EVD_SET_MAX_LDS((&k_nerf_train_fwd_generic<W, VKS>), lds);
+    EVD_SET_MAX_LDS((&k_nerf_train_fwd_generic<W, VKS, PDH>), lds);
     if (p.nbias > MlpLds<PREC>::BIAS_FLOATS) return fail(EVD_E_INVALID, "evd_nerf_mlp_train: %d bias floats exceed the LDS bias block", p.nbias);
-    hipLaunchKernelGGL((k_nerf_train_fwd_generic<W, VKS>), dim3((unsigned)blocks), dim3(NT), lds, st, p);
+    hipLaunchKernelGGL((k_nerf_train_fwd_generic<W, VKS, PDH>), dim3((unsigned)blocks), dim3(NT), lds, st, p);
     EVD_LAUNCH_CHECK();
     return EVD_OK;
 }
 
-int launch_nerf_train_fwd_generic(int W, const MlpParams& p, hipStream_t st) {
+int launch_nerf_train_fwd_generic(int W, const MlpParams& p, hipStream_t st, int pdh) {
     const bool widev = pe_ksteps(p.pe_lv) > 2;
+    if (pdh) {          // the pipelined network's stream_pd: one shape
+        if (W == 256 && !widev && pdh == 14) return launch_fwd<256, 2, 14>(p, st);      // (10, 4): two direction k-steps
+        return fail(EVD_E_INVALID, "evd_nerf_mlp_train_feature: no training kernel for the skip layer order %d at width %d", pdh, W);
+    }
     if (W == 64) return widev ? launch_fwd<64, 4>(p, st) : launch_fwd<64, 2>(p, st);
     if (W == 128) return widev ? launch_fwd<128, 4>(p, st) : launch_fwd<128, 2>(p, st);
     if (W == 256) return widev ? launch_fwd<256, 4>(p, st) : launch_fwd<256, 2>(p, st);
@@ -195,6 +203,25 @@ __global__ __launch_bounds__(256) void k_gen_rgb_dgrad(const float* __restrict__
         o[e] = m[e] > 0.f ? x : 0.f;
     }
     *reinterpret_cast<f32x4*>(out + s * H + k) = o;
+}
+
+// out[s, k] = src[s, k] (rows of lds floats), zero where a ReLU mask row is given and mask[s, k] <= 0: the gradient of a feature output
+// placed in a gradient plane before the dgrad that adds to it.  thread = 4 columns of one sample.
+__global__ __launch_bounds__(256) void k_gen_rows_in(const float* __restrict__ src, long lds, const float* __restrict__ mask, long nsamp, int Wd,
+                                                     float* __restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int per = Wd / 4;
+    const long s = i / per;
+    if (s >= nsamp) return;
+    const int k = (int)(i % per) * 4;
+    const float* x = src + s * lds + k;
+    f32x4 o = {x[0], x[1], x[2], x[3]};
+    if (mask) {
+        const f32x4 m = *reinterpret_cast<const f32x4*>(mask + s * Wd + k);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = m[e] > 0.f ? o[e] : 0.f;
+    }
+    *reinterpret_cast<f32x4*>(out + s * Wd + k) = o;
 }
 
 struct GenDgrad {
@@ -434,6 +461,12 @@ void GenChain::dgrad(int M, const float* G, int ldg, const float* Wm, int ldw, i
     if (hipGetLastError() != hipSuccess) rc = fail(EVD_E_HIP, "%s: dgrad launch failed", who);
 }
 
+int launch_gen_rows_in(const float* src, long lds, const float* mask, long nsamp, int Wd, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_gen_rows_in, dim3((unsigned)cdiv(nsamp * (Wd / 4), 256)), dim3(256), 0, st, src, lds, mask, nsamp, Wd, out);
+    EVD_LAUNCH_CHECK();
+    return EVD_OK;
+}
+
 int launch_gen_encode(const float* in, long nsamp, int L, int Lv, float* ep, float* ed, hipStream_t st) {
     hipLaunchKernelGGL(k_gen_encode, dim3((unsigned)cdiv(nsamp * 128, 256)), dim3(256), 0, st, in, nsamp, L, Lv, ep, ed);
     EVD_LAUNCH_CHECK();
@@ -472,12 +505,18 @@ int run_nerf_backward_generic(const GenBwdPlan& b, hipStream_t st) {
     // views_linears.0 on cat([feature, PE(dirs)]) (nerf.py:151-154); g0 = d its pre-activation [n, H]
     c.wgrad(g0, H, H, frow, W, W, b.grads.views_w, W + ICV, 0, b.grads.views_b);
     c.wgrad(g0, H, H, ed, GEN_ENC, ICV, b.grads.views_w, W + ICV, W, nullptr);
-    c.dgrad(H, g0, H, views_w, W + ICV, 0, W, g1, W, nullptr, 0, nullptr, nullptr, 0);          // g1 = d feature
+    const bool fg1 = b.d_feature && b.feature_kind == 1, fg2 = b.d_feature && b.feature_kind == 2;
+    auto rows_in = [&](const float* mask, float* out) { return launch_gen_rows_in(b.d_feature, b.ldf, mask, n, W, out, st); };
+    if (fg1)
+        if (int rc = rows_in(nullptr, g1)) return rc;
+    c.dgrad(H, g0, H, views_w, W + ICV, 0, W, g1, W, nullptr, 0, nullptr, nullptr, fg1 ? 1 : 0);          // g1 = d feature
     if (b.d_dirs) c.dgrad(H, g0, H, views_w, W + ICV, W, ICV, ded, GEN_ENC, nullptr, 0, nullptr, nullptr, 0);
     // feature_linear and alpha_linear on h_{D-1} (nerf.py:144-150)
     c.wgrad(g1, W, W, hrow(D - 1), W, W, b.grads.feature_w, W, 0, b.grads.feature_b);
     c.wgrad(b.d_raw + 3, 4, 1, hrow(D - 1), W, W, b.grads.alpha_w, W, 0, b.grads.alpha_b);
-    c.dgrad(W, g1, W, feature_w, W, 0, W, g0, W, hrow(D - 1), W, b.d_raw + 3, alpha_w, 0);      // g0 = d pre-activation of pts_linears[D-1]
+    if (fg2)
+        if (int rc = rows_in(hrow(D - 1), g0)) return rc;
+    c.dgrad(W, g1, W, feature_w, W, 0, W, g0, W, hrow(D - 1), W, b.d_raw + 3, alpha_w, fg2 ? 1 : 0);      // g0 = d pre-activation of pts_linears[D-1]
     // the trunk, last layer first; cur = d pre-activation of layer l
     float *cur = g0, *oth = g1;
     int pe_written = 0;

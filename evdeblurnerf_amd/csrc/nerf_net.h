@@ -17,6 +17,11 @@ struct evd_nerf {
     int nchunks[EVD_NUM_PREC];
     Packed pipe[EVD_NUM_PREC];               // software-pipelined kernel (where built): its own fragment order and chunking
     int pipe_chunks[EVD_NUM_PREC];
+    // the pipelined network only: a generic-format EVD_PREC_F16X3 stream whose skip layer has the PIPELINED kernel's k-step order
+    // (nerf_streams.h nerf_layers, pdh = KS - 2), for the training forward with a feature output (evd_nerf_mlp_train_feature): raw then
+    // has the bits of the pipelined training forward
+    Packed stream_pd;
+    int pd_chunks = 0, pd_pdh = 0;
     evd::DevBuf bias, bias_src;
     evd::PackedStreamC pipe_c;               // EVD_PREC_F16C: float16 + fp6 fragment stream, row-scale words (32 per output tile in bias order), re-pack maps
     // EVD_PREC_F16C inference: feature_linear folded into views_linears.0 (evd_api.hip k_fold_feature) -- its own stream, row scales and

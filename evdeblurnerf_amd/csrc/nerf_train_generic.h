@@ -5,6 +5,9 @@
 // Backward: per layer one wgrad launch (per-wavefront partial sums over a sample range, folded in a fixed order by k_gen_wreduce)
 // and one dgrad launch, both exact float32 products on the matrix cores (v_mfma_f32_32x32x2f32) with the parameters read in place
 // from the handle's float32 copy.  No floating-point atomics, no host synchronisation.
+// With a feature output (evd_nerf_mlp_train_feature / _backward_feature; every view-branch network, the pipelined 8 x 256 one included):
+// the feature is a plane of the store (GenStore::f() or h(D - 1)), its gradient one more addend placed by k_gen_rows_in ahead of a dgrad
+// that runs with `add`.
 #pragma once
 
 #include "evd_common.h"
@@ -36,9 +39,13 @@ constexpr size_t GEN_WS_FLOATS = (size_t)8 << 20;       // wgrad partial sums: a
 inline bool nerf_generic_trains(const evd_nerf* n, int prec) {
     return prec == EVD_PREC_F16X3 && !n->no_views && n->pipe_chunks[EVD_PREC_F16X3] == 0 && n->nchunks[EVD_PREC_F16X3] > 0;
 }
+// The entries with a feature output (evd_nerf_mlp_train_feature / evd_nerf_mlp_backward_feature) run these kernels for EVERY view-branch
+// network, the 8 x 256 / (10, 4) / skips [4] one included: a predicate of their own, the dispatch of the plain entries stays where it is.
+inline bool nerf_feature_trains(const evd_nerf* n, int prec) { return prec == EVD_PREC_F16X3 && !n->no_views && n->nchunks[EVD_PREC_F16X3] > 0; }
 inline size_t nerf_generic_store_bytes(const evd_nerf* n, long nsamp) { return (size_t)GenStore(nsamp, n->D, n->W).total() * sizeof(float); }
 
-int launch_nerf_train_fwd_generic(int W, const MlpParams& p, hipStream_t st);
+// pdh: the skip layer's k-step order of the stream in p (0 = the generic stream, evd_nerf::pd_pdh = evd_nerf::stream_pd)
+int launch_nerf_train_fwd_generic(int W, const MlpParams& p, hipStream_t st, int pdh = 0);
 
 struct GenBwdPlan {
     const evd_nerf* net;
@@ -49,6 +56,10 @@ struct GenBwdPlan {
     BwdGrads grads;
     int accumulate;
     float *d_pts, *d_dirs;      // [nsamp, 3] or null
+    // d loss / d feature rows [nsamp, W] of ldf floats, or null: feature_kind 1 = the feature_linear output, 2 = the ReLU output of
+    // pts_linears[D-1] (what the forward exposes as a plane of the store)
+    const float* d_feature = nullptr;
+    int ldf = 0, feature_kind = 0;
 };
 int run_nerf_backward_generic(const GenBwdPlan& b, hipStream_t st);
 
@@ -71,5 +82,8 @@ struct GenChain {
 // PE(pts), PE(dirs) as float32 rows of GEN_ENC columns from rows [nsamp, 8] = (pts xyz, 0, dirs xyz, 0); and d x [nsamp, 3] from d PE(x)
 int launch_gen_encode(const float* in, long nsamp, int L, int Lv, float* ep, float* ed, hipStream_t st);
 int launch_gen_encode_bwd(const float* enc, const float* denc, long nsamp, int L, float* dx, hipStream_t st);
+// out[s, k] = src[s, k] (rows of lds floats; k < Wd, a multiple of 4), zero where mask (rows of Wd floats, a ReLU output) is given and <= 0:
+// an output's own gradient placed in a gradient plane [nsamp, Wd] ahead of the dgrad that adds to it
+int launch_gen_rows_in(const float* src, long lds, const float* mask, long nsamp, int Wd, float* out, hipStream_t st);
 
 }  // namespace evd

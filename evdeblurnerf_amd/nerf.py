@@ -92,6 +92,41 @@ class _NerfMLP(torch.autograd.Function):
         return g, d_rb, None, None, None
 
 
+class _NerfMLPFeature(torch.autograd.Function):
+    """(raw, feature) = NeRF.mlpforward(..., want_feature) for training: one node on the generic float32-grade kernels
+    (evd_nerf_mlp_train_feature / _backward_feature); the feature [R, S, W] is a view of the activation store, and its gradient enters
+    the backward next to d raw (the AWP proposal's depth_feature in mode='nerf', renderer.py:238-257)"""
+
+    @staticmethod
+    def forward(ctx, flat, ray_batch, z_vals, net, precision):
+        raw, store, feature = net.mlpforward_train(ray_batch, z_vals, precision, want_feature=True)
+        ctx.net, ctx.precision, ctx.store = net, precision, store
+        ctx.rb, ctx.z = ray_batch, z_vals
+        ctx.accum = getattr(flat, "_evd_accum", None)
+        ctx.set_materialize_grads(False)
+        return raw, feature
+
+    @staticmethod
+    def backward(ctx, d_raw, d_feature):
+        L.note_backward()
+        R, S = ctx.z.shape
+        if d_raw is None:
+            d_raw = torch.zeros((R, S, 4), dtype=torch.float32, device=ctx.z.device)
+        acc = ctx.accum() if (ctx.accum is not None and ctx.needs_input_grad[0] and not torch.is_grad_enabled()) else None
+        rays = ctx.needs_input_grad[1]
+        g, d_pts, d_dirs = ctx.net.mlp_backward_feature_flat(d_raw, d_feature, ctx.store, ctx.precision, want_rays=rays, accumulate_into=acc)
+        d_rb = None
+        if rays:
+            rb, z = ctx.rb.detach().float(), ctx.z.detach().float()
+            d_rb = torch.zeros_like(rb)
+            d_pts = d_pts.reshape(R, S, 3)
+            d_rb[:, 0:3] = d_pts.sum(1)
+            d_rb[:, 3:6] = (d_pts * z[..., None]).sum(1)
+            d_rb[:, 8:11] = d_dirs.reshape(R, S, 3).sum(1)
+        ctx.store = None
+        return g, d_rb, None, None, None
+
+
 class NeRF:
     """One reference ``NeRF`` (D x W MLP, skip, view branch) with packed MFMA weight streams on the GPU."""
 
@@ -176,13 +211,28 @@ class NeRF:
     # Training forward: the same raw plus the activation store evd_nerf_mlp_backward consumes (f16 / bf16, or f16x3 = the float32-grade
     # mode with (hi, lo) fragments; 8 x 256 network).  Every other view-branch network trains in f16x3 on the generic kernels; the
     # per-network size queries are all this class knows about which path runs.
-    def mlpforward_train(self, ray_batch, z_vals, precision=None):
+    # want_feature: (raw, store, feature) on the generic kernels (f16x3, every view-branch network); the feature [R, S, W] that
+    # `extract_feature` selects is a float32 VIEW of the store (evd_nerf_mlp_train_feature), consumed by mlp_backward_feature_flat.
+    def mlpforward_train(self, ray_batch, z_vals, precision=None, want_feature=False):
         if not self.use_viewdirs:
             raise L.EvdError("the training path is not built for use_viewdirs=False networks")
         rb = ray_batch.contiguous().float()
         z = z_vals.contiguous().float()
         R, S = z.shape
         raw = torch.empty((R, S, 4), dtype=torch.float32, device=z.device)
+        if want_feature:
+            prec = L.PREC[precision or self.precision]
+            nb = int(L.lib().evd_nerf_train_feature_store_bytes(self._h, prec, R * S))
+            if nb == 0 and R * S > 0:
+                raise L.EvdError(f"no training path with a feature output in precision {precision or self.precision}: built for f16x3")
+            store = torch.empty((nb,), dtype=torch.uint8, device=z.device)
+            off, ld = C.c_long(0), C.c_long(0)
+            L.check(L.lib().evd_nerf_mlp_train_feature(self._h, prec, L.ptr(rb), L.ptr(z), R, S, L.ptr(raw), self._feature_kind(), L.ptr(store), nb,
+                                                        C.byref(off), C.byref(ld), L.stream_ptr()), "evd_nerf_mlp_train_feature")
+            if ld.value != self.W:
+                raise L.EvdError("evd_nerf_mlp_train_feature: unexpected feature row stride")
+            feature = store.view(torch.float32)[off.value:off.value + R * S * self.W].view(R, S, self.W)
+            return raw, store, feature
         nb = int(L.lib().evd_nerf_train_store_bytes_net(self._h, L.PREC[precision or self.precision], R * S))
         if nb == 0 and R * S > 0:
             raise L.EvdError(f"no training path for this network in precision {precision or self.precision}: the netdepth 8, netwidth 256, "
@@ -233,11 +283,54 @@ class NeRF:
         L.check(L.lib().evd_nerf_load_params(self._h, L.ptr(f), L.stream_ptr()), "evd_nerf_load_params")
         self._synced = (flat.data_ptr(), flat._version, L.backward_generation())
 
-    def mlp_train(self, flat, ray_batch, z_vals, precision=None):
-        """NeRF.mlpforward for training: raw [R,S,4] with autograd back to the flat parameter tensor (rays are constants)"""
+    def mlp_train(self, flat, ray_batch, z_vals, precision=None, want_feature=False):
+        """NeRF.mlpforward for training: raw [R,S,4] with autograd back to the flat parameter tensor (and to the rays when they require it).
+        want_feature: (raw, feature [R,S,W]) from one node whose backward takes both gradients (f16x3, the generic kernels)"""
         if getattr(self, "_synced", None) != (flat.data_ptr(), flat._version, L.backward_generation()):
             self.load_params(flat)
+        if want_feature:
+            return _NerfMLPFeature.apply(flat, ray_batch, z_vals, self, precision or self.precision)
         return _NerfMLP.apply(flat, ray_batch, z_vals, self, precision or self.precision)
+
+    def _feature_kind(self):
+        return 2 if self.extract_feature == "before_linear" else 1
+
+    def _grads_struct(self, flat, accumulate):
+        """evd_nerf_grads whose blocks point into the flat float32 tensor"""
+        gs = L.NerfGrads()
+        gs.accumulate = int(accumulate)
+        base = flat.data_ptr()
+        for key, shape, off in self.param_blocks():
+            name, kind = key.rsplit(".", 1)
+            field = "_w" if kind == "weight" else "_b"
+            if name.startswith("pts_linears."):
+                getattr(gs, "pts" + field)[int(name.split(".")[1])] = base + 4 * off
+            else:
+                head = {"views_linears.0": "views", "feature_linear": "feature", "alpha_linear": "alpha", "rgb_linear": "rgb"}[name]
+                setattr(gs, head + field, base + 4 * off)
+        return gs
+
+    # Backward of mlpforward_train(want_feature=True): gradients of sum(raw d_raw) + sum(feature d_feature)
+    def mlp_backward_feature_flat(self, d_raw, d_feature, store, precision=None, want_rays=False, accumulate_into=None):
+        """(flat parameter gradient, d pts [R*S,3] or None, d dirs [R*S,3] or None).  d_feature [R,S,W] or None (then the gradients of
+        mlp_backward_flat on the generic path); accumulate_into as in mlp_backward_flat (the returned flat gradient is then None)"""
+        g = d_raw.contiguous().float()
+        R, S = g.shape[:2]
+        prec = L.PREC[precision or self.precision]
+        self.param_blocks()
+        flat = accumulate_into if accumulate_into is not None else torch.zeros((self._nparam,), dtype=torch.float32, device=g.device)
+        gs = self._grads_struct(flat, accumulate_into is not None)
+        df = d_feature.contiguous().float() if d_feature is not None else None
+        if df is not None and tuple(df.shape) != (R, S, self.W):
+            raise L.EvdError(f"d_feature {tuple(df.shape)} is not [R, S, W] = {(R, S, self.W)}")
+        nb = int(L.lib().evd_nerf_backward_feature_workspace_bytes(self._h, prec))
+        ws = torch.empty((nb,), dtype=torch.uint8, device=g.device)
+        d_pts = torch.empty((R * S, 3), dtype=torch.float32, device=g.device) if want_rays else None
+        d_dirs = torch.empty((R * S, 3), dtype=torch.float32, device=g.device) if want_rays else None
+        L.check(L.lib().evd_nerf_mlp_backward_feature(self._h, prec, L.ptr(g), L.ptr(df), self.W, self._feature_kind(), R, S, L.ptr(store),
+                                                       store.numel(), C.byref(gs), L.ptr(d_pts), L.ptr(d_dirs), L.ptr(ws), nb, L.stream_ptr()),
+                "evd_nerf_mlp_backward_feature")
+        return (None if accumulate_into is not None else flat), d_pts, d_dirs
 
     # Backward of mlpforward_train: d_raw [R,S,4] -> flat gradient (what autograd gives for nerf.py:46-72)
     def mlp_backward_flat(self, d_raw, store, precision=None, pts=None, ray_batch=None, accumulate_into=None):
@@ -248,17 +341,7 @@ class NeRF:
         R, S = g.shape[:2]
         blocks = self.param_blocks()
         flat = accumulate_into if accumulate_into is not None else torch.zeros((self._nparam,), dtype=torch.float32, device=g.device)
-        gs = L.NerfGrads()
-        gs.accumulate = int(accumulate_into is not None)
-        base = flat.data_ptr()
-        for key, shape, off in blocks:
-            name, kind = key.rsplit(".", 1)
-            field = "_w" if kind == "weight" else "_b"
-            if name.startswith("pts_linears."):
-                getattr(gs, "pts" + field)[int(name.split(".")[1])] = base + 4 * off
-            else:
-                head = {"views_linears.0": "views", "feature_linear": "feature", "alpha_linear": "alpha", "rgb_linear": "rgb"}[name]
-                setattr(gs, head + field, base + 4 * off)
+        gs = self._grads_struct(flat, accumulate_into is not None)
         nb = int(L.lib().evd_nerf_backward_workspace_bytes_net(self._h, L.PREC[precision or self.precision]))
         ws = torch.empty((nb,), dtype=torch.uint8, device=g.device)
         want = pts is not None

@@ -217,6 +217,12 @@ class NeRFAll:
             if args.N_importance > 0:
                 common_f = dict(common, D=_args_get(args, "netdepth_fine", args.netdepth), W=_args_get(args, "netwidth_fine", args.netwidth))
                 self.mlp_fine = NeRF(state_dict, "mlp_fine.", **common_f)
+            # the proposal reads the LAST pass's per-sample feature (renderer.py:238-257; run_nerf.py:223 builds it with input_ch = netwidth)
+            awp_in = getattr(getattr(awpnet, "embed", None), "input_ch", None)
+            last_w = (self.mlp_fine or self.mlp_coarse).W
+            if self.use_awp and awp_in is not None and awp_in != last_w:
+                raise L.EvdError(f"kernel_use_awp: the AWP sample embedding reads {awp_in} channels per sample, the network whose feature it "
+                                 f"is handed has netwidth {last_w}")
         else:
             from .voxnerf import VoxelNeRFRayFeatures, VoxelNeRFSampleFeatures
             # kernel_type PBE: the coarse level composites its geo features and runs its colour network per ray (renderer.py:30-34,
@@ -420,6 +426,8 @@ class NeRFAll:
         (forward keeps activations, hand-written backward), compositing scan (autograd node), hierarchical resampling on the
         detached coarse weights (renderer.py:233 z_samples.detach()), fine pass.  Rays are constants (no pose gradients)."""
         from .rays import sample_pdf_merge
+        if want_feature:
+            self._check_nerf_feature_precision()
         rb = ray_batch.contiguous().float()
         R, S, Ni = rb.shape[0], int(N_samples), int(N_importance)
         f32 = dict(dtype=torch.float32, device=rb.device)
@@ -440,17 +448,36 @@ class NeRFAll:
         if self.mode == "c2f":
             return self._render_rays_train_c2f(rb, z0, flat_coarse, flat_fine, S, Ni, perturb, u, noise0, noise1, want_feature)
         rays_d = rb[:, 3:6].contiguous()
-        if want_feature:
-            raise NotImplementedError("depth_feature under autograd is built for mode='c2f' (the shipped AWP configs)")
-        raw0 = self.mlp_coarse.mlp_train(flat_coarse, rb, z0, self.train_precision)
+        # want_feature: the LAST pass returns its network's per-sample feature [R, S, W] as depth_feature (renderer.py:219-257) -- the
+        # fine network with N_importance > 0, else the coarse one; the coarse pass of a two-pass render asks for none
+        feat = None
+        if want_feature and Ni <= 0:
+            raw0, feat = self.mlp_coarse.mlp_train(flat_coarse, rb, z0, self.train_precision, want_feature=True)
+        else:
+            raw0 = self.mlp_coarse.mlp_train(flat_coarse, rb, z0, self.train_precision)
         rgb0, _, acc0, w0, depth0, _ = self.mlp_coarse.raw2outputs(raw0, z0, rays_d, None, 0., white_bkgd, noise=noise0)
         if Ni <= 0:
-            return {"rgb_map": rgb0, "depth_map": depth0, "acc_map": acc0, "weights": w0, "z_vals": z0}
+            ret = {"rgb_map": rgb0, "depth_map": depth0, "acc_map": acc0, "weights": w0, "z_vals": z0}
+            if feat is not None:
+                ret["depth_feature"] = feat
+            return ret
         _, zm, _, zstd = sample_pdf_merge(z0, w0.detach(), Ni, det=(perturb == 0.), u=u)
-        raw1 = self.mlp_fine.mlp_train(flat_fine, rb, zm, self.train_precision)
+        if want_feature:
+            raw1, feat = self.mlp_fine.mlp_train(flat_fine, rb, zm, self.train_precision, want_feature=True)
+        else:
+            raw1 = self.mlp_fine.mlp_train(flat_fine, rb, zm, self.train_precision)
         rgb, _, acc, w1, depth, _ = self.mlp_fine.raw2outputs(raw1, zm, rays_d, None, 0., white_bkgd, noise=noise1)
-        return {"rgb_map": rgb, "depth_map": depth, "acc_map": acc, "weights": w1, "z_vals": zm, "rgb0": rgb0, "depth0": depth0,
-                "acc0": acc0, "z_std": zstd}
+        ret = {"rgb_map": rgb, "depth_map": depth, "acc_map": acc, "weights": w1, "z_vals": zm, "rgb0": rgb0, "depth0": depth0,
+               "acc0": acc0, "z_std": zstd}
+        if feat is not None:
+            ret["depth_feature"] = feat
+        return ret
+
+    def _check_nerf_feature_precision(self):
+        """mode='nerf' with AWP: the per-sample feature and its gradient exist on the float32-grade generic kernels only"""
+        if self.mode == "nerf" and self.train_precision != "f16x3":
+            raise NotImplementedError(f"mode='nerf' with kernel_use_awp trains in precision f16x3 only (the per-sample feature of the NeRF network "
+                                      f"and its gradient are built on the float32-grade generic kernels), not in {self.train_precision}")
 
     def _render_rays_train_c2f(self, rb, z0, pc, pf, S, Ni, perturb, u, noise0, noise1, want_feature=False):
         """renderer.py:182-217 under autograd: tri-plane gathers (scatter-add backward), level networks (fused forward/backward),
@@ -557,6 +584,9 @@ class NeRFAll:
         composited features as `feats`.  kernel_noise_stage0: the stage-0 call's own [R, P, 2] draw."""
         other_loss, other_tensors = {}, {}
         use_kernel = self.kernelsnet is not None and not force_naive
+        if use_kernel and self.use_awp:
+            if self.kernel_type != "PBE":       # (PBE with mode='nerf': _check_kernel_type names that reason)
+                self._check_nerf_feature_precision()
         t_rand_stage0, noise_stage0, kernel_noise0 = kw.pop("t_rand_stage0", None), kw.pop("noise_stage0", None), kw.pop("kernel_noise_stage0", None)
         pbe, features, extra0 = False, None, {}
         if use_kernel:

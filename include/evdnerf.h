@@ -316,6 +316,28 @@ int evd_nerf_mlp_backward(const evd_nerf* net, int precision, const float* d_raw
                           const evd_nerf_grads* grads, const float* pts, const float* viewdirs, int vd_stride, float* d_pts,
                           float* d_dirs, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Training forward and backward WITH the per-sample feature the AWP proposal reads as depth_feature in mode='nerf'
+ * (networks/renderer.py:238-257; run_nerf.py:223 builds the proposal with input_ch = netwidth).  EVD_PREC_F16X3 only, and always the
+ * generic kernels of evd_nerf_mlp_train (float32 rows in the store, exact float32 backward, no atomics) -- for EVERY view-branch network of
+ * width 64 / 128 / 256, the 8 x 256 / (10, 4) / skips [4] one included; use_viewdirs=False networks and every other precision:
+ * EVD_E_INVALID (the size queries: 0).  The plain entries above are untouched by these.
+ *   evd_nerf_mlp_train_feature: raw bit-equal to evd_nerf_mlp_train's, for the 8 x 256 network too (the handle keeps a stream in the pipelined
+ *     kernel's skip-layer order for it).  feature_kind 1 = "after_linear" (the
+ *     feature_linear output, nerf.py:149-150), 2 = "before_linear" (the ReLU output of the last pts_linears layer, :141-142).  The feature
+ *     is a plane of the store, not a copy: row s (s < R * S; the store pads the sample count to 32, those rows are not written) starts
+ *     *feature_offset + s * *feature_stride FLOATS into the store and holds netwidth floats.  The backward leaves that plane as it is.
+ *   evd_nerf_mlp_backward_feature: the gradients of sum(raw d_raw) + sum(feature d_feature).  d_feature dev rows of d_feature_stride
+ *     floats ([R * S, netwidth]), or NULL: then exactly evd_nerf_mlp_backward on the generic path.  grads (accumulate included), d_pts,
+ *     d_dirs as there; the sample positions and directions are read from the store.
+ *   Sizes: evd_nerf_train_feature_store_bytes, evd_nerf_backward_feature_workspace_bytes. */
+size_t evd_nerf_train_feature_store_bytes(const evd_nerf* net, int precision, long nsamp);
+size_t evd_nerf_backward_feature_workspace_bytes(const evd_nerf* net, int precision);
+int evd_nerf_mlp_train_feature(const evd_nerf* net, int precision, const float* ray_batch, const float* z, long R, int S, float* raw,
+                               int feature_kind, void* store, size_t store_bytes, long* feature_offset, long* feature_stride, void* stream);
+int evd_nerf_mlp_backward_feature(const evd_nerf* net, int precision, const float* d_raw, const float* d_feature, long d_feature_stride,
+                                  int feature_kind, long R, int S, void* store, size_t store_bytes, const evd_nerf_grads* grads,
+                                  float* d_pts, float* d_dirs, void* workspace, size_t workspace_bytes, void* stream);
+
 /* raw2outputs: networks/nerf.py:74-129 (sigma_ch 3, rgb_ch0 0) and networks/pdrf/voxnerf.py:153-201
  * (sigma_ch 0, rgb_ch0 1).  raw dev [R,S,C], z dev [R,S], rays_d dev rows of rays_d_stride floats.
  * noise dev [R,S-1] optional (explicit randn*raw_noise_std draw).  rmnear_thresh <= 0 disables the
@@ -767,6 +789,30 @@ int evd_awp_embed_forward(const evd_awp_embed* a, int precision, const float* ge
 int evd_awp_embed_backward(const evd_awp_embed* a, int precision, const float* d_h_local, long nsamp, void* store, size_t store_bytes,
                            const evd_awp_embed_grads* grads, float* d_geo_rows, const unsigned* d_h_absmax, void* workspace,
                            size_t workspace_bytes, void* stream);
+
+/* The same sample embedding on FLOAT32 ROWS, for the inputs of mode='nerf': run_nerf.py:223 builds the proposal with input_ch = netwidth
+ * and the renderer hands it the NeRF network's per-sample feature (renderer.py:238-257).  input_ch 64 / 128 / 256, W_sam 64, D_sam 1..8
+ * (EVD_E_INVALID otherwise).  One launch per layer: out[s, m] = relu(b[m] + sum_k X[s, k] W[m, k]) in exact float32 on the matrix cores,
+ * k ascending; every layer's output rows are kept in `store` (evd_awp_embed_f32_store_bytes; required).  The backward runs the per-layer
+ * wgrad / dgrad launches of the generic NeRF training path (evd_nerf_mlp_backward): no atomics, the same bits on every call.
+ *   rows dev [n, input_ch] float32, rows of rows_stride floats (a multiple of 4, 16-byte aligned -- e.g. the feature plane
+ *     evd_nerf_mlp_train_feature leaves in its store); the backward reads the SAME rows again.
+ *   evd_awp_embed_f32_load_params: flat dev float32 arena W0, b0, W1, b1, ... (evd_awp_embed_f32_param_count elements).
+ *   evd_awp_embed_f32_backward: d_h_local dev [n, 64] -> parameter gradients in nn.Linear layout (overwritten; NULL = not wanted) and
+ *     d_rows dev [n, input_ch] (NULL = not wanted).  workspace: evd_awp_embed_f32_backward_workspace_bytes(). */
+typedef struct evd_awp_embed_f32 evd_awp_embed_f32;
+typedef struct { float *w[8], *b[8]; } evd_awp_embed_f32_grads;
+int evd_awp_embed_f32_create(const float* const* weights, const float* const* biases, int input_ch, int width, int depth, evd_awp_embed_f32** out);
+void evd_awp_embed_f32_destroy(evd_awp_embed_f32* a);
+long evd_awp_embed_f32_param_count(const evd_awp_embed_f32* a);
+int evd_awp_embed_f32_load_params(evd_awp_embed_f32* a, const float* params, void* stream);
+size_t evd_awp_embed_f32_store_bytes(const evd_awp_embed_f32* a, long nsamp);
+size_t evd_awp_embed_f32_backward_workspace_bytes(void);
+int evd_awp_embed_f32_forward(const evd_awp_embed_f32* a, const float* rows, long rows_stride, long nsamp, float* h_local, void* store,
+                              size_t store_bytes, void* stream);
+int evd_awp_embed_f32_backward(const evd_awp_embed_f32* a, const float* d_h_local, const float* rows, long rows_stride, long nsamp, void* store,
+                               size_t store_bytes, const evd_awp_embed_f32_grads* grads, float* d_rows, void* workspace, size_t workspace_bytes,
+                               void* stream);
 
 /* EDI prior (utils/edi.py:73-95): bii dev [steps-1, npix], blurry dev [npix] -> sharp dev [npix] */
 int evd_edi_deblur(const float* blurry, const float* bii, int steps, long npix, float* sharp, void* stream);

@@ -58,12 +58,14 @@ class RefLikeAWP(torch.nn.Module):
     module is MAMLike (mam="corr", the reference's structure) or a small stand-in with only the MAM's call contract
     (x_global [R, P, C], x_local [R P, S, 64]) -> [R, P, C] (mam="mean")."""
 
-    def __init__(self, P=5, W_mot=32, view_ch=4, mam="mean"):
+    def __init__(self, P=5, W_mot=32, view_ch=4, mam="mean", input_ch=128):
+        """input_ch: channels per sample the embedding reads -- 128 = fine_geo_feat_dim of the shipped mode='c2f' configs; a mode='nerf'
+        model's proposal reads netwidth channels (run_nerf.py:223)"""
         super().__init__()
         self.output_ch, self.ccw_fine_scale, self.ray_dir_freq = P, 0.05, 2
         ch = 3 * (1 + 2 * 2)            # a differentiable 2-frequency encoding (the reference's get_embedder(ray_dir_freq) is torch too)
         self.ray_dirs_embed_fn = lambda x: torch.cat([x] + [f(x * 2.0 ** k) for k in range(2) for f in (torch.sin, torch.cos)], -1)
-        self.sample_feature_embed_layer = torch.nn.ModuleList([torch.nn.Linear(128, 64)] + [torch.nn.Linear(64, 64) for _ in range(3)])
+        self.sample_feature_embed_layer = torch.nn.ModuleList([torch.nn.Linear(input_ch, 64)] + [torch.nn.Linear(64, 64) for _ in range(3)])
         self.motion_feature_embed_layer = torch.nn.ModuleList([torch.nn.Linear(64 + view_ch + ch, W_mot), torch.nn.Linear(W_mot, W_mot)])
         self.w_linear = torch.nn.Linear(W_mot, P)
         if mam == "corr":                # the reference's MotionAggregationModule structure (FusedAWP runs its per-sample part on the library)
