@@ -1,17 +1,17 @@
-// AWP sample embedding on float32 rows (kernel_awp_embed_generic.hip): AdaptiveWeightProposal.sample_feature_embed_layer, reference
+// AWP sample embedding on float32 rows (evd_awp_api.hip evd_awp_embed_f32_*): AdaptiveWeightProposal.sample_feature_embed_layer, reference
 // networks/dpnerf/awp.py:36-37,98-100, for the input widths of mode='nerf' -- run_nerf.py:223 builds the proposal with
 // input_ch = netwidth, and the renderer hands it the NeRF network's per-sample feature (renderer.py:238-257).
 // input_ch 64 / 128 / 256, width 64, depth 1..8.  Forward: one launch per layer of a float32 Linear + bias + ReLU on the matrix cores
-// (v_mfma_f32_32x32x2f32, exact float32 products); every layer's output rows stay in the embedding's own store.  Backward: the per-layer
-// launches of the generic NeRF training path (nerf_train_generic.h GenChain): no atomics, the same bits on every call.
+// (gen_rows.h k_gen_linear_relu: v_mfma_f32_32x32x2f32, exact float32 products); every layer's output rows stay in the embedding's own
+// store.  Backward: the per-layer launches of gen_rows.h (GenChain): no atomics, the same bits on every call.
 #pragma once
 
 #include "evd_common.h"
-#include "nerf_train_generic.h"
+#include "gen_rows.h"
 
 namespace evd {
 
-constexpr int AWPG_W = 64, AWPG_MAX_D = 8;
+constexpr int AWPG_MAX_D = 8;           // the width AWPG_W is the forward layer kernel's (gen_rows.h)
 inline bool awpg_shape_ok(int input_ch, int width, int depth) {
     return (input_ch == 64 || input_ch == 128 || input_ch == 256) && width == AWPG_W && depth >= 1 && depth <= AWPG_MAX_D;
 }
@@ -25,15 +25,5 @@ struct AwpGenStore {
     long g(int i) const { return nsp * AWPG_W * (D + i); }      // x 2: d loss / d pre-activation, ping-pong (what the backward writes)
     long total() const { return g(2); }
 };
-
-// out[s, m] = relu(bias[m] + sum_k X[s, k] Wm[m, k]), m < 64, k < K in ascending order; out2: a second copy of the rows, or null
-struct GenLinear {
-    const float* X; long ldx;       // [nsamp, K] rows of ldx floats (16-byte aligned rows)
-    const float* Wm;                // [64, K] nn.Linear layout
-    const float* bias;              // [64]
-    float *out, *out2;              // [nsamp, 64]
-    long nsamp;
-};
-int launch_gen_linear_relu(int K, const GenLinear& a, hipStream_t st);
 
 }  // namespace evd

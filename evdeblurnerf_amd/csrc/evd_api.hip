@@ -236,7 +236,7 @@ int evd_nerf_create(const evd_nerf_desc* d, evd_nerf** out) {
     }
     // generic training path (nerf_train_generic.h): its backward reads the float32 parameters in place
     // (every view-branch network: the entries with a feature output run that path for the pipelined network too)
-    if (!rc && (nerf_generic_trains(n, EVD_PREC_F16X3) || nerf_feature_trains(n, EVD_PREC_F16X3))) rc = n->params_f32.upload(arena.data(), arena.size() * sizeof(float));
+    if (!rc && nerf_feature_trains(n, EVD_PREC_F16X3)) rc = n->params_f32.upload(arena.data(), arena.size() * sizeof(float));
     if (rc) { evd_nerf_destroy(n); return rc; }
     *out = n;
     return EVD_OK;
@@ -306,16 +306,14 @@ int evd_nerf_mlp(const evd_nerf* net, int precision, const float* ray_batch, con
     EVD_REQUIRE(R >= 0 && S >= 1, "evd_nerf_mlp: bad shape R=%ld S=%d", R, S);
     EVD_REQUIRE(!feature || feature_kind == 1 || feature_kind == 2, "evd_nerf_mlp: feature_kind must be 1 or 2");
     if (R == 0) return EVD_OK;
-    MlpParams p{};
-    const bool piped = net->pipe_chunks[precision] > 0;
-    p.wstream = (const char*)(piped ? net->pipe[precision].data.p : net->stream[precision].data.p);
-    p.bias = (const float*)net->bias.p;
-    p.ray_batch = ray_batch; p.z = z; p.nsamp = R * (long)S; p.S = S; p.ncol = net->no_views ? 8 : 11; p.no_views = net->no_views;
-    p.pe_l = net->multires; p.pe_lv = net->multires_views;
     EVD_REQUIRE(!(net->no_views && feature && feature_kind == 1), "evd_nerf_mlp: a use_viewdirs=False network has no after_linear feature (nerf.py:159)");
     EVD_REQUIRE(!net->no_views || precision != EVD_PREC_F16C, "evd_nerf_mlp: EVD_PREC_F16C is not built for use_viewdirs=False networks");
-    p.D = net->D; p.skip = net->skip; p.nchunks = piped ? net->pipe_chunks[precision] : net->nchunks[precision]; p.nbias = (int)(net->bias.bytes / sizeof(float));
-    p.raw = raw; p.feature = feature; p.feature_kind = feature ? feature_kind : 0; p.act = nullptr; p.wscale = nullptr;
+    MlpParams p = nerf_mlp_params(net, ray_batch, z, R, S, raw);
+    const bool piped = net->pipe_chunks[precision] > 0;
+    p.wstream = (const char*)(piped ? net->pipe[precision].data.p : net->stream[precision].data.p);
+    p.nchunks = piped ? net->pipe_chunks[precision] : net->nchunks[precision];
+    p.no_views = net->no_views; p.pe_l = net->multires; p.pe_lv = net->multires_views;
+    p.feature = feature; p.feature_kind = feature ? feature_kind : 0;
     if (precision == EVD_PREC_F16C) {
         EVD_REQUIRE(net->pipe_chunks[precision] > 0, "evd_nerf_mlp: EVD_PREC_F16C is built for netdepth 8, netwidth 256, skips [4], multires 10 / 4 only");
         EVD_REQUIRE(!feature, "evd_nerf_mlp: EVD_PREC_F16C has no feature-row variant (use EVD_PREC_F16X3)");

@@ -4,6 +4,7 @@
 #include "awp_embed_generic.h"
 #include "evd_common.h"
 #include "frag_layout.h"
+#include "gen_rows.h"
 #include "nerf_mlp.h"
 #include "voxel_train.h"
 

@@ -2,7 +2,7 @@
 // activation store and the hand-written backward, on the handle's streams (voxel_net.h).
 #include "voxel_net.h"
 #include "awp_embed.h"
-#include "nerf_train_generic.h"
+#include "gen_rows.h"
 
 using namespace evd;
 

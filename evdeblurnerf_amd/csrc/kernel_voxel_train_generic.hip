@@ -1,9 +1,9 @@
-// Backward of a generic PDRF level (voxel_generic.h), EVD_PREC_F16X3: per layer one wgrad and one dgrad launch of the generic NeRF path
-// (nerf_train_generic.h GenChain: exact float32 on the matrix cores, per-wavefront partials folded in a fixed order, the parameters read
+// Backward of a generic PDRF level (voxel_generic.h), EVD_PREC_F16X3: per layer one wgrad and one dgrad launch of the float32-row kernels
+// (gen_rows.h GenChain: exact float32 on the matrix cores, per-wavefront partials folded in a fixed order, the parameters read
 // in place from the handle's float32 copy; no floating-point atomics, no host synchronisation).
 // reference: the autograd graph of networks/pdrf/voxnerf.py:210-221 (sigma net), :240-254 (colour net), networks/embedding.py:88-98.
 #include "voxel_generic.h"
-#include "nerf_train_generic.h"
+#include "gen_rows.h"
 #include "mlp_device.h"
 
 namespace evd {

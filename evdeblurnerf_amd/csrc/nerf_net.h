@@ -2,6 +2,7 @@
 #pragma once
 
 #include "evd_common.h"
+#include "nerf_mlp.h"
 #include "pack.h"
 
 // transposed-weight streams of the dgrad chain (nerf_train_kernel.h), in the order the chain runs them
@@ -37,3 +38,13 @@ struct evd_nerf {
     evd::RepackBatch batch;                  // table of every fragment stream, for the one-launch re-pack of evd_nerf_load_params
     mutable evd::SideStream side;            // backward entry: wgrad side stream of THIS handle (created on first use)
 };
+
+// What every MLP entry hands its kernel the same way; the stream and its chunk count, the encodings' frequency counts, the row scales, the
+// feature output and the activation store stay with the entry that chooses them.
+inline evd::MlpParams nerf_mlp_params(const evd_nerf* net, const float* ray_batch, const float* z, long R, int S, float* raw) {
+    evd::MlpParams p{};
+    p.bias = (const float*)net->bias.p; p.nbias = (int)(net->bias.bytes / sizeof(float));
+    p.ray_batch = ray_batch; p.z = z; p.nsamp = R * (long)S; p.S = S; p.ncol = net->no_views ? 8 : 11;
+    p.D = net->D; p.skip = net->skip; p.raw = raw;
+    return p;
+}

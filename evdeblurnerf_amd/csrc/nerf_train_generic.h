@@ -2,22 +2,21 @@
 // reference: the autograd graph of networks/nerf.py:46-72,131-162 (NeRF.mlpforward + eval), embedding.py:88-98.
 //
 // Forward: k_nerf_mlp_generic's body in the split-float16 mode, with every layer's output also written as float32 rows.
-// Backward: per layer one wgrad launch (per-wavefront partial sums over a sample range, folded in a fixed order by k_gen_wreduce)
-// and one dgrad launch, both exact float32 products on the matrix cores (v_mfma_f32_32x32x2f32) with the parameters read in place
-// from the handle's float32 copy.  No floating-point atomics, no host synchronisation.
+// Backward: the per-layer kernels of gen_rows.h -- per layer one wgrad launch (per-wavefront partial sums over a sample range, folded in a
+// fixed order by k_gen_wreduce) and one dgrad launch, both exact float32 products on the matrix cores (v_mfma_f32_32x32x2f32) with the
+// parameters read in place from the handle's float32 copy.  No floating-point atomics, no host synchronisation.
 // With a feature output (evd_nerf_mlp_train_feature / _backward_feature; every view-branch network, the pipelined 8 x 256 one included):
 // the feature is a plane of the store (GenStore::f() or h(D - 1)), its gradient one more addend placed by k_gen_rows_in ahead of a dgrad
 // that runs with `add`.
 #pragma once
 
 #include "evd_common.h"
+#include "gen_rows.h"
 #include "nerf_mlp.h"
 #include "nerf_net.h"
 #include "nerf_train.h"
 
 namespace evd {
-
-constexpr int GEN_ENC = 64;             // row width of the encoding planes: 3 (1 + 2 L) <= 63 columns in the reference's order, zero padded
 
 // The store: planes of float32 rows, nsp = nsamp rounded up to the 32-sample tile.  Offsets in floats.
 struct GenStore {
@@ -34,14 +33,10 @@ struct GenStore {
     __host__ __device__ long total() const { return enc(4); }
 };
 
-constexpr size_t GEN_WS_FLOATS = (size_t)8 << 20;       // wgrad partial sums: at least 102 sample ranges of the largest layer (256 x 319 + bias)
-
-inline bool nerf_generic_trains(const evd_nerf* n, int prec) {
-    return prec == EVD_PREC_F16X3 && !n->no_views && n->pipe_chunks[EVD_PREC_F16X3] == 0 && n->nchunks[EVD_PREC_F16X3] > 0;
-}
 // The entries with a feature output (evd_nerf_mlp_train_feature / evd_nerf_mlp_backward_feature) run these kernels for EVERY view-branch
-// network, the 8 x 256 / (10, 4) / skips [4] one included: a predicate of their own, the dispatch of the plain entries stays where it is.
+// network, the 8 x 256 / (10, 4) / skips [4] one included; the plain entries only where the pipelined kernels are not built.
 inline bool nerf_feature_trains(const evd_nerf* n, int prec) { return prec == EVD_PREC_F16X3 && !n->no_views && n->nchunks[EVD_PREC_F16X3] > 0; }
+inline bool nerf_generic_trains(const evd_nerf* n, int prec) { return nerf_feature_trains(n, prec) && n->pipe_chunks[EVD_PREC_F16X3] == 0; }
 inline size_t nerf_generic_store_bytes(const evd_nerf* n, long nsamp) { return (size_t)GenStore(nsamp, n->D, n->W).total() * sizeof(float); }
 
 // pdh: the skip layer's k-step order of the stream in p (0 = the generic stream, evd_nerf::pd_pdh = evd_nerf::stream_pd)
@@ -62,28 +57,5 @@ struct GenBwdPlan {
     int ldf = 0, feature_kind = 0;
 };
 int run_nerf_backward_generic(const GenBwdPlan& b, hipStream_t st);
-
-// The per-layer launches of that backward, shared with the generic PDRF level (kernel_voxel_train_generic.hip).  A failed launch sets rc
-// and turns the later calls into no-ops; `who` names the entry in the messages.
-struct GenChain {
-    long nsamp;
-    float* partial;             // GEN_WS_FLOATS floats
-    int accumulate;
-    hipStream_t st;
-    const char* who;
-    int rc = EVD_OK;
-    // dW[:, c0 : c0 + K] (and db) of one layer from its gradient rows G [nsamp, M] and its input rows X [nsamp, K]
-    void wgrad(const float* G, int ldg, int M, const float* X, int ldx, int K, float* dw, int ldw, int c0, float* db);
-    // out[s, k] = sum_{m < Mv} G[s, m] Wm[m, c0 + k], k < K (written up to the next multiple of 32: zeros); M = 32, 64, 128 or 256 columns of G
-    // are read, rows m >= Mv of Wm are not (Mv = 0: all M)
-    void dgrad(int M, const float* G, int ldg, const float* Wm, int ldw, int c0, int K, float* out, int ldo, const float* mask, int ldm,
-               const float* eg, const float* ew, int add, int Mv = 0);
-};
-// PE(pts), PE(dirs) as float32 rows of GEN_ENC columns from rows [nsamp, 8] = (pts xyz, 0, dirs xyz, 0); and d x [nsamp, 3] from d PE(x)
-int launch_gen_encode(const float* in, long nsamp, int L, int Lv, float* ep, float* ed, hipStream_t st);
-int launch_gen_encode_bwd(const float* enc, const float* denc, long nsamp, int L, float* dx, hipStream_t st);
-// out[s, k] = src[s, k] (rows of lds floats; k < Wd, a multiple of 4), zero where mask (rows of Wd floats, a ReLU output) is given and <= 0:
-// an output's own gradient placed in a gradient plane [nsamp, Wd] ahead of the dgrad that adds to it
-int launch_gen_rows_in(const float* src, long lds, const float* mask, long nsamp, int Wd, float* out, hipStream_t st);
 
 }  // namespace evd

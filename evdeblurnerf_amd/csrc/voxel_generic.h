@@ -26,7 +26,7 @@ inline bool voxel_standard_shape(int num_layers, int num_layers_color, int HD, i
 
 int voxel_mlp_generic_dispatch(int prec, int HD, const VoxMlpParams& p, const VoxGenShape& g, hipStream_t st);
 
-// ---- training of a generic level, EVD_PREC_F16X3 (kernel_voxel_train_generic.hip), built like the generic NeRF path (nerf_train_generic.h)
+// ---- training of a generic level, EVD_PREC_F16X3 (kernel_voxel_train_generic.hip), built like the generic NeRF path on the per-layer kernels of gen_rows.h
 // The store: planes of float32 rows, nsp = nsamp rounded up to the 32-sample tile.  Offsets in floats.
 constexpr int VG_FT_LD = 16 * VG_KF, VG_GEO_LD = 32 * VG_GT, VG_COL_LD = 32;
 struct VoxGenStore {

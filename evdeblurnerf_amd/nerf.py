@@ -61,70 +61,46 @@ class _Raw2Outputs(torch.autograd.Function):
 
 
 class _NerfMLP(torch.autograd.Function):
-    """raw = NeRF.mlpforward(rays, z; params) with the hand-written backward kernels (evd_nerf_mlp_train / _backward)"""
+    """raw = NeRF.mlpforward(rays, z; params) with the hand-written backward kernels (evd_nerf_mlp_train / _backward).
+    want_feature: (raw, feature) from one node on the generic float32-grade kernels (evd_nerf_mlp_train_feature / _backward_feature); the
+    feature [R, S, W] is a view of the activation store, and its gradient enters the backward next to d raw (the AWP proposal's
+    depth_feature in mode='nerf', renderer.py:238-257)"""
 
     @staticmethod
-    def forward(ctx, flat, ray_batch, z_vals, net, precision):
-        raw, store = net.mlpforward_train(ray_batch, z_vals, precision)
-        ctx.net, ctx.precision, ctx.store = net, precision, store
+    def forward(ctx, flat, ray_batch, z_vals, net, precision, want_feature=False):
+        out = net.mlpforward_train(ray_batch, z_vals, precision, want_feature=want_feature)
+        ctx.net, ctx.precision, ctx.store, ctx.want_feature = net, precision, out[1], want_feature
         ctx.rb, ctx.z = ray_batch, z_vals
         ctx.accum = getattr(flat, "_evd_accum", None)          # in-place gradient accumulation (renderer._FlatParams), opt-in
-        return raw
-
-    @staticmethod
-    def backward(ctx, d_raw):
-        L.note_backward()
-        d_rb = None
-        acc = ctx.accum() if (ctx.accum is not None and ctx.needs_input_grad[0] and not torch.is_grad_enabled()) else None
-        if ctx.needs_input_grad[1]:
-            # rays: pts = o + d z enters PE(pts) (layer 0 and the skip layer), the view direction PE(dirs); z is a constant
-            rb, z = ctx.rb.detach().contiguous().float(), ctx.z.detach().contiguous().float()
-            pts = (rb[:, None, 0:3] + rb[:, None, 3:6] * z[..., None]).contiguous()
-            g, d_pts, d_dirs = ctx.net.mlp_backward_flat(d_raw, ctx.store, ctx.precision, pts=pts, ray_batch=rb, accumulate_into=acc)
-            d_rb = torch.zeros_like(rb)
-            d_pts = d_pts.reshape(pts.shape)
-            d_rb[:, 0:3] = d_pts.sum(1)
-            d_rb[:, 3:6] = (d_pts * z[..., None]).sum(1)
-            d_rb[:, 8:11] = d_dirs.reshape(pts.shape).sum(1)
-        else:
-            g = ctx.net.mlp_backward_flat(d_raw, ctx.store, ctx.precision, accumulate_into=acc)
-        ctx.store = None
-        return g, d_rb, None, None, None
-
-
-class _NerfMLPFeature(torch.autograd.Function):
-    """(raw, feature) = NeRF.mlpforward(..., want_feature) for training: one node on the generic float32-grade kernels
-    (evd_nerf_mlp_train_feature / _backward_feature); the feature [R, S, W] is a view of the activation store, and its gradient enters
-    the backward next to d raw (the AWP proposal's depth_feature in mode='nerf', renderer.py:238-257)"""
-
-    @staticmethod
-    def forward(ctx, flat, ray_batch, z_vals, net, precision):
-        raw, store, feature = net.mlpforward_train(ray_batch, z_vals, precision, want_feature=True)
-        ctx.net, ctx.precision, ctx.store = net, precision, store
-        ctx.rb, ctx.z = ray_batch, z_vals
-        ctx.accum = getattr(flat, "_evd_accum", None)
         ctx.set_materialize_grads(False)
-        return raw, feature
+        return (out[0], out[2]) if want_feature else out[0]
 
     @staticmethod
-    def backward(ctx, d_raw, d_feature):
+    def backward(ctx, d_raw, d_feature=None):
         L.note_backward()
         R, S = ctx.z.shape
         if d_raw is None:
             d_raw = torch.zeros((R, S, 4), dtype=torch.float32, device=ctx.z.device)
         acc = ctx.accum() if (ctx.accum is not None and ctx.needs_input_grad[0] and not torch.is_grad_enabled()) else None
         rays = ctx.needs_input_grad[1]
-        g, d_pts, d_dirs = ctx.net.mlp_backward_feature_flat(d_raw, d_feature, ctx.store, ctx.precision, want_rays=rays, accumulate_into=acc)
+        pts = rb = None
+        if rays:
+            # rays: pts = o + d z enters PE(pts) (layer 0 and the skip layer), the view direction PE(dirs); z is a constant
+            rb, z = ctx.rb.detach().contiguous().float(), ctx.z.detach().contiguous().float()
+            if not ctx.want_feature:        # the feature forward's store keeps the sample positions, the plain entry reads them again
+                pts = (rb[:, None, 0:3] + rb[:, None, 3:6] * z[..., None]).contiguous()
+        g = ctx.net.mlp_backward_flat(d_raw, ctx.store, ctx.precision, pts=pts, ray_batch=rb, accumulate_into=acc, d_feature=d_feature,
+                                      feature_store=ctx.want_feature, want_rays=rays)
         d_rb = None
         if rays:
-            rb, z = ctx.rb.detach().float(), ctx.z.detach().float()
+            g, d_pts, d_dirs = g
             d_rb = torch.zeros_like(rb)
             d_pts = d_pts.reshape(R, S, 3)
             d_rb[:, 0:3] = d_pts.sum(1)
             d_rb[:, 3:6] = (d_pts * z[..., None]).sum(1)
             d_rb[:, 8:11] = d_dirs.reshape(R, S, 3).sum(1)
         ctx.store = None
-        return g, d_rb, None, None, None
+        return g, d_rb, None, None, None, None
 
 
 class NeRF:
@@ -212,7 +188,7 @@ class NeRF:
     # mode with (hi, lo) fragments; 8 x 256 network).  Every other view-branch network trains in f16x3 on the generic kernels; the
     # per-network size queries are all this class knows about which path runs.
     # want_feature: (raw, store, feature) on the generic kernels (f16x3, every view-branch network); the feature [R, S, W] that
-    # `extract_feature` selects is a float32 VIEW of the store (evd_nerf_mlp_train_feature), consumed by mlp_backward_feature_flat.
+    # `extract_feature` selects is a float32 VIEW of the store (evd_nerf_mlp_train_feature), consumed by mlp_backward_flat(feature_store=True).
     def mlpforward_train(self, ray_batch, z_vals, precision=None, want_feature=False):
         if not self.use_viewdirs:
             raise L.EvdError("the training path is not built for use_viewdirs=False networks")
@@ -220,27 +196,23 @@ class NeRF:
         z = z_vals.contiguous().float()
         R, S = z.shape
         raw = torch.empty((R, S, 4), dtype=torch.float32, device=z.device)
-        if want_feature:
-            prec = L.PREC[precision or self.precision]
-            nb = int(L.lib().evd_nerf_train_feature_store_bytes(self._h, prec, R * S))
-            if nb == 0 and R * S > 0:
-                raise L.EvdError(f"no training path with a feature output in precision {precision or self.precision}: built for f16x3")
-            store = torch.empty((nb,), dtype=torch.uint8, device=z.device)
-            off, ld = C.c_long(0), C.c_long(0)
-            L.check(L.lib().evd_nerf_mlp_train_feature(self._h, prec, L.ptr(rb), L.ptr(z), R, S, L.ptr(raw), self._feature_kind(), L.ptr(store), nb,
-                                                        C.byref(off), C.byref(ld), L.stream_ptr()), "evd_nerf_mlp_train_feature")
-            if ld.value != self.W:
-                raise L.EvdError("evd_nerf_mlp_train_feature: unexpected feature row stride")
-            feature = store.view(torch.float32)[off.value:off.value + R * S * self.W].view(R, S, self.W)
-            return raw, store, feature
-        nb = int(L.lib().evd_nerf_train_store_bytes_net(self._h, L.PREC[precision or self.precision], R * S))
+        prec, lib = L.PREC[precision or self.precision], L.lib()
+        nb = int((lib.evd_nerf_train_feature_store_bytes if want_feature else lib.evd_nerf_train_store_bytes_net)(self._h, prec, R * S))
         if nb == 0 and R * S > 0:
+            if want_feature:
+                raise L.EvdError(f"no training path with a feature output in precision {precision or self.precision}: built for f16x3")
             raise L.EvdError(f"no training path for this network in precision {precision or self.precision}: the netdepth 8, netwidth 256, "
                              "skips [4], multires 10 / 4 network trains in f16 / bf16 / f16x3 / f16c / f16m, every other one in f16x3")
         store = torch.empty((nb,), dtype=torch.uint8, device=z.device)
-        L.check(L.lib().evd_nerf_mlp_train(self._h, L.PREC[precision or self.precision], L.ptr(rb), L.ptr(z), R, S, L.ptr(raw),
-                                            L.ptr(store), nb, L.stream_ptr()), "evd_nerf_mlp_train")
-        return raw, store
+        if not want_feature:
+            L.check(lib.evd_nerf_mlp_train(self._h, prec, L.ptr(rb), L.ptr(z), R, S, L.ptr(raw), L.ptr(store), nb, L.stream_ptr()), "evd_nerf_mlp_train")
+            return raw, store
+        off, ld = C.c_long(0), C.c_long(0)
+        L.check(lib.evd_nerf_mlp_train_feature(self._h, prec, L.ptr(rb), L.ptr(z), R, S, L.ptr(raw), self._feature_kind(), L.ptr(store), nb,
+                                               C.byref(off), C.byref(ld), L.stream_ptr()), "evd_nerf_mlp_train_feature")
+        if ld.value != self.W:
+            raise L.EvdError("evd_nerf_mlp_train_feature: unexpected feature row stride")
+        return raw, store, store.view(torch.float32)[off.value:off.value + R * S * self.W].view(R, S, self.W)
 
     # ---- training path (f16 / bf16 on the 8 x 256 network) ------------------------------------------------------------
     # Parameters as ONE flat float32 tensor in the library's canonical order (include/evdnerf.h: evd_nerf_param_blocks).
@@ -288,9 +260,7 @@ class NeRF:
         want_feature: (raw, feature [R,S,W]) from one node whose backward takes both gradients (f16x3, the generic kernels)"""
         if getattr(self, "_synced", None) != (flat.data_ptr(), flat._version, L.backward_generation()):
             self.load_params(flat)
-        if want_feature:
-            return _NerfMLPFeature.apply(flat, ray_batch, z_vals, self, precision or self.precision)
-        return _NerfMLP.apply(flat, ray_batch, z_vals, self, precision or self.precision)
+        return _NerfMLP.apply(flat, ray_batch, z_vals, self, precision or self.precision, want_feature)
 
     def _feature_kind(self):
         return 2 if self.extract_feature == "before_linear" else 1
@@ -310,47 +280,39 @@ class NeRF:
                 setattr(gs, head + field, base + 4 * off)
         return gs
 
-    # Backward of mlpforward_train(want_feature=True): gradients of sum(raw d_raw) + sum(feature d_feature)
-    def mlp_backward_feature_flat(self, d_raw, d_feature, store, precision=None, want_rays=False, accumulate_into=None):
-        """(flat parameter gradient, d pts [R*S,3] or None, d dirs [R*S,3] or None).  d_feature [R,S,W] or None (then the gradients of
-        mlp_backward_flat on the generic path); accumulate_into as in mlp_backward_flat (the returned flat gradient is then None)"""
+    # Backward of mlpforward_train: d_raw [R,S,4] -> flat gradient (what autograd gives for nerf.py:46-72)
+    def mlp_backward_flat(self, d_raw, store, precision=None, pts=None, ray_batch=None, accumulate_into=None, d_feature=None,
+                          feature_store=False, want_rays=False):
+        """flat parameter gradient; with pts [R,S,3] and the ray batch also (flat, d pts [R*S,3], d dirs per sample [R*S,3]), the
+        gradients through the two positional encodings.  accumulate_into: a persistent flat float32 gradient buffer the kernels ADD
+        into (evd_nerf_grads.accumulate); the returned flat gradient is then None.
+        feature_store=True: `store` was written by mlpforward_train(want_feature=True) and goes back through
+        evd_nerf_mlp_backward_feature -- gradients of sum(raw d_raw) + sum(feature d_feature), d_feature [R,S,W] or None; that store keeps
+        the sample positions, so want_rays=True asks for (flat, d pts, d dirs) without pts / ray_batch"""
         g = d_raw.contiguous().float()
         R, S = g.shape[:2]
-        prec = L.PREC[precision or self.precision]
+        prec, lib = L.PREC[precision or self.precision], L.lib()
         self.param_blocks()
         flat = accumulate_into if accumulate_into is not None else torch.zeros((self._nparam,), dtype=torch.float32, device=g.device)
         gs = self._grads_struct(flat, accumulate_into is not None)
         df = d_feature.contiguous().float() if d_feature is not None else None
+        if df is not None and not feature_store:
+            raise L.EvdError("d_feature needs the store of mlpforward_train(want_feature=True): pass feature_store=True")
         if df is not None and tuple(df.shape) != (R, S, self.W):
             raise L.EvdError(f"d_feature {tuple(df.shape)} is not [R, S, W] = {(R, S, self.W)}")
-        nb = int(L.lib().evd_nerf_backward_feature_workspace_bytes(self._h, prec))
+        nb = int(lib.evd_nerf_backward_feature_workspace_bytes(self._h, prec) if feature_store else lib.evd_nerf_backward_workspace_bytes_net(self._h, prec))
         ws = torch.empty((nb,), dtype=torch.uint8, device=g.device)
-        d_pts = torch.empty((R * S, 3), dtype=torch.float32, device=g.device) if want_rays else None
-        d_dirs = torch.empty((R * S, 3), dtype=torch.float32, device=g.device) if want_rays else None
-        L.check(L.lib().evd_nerf_mlp_backward_feature(self._h, prec, L.ptr(g), L.ptr(df), self.W, self._feature_kind(), R, S, L.ptr(store),
-                                                       store.numel(), C.byref(gs), L.ptr(d_pts), L.ptr(d_dirs), L.ptr(ws), nb, L.stream_ptr()),
-                "evd_nerf_mlp_backward_feature")
-        return (None if accumulate_into is not None else flat), d_pts, d_dirs
-
-    # Backward of mlpforward_train: d_raw [R,S,4] -> flat gradient (what autograd gives for nerf.py:46-72)
-    def mlp_backward_flat(self, d_raw, store, precision=None, pts=None, ray_batch=None, accumulate_into=None):
-        """flat parameter gradient; with pts [R,S,3] and the ray batch also (flat, d pts [R*S,3], d dirs per sample [R*S,3]), the
-        gradients through the two positional encodings.  accumulate_into: a persistent flat float32 gradient buffer the kernels ADD
-        into (evd_nerf_grads.accumulate); the returned flat gradient is then None"""
-        g = d_raw.contiguous().float()
-        R, S = g.shape[:2]
-        blocks = self.param_blocks()
-        flat = accumulate_into if accumulate_into is not None else torch.zeros((self._nparam,), dtype=torch.float32, device=g.device)
-        gs = self._grads_struct(flat, accumulate_into is not None)
-        nb = int(L.lib().evd_nerf_backward_workspace_bytes_net(self._h, L.PREC[precision or self.precision]))
-        ws = torch.empty((nb,), dtype=torch.uint8, device=g.device)
-        want = pts is not None
+        want = want_rays or pts is not None
         d_pts = torch.empty((R * S, 3), dtype=torch.float32, device=g.device) if want else None
         d_dirs = torch.empty((R * S, 3), dtype=torch.float32, device=g.device) if want else None
-        vd = ray_batch[:, 8:11] if want else None              # a strided view: rows of 11 floats
-        L.check(L.lib().evd_nerf_mlp_backward(self._h, L.PREC[precision or self.precision], L.ptr(g), R, S, L.ptr(store), store.numel(),
-                                               C.byref(gs), L.ptr(pts), C.c_void_p(vd.data_ptr()) if want else None, 11, L.ptr(d_pts), L.ptr(d_dirs),
-                                               L.ptr(ws), nb, L.stream_ptr()), "evd_nerf_mlp_backward")
+        if feature_store:
+            L.check(lib.evd_nerf_mlp_backward_feature(self._h, prec, L.ptr(g), L.ptr(df), self.W, self._feature_kind(), R, S, L.ptr(store),
+                                                      store.numel(), C.byref(gs), L.ptr(d_pts), L.ptr(d_dirs), L.ptr(ws), nb, L.stream_ptr()),
+                    "evd_nerf_mlp_backward_feature")
+        else:
+            vd = C.c_void_p(ray_batch[:, 8:11].data_ptr()) if pts is not None else None      # a strided view: rows of 11 floats
+            L.check(lib.evd_nerf_mlp_backward(self._h, prec, L.ptr(g), R, S, L.ptr(store), store.numel(), C.byref(gs), L.ptr(pts), vd, 11,
+                                              L.ptr(d_pts), L.ptr(d_dirs), L.ptr(ws), nb, L.stream_ptr()), "evd_nerf_mlp_backward")
         if accumulate_into is not None:
             flat = None
         return (flat, d_pts, d_dirs) if want else flat

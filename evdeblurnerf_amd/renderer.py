@@ -450,11 +450,10 @@ class NeRFAll:
         rays_d = rb[:, 3:6].contiguous()
         # want_feature: the LAST pass returns its network's per-sample feature [R, S, W] as depth_feature (renderer.py:219-257) -- the
         # fine network with N_importance > 0, else the coarse one; the coarse pass of a two-pass render asks for none
-        feat = None
-        if want_feature and Ni <= 0:
-            raw0, feat = self.mlp_coarse.mlp_train(flat_coarse, rb, z0, self.train_precision, want_feature=True)
-        else:
-            raw0 = self.mlp_coarse.mlp_train(flat_coarse, rb, z0, self.train_precision)
+        def mlp(net, flat, z, want):        # (raw, feature or None)
+            out = net.mlp_train(flat, rb, z, self.train_precision, want_feature=want)
+            return out if want else (out, None)
+        raw0, feat = mlp(self.mlp_coarse, flat_coarse, z0, bool(want_feature) and Ni <= 0)
         rgb0, _, acc0, w0, depth0, _ = self.mlp_coarse.raw2outputs(raw0, z0, rays_d, None, 0., white_bkgd, noise=noise0)
         if Ni <= 0:
             ret = {"rgb_map": rgb0, "depth_map": depth0, "acc_map": acc0, "weights": w0, "z_vals": z0}
@@ -462,10 +461,7 @@ class NeRFAll:
                 ret["depth_feature"] = feat
             return ret
         _, zm, _, zstd = sample_pdf_merge(z0, w0.detach(), Ni, det=(perturb == 0.), u=u)
-        if want_feature:
-            raw1, feat = self.mlp_fine.mlp_train(flat_fine, rb, zm, self.train_precision, want_feature=True)
-        else:
-            raw1 = self.mlp_fine.mlp_train(flat_fine, rb, zm, self.train_precision)
+        raw1, feat = mlp(self.mlp_fine, flat_fine, zm, bool(want_feature))
         rgb, _, acc, w1, depth, _ = self.mlp_fine.raw2outputs(raw1, zm, rays_d, None, 0., white_bkgd, noise=noise1)
         ret = {"rgb_map": rgb, "depth_map": depth, "acc_map": acc, "weights": w1, "z_vals": zm, "rgb0": rgb0, "depth0": depth0,
                "acc0": acc0, "z_std": zstd}

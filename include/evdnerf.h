@@ -278,7 +278,7 @@ int evd_nerf_mlp(const evd_nerf* net, int precision, const float* ray_batch, con
  * split product -- twice the store (evd_nerf_train_store_bytes_prec), gradients equal to float32 autograd to ~1e-5.
  * evd_nerf_train_store_bytes = the half-precision size (kept for existing callers).
  * Every other view-branch network (netdepth 1..EVD_MAX_LAYERS, netwidth 64 / 128 / 256, one skip index or none, multires 0..10,
- * multires_views 0..10) trains in EVD_PREC_F16X3 only, on the generic kernels (csrc/kernel_nerf_train_generic.hip): the forward is
+ * multires_views 0..10) trains in EVD_PREC_F16X3 only, on the generic kernels (csrc/kernel_nerf_train_generic.hip, kernel_gen_rows.hip): the forward is
  * evd_nerf_mlp's generic kernel with stores (raw bit-equal to evd_nerf_mlp), the store holds float32 rows (sample position and
  * direction, every layer's output) and the backward's per-sample gradient rows, and the backward multiplies in exact float32 on the
  * matrix cores with no floating-point atomics (bit-reproducible).  The sizes depend on the network:

@@ -160,7 +160,7 @@ def _backward(net, name, kind, d_feat, accumulate_into=None):
     rb, z = case_inputs(name)[:2]
     ref = reference(name, kind)
     raw, store, feat = net.mlpforward_train(T(rb), T(z), want_feature=True)
-    return net.mlp_backward_feature_flat(T(ref["d_raw"]), d_feat, store, want_rays=True, accumulate_into=accumulate_into)
+    return net.mlp_backward_flat(T(ref["d_raw"]), store, d_feature=d_feat, feature_store=True, want_rays=True, accumulate_into=accumulate_into)
 
 
 @pytest.mark.parametrize("kind", [1, 2])
@@ -176,6 +176,24 @@ def test_without_a_feature_gradient_is_the_plain_backward(name, kind):
     for a, b in zip(got, want):
         assert torch.equal(a, b)
     assert got[0].abs().max().item() > 0
+
+
+@pytest.mark.parametrize("name", GENERIC)
+def test_node_without_a_feature_gradient_is_the_plain_node(name):
+    """NeRF.mlp_train(want_feature=True) with a gradient for raw alone (the node's d_feature is None) against NeRF.mlp_train without the
+    feature under the same d raw: the parameter gradient and the gradient that reaches the rays, bit for bit"""
+    net = make_net(name)
+    rb_np, z_np, d_raw = case_inputs(name)[:3]
+    grads = []
+    for want in (True, False):
+        flat = net.flat_params(case_state_dict(name))
+        rb = torch.tensor(rb_np, device=DEV, requires_grad=True)
+        out = net.mlp_train(flat, rb, T(z_np), want_feature=want)
+        raw = out[0] if want else out
+        (raw * T(d_raw)).sum().backward()
+        grads.append((flat.grad, rb.grad))
+    assert torch.equal(grads[0][0], grads[1][0]) and torch.equal(grads[0][1], grads[1][1])
+    assert grads[0][0].abs().max().item() > 0 and grads[0][1].abs().max().item() > 0
 
 
 @pytest.mark.parametrize("kind", [1, 2])
@@ -211,7 +229,7 @@ def test_refusals():
                 net.mlpforward_train(T(rb), T(z), precision=prec, want_feature=True)
             raw, store, feat = net.mlpforward_train(T(rb), T(z), want_feature=True)
             with pytest.raises(L.EvdError):
-                net.mlp_backward_feature_flat(torch.zeros_like(raw), torch.zeros_like(feat), store, precision=prec)
+                net.mlp_backward_flat(torch.zeros_like(raw), store, precision=prec, d_feature=torch.zeros_like(feat), feature_store=True)
     nv = NeRF(W.make_nerf_state_dict(31, 4, 64, use_viewdirs=False), D=4, W=64, use_viewdirs=False, precision="f16x3", extract_feature="before_linear")
     with pytest.raises(L.EvdError):
         nv.mlpforward_train(T(rb[:, :8]), T(z), want_feature=True)
